@@ -12,6 +12,11 @@ the JSON re-hydration of Results for Python is outside too: want_results=False, 
           (seed 42 + r), no collective on the data path; after the timed solves ONE all-reduce (RCCL over xGMI) sums the
           per-instance-type (NodeClaim count, $/h) vector of every rank's packing — the north_star's global packing summary.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (with the figures the timed steps' own
+timings give: roofline, pack kernel, phases). --full adds everything else: the Results digest against the oracle's pin,
+the end-to-end boundary costs, the configs[2] / [3] / [4] legs, the batched launch and the CPU baselines.
+--dump-outputs DIR writes what the last timed step handed its caller (float64 .npy files, see dump_outputs).
 """
 import argparse
 import json
@@ -366,11 +371,30 @@ def packing_vector(res, n_its):
     return vec
 
 
+def dump_outputs(directory, res, n_its, suffix=""):
+    """--dump-outputs: what Solve(want_results=False) — the timed path — returned to its caller in the last timed step, as float64
+    arrays: the per-instance-type NodeClaim count and $/h of the packing (ksolve_packing_vector), pods scheduled, NodeClaims, the
+    packing's $/h, whether the solve timed out and the reference-equivalent bin evaluations. The inputs are seeded, so two builds
+    run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    vec = packing_vector(res, n_its)
+    arrays = {"packing_vector_count": vec[:, 0], "packing_vector_cost": vec[:, 1],
+              "scheduled_pods": [res["scheduledPods"]], "node_claims": [res["counters"]["claims"]], "packing_cost": [res["packingCost"]],
+              "timed_out": [float(bool(res.get("timedOut")))], "reference_bin_evaluations": [res["counters"]["referenceBinEvaluations"]]}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (one Solve() each)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the Results digest against the oracle's pin, the end-to-end "
+                    "boundary costs, the configs[2] / [3] / [4] legs, the batched launch, the CPU baselines (the options below size them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float64; every rank "
+                    "writes its own, with a _rank<r> suffix when there are several)")
     ap.add_argument("--pods", type=int, default=1_000_000, help="pods per GPU (configs[1] = 1M)")
     ap.add_argument("--types", type=int, default=500)
     ap.add_argument("--cpu-sample", type=int, default=120_000, help="pods in the bounded cpu_baseline sample (about 10-30 s of one core with the round-4 oracle)")
@@ -400,6 +424,8 @@ def main():
     ap.add_argument("--solver-lib", default=None, help="TEST HOOK (tests/test_bench_contract.py, needs KSOLVE_BENCH_TEST_HOOK=1): a host build of the engine behind the same "
                     "C ABI, so that the launcher / collective / JSON contract can be exercised without a GPU; never a measurement, never a default")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.solver_lib and os.environ.get("KSOLVE_BENCH_TEST_HOOK") != "1":
         raise SystemExit("bench.py: --solver-lib is a test hook (set KSOLVE_BENCH_TEST_HOOK=1); the product has no CPU path")
     if args.solver_lib:
@@ -474,23 +500,29 @@ def main():
     scheduled = last["scheduledPods"]
     cost = last["packingCost"]
     claims = last["counters"]["claims"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, len(prob["instanceTypes"]), f"_rank{rank}" if world > 1 else "")
+    # the per-instance-type summary of the last timed step (ksolve_packing_vector, returned with every Solve());
+    # tests/test_distributed_gloo.py checks it against launch_type_vector on the oracle's claims
+    vec = packing_vector(last, len(prob["instanceTypes"]))
 
-    # ---- untimed: the packing itself (digest against the oracle's pin, per-instance-type summary) ----
-    t_full = time.perf_counter()
-    full = sched.Solve(want_results=True)
-    t_full = time.perf_counter() - t_full
-    # ... and re-hydrated the way a caller that keeps its pods by position does it (the cgo shim: go/ksolve_rehydrate.go walks
-    # pod_assignment / pod_slot; here Scheduler.PodsByClaim): the NodeClaims as objects + two flat arrays, no uid text
-    t_pos = time.perf_counter()
-    by_pos = sched.Solve(want_results="claims-compact")
-    pods_of = sched.PodsByClaim(len(by_pos["newNodeClaims"]))
-    t_pos = time.perf_counter() - t_pos
-    if [len(x) for x in pods_of] != [len(c["pods"]) for c in full["newNodeClaims"]]:
-        raise SystemExit("bench.py: re-hydration by position disagrees with the Results document")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity   # canonical Results digest (shared with the tests; does not touch oracle/)
-    digest, _ = parity.results_digest(full)
-    vec = packing_vector(full, len(prob["instanceTypes"]))   # ksolve_packing_vector; tests/test_distributed_gloo.py checks it against launch_type_vector on the oracle's claims
+    full = digest = t_full = t_pos = None
+    if args.full:
+        # ---- untimed: the packing itself (digest against the oracle's pin) ----
+        t_full = time.perf_counter()
+        full = sched.Solve(want_results=True)
+        t_full = time.perf_counter() - t_full
+        # ... and re-hydrated the way a caller that keeps its pods by position does it (the cgo shim: go/ksolve_rehydrate.go walks
+        # pod_assignment / pod_slot; here Scheduler.PodsByClaim): the NodeClaims as objects + two flat arrays, no uid text
+        t_pos = time.perf_counter()
+        by_pos = sched.Solve(want_results="claims-compact")
+        pods_of = sched.PodsByClaim(len(by_pos["newNodeClaims"]))
+        t_pos = time.perf_counter() - t_pos
+        if [len(x) for x in pods_of] != [len(c["pods"]) for c in full["newNodeClaims"]]:
+            raise SystemExit("bench.py: re-hydration by position disagrees with the Results document")
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import parity   # canonical Results digest (shared with the tests; does not touch oracle/)
+        digest, _ = parity.results_digest(full)
 
     if dist is not None:
         # max over ranks of the timed region; the global packing summary = the per-instance-type (count, $/h) vectors of all
@@ -512,7 +544,7 @@ def main():
     # north_star's global packing summary. The union is a packing of equal quality, not the reference's pod-for-pod answer for the
     # whole batch (the reference re-sorts ALL claims before every scan, scheduler.go:598): L2-canonical, see `calibration`.
     comp = None
-    if args.components_pods > 0:
+    if args.full and args.components_pods > 0:
         from karpenter_amd.components import split_components
         from karpenter_amd.scheduling import SolveBatch
         import numpy as np
@@ -652,7 +684,7 @@ def main():
 
     # ---- BASELINE configs[4] (all ranks take part): the consolidation replay over a resident cluster ----
     sweep = None
-    if args.sweep_nodes > 0:
+    if args.full and args.sweep_nodes > 0:
         sweep = config4_sweep(args, device_index, rank, world)
         if args.sweep_topology_sample > 0 and world == 1:
             sweep["with_topology_pods"] = config4_sweep(args, device_index, rank, world, topology=True)
@@ -715,7 +747,7 @@ def main():
     except (OSError, KeyError, ValueError):
         pass
     pin = None
-    if not args.no_parity_pin:
+    if args.full and not args.no_parity_pin:
         pin_path = os.path.join(ROOT, "tests", "golden", "fullsize", f"config2_p{args.pods}_t{args.types}_s{seed}.json")
         if os.path.exists(pin_path):
             with open(pin_path) as f:
@@ -780,12 +812,14 @@ def main():
                        "solve_and_rehydrate_uid_text_s": t_full, "pods_per_s_with_uid_text": scheduled / world / (t_open + t_full),
                        "note": "rank 0's problem; flatten (a few host threads) + upload + solve + download + re-hydration, nothing overlapped. by_position: NodeClaims as objects, "
                                "every pod put on its NodeClaim from the flat pod_assignment / pod_slot arrays (what the cgo shim does); uid_text: the Results document with "
-                               "a million uid strings formatted by the host library and parsed by Python"},
+                               "a million uid strings formatted by the host library and parsed by Python"} if args.full else None,
         "phases_ms": {k: sum(t.get(k, 0.0) for t in timings) / len(timings) for k in ("pack_kernel_ms", "classify_ms", "row_hash_ms", "sort_ms", "it_index_ms")},
         "counters": c,
     }
+    if not args.full:
+        del out["parity"], out["end_to_end"]     # both take solves of their own
     sched.close()
-    if args.topology_pods > 0 and world == 1:
+    if args.full and args.topology_pods > 0 and world == 1:
         # BASELINE configs[2] shape (podAntiAffinity + 3-zone topologySpreadConstraints, the reference benchmark's diverse mix): ONE
         # Solve() of the whole batch on the general engine (BIG variant: every anti-affinity pod is its own NodeClaim). The size asked
         # for is timed; its Results are checked against the oracle's pin when one exists for that size (the oracle is O(pods x
@@ -854,7 +888,7 @@ def main():
             if pinned and not args.no_parity_pin:
                 e["largest_pinned_size"] = topology_run(pinned[-1], 1)
         out["config2_topology"] = e
-    if args.beyond_lds_pods > 0 and world == 1:
+    if args.full and args.beyond_lds_pods > 0 and world == 1:
         # right above the benchmarked size: the same mix with more NodeClaims than the cursor engine's LDS plan holds
         pb = fx.config2(pods=args.beyond_lds_pods, n_types=args.types, seed=42)
         pb["options"]["device"] = device_index
@@ -885,7 +919,7 @@ def main():
         out["config3_components"] = comp
     if sweep is not None:
         out["config4_sweep"] = sweep
-    if args.batch_problems > 0 and world == 1:
+    if args.full and args.batch_problems > 0 and world == 1:
         # Independent problems (NodePool components / consolidation probes) in ONE launch of the pack kernel:
         # block b = the wavefront of problem b. Reported beside the headline, never part of `value`.
         from karpenter_amd.scheduling import SolveBatch
@@ -900,7 +934,7 @@ def main():
                           "note": "ksolve_solve_batch: one wavefront per independent problem, one kernel launch; includes prepass and result download of every problem"}
         for sc_ in scheds:
             sc_.close()
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         import oracle  # the checker, used here only as the reported CPU baseline
         sample = fx.config2(pods=args.cpu_sample, n_types=args.types, seed=42)
         runs = []

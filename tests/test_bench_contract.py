@@ -31,7 +31,7 @@ def _env():
 
 def test_single_rank_line(oracle):
     emu = parity.build_emu()
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--pods", "3000", "--types", "60", "--cpu-sample", "1500", "--cpu-runs", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--pods", "3000", "--types", "60", "--cpu-sample", "1500", "--cpu-runs", "3",
            "--topology-pods", "400", "--components-pods", "4000", "--components-types", "60", "--components-calibration-pods", "4000", "--whole-batch-pods", "3000", "--whole-batch-exact-pods", "4000", "--beyond-lds-pods", "0", "--batch-problems", "3", "--batch-pods", "400", "--sweep-nodes", "300", "--sweep-candidates", "40", "--sweep-sample", "6", "--sweep-topology-sample", "6", "--sweep-windows", "3", "--sweep-window-size", "12", "--solver-lib", emu]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -80,11 +80,44 @@ def test_single_rank_line(oracle):
     assert line["batched"]["problems"] == 3 and line["batched"]["value"] > 0
 
 
+def test_plain_run_is_the_headline_and_dumps_its_last_step(oracle, tmp_path):
+    """Without --full the line is the headline leg alone (no solve, leg or baseline beside the timed steps); --dump-outputs writes what
+    the last timed step returned — float64, the same in two runs, and the oracle's packing of the same seeded problem."""
+    import numpy as np
+    import bench
+    emu = parity.build_emu()
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pods", "3000", "--types", "60", "--dump-outputs", str(d), "--solver-lib", emu]
+        r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _json_line(r.stdout)
+        assert REQUIRED <= set(line) and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "int64" and line["higher_is_better"] is True
+        assert not {"parity", "end_to_end", "config2_topology", "config1_beyond_lds", "config3_components", "config4_sweep", "batched",
+                    "cpu_baseline", "cpu_baseline_full_size", "cpu_baseline_engine_host"} & set(line)
+        assert abs(line["value"] - line["packing"]["pods_scheduled"] / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+        assert len(json.dumps(line)) < 6000
+        dumps.append({f[:-len(".npy")]: np.load(d / f) for f in sorted(os.listdir(d))})
+    out = dumps[0]
+    assert set(out) == {"packing_vector_count", "packing_vector_cost", "scheduled_pods", "node_claims", "packing_cost", "timed_out", "reference_bin_evaluations"}
+    for name, a in out.items():
+        assert a.dtype == np.float64 and np.array_equal(a, dumps[1][name]), name
+    prob = fx.config2(pods=3000, n_types=60, seed=42)
+    want = oracle.solve(prob)
+    assert out["scheduled_pods"][0] == 3000 - len(want["podErrors"]) == line["packing"]["pods_scheduled"]
+    assert out["node_claims"][0] == len(want["newNodeClaims"]) == out["packing_vector_count"].sum() == line["packing"]["node_claims"]
+    assert abs(out["packing_cost"][0] - want["packingCost"]) <= 1e-9 * want["packingCost"] and out["timed_out"][0] == 0
+    assert out["reference_bin_evaluations"][0] == want["counters"]["binEvaluations"]
+    vec = bench.launch_type_vector(prob, want)       # the oracle's claims, each booked on its cheapest launch type
+    assert np.array_equal(out["packing_vector_count"], vec[:, 0]) and np.allclose(out["packing_vector_cost"], vec[:, 1], rtol=1e-12, atol=0)
+
+
 def test_two_ranks_under_the_drivers_launcher(oracle):
     emu = parity.build_emu()
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--pods", "2500", "--types", "60", "--components-pods", "4000", "--components-types", "60", "--components-calibration-pods", "4000", "--sweep-nodes", "300", "--sweep-candidates", "41", "--sweep-sample", "3", "--sweep-windows", "3", "--sweep-window-size", "12", "--solver-lib", emu]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--pods", "2500", "--types", "60", "--components-pods", "4000", "--components-types", "60", "--components-calibration-pods", "4000", "--sweep-nodes", "300", "--sweep-candidates", "41", "--sweep-sample", "3", "--sweep-windows", "3", "--sweep-window-size", "12", "--solver-lib", emu]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = _json_line(r.stdout)
