@@ -11,6 +11,33 @@
 // reference's Go tests. There is NO scheduling logic here: requirement intersection reuses the same flat algebra the
 // kernels use (csrc/reqalg.h), and anything the device build cannot solve is reported as "unsupported", never solved
 // on the CPU.
+//
+// NewScheduler (ksched_open) is a ProblemBuilder run phase by phase; each phase is one member function, in this order
+// (KSCHED_TRACE=1 prints the quoted names with the wall time of the phase before them):
+//   "instance types"       read_instance_types: names, offerings (types.go:476-483), reservation capacities
+//                          (reservationmanager.go:45-60), requirements
+//   "node pools"           read_node_pools: OrderByWeight templates (nodepool.go:161-171, nodeclaimtemplate.go:66-94), taints,
+//                          every non-static pool for the domain groups (topology.go:105-146, scheduler.go:139-147)
+//   "pods"                 read_pods (explicit pods, pod groups, uid order), build_ladders (newPodRequirements
+//                          requirements.go:91-118, StrictRequirements scheduler.go:561-566, Preferences.Relax preferences.go:38-115)
+//   "daemonset pods"       read_daemonset_pods (scheduler.go:972-1043)
+//   "existing nodes"       read_existing_nodes: sortExistingNodes (scheduler.go:845-858), NewExistingNode (existingnode.go:72)
+//   "resources"            read_resources: dimensions and exact scales (resources.go:30-38, :83-97; types.go:274-277)
+//   "dictionary complete"  finalize_dictionary, then the tables that need value indices:
+//                          flatten_instance_types (computeAllocatable types.go:271-294, groupOfferingsByOverride types.go:224-269),
+//                          flatten_reservations, flatten_templates (updateRemainingResources scheduler.go:835-842),
+//                          flatten_host_ports (hostportusage.go:39-117), flatten_daemon_groups (scheduler.go:972-1043),
+//                          flatten_nodes (scheduler.go:805-832, existingnode.go:50-64), encode_pod_variants (scheduler.go:217-229),
+//                          flatten_volume_requirements (scheduler.go:138, :572), flatten_volume_limits (volumeusage.go:178-209,
+//                          existingnode.go:88, :179), fill_pod_rows
+//   "topology groups"      read_cluster_pods; domain_groups_from_pools (buildDomainGroups topology.go:105-146,
+//                          topologydomaingroup.go:36-72), node_topology_facts, inverse_groups_of_bound_pods (topology.go:310-355),
+//                          discover_groups (NewTopology topology.go:68-103, Update :162-194, newForTopologies :461-495,
+//                          newForAffinities :498-538, NewTopologyGroup topologygroup.go:79-126, Hash :188-222, countDomains
+//                          topology.go:361-459, topologynodefilter.go:50-96); flatten_topology_groups, flatten_pod_topology_masks
+//   "describe"             flag_pods_of_deleting_nodes, describe (ksolve_problem_desc from the builder's members), solver_options
+//   "ksolve_create"        the device library
+//   "session tables"       fill_session: what probes, sweeps and Results need is moved out of the builder, which then goes
 #include <dlfcn.h>
 #include <pthread.h>
 
@@ -126,6 +153,7 @@ const char* kZone = "topology.kubernetes.io/zone";
 const char* kInstanceType = "node.kubernetes.io/instance-type";
 const char* kCapacityType = "karpenter.sh/capacity-type";
 const char* kNodePool = "karpenter.sh/nodepool";
+const char* kReservationID = "karpenter.sh/reservation-id";   // cloudprovider.ReservationIDLabel
 
 std::string normalize_key(const std::string& k) {  // v1.NormalizedLabels — labels.go:121-127
   static const std::map<std::string, std::string> n = {{"failure-domain.beta.kubernetes.io/zone", kZone},
@@ -305,6 +333,13 @@ struct ReqTableBuilder {
     if (!gte.empty()) for (int k = 0; k < n_keys; ++k) { gte[(size_t)e * n_keys + k] = b.gte[k]; lte[(size_t)e * n_keys + k] = b.lte[k]; }
     if (!minv.empty()) for (int k = 0; k < n_keys; ++k) minv[(size_t)e * n_keys + k] = b.minv[k];
   }
+  // set e as a ReqRef (the non-lazy tables: instance types, templates); minValues only where the caller intersects with them
+  ks::ReqRef row(int e, bool with_minv) const {
+    ks::ReqRef r;
+    r.mask = mask.data() + (size_t)e * req_words; r.defined = defined[e]; r.complement = complement[e]; r.has_gte = has_gte[e]; r.has_lte = has_lte[e];
+    r.gte = gte.data() + (size_t)e * n_keys; r.lte = lte.data() + (size_t)e * n_keys; r.minv = with_minv ? minv.data() + (size_t)e * n_keys : nullptr;
+    return r;
+  }
   ksolve_reqsets view() const {
     ksolve_reqsets r{};
     r.n = (uint32_t)n; r.mask = mask.data(); r.defined = defined.data(); r.complement = complement.data();
@@ -374,6 +409,11 @@ struct Flattener {
     else throw std::runtime_error("bad operator " + e.op);
   }
   static void clear(ks::ReqBuf& b) { memset(&b, 0, sizeof(b)); for (int k = 0; k < ks::kMaxKeys; ++k) b.minv[k] = -1; }
+  // the intersection of a list of expressions (Requirements.Add over NewRequirementWithFlexibility, requirements.go:120-135)
+  void encode_all(const std::vector<Expr>& exprs, ks::ReqBuf& b) {
+    clear(b);
+    for (auto& e : exprs) { ks::ReqBuf one; encode(e, one); ks::reqbuf_add(kd, b, ks::reqbuf_ref_with_minv(one)); }
+  }
 };
 
 // metav1.LabelSelector as labels.Selector: nil matches nothing, empty matches everything (topologygroup.go:101-104,:443)
@@ -484,6 +524,41 @@ struct PodSpec {
   std::vector<std::vector<Expr>> volume_requirements;        // volumeReqsByPod[uid] (scheduler.go:138, :572): alternatives, in order
   std::vector<std::pair<std::string, std::string>> volumes;   // scheduling.GetVolumes(pod) (volumeusage.go:83-114): <CSI driver, PVC>
 };
+
+// ---- the intermediate model of a problem being flattened (ProblemBuilder) ----
+struct Off { int zone, ct; double price; bool available; int rid; std::map<std::string, i128> cap_ov; bool has_oh; std::map<std::string, i128> oh_ov; };
+struct Pool { const Value* v; std::string name; int weight; };
+struct AnyPool { const Value* v; uint64_t taints; };
+struct GroupSpan { size_t at; long long cnt; uint64_t seed; std::vector<int32_t> node; };
+struct NodeIn { const Value* v; std::string name, hostname; bool initialized; };
+struct Variant { std::vector<Expr> reqs, strict; std::vector<Toleration> tolerations; PodSpec pod; };
+struct Enc { ks::ReqBuf reqs, strict; uint64_t tol; std::vector<int64_t> req; };
+struct HGroup {
+  int type = 0; std::string key; bool inverse = false, initial = false;
+  int alias = -1;   // class of same-hash groups created by relaxation with different contents (first creator wins at solve time)
+  std::set<std::string> namespaces; Selector sel; int max_skew = 0, min_domains = -1;
+  std::string taint_policy, affinity_policy;
+  std::vector<std::vector<Expr>> freqs; uint64_t ftol = 0;
+  std::string identity;
+  std::set<std::string> domains; std::map<std::string, int> counts;
+  std::set<std::string> universe; std::map<std::string, int> node_regs;   // resident clusters: where a registered domain comes from
+  std::string content() const {
+    std::string c = identity + "|md" + std::to_string(min_domains) + "|tol" + std::to_string(ftol) + "|";
+    for (auto& d : domains) c += d + ",";
+    c += "|";
+    return c + filter_text();
+  }
+  std::string filter_text() const {   // the node filter's requirement sets, values included
+    std::string c;
+    for (auto& r : freqs) { for (auto& e : r) { c += e.key + " " + e.op + " ["; for (auto& v : e.values) c += v + ","; c += "];"; } c += "/"; }
+    return c;
+  }
+};
+struct KeyDomains { std::vector<int32_t> label_val, pod_val; std::vector<std::string> names; };   // pod_val: hostname falls back to the node's name (topology.go:438-442)
+i128 res_get(const std::map<std::string, i128>& m, const std::string& k) { auto it = m.find(k); return it == m.end() ? (i128)0 : it->second; }
+std::set<std::string> namespace_list(const std::string& ns, const AffTerm& term) {
+  return (term.namespaces.empty() && !term.resolved) ? std::set<std::string>{ns} : std::set<std::string>(term.namespaces.begin(), term.namespaces.end());
+}
 
 // Go's insertion sort (sort.Slice on <= 12 elements is a stable insertion sort; pods with more than 12 preferred
 // node-affinity terms are rejected so the unstable pdqsort path is never needed here) — requirements.go:102
@@ -737,39 +812,151 @@ struct Session {
 
 static char* session_error(Session* s) { char* r = error_json(s->error_kind.c_str(), s->error); return r; }
 
-// NewScheduler: parse + flatten the problem document and upload it through ksolve_create. Returns a session handle
-// (never null); ksched_error(session) is non-null when it failed.
-extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
-  Session* S = new Session();
-  Api& api = S->api;
-  std::string err;
-  if (!api.load(solver_lib, err)) { S->error_kind = "load"; S->error = err; return S; }
-  ksolve_handle*& handle = S->handle;
-  // KSCHED_TRACE=1: wall time of every phase of NewScheduler on stderr
-  const bool tracing = getenv("KSCHED_TRACE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto trace = [&](const char* next) {
-    if (!tracing) return;
+// KSCHED_TRACE=1: wall time of every phase of NewScheduler on stderr
+struct PhaseTrace {
+  const bool on = getenv("KSCHED_TRACE") != nullptr;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void operator()(const char* next) {
+    if (!on) return;
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "ksched_open: %8.1f ms until '%s'\n", std::chrono::duration<double, std::milli>(now - t_last).count(), next);
-    t_last = now;
-  };
-  try {
-    S->root = kj::Parser(problem_json).parse();
-    Value& root = S->root;
-    Flattener& fl = S->fl;
+    fprintf(stderr, "ksched_open: %8.1f ms until '%s'\n", std::chrono::duration<double, std::milli>(now - last).count(), next);
+    last = now;
+  }
+};
+
+// The flat problem of one NewScheduler call under construction: the intermediate model the phases share and every array
+// ksolve_problem_desc points into (describe() hands out raw pointers, so the builder outlives ksolve_create). The phases are the
+// member functions below, in the order ksched_open runs them; each fills the members listed under its name. The order of the
+// phases and of the loops inside them fixes dictionary value indices, taint bits, resource columns and group ids.
+struct ProblemBuilder {
+  const Value& root;                      // the problem document (the session keeps it)
+  const Value& opts;
+  const bool ignore_prefs;
+  Flattener fl;                           // dictionary + encode(); moved into the session at the end
+  Dictionary& D = fl.dict;
+  // instance types
+  const std::vector<Value>& its_json;
+  int n_its = 0, k_it = -1, k_zone = -1, k_ct = -1, k_rid = -1, n_resv = 0, n_zones = 0, n_cts = 0;
+  std::map<std::string, int> it_index;
+  std::vector<std::vector<Expr>> it_exprs;
+  std::vector<std::vector<Off>> it_offs;
+  std::vector<int32_t> resv_capacity;     // per reservation id: the most pessimistic ReservationCapacity (reservationmanager.go:45-60)
+  // node pools
+  std::vector<Pool> pools;                // the templates, OrderByWeight
+  std::vector<AnyPool> all_pools;         // every non-static NodePool, also those without instance types (topology.go:105-146, scheduler.go:139-147)
+  int n_templates = 0;
+  std::vector<std::vector<Expr>> tmpl_exprs;
+  std::vector<Taint> distinct_taints;
+  std::vector<uint64_t> tmpl_taints;
+  bool tolerate_prefer_no_schedule = false;
+  // pods
+  std::vector<std::pair<std::string, std::map<std::string, std::string>>> namespace_lister;
+  std::vector<PodSpec> specs;             // distinct pod templates (each explicit pod is its own spec)
+  std::vector<int> pod_spec;              // per pod -> spec
+  std::vector<uint64_t> uid_hi, uid_lo;
+  UidTexts uid_text;                      // explicit pods only (group pods: regenerated on demand)
+  std::vector<std::pair<uint64_t, uint64_t>> group_of_pod;   // (seed, index) for group pods
+  std::vector<int> pod_node_input;        // group pods bound to a node: index into the problem's stateNodes list, else -1
+  int n_pods = 0;
+  std::vector<std::vector<Variant>> ladders;   // per spec: row 0 = as submitted, then one per Preferences.Relax step
+  // daemonset pods
+  std::vector<PodSpec> daemons;
+  // existing nodes
+  std::vector<NodeIn> nodes;              // sortExistingNodes order
+  int n_nodes = 0;
+  std::vector<int32_t> pod_node_sorted;   // the existing node every pod is bound to (sorted index), -1 = none
+  std::vector<int32_t> node_input_index;  // position in the problem's stateNodes list -> sorted node index
+  bool resident = false, hostname_selected = false;
+  std::vector<std::vector<Expr>> node_exprs;
+  std::vector<uint64_t> node_taints;
+  // resources
+  std::vector<std::string> res_names;
+  int n_res = 0;
+  std::vector<i128> scale;                // nano-units per device unit
+  std::vector<std::map<std::string, i128>> it_cap, it_over, tmpl_limits, node_avail, node_cap, node_ds;
+  std::vector<bool> tmpl_has_limits;
+  // dictionary complete: instance types, override groups, reservations
+  int it_words = 1, nk = 0, rw = 0;
+  std::vector<int64_t> it_alloc, it_capv, xg_alloc;
+  std::vector<uint64_t> it_avail, it_base_avail, xg_avail;
+  std::vector<double> it_price, resv_price;
+  std::vector<uint32_t> xg_it, it_resv_first;
+  std::vector<uint8_t> resv_zone, resv_id;
+  ReqTableBuilder it_reqs;
+  // templates (node_tmpl, node_limit_cap: what a probe needs of the pools' limits)
+  ReqTableBuilder tmpl_reqs;
+  std::vector<uint64_t> tmpl_its;
+  std::vector<uint32_t> tmpl_limit_mask;
+  std::vector<int64_t> tmpl_lim, node_limit_cap;
+  std::vector<int> node_tmpl;
+  // host ports
+  std::vector<HostPort> hp_dict;
+  bool hp_on = false;
+  std::vector<uint64_t> spec_hp, spec_hpc, daemon_hp, node_hp;
+  // daemon-overhead groups
+  std::vector<uint32_t> dg_first;
+  std::vector<uint64_t> dg_its, dg_hp;
+  std::vector<int64_t> dg_ov;
+  std::vector<uint8_t> dg_nonempty;
+  // existing node tables
+  ReqTableBuilder node_reqs;
+  std::vector<int64_t> node_remaining;
+  std::vector<uint8_t> node_init, node_uca;
+  // pod rows
+  std::vector<int> spec_first_extra;      // first ladder row of a spec, -1 = none
+  int n_rows = 0;
+  std::vector<std::vector<Enc>> enc;      // each (spec, variant) encoded once
+  bool strict_differs = false;
+  std::vector<int64_t> pod_requests, pod_creation;
+  ReqTableBuilder pod_reqs, pod_strict;
+  std::vector<uint64_t> pod_tol, pod_hp, pod_hpc;
+  std::vector<int32_t> pod_next;
+  std::vector<uint8_t> pod_pending, pod_from_deleting;
+  // volumes and CSI limits
+  bool any_volume = false;
+  std::vector<uint32_t> spec_vol_first, spec_vol_count, pod_vol_first, pod_vol_count;
+  ReqTableBuilder vol_reqs;
+  std::vector<std::string> pv_drivers;
+  std::vector<uint8_t> volume_driver;
+  std::vector<uint32_t> pod_pv_first, pod_pvs, node_pv_first, node_pvs;
+  std::vector<int32_t> node_pv_limit;
+  // topology groups: the model ...
+  bool any_topology = false;
+  std::vector<PodSpec> cluster_pods;
+  std::map<std::string, std::map<std::string, std::vector<uint64_t>>> domain_groups;   // key -> domain -> taint sets of the pools that offer it
+  std::vector<ks::ReqBuf> node_label_reqs;                       // state-node label sets (countDomains uses the raw labels, topology.go:376,441)
+  std::vector<std::map<std::string, std::string>> node_labels;
+  std::map<std::string, int> node_by_name;
+  std::vector<std::vector<int32_t>> spec_bound_nodes;           // resident clusters: the nodes of each spec's bound pods
+  std::set<std::string> excluded;
+  std::vector<char> node_has_node;
+  std::map<std::string, KeyDomains> key_domains;
+  std::map<std::string, std::vector<char>> filter_verdicts;     // by what a node filter consists of
+  std::vector<HGroup> groups, inverse;
+  int n_alias_classes = 0, G = 0;
+  std::vector<std::vector<std::vector<int>>> variant_owned;     // group ids per (spec, variant)
+  std::vector<std::vector<int>> spec_inverse_owned;
+  // ... and its flat form
+  std::vector<uint8_t> tg_type, tg_inverse, tg_initial, tg_fa, tg_ft;
+  std::vector<int32_t> tg_key, tg_skew, tg_mind, tg_alias, tg_counts, tg_node_counts, tg_regs, node_host_value;
+  std::vector<uint32_t> tg_ffirst;
+  std::vector<uint64_t> tg_ftol, tg_domains, tg_universe, pod_topo_owned, pod_topo_selected;
+  std::vector<uint16_t> value_rank;
+  ReqTableBuilder tg_freqs;
+  uint32_t dom_words = 1;
+
+  explicit ProblemBuilder(const Value& problem)
+      : root(problem), opts(problem.at("options")), ignore_prefs(opts.at("preferencePolicy").s("Respect") == "Ignore"), its_json(problem.at("instanceTypes").items()) {
     for (const char* k : {kNodePool, kZone, "topology.kubernetes.io/region", kInstanceType, "kubernetes.io/arch", "kubernetes.io/os", kCapacityType, "node.kubernetes.io/windows-build"}) fl.well_known.insert(k);
     for (auto& k : root.at("wellKnownLabels").items()) fl.well_known.insert(k.s());
-    const Value& opts = root.at("options");
-    bool ignore_prefs = opts.at("preferencePolicy").s("Respect") == "Ignore";
+  }
+  ~ProblemBuilder() { t_namespace_lister = nullptr; }   // never leave it pointing at this builder
+  ProblemBuilder(const ProblemBuilder&) = delete;
 
-    trace("instance types");
-    // ---- instance types ----
-    const auto& its_json = root.at("instanceTypes").items();
-    const int n_its = (int)its_json.size();
-    std::map<std::string, int> it_index;
-    Dictionary& D = fl.dict;
-    int k_it = D.key(kInstanceType), k_zone = D.key(kZone), k_ct = D.key(kCapacityType);
+  // ---- instance types ----
+  void read_instance_types() {
+    n_its = (int)its_json.size();
+    k_it = D.key(kInstanceType); k_zone = D.key(kZone); k_ct = D.key(kCapacityType);
     for (int i = 0; i < n_its; ++i) {
       const std::string name = its_json[i].at("name").s();
       if (it_index.count(name)) throw std::runtime_error("duplicate instance type " + name);
@@ -777,12 +964,8 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       D.value(k_it, name);
     }
     // offering zones / capacity types first so their value indices are the offering cell coordinates
-    std::vector<std::vector<Expr>> it_exprs(n_its);
-    struct Off { int zone, ct; double price; bool available; int rid; std::map<std::string, i128> cap_ov; bool has_oh; std::map<std::string, i128> oh_ov; };
-    std::vector<std::vector<Off>> it_offs(n_its);
-    const char* kReservationID = "karpenter.sh/reservation-id";   // cloudprovider.ReservationIDLabel
-    int k_rid = -1;
-    std::vector<int32_t> resv_capacity;   // per reservation id: the most pessimistic ReservationCapacity (reservationmanager.go:45-60)
+    it_exprs.resize(n_its);
+    it_offs.resize(n_its);
     for (int i = 0; i < n_its; ++i)
       for (auto& of : its_json[i].at("offerings").items()) {
         std::string zone, ct, rid;
@@ -812,36 +995,31 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         } else if (!rid.empty()) throw Unsupported("reservation id on a non-reserved offering");
         it_offs[i].push_back({D.value(k_zone, zone), D.value(k_ct, ct), of.at("price").d(), of.at("available").boolean_or(true), ridx, cap_ov, has_oh, oh_ov});
       }
-    const int n_resv = (int)resv_capacity.size();
+    n_resv = (int)resv_capacity.size();
     if (n_resv > 64) throw Unsupported("more than 64 capacity reservations");
-    const int n_zones = (int)D.values[k_zone].size(), n_cts = (int)D.values[k_ct].size();
+    n_zones = (int)D.values[k_zone].size(); n_cts = (int)D.values[k_ct].size();
     if (n_zones > KSOLVE_MAX_ZONES || n_cts > KSOLVE_MAX_CAPTYPES) throw Unsupported("more than 16 offering zones or 4 capacity types");
     for (int i = 0; i < n_its; ++i) { it_exprs[i] = parse_exprs(its_json[i].at("requirements")); for (auto& e : it_exprs[i]) D.note(e); }
+  }
 
-    trace("node pools");
-    // ---- node pools -> templates (OrderByWeight; static pools and pools without instance types are skipped) ----
-    struct Pool { const Value* v; std::string name; int weight; };
-    std::vector<Pool> pools;
+  int taint_id(const Taint& t) {
+    for (size_t i = 0; i < distinct_taints.size(); ++i) if (!(distinct_taints[i] < t) && !(t < distinct_taints[i])) return (int)i;
+    distinct_taints.push_back(t);
+    if (distinct_taints.size() > 64) throw Unsupported("more than 64 distinct taints");
+    return (int)distinct_taints.size() - 1;
+  }
+  // ---- node pools -> templates (OrderByWeight; static pools and pools without instance types are skipped) ----
+  void read_node_pools() {
     for (auto& np : root.at("nodePools").items()) {
       if (np.at("static").boolean_or(false)) continue;
       if (np.has("instanceTypes") && !np.at("instanceTypes").is_null() && np.at("instanceTypes").items().empty()) continue;
       pools.push_back({&np, np.at("name").s(), (int)np.at("weight").i(0)});
     }
     std::sort(pools.begin(), pools.end(), [](const Pool& a, const Pool& b) { return a.weight != b.weight ? a.weight > b.weight : a.name > b.name; });
-    const int n_templates = (int)pools.size();
+    n_templates = (int)pools.size();
     if (n_templates > KSOLVE_MAX_TEMPLATES) throw Unsupported("more than 32 NodePools");
-    std::vector<std::vector<Expr>> tmpl_exprs(n_templates);
-    std::vector<Taint> distinct_taints;
-    auto taint_id = [&](const Taint& t) {
-      for (size_t i = 0; i < distinct_taints.size(); ++i) if (!(distinct_taints[i] < t) && !(t < distinct_taints[i])) return (int)i;
-      distinct_taints.push_back(t);
-      if (distinct_taints.size() > 64) throw Unsupported("more than 64 distinct taints");
-      return (int)distinct_taints.size() - 1;
-    };
-    std::vector<uint64_t> tmpl_taints(n_templates, 0);
-    bool tolerate_prefer_no_schedule = false;
-    struct AnyPool { const Value* v; uint64_t taints; };
-    std::vector<AnyPool> all_pools;   // every non-static NodePool, also those without instance types (topology.go:105-146, scheduler.go:139-147)
+    tmpl_exprs.resize(n_templates);
+    tmpl_taints.assign(n_templates, 0);
     for (auto& np : root.at("nodePools").items()) {
       if (np.at("static").boolean_or(false)) continue;
       uint64_t m = 0;
@@ -863,31 +1041,19 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       tmpl_exprs[t].push_back(Expr{"karpenter.sh/registered", "In", {"true"}, -1});
       tmpl_exprs[t].push_back(Expr{"karpenter.sh/initialized", "In", {"true"}, -1});
       for (auto& e : tmpl_exprs[t]) D.note(e);
-      for (auto& tv : np.at("taints").items()) {
-        Taint x{tv.at("key").s(), tv.at("value").s(), tv.at("effect").s()};
-        tmpl_taints[t] |= 1ull << taint_id(x);
-        if (x.effect == "PreferNoSchedule") tolerate_prefer_no_schedule = true;
-      }
+      for (auto& ap : all_pools) if (ap.v == &np) tmpl_taints[t] = ap.taints;   // numbered above, with every other non-static pool's
     }
+  }
 
-    trace("pods");
-    // ---- pods (explicit list + deterministic groups) ----
-    std::vector<std::pair<std::string, std::map<std::string, std::string>>> namespace_lister;
+  // ---- pods (explicit list + deterministic groups) ----
+  void read_pods() {
     for (auto& nv : root.at("namespaces").items()) {
       std::map<std::string, std::string> labels;
       for (auto& kv : nv.at("labels").members()) labels[kv.first] = kv.second.s();
       namespace_lister.push_back({nv.at("name").s(), labels});
     }
-    t_namespace_lister = &namespace_lister;   // read by parse_aff_term for every pod parsed below (this thread only)
-    struct ListerScope { ~ListerScope() { t_namespace_lister = nullptr; } } lister_scope;   // never leave it pointing at this frame
-    struct Row { int spec; };  // index into specs
-    std::vector<PodSpec> specs;           // distinct pod templates (each explicit pod is its own spec)
-    std::vector<int> pod_spec;            // per pod -> spec
-    std::vector<uint64_t> uid_hi, uid_lo;
-    UidTexts uid_text;    // explicit pods only (group pods: regenerated on demand)
-    std::vector<std::pair<uint64_t, uint64_t>> group_of_pod;  // (seed, index) for group pods
+    t_namespace_lister = &namespace_lister;   // read by parse_aff_term for every pod parsed from here on (this thread only), until the builder goes
     bool all_uuid = true;
-    std::vector<int> pod_node_input;      // group pods bound to a node: index into the problem's stateNodes list, else -1
     for (auto& pv : root.at("pods").items()) {
       specs.push_back(parse_pod(pv));
       pod_spec.push_back((int)specs.size() - 1);
@@ -896,7 +1062,6 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       uid_hi.push_back(hi); uid_lo.push_back(lo); uid_text.push_back(specs.back().uid); group_of_pod.push_back({0, 0});
       pod_node_input.push_back(-1);
     }
-    struct GroupSpan { size_t at; long long cnt; uint64_t seed; std::vector<int32_t> node; };
     std::vector<GroupSpan> spans;
     for (auto& g : root.at("podGroups").items()) {
       specs.push_back(parse_pod(g.at("template")));
@@ -934,7 +1099,7 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         if (!sp.node.empty()) pod_node_input[p] = (int)sp.node[(size_t)i];
       });
     }
-    const int n_pods = (int)pod_spec.size();
+    n_pods = (int)pod_spec.size();
     if (!all_uuid) {
       // UIDs that are not lower-case UUIDs: order them as strings on the host and hand the device their rank
       std::vector<int> order(n_pods);
@@ -945,9 +1110,10 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       std::sort(order.begin(), order.end(), [&](int a, int b) { return texts[a] < texts[b]; });
       for (int r = 0; r < n_pods; ++r) { uid_hi[order[r]] = 0; uid_lo[order[r]] = (uint64_t)r; }
     }
-    // requirement ladders per spec: row 0 = as submitted, then one row per Preferences.Relax step (preferences.go:38-57)
-    struct Variant { std::vector<Expr> reqs, strict; std::vector<Toleration> tolerations; PodSpec pod; };
-    std::vector<std::vector<Variant>> ladders(specs.size());
+  }
+  // requirement ladders per spec: row 0 = as submitted, then one row per Preferences.Relax step (preferences.go:38-57)
+  void build_ladders() {
+    ladders.resize(specs.size());
     for (size_t si = 0; si < specs.size(); ++si) {
       PodSpec p = specs[si];
       for (;;) {
@@ -1008,9 +1174,10 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         break;
       }
     }
-    trace("daemonset pods");
-    // ---- daemonset pods: only their scheduling constraints and requests matter (scheduler.go:972-1043) ----
-    std::vector<PodSpec> daemons;
+  }
+
+  // ---- daemonset pods: only their scheduling constraints and requests matter (scheduler.go:972-1043) ----
+  void read_daemonset_pods() {
     for (auto& dv : root.at("daemonSetPods").items()) {
       daemons.push_back(parse_pod(dv));
       const PodSpec& dp = daemons.back();
@@ -1018,20 +1185,19 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       for (auto& term : dp.required_terms) for (auto& e : term) D.note(e);
     }
     if (daemons.size() > 64) throw Unsupported("more than 64 daemonset pods");
-    trace("existing nodes");
-    // ---- existing nodes (state.StateNode read accessors): sortExistingNodes order (scheduler.go:845-858) ----
-    struct NodeIn { const Value* v; std::string name, hostname; bool initialized; };
-    std::vector<NodeIn> nodes;
+  }
+
+  // ---- existing nodes (state.StateNode read accessors): sortExistingNodes order (scheduler.go:845-858) ----
+  void read_existing_nodes() {
     for (auto& nv : root.at("stateNodes").items()) {
       NodeIn n{&nv, nv.at("name").s(), "", nv.at("initialized").boolean_or(true)};
       n.hostname = nv.has("hostname") ? nv.at("hostname").s() : (nv.at("labels").has(kHostname) ? nv.at("labels").at(kHostname).s() : n.name);
       nodes.push_back(n);
     }
     std::stable_sort(nodes.begin(), nodes.end(), [](const NodeIn& a, const NodeIn& b) { if (a.initialized != b.initialized) return a.initialized; return a.name < b.name; });
-    const int n_nodes = (int)nodes.size();
+    n_nodes = (int)nodes.size();
     // the existing node every pod is bound to (sorted index), -1 = none: explicit pods by nodeName, group pods by nodeIndex
-    std::vector<int32_t> pod_node_sorted(n_pods, -1);
-    std::vector<int32_t> node_input_index;
+    pod_node_sorted.assign(n_pods, -1);
     {
       std::map<std::string, int> sorted_index;
       for (int e = 0; e < n_nodes; ++e) sorted_index[nodes[e].name] = e;
@@ -1047,14 +1213,14 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       }
     }
     // options.residentCluster: the problem is a whole cluster — bound pods are pod rows, every simulation is a probe (ksolve_sweep)
-    const bool resident = opts.at("residentCluster").boolean_or(false);
-    std::vector<std::vector<Expr>> node_exprs(n_nodes);
-    std::vector<uint64_t> node_taints(n_nodes, 0);
+    resident = opts.at("residentCluster").boolean_or(false);
+    node_exprs.resize(n_nodes);
+    node_taints.assign(n_nodes, 0);
     // Every requirement source other than the nodes has been noted by now. When none of them mentions kubernetes.io/hostname
     // — no pod, NodePool, instance type or daemonset selects on it — a node's own hostname requirement (existingnode.go:72)
     // can never meet another requirement on that key (hostname topology groups count per node index, not per dictionary
     // value), so it is left out instead of spending one dictionary value per node (a 10k-node cluster would need 157 words).
-    const bool hostname_selected = D.key_index.count(kHostname) != 0;
+    hostname_selected = D.key_index.count(kHostname) != 0;
     for (int e = 0; e < n_nodes; ++e) {
       node_exprs[e] = label_exprs(nodes[e].v->at("labels"));
       // NewExistingNode adds hostname In [HostName()] (existingnode.go:72); drop a hostname label so it is not intersected twice
@@ -1064,13 +1230,14 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       for (auto& x : node_exprs[e]) D.note(x);
       for (auto& tv : nodes[e].v->at("taints").items()) node_taints[e] |= 1ull << taint_id(Taint{tv.at("key").s(), tv.at("value").s(), tv.at("effect").s()});
     }
+  }
 
-    trace("resources");
-    // ---- resources: dimensions and exact scales ----
-    std::vector<std::string> res_names = {"cpu", "memory"};
+  // ---- resources: dimensions and exact scales ----
+  void read_resources() {
+    res_names = {"cpu", "memory"};
     auto add_res = [&](const std::string& r) { if (r == "nodes") return; if (std::find(res_names.begin(), res_names.end(), r) == res_names.end()) res_names.push_back(r); };
     add_res("pods");
-    std::vector<std::map<std::string, i128>> it_cap(n_its), it_over(n_its);
+    it_cap.resize(n_its); it_over.resize(n_its);
     for (int i = 0; i < n_its; ++i) {
       it_cap[i] = parse_resources(its_json[i].at("capacity")); it_over[i] = parse_resources(its_json[i].at("overhead"));
       for (auto& kv : it_cap[i]) add_res(kv.first);
@@ -1078,24 +1245,24 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
     }
     for (auto& s : specs) for (auto& kv : s.requests) add_res(kv.first);
     for (auto& dp : daemons) for (auto& kv : dp.requests) add_res(kv.first);
-    std::vector<std::map<std::string, i128>> tmpl_limits(n_templates);
-    std::vector<bool> tmpl_has_limits(n_templates, false);
+    tmpl_limits.resize(n_templates);
+    tmpl_has_limits.assign(n_templates, false);
     for (int t = 0; t < n_templates; ++t) {
       const Value& np = *pools[t].v;
       if (np.has("limits") && !np.at("limits").is_null()) { tmpl_has_limits[t] = true; tmpl_limits[t] = parse_resources(np.at("limits")); for (auto& kv : tmpl_limits[t]) add_res(kv.first); }
     }
-    std::vector<std::map<std::string, i128>> node_avail(n_nodes), node_cap(n_nodes), node_ds(n_nodes);
+    node_avail.resize(n_nodes); node_cap.resize(n_nodes); node_ds.resize(n_nodes);
     for (int e = 0; e < n_nodes; ++e) {
       node_avail[e] = parse_resources(nodes[e].v->at("available")); node_cap[e] = parse_resources(nodes[e].v->at("capacity"));
       node_ds[e] = parse_resources(nodes[e].v->at("daemonSetRequests"));
       for (auto& kv : node_avail[e]) add_res(kv.first);
     }
-    const int n_res = (int)res_names.size();
+    n_res = (int)res_names.size();
     if (n_res > KSOLVE_MAX_RES) throw Unsupported("more than 8 resource dimensions");
     // nano-units per device unit: the greatest common divisor of every quantity of the dimension, so that the device
     // integers are exact and as small as possible (with Mi-granular memory and milli-cpu they fit 32 bits, which lets the
     // lite engine keep its instance-type tables as int32 registers)
-    std::vector<i128> scale(n_res, 0);
+    scale.assign(n_res, 0);
     auto gcd128 = [](i128 a, i128 b) { while (b) { i128 t = a % b; a = b; b = t; } return a; };
     auto consider = [&](const std::map<std::string, i128>& m) {
       for (auto& kv : m) {
@@ -1119,49 +1286,47 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
     for (int t = 0; t < n_templates; ++t) consider(tmpl_limits[t]);
     for (int e = 0; e < n_nodes; ++e) { consider(node_avail[e]); consider(node_cap[e]); }
     for (int r = 0; r < n_res; ++r) if (scale[r] == 0) scale[r] = 1000000000;
-    auto to_dev = [&](int r, i128 nano) {
-      if (nano % scale[r] != 0) throw std::runtime_error("internal: a quantity of " + res_names[r] + " was not part of the scale computation");
-      i128 v = nano / scale[r];
-      if (v > (i128)(INT64_MAX / 4) || v < -(i128)(INT64_MAX / 4)) throw Unsupported("resource quantity does not fit the device's exact int64 encoding");
-      return (int64_t)v;
-    };
-    auto res_get = [&](const std::map<std::string, i128>& m, const std::string& k) { auto it = m.find(k); return it == m.end() ? (i128)0 : it->second; };
+  }
+  int64_t to_dev(int r, i128 nano) const {
+    if (nano % scale[r] != 0) throw std::runtime_error("internal: a quantity of " + res_names[r] + " was not part of the scale computation");
+    i128 v = nano / scale[r];
+    if (v > (i128)(INT64_MAX / 4) || v < -(i128)(INT64_MAX / 4)) throw Unsupported("resource quantity does not fit the device's exact int64 encoding");
+    return (int64_t)v;
+  }
 
-    trace("dictionary complete");
-    // ---- dictionary is complete ----
-    const int it_words = std::max(1, (n_its + 63) / 64);
+  // ---- dictionary is complete ----
+  void finalize_dictionary() {
+    it_words = std::max(1, (n_its + 63) / 64);
     fl.finalize_dictionary(it_words);
-    const int nk = fl.kd.n_keys, rw = fl.kd.req_words;
-
-    // newPodRequirements(pod, required only) of a daemonset pod — requirements.go:74-118
-    auto daemon_reqs = [&](const PodSpec& dp) {
-      ks::ReqBuf b;
-      Flattener::clear(b);
-      std::vector<Expr> ex = label_exprs(dp.node_selector);
-      if (dp.has_node_affinity && dp.has_required && !dp.required_terms.empty()) for (auto& e : dp.required_terms[0]) ex.push_back(e);
-      for (auto& e : ex) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
-      return b;
-    };
-    // instance type tables
-    std::vector<int64_t> it_alloc((size_t)n_res * n_its), it_capv((size_t)n_res * n_its);
-    std::vector<uint64_t> it_avail(n_its, 0);
-    std::vector<double> it_price((size_t)n_its * 64, 0.0);
-    ReqTableBuilder it_reqs;
+    nk = fl.kd.n_keys; rw = fl.kd.req_words;
+  }
+  // newPodRequirements(pod, required only) of a daemonset pod — requirements.go:74-118
+  ks::ReqBuf daemon_reqs(const PodSpec& dp) {
+    std::vector<Expr> ex = label_exprs(dp.node_selector);
+    if (dp.has_node_affinity && dp.has_required && !dp.required_terms.empty()) for (auto& e : dp.required_terms[0]) ex.push_back(e);
+    ks::ReqBuf b;
+    fl.encode_all(ex, b);
+    return b;
+  }
+  // computeAllocatable (types.go:271-294): capacity - overhead over capacity's keys (resources.Subtract, resources.go:83-97),
+  // then hugepage reservations come out of the allocatable memory, one clamp at zero per hugepage size (capacity is a
+  // map, visited here in name order — the clamps commute)
+  void compute_alloc(const std::map<std::string, i128>& cap, const std::map<std::string, i128>& over, int64_t* out, size_t stride) const {
+    for (int r = 0; r < n_res; ++r) {
+      i128 alloc = cap.count(res_names[r]) ? res_get(cap, res_names[r]) - res_get(over, res_names[r]) : 0;
+      if (r == 1) for (auto& kv : cap) if (kv.first.rfind("hugepages-", 0) == 0) { alloc -= kv.second; if (alloc < 0) alloc = 0; }
+      out[(size_t)r * stride] = to_dev(r, alloc);
+    }
+  }
+  // instance type tables and offering override groups
+  void flatten_instance_types() {
+    it_alloc.assign((size_t)n_res * n_its, 0); it_capv.assign((size_t)n_res * n_its, 0);
+    it_avail.assign(n_its, 0);
+    it_price.assign((size_t)n_its * 64, 0.0);
     it_reqs.init(n_its, rw, nk);
-    // computeAllocatable (types.go:271-294): capacity - overhead over capacity's keys (resources.Subtract, resources.go:83-97),
-    // then hugepage reservations come out of the allocatable memory, one clamp at zero per hugepage size (capacity is a
-    // map, visited here in name order — the clamps commute)
-    auto compute_alloc = [&](const std::map<std::string, i128>& cap, const std::map<std::string, i128>& over, int64_t* out, size_t stride) {
-      for (int r = 0; r < n_res; ++r) {
-        i128 alloc = cap.count(res_names[r]) ? res_get(cap, res_names[r]) - res_get(over, res_names[r]) : 0;
-        if (r == 1) for (auto& kv : cap) if (kv.first.rfind("hugepages-", 0) == 0) { alloc -= kv.second; if (alloc < 0) alloc = 0; }
-        out[(size_t)r * stride] = to_dev(r, alloc);
-      }
-    };
     // offering override groups (groupOfferingsByOverride, types.go:224-269): available offerings with a non-empty
     // CapacityOverride or an OverheadOverride, grouped by the override pair in first-seen order behind the base group
-    std::vector<uint64_t> it_base_avail(n_its, 0), xg_avail;
-    std::vector<uint32_t> xg_it;
+    it_base_avail.assign(n_its, 0);
     std::vector<std::vector<int64_t>> xg_alloc_rows;   // per group: n_res values
     for (int i = 0; i < n_its; ++i) {
       for (int r = 0; r < n_res; ++r) it_capv[(size_t)r * n_its + i] = to_dev(r, res_get(it_cap[i], res_names[r]));
@@ -1189,30 +1354,32 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         }
       }
       ks::ReqBuf b;
-      Flattener::clear(b);
-      for (auto& e : it_exprs[i]) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
+      fl.encode_all(it_exprs[i], b);
       it_reqs.put(i, b);
     }
-    std::vector<uint32_t> it_resv_first(n_its + 1, 0);
-    std::vector<uint8_t> resv_zone, resv_id;
-    std::vector<double> resv_price;
+    xg_alloc.assign((size_t)n_res * xg_it.size(), 0);
+    for (size_t e = 0; e < xg_it.size(); ++e) for (int r = 0; r < n_res; ++r) xg_alloc[(size_t)r * xg_it.size() + e] = xg_alloc_rows[e][r];
+  }
+  // reserved offerings per instance type (reservationmanager.go:45-60)
+  void flatten_reservations() {
+    it_resv_first.assign(n_its + 1, 0);
     for (int i = 0; i < n_its; ++i) {
       for (auto& o : it_offs[i]) if (o.rid >= 0 && o.available) { resv_zone.push_back((uint8_t)o.zone); resv_id.push_back((uint8_t)o.rid); resv_price.push_back(o.price); }
       it_resv_first[i + 1] = (uint32_t)resv_zone.size();
     }
     if (resv_zone.empty()) { resv_zone.push_back(0); resv_id.push_back(0); resv_price.push_back(0); }
-    // templates
-    ReqTableBuilder tmpl_reqs;
+  }
+  // templates: requirements, instance types, remaining limits
+  void flatten_templates() {
     tmpl_reqs.init(n_templates, rw, nk);
-    std::vector<uint64_t> tmpl_its((size_t)n_templates * it_words, 0);
-    std::vector<uint32_t> tmpl_limit_mask(n_templates, 0);
-    std::vector<int64_t> tmpl_lim((size_t)n_templates * (n_res + 1), 0);
-    S->node_tmpl.assign(n_nodes, -1);
-    S->node_limit_cap.assign((size_t)n_nodes * (n_res + 1), 0);
+    tmpl_its.assign((size_t)n_templates * it_words, 0);
+    tmpl_limit_mask.assign(n_templates, 0);
+    tmpl_lim.assign((size_t)n_templates * (n_res + 1), 0);
+    node_tmpl.assign(n_nodes, -1);
+    node_limit_cap.assign((size_t)n_nodes * (n_res + 1), 0);
     for (int t = 0; t < n_templates; ++t) {
       ks::ReqBuf b;
-      Flattener::clear(b);
-      for (auto& e : tmpl_exprs[t]) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
+      fl.encode_all(tmpl_exprs[t], b);
       tmpl_reqs.put(t, b);
       const Value& np = *pools[t].v;
       if (np.has("instanceTypes") && !np.at("instanceTypes").is_null()) {
@@ -1235,13 +1402,13 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         for (int e = 0; e < n_nodes; ++e) {
           const Value& nl = nodes[e].v->at("labels");
           if (!nl.has(kNodePool) || nl.at(kNodePool).s() != pools[t].name) continue;
-          S->node_tmpl[e] = t;
+          node_tmpl[e] = t;
           for (auto& kv : tmpl_limits[t]) {
             auto f = node_cap[e].find(kv.first);
             if (f == node_cap[e].end()) continue;
-            if (kv.first == "nodes") { S->node_limit_cap[(size_t)e * (n_res + 1) + n_res] = (int64_t)(f->second / 1000000000); continue; }
+            if (kv.first == "nodes") { node_limit_cap[(size_t)e * (n_res + 1) + n_res] = (int64_t)(f->second / 1000000000); continue; }
             int r = (int)(std::find(res_names.begin(), res_names.end(), kv.first) - res_names.begin());
-            S->node_limit_cap[(size_t)e * (n_res + 1) + r] = to_dev(r, f->second);
+            node_limit_cap[(size_t)e * (n_res + 1) + r] = to_dev(r, f->second);
           }
         }
         for (auto& kv : tmpl_limits[t]) {
@@ -1252,109 +1419,103 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         }
       }
     }
-    // daemon-overhead groups per template (scheduler.go:972-1043): instance types keyed by the set of daemonset pods that
-    // could run on a node of that type from that NodePool
-    // host ports: the distinct <ip, port, protocol> triples of the problem, one bit each. They only matter when a pod to
-    // be scheduled binds one; then the triples of daemon pods and of the existing nodes' bound pods join the dictionary.
-    std::vector<HostPort> hp_dict;
-    bool hp_on = false;
+  }
+  uint64_t hp_mask(const std::vector<HostPort>& ports) {
+    uint64_t m = 0;
+    for (auto& h : ports) {
+      size_t i = 0;
+      for (; i < hp_dict.size(); ++i) if (hp_dict[i] == h) break;
+      if (i == hp_dict.size()) { if (hp_dict.size() == 64) throw Unsupported("more than 64 distinct host ports"); hp_dict.push_back(h); }
+      m |= 1ull << i;
+    }
+    return m;
+  }
+  uint64_t hp_conflicts(uint64_t use) const {   // every triple of the dictionary that Matches one of `use`
+    uint64_t m = 0;
+    for (size_t i = 0; i < hp_dict.size(); ++i) if ((use >> i) & 1) for (size_t j = 0; j < hp_dict.size(); ++j) if (hp_dict[i].matches(hp_dict[j])) m |= 1ull << j;
+    return m;
+  }
+  // host ports: the distinct <ip, port, protocol> triples of the problem, one bit each. They only matter when a pod to
+  // be scheduled binds one; then the triples of daemon pods and of the existing nodes' bound pods join the dictionary.
+  void flatten_host_ports() {
     for (auto& sp : specs) hp_on = hp_on || !sp.host_ports.empty();
-    auto hp_mask = [&](const std::vector<HostPort>& ports) {
-      uint64_t m = 0;
-      for (auto& h : ports) {
-        size_t i = 0;
-        for (; i < hp_dict.size(); ++i) if (hp_dict[i] == h) break;
-        if (i == hp_dict.size()) { if (hp_dict.size() == 64) throw Unsupported("more than 64 distinct host ports"); hp_dict.push_back(h); }
-        m |= 1ull << i;
-      }
-      return m;
-    };
-    std::vector<uint64_t> spec_hp(specs.size(), 0), daemon_hp(daemons.size(), 0), node_hp(n_nodes, 0), dg_hp;
+    spec_hp.assign(specs.size(), 0); daemon_hp.assign(daemons.size(), 0); node_hp.assign(n_nodes, 0);
     if (hp_on) {
       for (size_t si = 0; si < specs.size(); ++si) spec_hp[si] = hp_mask(specs[si].host_ports);
       for (size_t di = 0; di < daemons.size(); ++di) daemon_hp[di] = hp_mask(daemons[di].host_ports);
       for (int e = 0; e < n_nodes; ++e) node_hp[e] = hp_mask(parse_host_ports(nodes[e].v->at("hostPorts")));
     }
-    auto hp_conflicts = [&](uint64_t use) {   // every triple of the dictionary that Matches one of `use`
-      uint64_t m = 0;
-      for (size_t i = 0; i < hp_dict.size(); ++i) if ((use >> i) & 1) for (size_t j = 0; j < hp_dict.size(); ++j) if (hp_dict[i].matches(hp_dict[j])) m |= 1ull << j;
-      return m;
-    };
-    std::vector<uint32_t> dg_first;
-    std::vector<uint64_t> dg_its;
-    std::vector<int64_t> dg_ov;
-    std::vector<uint8_t> dg_nonempty;
-    if (!daemons.empty()) {
-      struct DTerm { std::vector<ks::ReqBuf> reqs; };
-      std::vector<DTerm> dterms(daemons.size());
-      for (size_t di = 0; di < daemons.size(); ++di) {
-        PodSpec p = daemons[di];
-        for (;;) {   // isDaemonPodCompatible relaxes required node-affinity terms one by one (scheduler.go:1029-1043)
-          dterms[di].reqs.push_back(daemon_reqs(p));
-          if (p.has_node_affinity && p.has_required && p.required_terms.size() > 1) { p.required_terms.erase(p.required_terms.begin()); continue; }
-          break;
-        }
+  }
+  // daemon-overhead groups per template (scheduler.go:972-1043): instance types keyed by the set of daemonset pods that
+  // could run on a node of that type from that NodePool
+  void flatten_daemon_groups() {
+    if (daemons.empty()) return;
+    struct DTerm { std::vector<ks::ReqBuf> reqs; };
+    std::vector<DTerm> dterms(daemons.size());
+    for (size_t di = 0; di < daemons.size(); ++di) {
+      PodSpec p = daemons[di];
+      for (;;) {   // isDaemonPodCompatible relaxes required node-affinity terms one by one (scheduler.go:1029-1043)
+        dterms[di].reqs.push_back(daemon_reqs(p));
+        if (p.has_node_affinity && p.has_required && p.required_terms.size() > 1) { p.required_terms.erase(p.required_terms.begin()); continue; }
+        break;
       }
-      dg_first.push_back(0);
-      for (int t = 0; t < n_templates; ++t) {
-        ks::ReqRef tr;
-        tr.mask = tmpl_reqs.mask.data() + (size_t)t * rw; tr.defined = tmpl_reqs.defined[t]; tr.complement = tmpl_reqs.complement[t];
-        tr.has_gte = tmpl_reqs.has_gte[t]; tr.has_lte = tmpl_reqs.has_lte[t]; tr.gte = tmpl_reqs.gte.data() + (size_t)t * nk; tr.lte = tmpl_reqs.lte.data() + (size_t)t * nk; tr.minv = nullptr;
-        std::vector<uint64_t> tolerated(daemons.size(), 0);
-        for (size_t di = 0; di < daemons.size(); ++di) {
-          std::vector<Toleration> tols = daemons[di].tolerations;
-          tols.push_back({"", "Exists", "", "PreferNoSchedule"});
-          bool ok = true;
-          for (size_t ti = 0; ti < distinct_taints.size(); ++ti) if ((tmpl_taints[t] >> ti) & 1) {
-            bool one = false;
-            for (auto& tl : tols) one = one || tolerates(tl, distinct_taints[ti]);
-            ok = ok && one;
-          }
-          tolerated[di] = ok;
-        }
-        std::vector<uint64_t> keys;   // group key = mask of compatible daemons, in order of first appearance
-        const size_t base = dg_nonempty.size();
-        for (int i = 0; i < n_its; ++i) {
-          if (!((tmpl_its[(size_t)t * it_words + i / 64] >> (i % 64)) & 1)) continue;
-          ks::ReqRef ir; ir.mask = it_reqs.mask.data() + (size_t)i * rw; ir.defined = it_reqs.defined[i]; ir.complement = it_reqs.complement[i];
-          ir.has_gte = it_reqs.has_gte[i]; ir.has_lte = it_reqs.has_lte[i]; ir.gte = it_reqs.gte.data() + (size_t)i * nk; ir.lte = it_reqs.lte.data() + (size_t)i * nk; ir.minv = nullptr;
-          uint64_t key = 0;
-          for (size_t di = 0; di < daemons.size(); ++di) {
-            if (!tolerated[di]) continue;
-            for (auto& rq : dterms[di].reqs) {
-              ks::ReqRef q = ks::reqbuf_ref_with_minv(rq);
-              if (ks::reqs_compatible(fl.kd, tr, q, true) == ks::COMPAT_OK && ks::reqs_intersect(fl.kd, ir, q)) { key |= 1ull << di; break; }
-            }
-          }
-          size_t gi = 0;
-          for (; gi < keys.size(); ++gi) if (keys[gi] == key) break;
-          if (gi == keys.size()) {
-            keys.push_back(key);
-            dg_its.resize(dg_its.size() + it_words, 0);
-            dg_nonempty.push_back(key != 0);
-            { uint64_t m = 0; for (size_t di = 0; di < daemons.size(); ++di) if ((key >> di) & 1) m |= daemon_hp[di]; dg_hp.push_back(m); }   // scheduler.go:990-993
-            for (int r = 0; r < n_res; ++r) {
-              i128 sum = 0;
-              for (size_t di = 0; di < daemons.size(); ++di) if ((key >> di) & 1) sum += res_names[r] == "pods" ? (i128)1000000000 : res_get(daemons[di].requests, res_names[r]);
-              dg_ov.push_back(to_dev(r, sum));
-            }
-          }
-          dg_its[(base + gi) * it_words + i / 64] |= 1ull << (i % 64);
-        }
-        if (keys.empty()) { dg_its.resize(dg_its.size() + it_words, 0); dg_nonempty.push_back(0); dg_hp.push_back(0); for (int r = 0; r < n_res; ++r) dg_ov.push_back(0); }
-        dg_first.push_back((uint32_t)dg_nonempty.size());
-      }
-      if (dg_nonempty.size() > 64) throw Unsupported("more than 64 daemon-overhead groups");
     }
-    // existing node tables
-    ReqTableBuilder node_reqs;
+    dg_first.push_back(0);
+    for (int t = 0; t < n_templates; ++t) {
+      const ks::ReqRef tr = tmpl_reqs.row(t, false);
+      std::vector<uint64_t> tolerated(daemons.size(), 0);
+      for (size_t di = 0; di < daemons.size(); ++di) {
+        std::vector<Toleration> tols = daemons[di].tolerations;
+        tols.push_back({"", "Exists", "", "PreferNoSchedule"});
+        bool ok = true;
+        for (size_t ti = 0; ti < distinct_taints.size(); ++ti) if ((tmpl_taints[t] >> ti) & 1) {
+          bool one = false;
+          for (auto& tl : tols) one = one || tolerates(tl, distinct_taints[ti]);
+          ok = ok && one;
+        }
+        tolerated[di] = ok;
+      }
+      std::vector<uint64_t> keys;   // group key = mask of compatible daemons, in order of first appearance
+      const size_t base = dg_nonempty.size();
+      for (int i = 0; i < n_its; ++i) {
+        if (!((tmpl_its[(size_t)t * it_words + i / 64] >> (i % 64)) & 1)) continue;
+        const ks::ReqRef ir = it_reqs.row(i, false);
+        uint64_t key = 0;
+        for (size_t di = 0; di < daemons.size(); ++di) {
+          if (!tolerated[di]) continue;
+          for (auto& rq : dterms[di].reqs) {
+            ks::ReqRef q = ks::reqbuf_ref_with_minv(rq);
+            if (ks::reqs_compatible(fl.kd, tr, q, true) == ks::COMPAT_OK && ks::reqs_intersect(fl.kd, ir, q)) { key |= 1ull << di; break; }
+          }
+        }
+        size_t gi = 0;
+        for (; gi < keys.size(); ++gi) if (keys[gi] == key) break;
+        if (gi == keys.size()) {
+          keys.push_back(key);
+          dg_its.resize(dg_its.size() + it_words, 0);
+          dg_nonempty.push_back(key != 0);
+          { uint64_t m = 0; for (size_t di = 0; di < daemons.size(); ++di) if ((key >> di) & 1) m |= daemon_hp[di]; dg_hp.push_back(m); }   // scheduler.go:990-993
+          for (int r = 0; r < n_res; ++r) {
+            i128 sum = 0;
+            for (size_t di = 0; di < daemons.size(); ++di) if ((key >> di) & 1) sum += res_names[r] == "pods" ? (i128)1000000000 : res_get(daemons[di].requests, res_names[r]);
+            dg_ov.push_back(to_dev(r, sum));
+          }
+        }
+        dg_its[(base + gi) * it_words + i / 64] |= 1ull << (i % 64);
+      }
+      if (keys.empty()) { dg_its.resize(dg_its.size() + it_words, 0); dg_nonempty.push_back(0); dg_hp.push_back(0); for (int r = 0; r < n_res; ++r) dg_ov.push_back(0); }
+      dg_first.push_back((uint32_t)dg_nonempty.size());
+    }
+    if (dg_nonempty.size() > 64) throw Unsupported("more than 64 daemon-overhead groups");
+  }
+  // existing node tables
+  void flatten_nodes() {
     node_reqs.init(n_nodes, rw, nk);
-    std::vector<int64_t> node_remaining((size_t)n_res * std::max(1, n_nodes), 0);
-    std::vector<uint8_t> node_init(std::max(1, n_nodes), 0), node_uca(std::max(1, n_nodes), 0);
+    node_remaining.assign((size_t)n_res * std::max(1, n_nodes), 0);
+    node_init.assign(std::max(1, n_nodes), 0); node_uca.assign(std::max(1, n_nodes), 0);
     for (int e = 0; e < n_nodes; ++e) {
       ks::ReqBuf b;
-      Flattener::clear(b);
-      for (auto& x : node_exprs[e]) { ks::ReqBuf one; fl.encode(x, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
+      fl.encode_all(node_exprs[e], b);
       node_reqs.put(e, b);
       // daemons that would run on the node minus what already runs there (scheduler.go:805-832, existingnode.go:50-64)
       std::map<std::string, i128> daemon;
@@ -1390,49 +1551,48 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       node_init[e] = nodes[e].initialized ? 1 : 0;
       node_uca[e] = (opts.at("consolidationSimulation").boolean_or(false) && nodes[e].v->at("underConsolidateAfter").boolean_or(false)) ? 1 : 0;
     }
-    // pod rows: rows [0,n_pods) are the pods; ladder rows are shared per spec and appended after
-    std::vector<int> spec_first_extra(specs.size(), -1);
-    int n_rows = n_pods;
+  }
+  // one row of the pod tables from an encoded variant: writes index `row` of each table and nothing else (fill_pod_rows runs it on several threads)
+  void put_row(int row, const Enc& e) {
+    for (int r = 0; r < n_res; ++r) pod_requests[(size_t)r * n_rows + row] = e.req[r];
+    pod_reqs.put(row, e.reqs); if (strict_differs) pod_strict.put(row, e.strict); pod_tol[row] = e.tol;
+  }
+  // pod rows: rows [0,n_pods) are the pods; ladder rows are shared per spec and appended after
+  void encode_pod_variants() {
+    spec_first_extra.assign(specs.size(), -1);
+    n_rows = n_pods;
     for (size_t si = 0; si < specs.size(); ++si) if (ladders[si].size() > 1) { spec_first_extra[si] = n_rows; n_rows += (int)ladders[si].size() - 1; }
-    std::vector<int64_t> pod_requests((size_t)n_res * n_rows);
-    ReqTableBuilder pod_reqs, pod_strict;
+    pod_requests.assign((size_t)n_res * n_rows, 0);
     pod_reqs.init(n_rows, rw, nk, true);
-    std::vector<uint64_t> pod_tol(n_rows, 0), pod_hp(n_rows, 0), pod_hpc(n_rows, 0);
-    std::vector<int32_t> pod_next(n_rows, -1);
-    std::vector<int64_t> pod_creation(n_pods);
-    std::vector<uint8_t> pod_pending(n_pods);
+    pod_tol.assign(n_rows, 0); pod_hp.assign(n_rows, 0); pod_hpc.assign(n_rows, 0);
+    pod_next.assign(n_rows, -1);
+    pod_creation.assign(n_pods, 0);
+    pod_pending.assign(n_pods, 0);
     // encode each (spec, variant) once, then replicate to its rows
-    struct Enc { ks::ReqBuf reqs, strict; uint64_t tol; std::vector<int64_t> req; };
-    std::vector<std::vector<Enc>> enc(specs.size());
+    enc.resize(specs.size());
     for (size_t si = 0; si < specs.size(); ++si) {
       std::vector<int64_t> req(n_res);
       for (int r = 0; r < n_res; ++r) req[r] = to_dev(r, res_names[r] == "pods" ? (i128)1000000000 : res_get(specs[si].requests, res_names[r]));
       for (auto& v : ladders[si]) {
         Enc e;
-        Flattener::clear(e.reqs); Flattener::clear(e.strict);
-        for (auto& x : v.reqs) { ks::ReqBuf one; fl.encode(x, one); ks::reqbuf_add(fl.kd, e.reqs, ks::reqbuf_ref_with_minv(one)); }
-        for (auto& x : v.strict) { ks::ReqBuf one; fl.encode(x, one); ks::reqbuf_add(fl.kd, e.strict, ks::reqbuf_ref_with_minv(one)); }
-        e.tol = 0;
-        for (size_t ti = 0; ti < distinct_taints.size(); ++ti) for (auto& t : v.tolerations) if (tolerates(t, distinct_taints[ti])) { e.tol |= 1ull << ti; break; }
+        fl.encode_all(v.reqs, e.reqs);
+        fl.encode_all(v.strict, e.strict);
+        e.tol = tol_mask(v.tolerations);
         e.req = req;
         enc[si].push_back(e);
       }
     }
     // StrictRequirements (without the preferred terms, scheduler.go:217-229) differ from Requirements only for pods with
     // preferences: when no variant of any pod has one, the strict table IS the requirement table (one upload, one stream)
-    bool strict_differs = false;
     for (auto& ev : enc) for (auto& e : ev) strict_differs = strict_differs || memcmp(&e.reqs, &e.strict, sizeof(ks::ReqBuf)) != 0;
     if (strict_differs) pod_strict.init(n_rows, rw, nk, true);
-    auto put_row = [&](int row, const Enc& e) {
-      for (int r = 0; r < n_res; ++r) pod_requests[(size_t)r * n_rows + row] = e.req[r];
-      pod_reqs.put(row, e.reqs); if (strict_differs) pod_strict.put(row, e.strict); pod_tol[row] = e.tol;
-    };
-    std::vector<uint64_t> spec_hpc(specs.size(), 0);
+    spec_hpc.assign(specs.size(), 0);
     for (size_t si = 0; si < specs.size(); ++si) spec_hpc[si] = hp_conflicts(spec_hp[si]);
-    // volume requirement alternatives (PodData.VolumeRequirements): one requirement set per alternative, equal lists shared
-    bool any_volume = false;
+  }
+  // volume requirement alternatives (PodData.VolumeRequirements): one requirement set per alternative, equal lists shared
+  void flatten_volume_requirements() {
     for (auto& sp : specs) any_volume = any_volume || !sp.volume_requirements.empty();
-    std::vector<uint32_t> spec_vol_first(specs.size(), 0), spec_vol_count(specs.size(), 0), pod_vol_first, pod_vol_count;
+    spec_vol_first.assign(specs.size(), 0); spec_vol_count.assign(specs.size(), 0);
     std::vector<ks::ReqBuf> vol_sets;
     if (any_volume) {
       std::map<std::string, std::pair<uint32_t, uint32_t>> lists;
@@ -1459,73 +1619,69 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       }
       pod_vol_first.assign(n_rows, 0); pod_vol_count.assign(n_rows, 0);
     }
-    ReqTableBuilder vol_reqs;
-    // ---- CSI volume limits of existing nodes (VolumeUsage, volumeusage.go:178-209; existingnode.go:88, :179) ----
-    // Only drivers that have a limit on some node can ever reject a pod; volumes of other drivers are dropped here.
-    std::vector<std::string> pv_drivers;
-    std::vector<uint8_t> volume_driver;
-    std::vector<uint32_t> pod_pv_first, pod_pvs, node_pv_first, node_pvs;
-    std::vector<int32_t> node_pv_limit;
-    {
-      std::map<std::string, int> drv;
-      for (int e = 0; e < n_nodes; ++e)
-        for (auto& kv : nodes[e].v->at("volumeUsage").at("limits").members()) if (!drv.count(kv.first)) { const int id = (int)drv.size(); drv[kv.first] = id; pv_drivers.push_back(kv.first); }
-      if (pv_drivers.size() > KSOLVE_MAX_VOLUME_DRIVERS) throw Unsupported("more than 8 CSI drivers with volume limits");
-      if (!pv_drivers.empty()) {
-        const int nd = (int)pv_drivers.size();
-        std::map<std::pair<int, std::string>, uint32_t> vol_id;
-        auto vid = [&](const std::string& d, const std::string& c) -> int64_t {
-          auto f = drv.find(d);
-          if (f == drv.end()) return -1;
-          auto key = std::make_pair(f->second, c);
-          auto g = vol_id.find(key);
-          if (g != vol_id.end()) return g->second;
-          const uint32_t id = (uint32_t)vol_id.size();
-          vol_id[key] = id; volume_driver.push_back((uint8_t)f->second);
-          return id;
-        };
-        std::vector<std::vector<uint32_t>> spec_pvs(specs.size());
-        for (size_t si = 0; si < specs.size(); ++si) {
-          for (auto& dv : specs[si].volumes) { const int64_t id = vid(dv.first, dv.second); if (id >= 0) spec_pvs[si].push_back((uint32_t)id); }
-          std::sort(spec_pvs[si].begin(), spec_pvs[si].end());
-          spec_pvs[si].erase(std::unique(spec_pvs[si].begin(), spec_pvs[si].end()), spec_pvs[si].end());
-        }
-        pod_pv_first.assign((size_t)n_pods + 1, 0);
-        for (int p = 0; p < n_pods; ++p) { pod_pv_first[p] = (uint32_t)pod_pvs.size(); pod_pvs.insert(pod_pvs.end(), spec_pvs[pod_spec[p]].begin(), spec_pvs[pod_spec[p]].end()); }
-        pod_pv_first[n_pods] = (uint32_t)pod_pvs.size();
-        node_pv_first.assign((size_t)n_nodes + 1, 0);
-        node_pv_limit.assign((size_t)n_nodes * nd, -1);
-        for (int e = 0; e < n_nodes; ++e) {
-          node_pv_first[e] = (uint32_t)node_pvs.size();
-          std::vector<uint32_t> ids;
-          for (auto& vv : nodes[e].v->at("volumeUsage").at("volumes").items()) { const int64_t id = vid(vv.at("driver").s(), vv.at("pvc").s()); if (id >= 0) ids.push_back((uint32_t)id); }
-          std::sort(ids.begin(), ids.end());
-          ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-          node_pvs.insert(node_pvs.end(), ids.begin(), ids.end());
-          std::vector<int> used(nd, 0);
-          for (uint32_t id : ids) used[volume_driver[id]]++;
-          bool over = false;
-          for (auto& kv : nodes[e].v->at("volumeUsage").at("limits").members()) {
-            const int dq = drv.at(kv.first);
-            node_pv_limit[(size_t)e * nd + dq] = (int32_t)kv.second.i();
-            if (used[dq] > kv.second.i()) over = true;
-          }
-          // already over a limit: ExceedsLimits fails for every pod, with or without volumes (it walks the union's drivers)
-          if (over) node_remaining[(size_t)0 * n_nodes + e] = -1;
-        }
-        node_pv_first[n_nodes] = (uint32_t)node_pvs.size();
-        if (pod_pvs.empty()) pod_pvs.push_back(0);
-        if (node_pvs.empty()) node_pvs.push_back(0);
-      }
-    }
     vol_reqs.init((int)vol_sets.size(), rw, nk);
     for (size_t i = 0; i < vol_sets.size(); ++i) vol_reqs.put((int)i, vol_sets[i]);
-    {
-      bool bounds = false, minv = false;
-      for (auto& ev : enc) for (auto& e : ev) { bounds = bounds || ((e.reqs.has_gte | e.reqs.has_lte | e.strict.has_gte | e.strict.has_lte) != 0); minv = minv || e.reqs.has_minv || e.strict.has_minv; }
-      pod_reqs.ensure_columns(bounds, minv);
-      if (strict_differs) pod_strict.ensure_columns(bounds, minv);
+  }
+  // ---- CSI volume limits of existing nodes (VolumeUsage, volumeusage.go:178-209; existingnode.go:88, :179) ----
+  // Only drivers that have a limit on some node can ever reject a pod; volumes of other drivers are dropped here.
+  void flatten_volume_limits() {
+    std::map<std::string, int> drv;
+    for (int e = 0; e < n_nodes; ++e)
+      for (auto& kv : nodes[e].v->at("volumeUsage").at("limits").members()) if (!drv.count(kv.first)) { const int id = (int)drv.size(); drv[kv.first] = id; pv_drivers.push_back(kv.first); }
+    if (pv_drivers.size() > KSOLVE_MAX_VOLUME_DRIVERS) throw Unsupported("more than 8 CSI drivers with volume limits");
+    if (!pv_drivers.empty()) {
+      const int nd = (int)pv_drivers.size();
+      std::map<std::pair<int, std::string>, uint32_t> vol_id;
+      auto vid = [&](const std::string& d, const std::string& c) -> int64_t {
+        auto f = drv.find(d);
+        if (f == drv.end()) return -1;
+        auto key = std::make_pair(f->second, c);
+        auto g = vol_id.find(key);
+        if (g != vol_id.end()) return g->second;
+        const uint32_t id = (uint32_t)vol_id.size();
+        vol_id[key] = id; volume_driver.push_back((uint8_t)f->second);
+        return id;
+      };
+      std::vector<std::vector<uint32_t>> spec_pvs(specs.size());
+      for (size_t si = 0; si < specs.size(); ++si) {
+        for (auto& dv : specs[si].volumes) { const int64_t id = vid(dv.first, dv.second); if (id >= 0) spec_pvs[si].push_back((uint32_t)id); }
+        std::sort(spec_pvs[si].begin(), spec_pvs[si].end());
+        spec_pvs[si].erase(std::unique(spec_pvs[si].begin(), spec_pvs[si].end()), spec_pvs[si].end());
+      }
+      pod_pv_first.assign((size_t)n_pods + 1, 0);
+      for (int p = 0; p < n_pods; ++p) { pod_pv_first[p] = (uint32_t)pod_pvs.size(); pod_pvs.insert(pod_pvs.end(), spec_pvs[pod_spec[p]].begin(), spec_pvs[pod_spec[p]].end()); }
+      pod_pv_first[n_pods] = (uint32_t)pod_pvs.size();
+      node_pv_first.assign((size_t)n_nodes + 1, 0);
+      node_pv_limit.assign((size_t)n_nodes * nd, -1);
+      for (int e = 0; e < n_nodes; ++e) {
+        node_pv_first[e] = (uint32_t)node_pvs.size();
+        std::vector<uint32_t> ids;
+        for (auto& vv : nodes[e].v->at("volumeUsage").at("volumes").items()) { const int64_t id = vid(vv.at("driver").s(), vv.at("pvc").s()); if (id >= 0) ids.push_back((uint32_t)id); }
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        node_pvs.insert(node_pvs.end(), ids.begin(), ids.end());
+        std::vector<int> used(nd, 0);
+        for (uint32_t id : ids) used[volume_driver[id]]++;
+        bool over = false;
+        for (auto& kv : nodes[e].v->at("volumeUsage").at("limits").members()) {
+          const int dq = drv.at(kv.first);
+          node_pv_limit[(size_t)e * nd + dq] = (int32_t)kv.second.i();
+          if (used[dq] > kv.second.i()) over = true;
+        }
+        // already over a limit: ExceedsLimits fails for every pod, with or without volumes (it walks the union's drivers)
+        if (over) node_remaining[(size_t)0 * n_nodes + e] = -1;
+      }
+      node_pv_first[n_nodes] = (uint32_t)node_pvs.size();
+      if (pod_pvs.empty()) pod_pvs.push_back(0);
+      if (node_pvs.empty()) node_pvs.push_back(0);
     }
+  }
+  // every pod row from its (spec, variant) encoding: rows [0, n_pods) are the pods, the ladder rows follow
+  void fill_pod_rows() {
+    bool bounds = false, minv = false;
+    for (auto& ev : enc) for (auto& e : ev) { bounds = bounds || ((e.reqs.has_gte | e.reqs.has_lte | e.strict.has_gte | e.strict.has_lte) != 0); minv = minv || e.reqs.has_minv || e.strict.has_minv; }
+    pod_reqs.ensure_columns(bounds, minv);
+    if (strict_differs) pod_strict.ensure_columns(bounds, minv);
     parallel_for((size_t)n_pods, [&](size_t pp) {     // every pod's row is its spec's encoding: independent writes
       const int p = (int)pp, si = pod_spec[p];
       put_row(p, enc[si][0]);
@@ -1543,412 +1699,397 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
         if (any_volume) { pod_vol_first[row] = spec_vol_first[si]; pod_vol_count[row] = spec_vol_count[si]; }
         pod_next[row] = vi + 1 < ladders[si].size() ? row + 1 : -1;
       }
+  }
 
-    trace("topology groups");
-    // ---- topology groups (NewTopology, topology.go:68-103; Update, :162-194) --------------------------------
-    // The device keeps one counter per (group, domain); which groups exist, what they select and what each pod variant
-    // owns is object wrangling done here. Group identity follows TopologyGroup.Hash() (topologygroup.go:188-222):
-    // key, type, namespaces, selector, maxSkew and — of the node filter — only what hashstructure can see (requirement
-    // KEYS and minValues, policies, tolerations); minDomains and requirement values are not part of it.
-    struct HGroup {
-      int type = 0; std::string key; bool inverse = false, initial = false;
-      int alias = -1;   // class of same-hash groups created by relaxation with different contents (first creator wins at solve time)
-      std::set<std::string> namespaces; Selector sel; int max_skew = 0, min_domains = -1;
-      std::string taint_policy, affinity_policy;
-      std::vector<std::vector<Expr>> freqs; uint64_t ftol = 0;
-      std::string identity;
-      std::set<std::string> domains; std::map<std::string, int> counts;
-      std::set<std::string> universe; std::map<std::string, int> node_regs;   // resident clusters: where a registered domain comes from
-      std::string content() const {
-        std::string c = identity + "|md" + std::to_string(min_domains) + "|tol" + std::to_string(ftol) + "|";
-        for (auto& d : domains) c += d + ",";
-        c += "|";
-        for (auto& r : freqs) { for (auto& e : r) { c += e.key + " " + e.op + " ["; for (auto& v : e.values) c += v + ","; c += "];"; } c += "/"; }
-        return c;
-      }
-    };
-    std::vector<HGroup> groups;
-    std::map<std::string, std::vector<int>> alias_members;
-    int n_alias_classes = 0;
-    std::vector<std::vector<std::vector<int>>> variant_owned(specs.size());   // group ids per (spec, variant)
-    std::vector<std::vector<int>> spec_inverse_owned(specs.size());
-    bool any_topology = false;
+  // ---- topology groups (NewTopology, topology.go:68-103; Update, :162-194) --------------------------------
+  // The device keeps one counter per (group, domain); which groups exist, what they select and what each pod variant
+  // owns is object wrangling done here. Group identity follows TopologyGroup.Hash() (topologygroup.go:188-222):
+  // key, type, namespaces, selector, maxSkew and — of the node filter — only what hashstructure can see (requirement
+  // KEYS and minValues, policies, tolerations); minDomains and requirement values are not part of it.
+  uint64_t tol_mask(const std::vector<Toleration>& tols) const {
+    uint64_t m = 0;
+    for (size_t ti = 0; ti < distinct_taints.size(); ++ti) for (auto& t : tols) if (tolerates(t, distinct_taints[ti])) { m |= 1ull << ti; break; }
+    return m;
+  }
+  void read_cluster_pods() {
+    variant_owned.resize(specs.size()); spec_inverse_owned.resize(specs.size());
     for (auto& sp : specs) if (!sp.tscs.empty() || sp.has_pod_affinity || sp.has_pod_anti) any_topology = true;
-    std::vector<PodSpec> cluster_pods;
     for (auto& cv : root.at("clusterPods").items()) cluster_pods.push_back(parse_pod(cv));
     for (auto& cp : cluster_pods) if (cp.has_pod_anti && !cp.anti_required.empty()) any_topology = true;
-    auto tol_mask = [&](const std::vector<Toleration>& tols) {
-      uint64_t m = 0;
-      for (size_t ti = 0; ti < distinct_taints.size(); ++ti) for (auto& t : tols) if (tolerates(t, distinct_taints[ti])) { m |= 1ull << ti; break; }
-      return m;
+  }
+  // buildDomainGroups — topology.go:105-146 ; TopologyDomainGroup.Insert — topologydomaingroup.go:36-57
+  void domain_groups_from_pools() {
+    auto dg_insert = [&](const std::string& key, const std::string& dom, uint64_t taints) {
+      auto& m = domain_groups[key];
+      auto it = m.find(dom);
+      if (it == m.end() || taints == 0) { m[dom] = {taints}; return; }
+      if (it->second[0] == 0) return;
+      it->second.push_back(taints);
     };
-    if (any_topology) {
-      // buildDomainGroups — topology.go:105-146 ; TopologyDomainGroup.Insert — topologydomaingroup.go:36-57
-      std::map<std::string, std::map<std::string, std::vector<uint64_t>>> dg;
-      auto dg_insert = [&](const std::string& key, const std::string& dom, uint64_t taints) {
-        auto& m = dg[key];
-        auto it = m.find(dom);
-        if (it == m.end() || taints == 0) { m[dom] = {taints}; return; }
-        if (it->second[0] == 0) return;
-        it->second.push_back(taints);
-      };
-      for (auto& ap : all_pools) {
-        const Value& np = *ap.v;
-        std::vector<Expr> pe = parse_exprs(np.at("requirements"));
-        for (auto& e : label_exprs(np.at("labels"))) pe.push_back(e);
-        ks::ReqBuf pb;
-        Flattener::clear(pb);
-        for (auto& e : pe) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, pb, ks::reqbuf_ref_with_minv(one)); }
-        auto each_value = [&](const ks::ReqBuf& b, bool only_in, uint64_t taints) {
-          for (int k = 0; k < nk; ++k) {
-            if (!((b.defined >> k) & 1)) continue;
-            if (only_in && (((b.complement >> k) & 1) || !ks::key_nonempty(fl.kd, b.mask, k))) continue;
-            for (size_t v = 0; v < D.values[k].size(); ++v) {
-              size_t pos = (size_t)fl.key_word_off[k] * 64 + v;
-              if ((b.mask[pos / 64] >> (pos % 64)) & 1) dg_insert(D.keys[k], D.values[k][v], taints);   // requirement.Values(): the stored set
-            }
+    for (auto& ap : all_pools) {
+      const Value& np = *ap.v;
+      std::vector<Expr> pe = parse_exprs(np.at("requirements"));
+      for (auto& e : label_exprs(np.at("labels"))) pe.push_back(e);
+      ks::ReqBuf pb;
+      Flattener::clear(pb);
+      for (auto& e : pe) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, pb, ks::reqbuf_ref_with_minv(one)); }
+      auto each_value = [&](const ks::ReqBuf& b, bool only_in, uint64_t taints) {
+        for (int k = 0; k < nk; ++k) {
+          if (!((b.defined >> k) & 1)) continue;
+          if (only_in && (((b.complement >> k) & 1) || !ks::key_nonempty(fl.kd, b.mask, k))) continue;
+          for (size_t v = 0; v < D.values[k].size(); ++v) {
+            size_t pos = (size_t)fl.key_word_off[k] * 64 + v;
+            if ((b.mask[pos / 64] >> (pos % 64)) & 1) dg_insert(D.keys[k], D.values[k][v], taints);   // requirement.Values(): the stored set
           }
-        };
-        std::vector<int> members;
-        if (np.has("instanceTypes") && !np.at("instanceTypes").is_null()) { for (auto& n : np.at("instanceTypes").items()) members.push_back(it_index.at(n.s())); }
-        else for (int i = 0; i < n_its; ++i) members.push_back(i);
-        for (int i : members) {
-          ks::ReqBuf b = pb;
-          ks::ReqRef ir; ir.mask = it_reqs.mask.data() + (size_t)i * rw; ir.defined = it_reqs.defined[i]; ir.complement = it_reqs.complement[i];
-          ir.has_gte = it_reqs.has_gte[i]; ir.has_lte = it_reqs.has_lte[i]; ir.gte = it_reqs.gte.data() + (size_t)i * nk; ir.lte = it_reqs.lte.data() + (size_t)i * nk; ir.minv = it_reqs.minv.data() + (size_t)i * nk;
-          ks::reqbuf_add(fl.kd, b, ir);
-          each_value(b, false, ap.taints);
         }
-        each_value(pb, true, ap.taints);
+      };
+      std::vector<int> members;
+      if (np.has("instanceTypes") && !np.at("instanceTypes").is_null()) { for (auto& n : np.at("instanceTypes").items()) members.push_back(it_index.at(n.s())); }
+      else for (int i = 0; i < n_its; ++i) members.push_back(i);
+      for (int i : members) {
+        ks::ReqBuf b = pb;
+        ks::ReqRef ir; ir.mask = it_reqs.mask.data() + (size_t)i * rw; ir.defined = it_reqs.defined[i]; ir.complement = it_reqs.complement[i];
+        ir.has_gte = it_reqs.has_gte[i]; ir.has_lte = it_reqs.has_lte[i]; ir.gte = it_reqs.gte.data() + (size_t)i * nk; ir.lte = it_reqs.lte.data() + (size_t)i * nk; ir.minv = it_reqs.minv.data() + (size_t)i * nk;
+        ks::reqbuf_add(fl.kd, b, ir);
+        each_value(b, false, ap.taints);
       }
-      // state-node label sets (countDomains uses the raw labels, topology.go:376,441)
-      std::vector<ks::ReqBuf> node_label_reqs(n_nodes);
-      std::vector<std::map<std::string, std::string>> node_labels(n_nodes);
+      each_value(pb, true, ap.taints);
+    }
+  }
+  // what countDomains asks of the state nodes and of the pods bound to them, once for all groups
+  void node_topology_facts() {
+    // state-node label sets (countDomains uses the raw labels, topology.go:376,441)
+    node_label_reqs.resize(n_nodes);
+    node_labels.resize(n_nodes);
+    for (int e = 0; e < n_nodes; ++e) {
+      Flattener::clear(node_label_reqs[e]);
+      for (auto& x : label_exprs(nodes[e].v->at("labels"))) {
+        node_labels[e][x.key] = x.values[0];
+        if (x.key == kHostname && !hostname_selected) continue;   // not in the dictionary: nothing selects on it (see above)
+        ks::ReqBuf one; fl.encode(x, one); ks::reqbuf_add(fl.kd, node_label_reqs[e], ks::reqbuf_ref_with_minv(one));
+      }
+    }
+    for (int e = 0; e < n_nodes; ++e) node_by_name[nodes[e].name] = e;
+    // a resident cluster counts its bound pods although they are pod rows: a probe takes its displaced pods' share out again
+    spec_bound_nodes.resize(specs.size());
+    if (resident) for (int p = 0; p < n_pods; ++p) if (pod_node_sorted[p] >= 0) spec_bound_nodes[pod_spec[p]].push_back(pod_node_sorted[p]);
+    // pods being scheduled are not counted from the cluster (topology.go:92-94)
+    if (!cluster_pods.empty() && !resident) for (int p = 0; p < n_pods; ++p) {
+      if (!uid_text[p].empty()) excluded.insert(uid_text[p]);
+      else { std::string t; uint64_t a, b; group_uid(group_of_pod[p].first, group_of_pod[p].second, a, b, &t); excluded.insert(t); }
+    }
+    node_has_node.assign(n_nodes, 1);
+    for (int e = 0; e < n_nodes; ++e) node_has_node[e] = nodes[e].v->at("hasNode").boolean_or(true) ? 1 : 0;
+  }
+  bool filter_matches(const HGroup& g, uint64_t taints, const ks::ReqBuf& reqs) {   // topologynodefilter.go:68-96
+    if (g.taint_policy == "Honor" && (taints & ~g.ftol)) return false;
+    if (g.affinity_policy != "Honor" || g.freqs.empty()) return true;
+    for (auto& r : g.freqs) {
+      ks::ReqBuf b;
+      fl.encode_all(r, b);
+      if (ks::reqs_compatible(fl.kd, ks::reqbuf_ref_with_minv(reqs), ks::reqbuf_ref_with_minv(b), false) == ks::COMPAT_OK) return true;
+    }
+    return false;
+  }
+  // NewTopologyGroup — topologygroup.go:79-126
+  HGroup make_group(int type, const std::string& key, const PodSpec& pod, const std::set<std::string>& namespaces, const Selector& sel,
+                    int max_skew, int min_domains, const std::string& taint_policy, const std::string& affinity_policy) const {
+    HGroup g;
+    g.type = type; g.key = key; g.namespaces = namespaces; g.sel = sel; g.max_skew = max_skew; g.min_domains = min_domains;
+    std::string fview;
+    if (type == 0) {
+      g.taint_policy = taint_policy.empty() ? "Ignore" : taint_policy;
+      g.affinity_policy = affinity_policy.empty() ? "Honor" : affinity_policy;
+      g.ftol = tol_mask(pod.tolerations);
+      std::vector<Expr> selx = label_exprs(pod.node_selector);
+      if (!pod.has_node_affinity || !pod.has_required) g.freqs.push_back(selx);
+      else for (auto& term : pod.required_terms) { std::vector<Expr> r = selx; for (auto& e : term) r.push_back(e); g.freqs.push_back(r); }
+      std::set<std::set<std::string>> rv;
+      for (auto& r : g.freqs) { std::set<std::string> ks_; for (auto& e : r) ks_.insert(e.key); rv.insert(ks_); }
+      for (auto& r : rv) { for (auto& k : r) fview += k + ","; fview += "/"; }
+      std::set<std::tuple<std::string, std::string, std::string, std::string>> tv;
+      for (auto& t : pod.tolerations) tv.insert({t.key, t.op, t.value, t.effect});
+      fview += "|";
+      for (auto& t : tv) fview += std::get<0>(t) + ":" + std::get<1>(t) + ":" + std::get<2>(t) + ":" + std::get<3>(t) + ",";
+    }
+    g.identity = key + "|" + std::to_string(type) + "|";
+    for (auto& n : namespaces) g.identity += n + ",";
+    g.identity += "|" + std::to_string(max_skew) + "|" + g.taint_policy + "|" + g.affinity_policy + "|" + fview + "|" + sel.canon();
+    // ForEachDomain — topologydomaingroup.go:61-72
+    const uint64_t ptol = tol_mask(pod.tolerations);
+    auto dgi = domain_groups.find(key);
+    if (dgi != domain_groups.end()) for (auto& kv : dgi->second) {
+      bool ok = g.taint_policy == "Ignore";
+      if (!ok) for (uint64_t taints : kv.second) if (!(taints & ~ptol)) { ok = true; break; }
+      if (ok) g.domains.insert(kv.first);
+    }
+    g.universe = g.domains;
+    return g;
+  }
+  // countDomains — topology.go:361-459. A resident cluster asks this of 100k nodes and 2M bound pods for every group (and once
+  // per disruption pass), so the per-node facts are worked out once and the counting itself runs on integers: the node's domain
+  // under a key as an id (per KEY), whether the node passes a group's node filter (per distinct FILTER), whether it has a Node.
+  KeyDomains& domains_of_key(const std::string& key) {
+    auto f = key_domains.find(key);
+    if (f != key_domains.end()) return f->second;
+    KeyDomains& kd2 = key_domains[key];
+    kd2.label_val.assign(n_nodes, -1); kd2.pod_val.assign(n_nodes, -1);
+    std::unordered_map<std::string, int32_t> ids;
+    auto id_of = [&](const std::string& v) { auto r = ids.emplace(v, (int32_t)kd2.names.size()); if (r.second) kd2.names.push_back(v); return r.first->second; };
+    for (int e = 0; e < n_nodes; ++e) {
+      auto it = node_labels[e].find(key);
+      if (it != node_labels[e].end()) kd2.label_val[e] = kd2.pod_val[e] = id_of(it->second);
+      else if (key == kHostname) kd2.pod_val[e] = id_of(nodes[e].name);
+    }
+    return kd2;
+  }
+  const std::vector<char>& nodes_passing(const HGroup& g) {
+    const std::string sig = g.taint_policy + "|" + g.affinity_policy + "|" + std::to_string(g.ftol) + "|" + g.filter_text();
+    auto f = filter_verdicts.find(sig);
+    if (f != filter_verdicts.end()) return f->second;
+    std::vector<char>& ok = filter_verdicts[sig];
+    ok.assign(n_nodes, 1);
+    if (g.taint_policy == "Honor" || (g.affinity_policy == "Honor" && !g.freqs.empty())) {
+      std::vector<ks::ReqBuf> enc_f;   // the filter's requirement sets, encoded once
+      for (auto& r : g.freqs) { ks::ReqBuf b; fl.encode_all(r, b); enc_f.push_back(b); }
       for (int e = 0; e < n_nodes; ++e) {
-        Flattener::clear(node_label_reqs[e]);
-        for (auto& x : label_exprs(nodes[e].v->at("labels"))) {
-          node_labels[e][x.key] = x.values[0];
-          if (x.key == kHostname && !hostname_selected) continue;   // not in the dictionary: nothing selects on it (see above)
-          ks::ReqBuf one; fl.encode(x, one); ks::reqbuf_add(fl.kd, node_label_reqs[e], ks::reqbuf_ref_with_minv(one));
+        bool pass = !(g.taint_policy == "Honor" && (node_taints[e] & ~g.ftol));
+        if (pass && g.affinity_policy == "Honor" && !enc_f.empty()) {
+          pass = false;
+          for (auto& b : enc_f) if (ks::reqs_compatible(fl.kd, ks::reqbuf_ref_with_minv(node_label_reqs[e]), ks::reqbuf_ref_with_minv(b), false) == ks::COMPAT_OK) { pass = true; break; }
         }
+        ok[e] = pass ? 1 : 0;
       }
-      std::map<std::string, int> node_by_name;
-      for (int e = 0; e < n_nodes; ++e) node_by_name[nodes[e].name] = e;
-      // a resident cluster counts its bound pods although they are pod rows: a probe takes its displaced pods' share out again
-      std::vector<std::vector<int32_t>> spec_bound_nodes(specs.size());
-      if (resident) for (int p = 0; p < n_pods; ++p) if (pod_node_sorted[p] >= 0) spec_bound_nodes[pod_spec[p]].push_back(pod_node_sorted[p]);
-      std::set<std::string> excluded;   // pods being scheduled are not counted from the cluster (topology.go:92-94)
-      if (!cluster_pods.empty() && !resident) for (int p = 0; p < n_pods; ++p) {
-        if (!uid_text[p].empty()) excluded.insert(uid_text[p]);
-        else { std::string t; uint64_t a, b; group_uid(group_of_pod[p].first, group_of_pod[p].second, a, b, &t); excluded.insert(t); }
-      }
-      auto filter_matches = [&](const HGroup& g, uint64_t taints, const ks::ReqBuf& reqs) {   // topologynodefilter.go:68-96
-        if (g.taint_policy == "Honor" && (taints & ~g.ftol)) return false;
-        if (g.affinity_policy != "Honor" || g.freqs.empty()) return true;
-        for (auto& r : g.freqs) {
-          ks::ReqBuf b;
-          Flattener::clear(b);
-          for (auto& e : r) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
-          if (ks::reqs_compatible(fl.kd, ks::reqbuf_ref_with_minv(reqs), ks::reqbuf_ref_with_minv(b), false) == ks::COMPAT_OK) return true;
-        }
-        return false;
-      };
-      // NewTopologyGroup — topologygroup.go:79-126
-      auto make_group = [&](int type, const std::string& key, const PodSpec& pod, const std::set<std::string>& namespaces, const Selector& sel,
-                            int max_skew, int min_domains, const std::string& taint_policy, const std::string& affinity_policy) {
-        HGroup g;
-        g.type = type; g.key = key; g.namespaces = namespaces; g.sel = sel; g.max_skew = max_skew; g.min_domains = min_domains;
-        std::string fview;
-        if (type == 0) {
-          g.taint_policy = taint_policy.empty() ? "Ignore" : taint_policy;
-          g.affinity_policy = affinity_policy.empty() ? "Honor" : affinity_policy;
-          g.ftol = tol_mask(pod.tolerations);
-          std::vector<Expr> selx = label_exprs(pod.node_selector);
-          if (!pod.has_node_affinity || !pod.has_required) g.freqs.push_back(selx);
-          else for (auto& term : pod.required_terms) { std::vector<Expr> r = selx; for (auto& e : term) r.push_back(e); g.freqs.push_back(r); }
-          std::set<std::set<std::string>> rv;
-          for (auto& r : g.freqs) { std::set<std::string> ks_; for (auto& e : r) ks_.insert(e.key); rv.insert(ks_); }
-          for (auto& r : rv) { for (auto& k : r) fview += k + ","; fview += "/"; }
-          std::set<std::tuple<std::string, std::string, std::string, std::string>> tv;
-          for (auto& t : pod.tolerations) tv.insert({t.key, t.op, t.value, t.effect});
-          fview += "|";
-          for (auto& t : tv) fview += std::get<0>(t) + ":" + std::get<1>(t) + ":" + std::get<2>(t) + ":" + std::get<3>(t) + ",";
-        }
-        g.identity = key + "|" + std::to_string(type) + "|";
-        for (auto& n : namespaces) g.identity += n + ",";
-        g.identity += "|" + std::to_string(max_skew) + "|" + g.taint_policy + "|" + g.affinity_policy + "|" + fview + "|" + sel.canon();
-        // ForEachDomain — topologydomaingroup.go:61-72
-        const uint64_t ptol = tol_mask(pod.tolerations);
-        auto dgi = dg.find(key);
-        if (dgi != dg.end()) for (auto& kv : dgi->second) {
-          bool ok = g.taint_policy == "Ignore";
-          if (!ok) for (uint64_t taints : kv.second) if (!(taints & ~ptol)) { ok = true; break; }
-          if (ok) g.domains.insert(kv.first);
-        }
-        g.universe = g.domains;
-        return g;
-      };
-      // countDomains — topology.go:361-459. A resident cluster asks this of 100k nodes and 2M bound pods for every group (and once
-      // per disruption pass), so the per-node facts are worked out once and the counting itself runs on integers: the node's domain
-      // under a key as an id (per KEY), whether the node passes a group's node filter (per distinct FILTER), whether it has a Node.
-      struct KeyDomains { std::vector<int32_t> label_val, pod_val; std::vector<std::string> names; };   // pod_val: hostname falls back to the node's name (:438-442)
-      std::map<std::string, KeyDomains> key_domains;
-      auto domains_of_key = [&](const std::string& key) -> KeyDomains& {
-        auto f = key_domains.find(key);
-        if (f != key_domains.end()) return f->second;
-        KeyDomains& kd2 = key_domains[key];
-        kd2.label_val.assign(n_nodes, -1); kd2.pod_val.assign(n_nodes, -1);
-        std::unordered_map<std::string, int32_t> ids;
-        auto id_of = [&](const std::string& v) { auto r = ids.emplace(v, (int32_t)kd2.names.size()); if (r.second) kd2.names.push_back(v); return r.first->second; };
-        for (int e = 0; e < n_nodes; ++e) {
-          auto it = node_labels[e].find(key);
-          if (it != node_labels[e].end()) kd2.label_val[e] = kd2.pod_val[e] = id_of(it->second);
-          else if (key == kHostname) kd2.pod_val[e] = id_of(nodes[e].name);
-        }
-        return kd2;
-      };
-      std::vector<char> node_has_node(n_nodes, 1);
-      for (int e = 0; e < n_nodes; ++e) node_has_node[e] = nodes[e].v->at("hasNode").boolean_or(true) ? 1 : 0;
-      std::map<std::string, std::vector<char>> filter_verdicts;   // by what a node filter consists of
-      auto nodes_passing = [&](const HGroup& g) -> const std::vector<char>& {
-        std::string sig = g.taint_policy + "|" + g.affinity_policy + "|" + std::to_string(g.ftol) + "|";
-        for (auto& r : g.freqs) { for (auto& e : r) { sig += e.key + " " + e.op + " ["; for (auto& v : e.values) sig += v + ","; sig += "];"; } sig += "/"; }
-        auto f = filter_verdicts.find(sig);
-        if (f != filter_verdicts.end()) return f->second;
-        std::vector<char>& ok = filter_verdicts[sig];
-        ok.assign(n_nodes, 1);
-        if (g.taint_policy == "Honor" || (g.affinity_policy == "Honor" && !g.freqs.empty())) {
-          std::vector<ks::ReqBuf> enc_f;   // the filter's requirement sets, encoded once
-          for (auto& r : g.freqs) { ks::ReqBuf b; Flattener::clear(b); for (auto& e : r) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); } enc_f.push_back(b); }
-          for (int e = 0; e < n_nodes; ++e) {
-            bool pass = !(g.taint_policy == "Honor" && (node_taints[e] & ~g.ftol));
-            if (pass && g.affinity_policy == "Honor" && !enc_f.empty()) {
-              pass = false;
-              for (auto& b : enc_f) if (ks::reqs_compatible(fl.kd, ks::reqbuf_ref_with_minv(node_label_reqs[e]), ks::reqbuf_ref_with_minv(b), false) == ks::COMPAT_OK) { pass = true; break; }
-            }
-            ok[e] = pass ? 1 : 0;
-          }
-        }
-        return ok;
-      };
-      auto count_domains = [&](HGroup& g) {
-        KeyDomains& kd2 = domains_of_key(g.key);
-        const std::vector<char>& node_ok = nodes_passing(g);
-        std::vector<int32_t> regs(kd2.names.size(), 0), cnt(kd2.names.size(), 0);
-        for (int e = 0; e < n_nodes; ++e) if (node_has_node[e] && node_ok[e] && kd2.label_val[e] >= 0) regs[kd2.label_val[e]]++;
-        if (resident) {
-          // the bound pod rows, spec by spec (a 2M-pod cluster is a few hundred specs)
-          for (size_t si = 0; si < specs.size(); ++si) {
-            if (spec_bound_nodes[si].empty() || !g.namespaces.count(specs[si].ns) || (!g.sel.nil && !g.sel.matches(specs[si].labels))) continue;
-            if (specs[si].phase == "Failed" || specs[si].phase == "Succeeded") continue;
-            for (int32_t e : spec_bound_nodes[si]) { const int32_t v = kd2.pod_val[e]; if (v >= 0 && node_ok[e]) cnt[v]++; }
-          }
-        }
-        for (size_t v = 0; v < regs.size(); ++v) {
-          if (regs[v]) { g.domains.insert(kd2.names[v]); g.node_regs[kd2.names[v]] += regs[v]; }
-          if (cnt[v]) { g.counts[kd2.names[v]] += cnt[v]; g.domains.insert(kd2.names[v]); }
-        }
-        for (auto& cp : cluster_pods) {
-          if (!g.namespaces.count(cp.ns)) continue;
-          if (!g.sel.nil && !g.sel.matches(cp.labels)) continue;
-          if (cp.node_name.empty() || cp.phase == "Failed" || cp.phase == "Succeeded") continue;
-          if (excluded.count(cp.uid)) continue;
-          auto nf = node_by_name.find(cp.node_name);
-          if (nf == node_by_name.end()) continue;
-          const int e = nf->second;
-          std::string dom;
-          auto it = node_labels[e].find(g.key);
-          if (it != node_labels[e].end()) dom = it->second;
-          else if (g.key == kHostname) dom = nodes[e].name;
-          else continue;
-          if (!filter_matches(g, node_taints[e], node_label_reqs[e])) continue;
-          g.counts[dom]++; g.domains.insert(dom);
-        }
-      };
-      auto namespace_list = [](const std::string& ns, const AffTerm& term) {
-        return (term.namespaces.empty() && !term.resolved) ? std::set<std::string>{ns} : std::set<std::string>(term.namespaces.begin(), term.namespaces.end());
-      };
-      // inverse anti-affinity groups — topology.go:310-355
-      std::vector<HGroup> inverse;
-      auto inverse_for = [&](const PodSpec& pod, int node) {
-        std::vector<int> owned;
-        for (auto& term : pod.anti_required) {
-          HGroup g = make_group(2, term.key, pod, namespace_list(pod.ns, term), term.sel, INT32_MAX, -1, "", "");
-          int id = -1;
-          for (size_t i = 0; i < inverse.size(); ++i) if (inverse[i].identity == g.identity) { id = (int)i; break; }
-          if (id < 0) { g.inverse = true; g.initial = true; inverse.push_back(g); id = (int)inverse.size() - 1; }
-          if (node >= 0) { auto it = node_labels[node].find(inverse[id].key); if (it != node_labels[node].end()) { inverse[id].counts[it->second]++; inverse[id].domains.insert(it->second); } }
-          owned.push_back(id);
-        }
-        return owned;
-      };
-      for (auto& cp : cluster_pods) {
-        if (!(cp.has_pod_anti && !cp.anti_required.empty())) continue;
-        if (excluded.count(cp.uid)) continue;
-        auto nf = node_by_name.find(cp.node_name);
-        if (nf == node_by_name.end()) continue;
-        inverse_for(cp, nf->second);
-      }
-      if (resident) for (size_t si = 0; si < specs.size(); ++si) {
-        if (spec_bound_nodes[si].empty() || !(specs[si].has_pod_anti && !specs[si].anti_required.empty())) continue;
-        const std::vector<int> ids = inverse_for(specs[si], -1);
-        for (int id : ids) for (int32_t e : spec_bound_nodes[si]) { auto it = node_labels[e].find(inverse[id].key); if (it != node_labels[e].end()) { inverse[id].counts[it->second]++; inverse[id].domains.insert(it->second); } }
-      }
-      std::vector<std::vector<std::vector<int>>> variant_groups(specs.size());
-      std::map<std::string, int> group_by_identity;
-      for (int pass = 0; pass < 2; ++pass) {   // pass 0: NewTopology sees every pod as submitted; pass 1: groups that only relaxed variants own
-        for (size_t si = 0; si < specs.size(); ++si) {
-          if (pass == 0) {
-            variant_groups[si].resize(ladders[si].size());
-            const PodSpec& p0 = ladders[si][0].pod;
-            const bool any_anti = p0.has_pod_anti && (!p0.anti_required.empty() || !p0.anti_preferred.empty());
-            const bool req_anti = any_anti && !p0.anti_required.empty();
-            if ((ignore_prefs && req_anti) || (!ignore_prefs && any_anti)) spec_inverse_owned[si] = inverse_for(p0, -1);
-          }
-          for (size_t vi = pass == 0 ? 0 : 1; vi < (pass == 0 ? 1 : ladders[si].size()); ++vi) {
-            const PodSpec& p = ladders[si][vi].pod;
-            std::vector<HGroup> tgs;
-            for (auto& t : p.tscs) {   // newForTopologies — topology.go:461-495
-              if (ignore_prefs && t.when != "DoNotSchedule") continue;
-              tgs.push_back(make_group(0, t.key, p, {p.ns}, t.sel, t.max_skew, t.min_domains, t.taint_policy, t.affinity_policy));
-            }
-            if (p.has_pod_affinity) {  // newForAffinities — topology.go:498-538
-              for (auto& t : p.aff_required) tgs.push_back(make_group(1, t.key, p, namespace_list(p.ns, t), t.sel, INT32_MAX, -1, "", ""));
-              if (!ignore_prefs) for (auto& t : p.aff_preferred) tgs.push_back(make_group(1, t.second.key, p, namespace_list(p.ns, t.second), t.second.sel, INT32_MAX, -1, "", ""));
-            }
-            if (p.has_pod_anti) {
-              for (auto& t : p.anti_required) tgs.push_back(make_group(2, t.key, p, namespace_list(p.ns, t), t.sel, INT32_MAX, -1, "", ""));
-              if (!ignore_prefs) for (auto& t : p.anti_preferred) tgs.push_back(make_group(2, t.second.key, p, namespace_list(p.ns, t.second), t.second.sel, INT32_MAX, -1, "", ""));
-            }
-            for (auto& tg : tgs) {
-              auto found = group_by_identity.find(tg.identity);
-              int id = found == group_by_identity.end() ? -1 : found->second;
-              if (id < 0) {
-                count_domains(tg);
-                tg.initial = pass == 0;
-                groups.push_back(tg);
-                id = (int)groups.size() - 1;
-                group_by_identity[tg.identity] = id;
-              } else if (!groups[id].initial) {
-                // a group that first appears when some pod relaxes is created by whichever pod relaxes first, and every
-                // later owner joins that one (Topology.Update looks the group up by hash, topology.go:162-194). Creators
-                // that would build different contents under one hash become members of an alias class; the solver keeps
-                // the member that is created first
-                count_domains(tg);
-                const std::string want = tg.content();
-                int match = -1;
-                for (int m : alias_members[tg.identity]) if (groups[m].content() == want) { match = m; break; }
-                if (match < 0 && groups[id].content() == want) match = id;
-                if (match < 0) {
-                  auto& members = alias_members[tg.identity];
-                  if (members.empty()) { members.push_back(id); groups[id].alias = n_alias_classes++; }
-                  tg.initial = false; tg.alias = groups[id].alias;
-                  groups.push_back(tg);
-                  match = (int)groups.size() - 1;
-                  members.push_back(match);
-                }
-                id = match;
-              }
-              variant_groups[si][vi].push_back(id);
-            }
-          }
-        }
-      }
-      if (groups.size() + inverse.size() > KSOLVE_MAX_TOPO_GROUPS) throw Unsupported("more than 1024 topology groups");
-      const size_t n_regular = groups.size();
-      for (auto& g : inverse) groups.push_back(g);
+    }
+    return ok;
+  }
+  void count_domains(HGroup& g) {
+    KeyDomains& kd2 = domains_of_key(g.key);
+    const std::vector<char>& node_ok = nodes_passing(g);
+    std::vector<int32_t> regs(kd2.names.size(), 0), cnt(kd2.names.size(), 0);
+    for (int e = 0; e < n_nodes; ++e) if (node_has_node[e] && node_ok[e] && kd2.label_val[e] >= 0) regs[kd2.label_val[e]]++;
+    if (resident) {
+      // the bound pod rows, spec by spec (a 2M-pod cluster is a few hundred specs)
       for (size_t si = 0; si < specs.size(); ++si) {
-        variant_owned[si].resize(ladders[si].size());
-        for (size_t vi = 0; vi < ladders[si].size(); ++vi) {
-          variant_owned[si][vi] = variant_groups[si][vi];
-          for (int id : spec_inverse_owned[si]) variant_owned[si][vi].push_back((int)n_regular + id);
-        }
+        if (spec_bound_nodes[si].empty() || !g.namespaces.count(specs[si].ns) || (!g.sel.nil && !g.sel.matches(specs[si].labels))) continue;
+        if (specs[si].phase == "Failed" || specs[si].phase == "Succeeded") continue;
+        for (int32_t e : spec_bound_nodes[si]) { const int32_t v = kd2.pod_val[e]; if (v >= 0 && node_ok[e]) cnt[v]++; }
       }
     }
-    const int G = (int)groups.size();
-    std::vector<uint8_t> tg_type(G), tg_inverse(G), tg_initial(G), tg_fa(G), tg_ft(G);
-    std::vector<int32_t> tg_key(G), tg_skew(G), tg_mind(G), tg_alias(G, -1);
-    std::vector<uint32_t> tg_ffirst(G + 1, 0);
-    std::vector<uint64_t> tg_ftol(G), tg_domains;
-    std::vector<int32_t> tg_counts, tg_node_counts, tg_regs;
-    std::vector<uint64_t> tg_universe;
-    std::vector<uint16_t> value_rank((size_t)rw * 64, 0);
-    std::vector<int32_t> node_host_value(std::max(1, n_nodes), -1);
-    std::vector<uint64_t> pod_topo_owned, pod_topo_selected;
-    ReqTableBuilder tg_freqs;
-    uint32_t dom_words = 1;
-    if (G) {
-      for (auto& g : groups) if (g.key != kHostname) { int k = D.key_index.at(g.key); dom_words = std::max(dom_words, fl.key_word_off[k + 1] - fl.key_word_off[k]); }
-      tg_domains.assign((size_t)G * dom_words, 0); tg_counts.assign((size_t)G * dom_words * 64, 0); tg_node_counts.assign((size_t)G * std::max(1, n_nodes), 0);
-      if (resident) { tg_universe.assign((size_t)G * dom_words, 0); tg_regs.assign((size_t)G * dom_words * 64, 0); }
-      int n_f = 0;
-      for (auto& g : groups) n_f += (int)g.freqs.size();
-      tg_freqs.init(std::max(1, n_f), rw, nk);
-      std::unordered_map<std::string, int> node_of_hostname;   // a hostname group of a 100k-node cluster counts pods on most of them
-      int fi = 0;
-      for (int gi = 0; gi < G; ++gi) {
-        const HGroup& g = groups[gi];
-        tg_type[gi] = (uint8_t)g.type; tg_inverse[gi] = g.inverse; tg_initial[gi] = g.initial;
-        tg_skew[gi] = g.max_skew; tg_mind[gi] = g.min_domains; tg_alias[gi] = g.alias;
-        tg_fa[gi] = g.affinity_policy == "Honor"; tg_ft[gi] = g.taint_policy == "Honor"; tg_ftol[gi] = g.ftol;
-        tg_ffirst[gi] = (uint32_t)fi;
-        for (auto& r : g.freqs) {
-          ks::ReqBuf b;
-          Flattener::clear(b);
-          for (auto& e : r) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
-          tg_freqs.put(fi++, b);
+    for (size_t v = 0; v < regs.size(); ++v) {
+      if (regs[v]) { g.domains.insert(kd2.names[v]); g.node_regs[kd2.names[v]] += regs[v]; }
+      if (cnt[v]) { g.counts[kd2.names[v]] += cnt[v]; g.domains.insert(kd2.names[v]); }
+    }
+    for (auto& cp : cluster_pods) {
+      if (!g.namespaces.count(cp.ns)) continue;
+      if (!g.sel.nil && !g.sel.matches(cp.labels)) continue;
+      if (cp.node_name.empty() || cp.phase == "Failed" || cp.phase == "Succeeded") continue;
+      if (excluded.count(cp.uid)) continue;
+      auto nf = node_by_name.find(cp.node_name);
+      if (nf == node_by_name.end()) continue;
+      const int e = nf->second;
+      std::string dom;
+      auto it = node_labels[e].find(g.key);
+      if (it != node_labels[e].end()) dom = it->second;
+      else if (g.key == kHostname) dom = nodes[e].name;
+      else continue;
+      if (!filter_matches(g, node_taints[e], node_label_reqs[e])) continue;
+      g.counts[dom]++; g.domains.insert(dom);
+    }
+  }
+  // inverse anti-affinity groups — topology.go:310-355
+  std::vector<int> inverse_for(const PodSpec& pod, int node) {
+    std::vector<int> owned;
+    for (auto& term : pod.anti_required) {
+      HGroup g = make_group(2, term.key, pod, namespace_list(pod.ns, term), term.sel, INT32_MAX, -1, "", "");
+      int id = -1;
+      for (size_t i = 0; i < inverse.size(); ++i) if (inverse[i].identity == g.identity) { id = (int)i; break; }
+      if (id < 0) { g.inverse = true; g.initial = true; inverse.push_back(g); id = (int)inverse.size() - 1; }
+      if (node >= 0) { auto it = node_labels[node].find(inverse[id].key); if (it != node_labels[node].end()) { inverse[id].counts[it->second]++; inverse[id].domains.insert(it->second); } }
+      owned.push_back(id);
+    }
+    return owned;
+  }
+  void inverse_groups_of_bound_pods() {
+    for (auto& cp : cluster_pods) {
+      if (!(cp.has_pod_anti && !cp.anti_required.empty())) continue;
+      if (excluded.count(cp.uid)) continue;
+      auto nf = node_by_name.find(cp.node_name);
+      if (nf == node_by_name.end()) continue;
+      inverse_for(cp, nf->second);
+    }
+    if (resident) for (size_t si = 0; si < specs.size(); ++si) {
+      if (spec_bound_nodes[si].empty() || !(specs[si].has_pod_anti && !specs[si].anti_required.empty())) continue;
+      const std::vector<int> ids = inverse_for(specs[si], -1);
+      for (int id : ids) for (int32_t e : spec_bound_nodes[si]) { auto it = node_labels[e].find(inverse[id].key); if (it != node_labels[e].end()) { inverse[id].counts[it->second]++; inverse[id].domains.insert(it->second); } }
+    }
+  }
+  // the groups every pod variant owns: identity by hash, alias classes for same-hash groups that relaxation creates with different contents
+  void discover_groups() {
+    std::map<std::string, std::vector<int>> alias_members;
+    std::vector<std::vector<std::vector<int>>> variant_groups(specs.size());
+    std::map<std::string, int> group_by_identity;
+    for (int pass = 0; pass < 2; ++pass) {   // pass 0: NewTopology sees every pod as submitted; pass 1: groups that only relaxed variants own
+      for (size_t si = 0; si < specs.size(); ++si) {
+        if (pass == 0) {
+          variant_groups[si].resize(ladders[si].size());
+          const PodSpec& p0 = ladders[si][0].pod;
+          const bool any_anti = p0.has_pod_anti && (!p0.anti_required.empty() || !p0.anti_preferred.empty());
+          const bool req_anti = any_anti && !p0.anti_required.empty();
+          if ((ignore_prefs && req_anti) || (!ignore_prefs && any_anti)) spec_inverse_owned[si] = inverse_for(p0, -1);
         }
-        if (g.key == kHostname) {
-          tg_key[gi] = -1;
-          if (node_of_hostname.empty()) for (int e = n_nodes - 1; e >= 0; --e) node_of_hostname[nodes[e].hostname] = e;   // the first node of a hostname wins, as the linear search it replaces did
-          for (auto& kv : g.counts) {
-            auto f = node_of_hostname.find(kv.first);
-            if (f == node_of_hostname.end()) throw Unsupported("pods counted on a hostname that is not a state node");
-            tg_node_counts[(size_t)gi * n_nodes + f->second] += kv.second;
+        for (size_t vi = pass == 0 ? 0 : 1; vi < (pass == 0 ? 1 : ladders[si].size()); ++vi) {
+          const PodSpec& p = ladders[si][vi].pod;
+          std::vector<HGroup> tgs;
+          for (auto& t : p.tscs) {   // newForTopologies — topology.go:461-495
+            if (ignore_prefs && t.when != "DoNotSchedule") continue;
+            tgs.push_back(make_group(0, t.key, p, {p.ns}, t.sel, t.max_skew, t.min_domains, t.taint_policy, t.affinity_policy));
           }
-          continue;
-        }
-        const int k = D.key_index.at(g.key);
-        tg_key[gi] = k;
-        for (auto& dom : g.domains) {
-          auto vi = D.value_index[k].find(dom);
-          if (vi == D.value_index[k].end()) throw std::runtime_error("topology domain " + dom + " missing from the dictionary");
-          tg_domains[(size_t)gi * dom_words + vi->second / 64] |= 1ull << (vi->second % 64);
-        }
-        for (auto& kv : g.counts) tg_counts[(size_t)gi * dom_words * 64 + D.value_index[k].at(kv.first)] = kv.second;
-        if (resident) {
-          for (auto& dom : g.universe) { const int v = D.value_index[k].at(dom); tg_universe[(size_t)gi * dom_words + v / 64] |= 1ull << (v % 64); }
-          for (auto& kv : g.node_regs) tg_regs[(size_t)gi * dom_words * 64 + D.value_index[k].at(kv.first)] = kv.second;
+          if (p.has_pod_affinity) {  // newForAffinities — topology.go:498-538
+            for (auto& t : p.aff_required) tgs.push_back(make_group(1, t.key, p, namespace_list(p.ns, t), t.sel, INT32_MAX, -1, "", ""));
+            if (!ignore_prefs) for (auto& t : p.aff_preferred) tgs.push_back(make_group(1, t.second.key, p, namespace_list(p.ns, t.second), t.second.sel, INT32_MAX, -1, "", ""));
+          }
+          if (p.has_pod_anti) {
+            for (auto& t : p.anti_required) tgs.push_back(make_group(2, t.key, p, namespace_list(p.ns, t), t.sel, INT32_MAX, -1, "", ""));
+            if (!ignore_prefs) for (auto& t : p.anti_preferred) tgs.push_back(make_group(2, t.second.key, p, namespace_list(p.ns, t.second), t.second.sel, INT32_MAX, -1, "", ""));
+          }
+          for (auto& tg : tgs) {
+            auto found = group_by_identity.find(tg.identity);
+            int id = found == group_by_identity.end() ? -1 : found->second;
+            if (id < 0) {
+              count_domains(tg);
+              tg.initial = pass == 0;
+              groups.push_back(tg);
+              id = (int)groups.size() - 1;
+              group_by_identity[tg.identity] = id;
+            } else if (!groups[id].initial) {
+              // a group that first appears when some pod relaxes is created by whichever pod relaxes first, and every
+              // later owner joins that one (Topology.Update looks the group up by hash, topology.go:162-194). Creators
+              // that would build different contents under one hash become members of an alias class; the solver keeps
+              // the member that is created first
+              count_domains(tg);
+              const std::string want = tg.content();
+              int match = -1;
+              for (int m : alias_members[tg.identity]) if (groups[m].content() == want) { match = m; break; }
+              if (match < 0 && groups[id].content() == want) match = id;
+              if (match < 0) {
+                auto& members = alias_members[tg.identity];
+                if (members.empty()) { members.push_back(id); groups[id].alias = n_alias_classes++; }
+                tg.initial = false; tg.alias = groups[id].alias;
+                groups.push_back(tg);
+                match = (int)groups.size() - 1;
+                members.push_back(match);
+              }
+              id = match;
+            }
+            variant_groups[si][vi].push_back(id);
+          }
         }
       }
-      tg_ffirst[G] = (uint32_t)fi;
-      for (int k = 0; k < nk; ++k) {
-        std::vector<int> order(D.values[k].size());
-        for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return D.values[k][a] < D.values[k][b]; });
-        if (order.size() > 65535) throw Unsupported("more than 65535 values under one label key");
-        for (size_t r = 0; r < order.size(); ++r) value_rank[(size_t)fl.key_word_off[k] * 64 + order[r]] = (uint16_t)r;
-      }
-      if (fl.kd.key_hostname >= 0) for (int e = 0; e < n_nodes; ++e) {
-        auto vi = D.value_index[fl.kd.key_hostname].find(nodes[e].hostname);
-        if (vi != D.value_index[fl.kd.key_hostname].end()) node_host_value[e] = vi->second;
-      }
-      const int tw = (G + 63) / 64;
-      pod_topo_owned.assign((size_t)n_rows * tw, 0); pod_topo_selected.assign((size_t)n_rows * tw, 0);
-      std::vector<std::vector<uint64_t>> spec_selected(specs.size(), std::vector<uint64_t>(tw, 0));
-      for (size_t si = 0; si < specs.size(); ++si)
-        for (int gi = 0; gi < G; ++gi) if (groups[gi].namespaces.count(specs[si].ns) && groups[gi].sel.matches(specs[si].labels)) spec_selected[si][gi / 64] |= 1ull << (gi % 64);
-      auto put_masks = [&](int row, size_t si, size_t vi) {
-        for (int id : variant_owned[si][vi]) pod_topo_owned[(size_t)row * tw + id / 64] |= 1ull << (id % 64);
-        for (int w = 0; w < tw; ++w) pod_topo_selected[(size_t)row * tw + w] = spec_selected[si][w];
-      };
-      for (int p = 0; p < n_pods; ++p) put_masks(p, (size_t)pod_spec[p], 0);
-      for (size_t si = 0; si < specs.size(); ++si) if (spec_first_extra[si] >= 0)
-        for (size_t vi = 1; vi < ladders[si].size(); ++vi) put_masks(spec_first_extra[si] + (int)vi - 1, si, vi);
     }
+    if (groups.size() + inverse.size() > KSOLVE_MAX_TOPO_GROUPS) throw Unsupported("more than 1024 topology groups");
+    const size_t n_regular = groups.size();
+    for (auto& g : inverse) groups.push_back(g);
+    for (size_t si = 0; si < specs.size(); ++si) {
+      variant_owned[si].resize(ladders[si].size());
+      for (size_t vi = 0; vi < ladders[si].size(); ++vi) {
+        variant_owned[si][vi] = variant_groups[si][vi];
+        for (int id : spec_inverse_owned[si]) variant_owned[si][vi].push_back((int)n_regular + id);
+      }
+    }
+  }
+  // the flat tg_* arrays
+  void flatten_topology_groups() {
+    G = (int)groups.size();
+    tg_type.assign(G, 0); tg_inverse.assign(G, 0); tg_initial.assign(G, 0); tg_fa.assign(G, 0); tg_ft.assign(G, 0);
+    tg_key.assign(G, 0); tg_skew.assign(G, 0); tg_mind.assign(G, 0); tg_alias.assign(G, -1);
+    tg_ffirst.assign(G + 1, 0);
+    tg_ftol.assign(G, 0);
+    value_rank.assign((size_t)rw * 64, 0);
+    node_host_value.assign(std::max(1, n_nodes), -1);
+    if (!G) return;
+    for (auto& g : groups) if (g.key != kHostname) { int k = D.key_index.at(g.key); dom_words = std::max(dom_words, fl.key_word_off[k + 1] - fl.key_word_off[k]); }
+    tg_domains.assign((size_t)G * dom_words, 0); tg_counts.assign((size_t)G * dom_words * 64, 0); tg_node_counts.assign((size_t)G * std::max(1, n_nodes), 0);
+    if (resident) { tg_universe.assign((size_t)G * dom_words, 0); tg_regs.assign((size_t)G * dom_words * 64, 0); }
+    int n_f = 0;
+    for (auto& g : groups) n_f += (int)g.freqs.size();
+    tg_freqs.init(std::max(1, n_f), rw, nk);
+    std::unordered_map<std::string, int> node_of_hostname;   // a hostname group of a 100k-node cluster counts pods on most of them
+    int fi = 0;
+    for (int gi = 0; gi < G; ++gi) {
+      const HGroup& g = groups[gi];
+      tg_type[gi] = (uint8_t)g.type; tg_inverse[gi] = g.inverse; tg_initial[gi] = g.initial;
+      tg_skew[gi] = g.max_skew; tg_mind[gi] = g.min_domains; tg_alias[gi] = g.alias;
+      tg_fa[gi] = g.affinity_policy == "Honor"; tg_ft[gi] = g.taint_policy == "Honor"; tg_ftol[gi] = g.ftol;
+      tg_ffirst[gi] = (uint32_t)fi;
+      for (auto& r : g.freqs) {
+        ks::ReqBuf b;
+        Flattener::clear(b);
+        for (auto& e : r) { ks::ReqBuf one; fl.encode(e, one); ks::reqbuf_add(fl.kd, b, ks::reqbuf_ref_with_minv(one)); }
+        tg_freqs.put(fi++, b);
+      }
+      if (g.key == kHostname) {
+        tg_key[gi] = -1;
+        if (node_of_hostname.empty()) for (int e = n_nodes - 1; e >= 0; --e) node_of_hostname[nodes[e].hostname] = e;   // the first node of a hostname wins, as the linear search it replaces did
+        for (auto& kv : g.counts) {
+          auto f = node_of_hostname.find(kv.first);
+          if (f == node_of_hostname.end()) throw Unsupported("pods counted on a hostname that is not a state node");
+          tg_node_counts[(size_t)gi * n_nodes + f->second] += kv.second;
+        }
+        continue;
+      }
+      const int k = D.key_index.at(g.key);
+      tg_key[gi] = k;
+      for (auto& dom : g.domains) {
+        auto vi = D.value_index[k].find(dom);
+        if (vi == D.value_index[k].end()) throw std::runtime_error("topology domain " + dom + " missing from the dictionary");
+        tg_domains[(size_t)gi * dom_words + vi->second / 64] |= 1ull << (vi->second % 64);
+      }
+      for (auto& kv : g.counts) tg_counts[(size_t)gi * dom_words * 64 + D.value_index[k].at(kv.first)] = kv.second;
+      if (resident) {
+        for (auto& dom : g.universe) { const int v = D.value_index[k].at(dom); tg_universe[(size_t)gi * dom_words + v / 64] |= 1ull << (v % 64); }
+        for (auto& kv : g.node_regs) tg_regs[(size_t)gi * dom_words * 64 + D.value_index[k].at(kv.first)] = kv.second;
+      }
+    }
+    tg_ffirst[G] = (uint32_t)fi;
+    for (int k = 0; k < nk; ++k) {
+      std::vector<int> order(D.values[k].size());
+      for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+      std::sort(order.begin(), order.end(), [&](int a, int b) { return D.values[k][a] < D.values[k][b]; });
+      if (order.size() > 65535) throw Unsupported("more than 65535 values under one label key");
+      for (size_t r = 0; r < order.size(); ++r) value_rank[(size_t)fl.key_word_off[k] * 64 + order[r]] = (uint16_t)r;
+    }
+    if (fl.kd.key_hostname >= 0) for (int e = 0; e < n_nodes; ++e) {
+      auto vi = D.value_index[fl.kd.key_hostname].find(nodes[e].hostname);
+      if (vi != D.value_index[fl.kd.key_hostname].end()) node_host_value[e] = vi->second;
+    }
+  }
+  // which groups each pod row owns and is selected by
+  void flatten_pod_topology_masks() {
+    if (!G) return;
+    const int tw = (G + 63) / 64;
+    pod_topo_owned.assign((size_t)n_rows * tw, 0); pod_topo_selected.assign((size_t)n_rows * tw, 0);
+    std::vector<std::vector<uint64_t>> spec_selected(specs.size(), std::vector<uint64_t>(tw, 0));
+    for (size_t si = 0; si < specs.size(); ++si)
+      for (int gi = 0; gi < G; ++gi) if (groups[gi].namespaces.count(specs[si].ns) && groups[gi].sel.matches(specs[si].labels)) spec_selected[si][gi / 64] |= 1ull << (gi % 64);
+    auto put_masks = [&](int row, size_t si, size_t vi) {
+      for (int id : variant_owned[si][vi]) pod_topo_owned[(size_t)row * tw + id / 64] |= 1ull << (id % 64);
+      for (int w = 0; w < tw; ++w) pod_topo_selected[(size_t)row * tw + w] = spec_selected[si][w];
+    };
+    for (int p = 0; p < n_pods; ++p) put_masks(p, (size_t)pod_spec[p], 0);
+    for (size_t si = 0; si < specs.size(); ++si) if (spec_first_extra[si] >= 0)
+      for (size_t vi = 1; vi < ladders[si].size(); ++vi) put_masks(spec_first_extra[si] + (int)vi - 1, si, vi);
+  }
 
-    trace("describe");
-    // ---- describe & solve ----
+  // ---- describe & solve ----
+  void flag_pods_of_deleting_nodes() {
+    pod_from_deleting.assign(std::max(1, n_pods), 0);
+    std::set<std::string> deleting;
+    for (auto& nn : root.at("deletingNodeNames").items()) deleting.insert(nn.s());
+    if (!deleting.empty()) for (int p = 0; p < n_pods; ++p) if (deleting.count(specs[pod_spec[p]].node_name)) pod_from_deleting[p] = 1;
+  }
+  // the descriptor: raw pointers into this builder's members, good for as long as it lives and is not modified
+  ksolve_problem_desc describe() const {
     ksolve_problem_desc d{};
     d.abi_version = KSOLVE_ABI_VERSION;
     d.n_keys = (uint32_t)nk; d.key_word_off = fl.key_word_off.data(); d.well_known_mask = fl.kd.well_known_mask;
@@ -1957,8 +2098,6 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
     d.n_res = (uint32_t)n_res;
     d.n_its = (uint32_t)n_its; d.it_allocatable = it_alloc.data(); d.it_capacity = it_capv.data(); d.it_reqs = it_reqs.view();
     d.it_offering_avail = it_avail.data(); d.it_offering_price = it_price.data(); d.n_zones = (uint32_t)n_zones; d.n_captypes = (uint32_t)n_cts;
-    std::vector<int64_t> xg_alloc((size_t)n_res * xg_it.size());
-    for (size_t e = 0; e < xg_it.size(); ++e) for (int r = 0; r < n_res; ++r) xg_alloc[(size_t)r * xg_it.size() + e] = xg_alloc_rows[e][r];
     if (!xg_it.empty()) {
       if (xg_it.size() > KSOLVE_MAX_OVERRIDE_GROUPS) throw Unsupported("more than 4096 offering override groups");
       d.n_override_groups = (uint32_t)xg_it.size(); d.override_it = xg_it.data(); d.override_allocatable = xg_alloc.data();
@@ -1978,7 +2117,7 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       if (!dg_first.empty()) d.daemon_group_host_ports = dg_hp.data();
     }
     if (any_volume) {
-      d.n_volume_reqs = (uint32_t)vol_sets.size(); d.volume_reqs = vol_reqs.view();
+      d.n_volume_reqs = (uint32_t)vol_reqs.n; d.volume_reqs = vol_reqs.view();
       d.pod_volume_first = pod_vol_first.data(); d.pod_volume_count = pod_vol_count.data();
     }
     d.pod_creation = pod_creation.data(); d.pod_uid_hi = uid_hi.data(); d.pod_uid_lo = uid_lo.data(); d.pod_is_pending = pod_pending.data();
@@ -1986,12 +2125,6 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
     d.key_hostname = fl.kd.key_hostname;
     d.n_nodes = (uint32_t)n_nodes; d.node_reqs = node_reqs.view(); d.node_taints = node_taints.data(); d.node_remaining = node_remaining.data();
     d.node_initialized = node_init.data(); d.node_under_consolidate_after = node_uca.data();
-    std::vector<uint8_t> pod_from_deleting(std::max(1, n_pods), 0);
-    {
-      std::set<std::string> deleting;
-      for (auto& nn : root.at("deletingNodeNames").items()) deleting.insert(nn.s());
-      if (!deleting.empty()) for (int p = 0; p < n_pods; ++p) if (deleting.count(specs[pod_spec[p]].node_name)) pod_from_deleting[p] = 1;
-    }
     d.pod_from_deleting_node = pod_from_deleting.data();
     if (resident) d.pod_node = pod_node_sorted.data();
     if (!pv_drivers.empty()) {
@@ -2008,9 +2141,11 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
       t.filter_tolerates = tg_ftol.data(); t.value_rank = value_rank.data(); t.node_hostname_value = node_host_value.data();
       if (n_alias_classes) { t.alias_class = tg_alias.data(); t.n_alias_classes = (uint32_t)n_alias_classes; }
       if (resident) { t.domain_universe = tg_universe.data(); t.domain_node_regs = tg_regs.data(); }
-      S->n_topo_groups = G; S->n_alias_classes = n_alias_classes;
       d.pod_topo_owned = pod_topo_owned.data(); d.pod_topo_selected = pod_topo_selected.data();
     }
+    return d;
+  }
+  ksolve_options solver_options() const {
     ksolve_options ko{};
     ko.min_values_best_effort = opts.at("minValuesPolicy").s("Strict") == "BestEffort";
     ko.max_claims = (uint32_t)opts.at("maxClaims").i(0);
@@ -2021,48 +2156,84 @@ extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
     ko.reserved_capacity = opts.at("reservedCapacity").boolean_or(false) ? 1 : 0;
     ko.reserved_offering_strict = opts.at("reservedOfferingMode").s("Fallback") == "Strict" ? 1 : 0;
     { const std::string eng = opts.at("engine").s("auto"); ko.engine = eng == "general" ? 1u : eng == "cursor" ? 2u : eng == "cursor-wide" ? 3u : eng == "cursor-hbm" ? 4u : eng == "cursor-pair" ? 5u : eng == "spread" ? 6u : 0u; }
+    return ko;
+  }
 
+  // ---- session tables: what probes, sweeps and Results re-hydration read later is moved out; the builder is spent afterwards ----
+  void fill_session(Session& S) {
+    for (auto& p : pools) S.pool_names.push_back(p.name);
+    for (auto& n : nodes) { S.node_names.push_back(n.name); S.node_initialized.push_back(n.initialized ? 1 : 0); }
+    S.uid_text = std::move(uid_text); S.group_of_pod = std::move(group_of_pod); S.res_names = std::move(res_names); S.scale = std::move(scale);
+    for (int i = 0; i < n_its; ++i) S.it_names.push_back(its_json[i].at("name").s());
+    S.k_rid = k_rid;
+    S.n_pods = n_pods; S.n_rows = n_rows; S.n_its = n_its; S.n_res = n_res; S.it_words = it_words;
+    S.n_templates = n_templates; S.tmpl_lim = std::move(tmpl_lim); S.strict_shared = !strict_differs;
+    S.node_tmpl = std::move(node_tmpl); S.node_limit_cap = std::move(node_limit_cap);
+    S.n_topo_groups = G; S.n_alias_classes = n_alias_classes;
+    // what ksched_sweep needs: the node of every pod, its pending / deleting flags, offerings and requirement values per type
+    S.node_input_index = std::move(node_input_index);
+    S.pod_node = std::move(pod_node_sorted);
+    S.pod_pending_flag = std::move(pod_pending);
+    pod_from_deleting.resize(n_pods);
+    S.pod_deleting_flag = std::move(pod_from_deleting);
+    S.it_offerings.resize(n_its);
+    for (int i = 0; i < n_its; ++i) for (auto& o : it_offs[i]) S.it_offerings[i].push_back({o.zone, o.ct, o.rid, o.price, o.available});
+    std::map<std::string, int> it_by_name;
+    for (int i = 0; i < n_its; ++i) it_by_name.emplace(S.it_names[i], i);
+    S.node_it.assign(nodes.size(), -1); S.node_price.assign(nodes.size(), 0.0); S.node_spot.assign(nodes.size(), 0);
+    for (size_t e = 0; e < nodes.size(); ++e) {
+      const Value& nl = nodes[e].v->at("labels");
+      auto label = [&](const char* k) { return nl.has(k) ? nl.at(k).s() : std::string(); };
+      const std::string ctl = label(kCapacityType), zl = label(kZone);
+      S.node_spot[e] = ctl == "spot" ? 1 : 0;
+      auto f = it_by_name.find(label(kInstanceType));
+      if (f == it_by_name.end()) continue;
+      S.node_it[e] = f->second;
+      auto zi = D.value_index[k_zone].find(zl); auto ci = D.value_index[k_ct].find(ctl);
+      if (zi == D.value_index[k_zone].end() || ci == D.value_index[k_ct].end()) continue;
+      for (auto& o : it_offs[f->second]) if (o.zone == zi->second && o.ct == ci->second) { S.node_price[e] = o.price != o.price ? 0.0 : o.price; break; }
+    }
+    S.it_exprs = std::move(it_exprs);
+    S.fl = std::move(fl);   // last: D refers to it
+  }
+};
+
+// NewScheduler: parse + flatten the problem document and upload it through ksolve_create. Returns a session handle
+// (never null); ksched_error(session) is non-null when it failed.
+extern "C" void* ksched_open(const char* problem_json, const char* solver_lib) {
+  Session* S = new Session();
+  Api& api = S->api;
+  std::string err;
+  if (!api.load(solver_lib, err)) { S->error_kind = "load"; S->error = err; return S; }
+  PhaseTrace trace;
+  try {
+    S->root = kj::Parser(problem_json).parse();
+    ProblemBuilder b(S->root);
+    trace("instance types");       b.read_instance_types();
+    trace("node pools");           b.read_node_pools();
+    trace("pods");                 b.read_pods(); b.build_ladders();
+    trace("daemonset pods");       b.read_daemonset_pods();
+    trace("existing nodes");       b.read_existing_nodes();
+    trace("resources");            b.read_resources();
+    trace("dictionary complete");  b.finalize_dictionary();
+    b.flatten_instance_types(); b.flatten_reservations(); b.flatten_templates(); b.flatten_host_ports(); b.flatten_daemon_groups();
+    b.flatten_nodes(); b.encode_pod_variants(); b.flatten_volume_requirements(); b.flatten_volume_limits(); b.fill_pod_rows();
+    trace("topology groups");      b.read_cluster_pods();
+    if (b.any_topology) { b.domain_groups_from_pools(); b.node_topology_facts(); b.inverse_groups_of_bound_pods(); b.discover_groups(); }
+    b.flatten_topology_groups(); b.flatten_pod_topology_masks();
+    trace("describe");             b.flag_pods_of_deleting_nodes();
+    const ksolve_problem_desc d = b.describe();
+    const ksolve_options ko = b.solver_options();
     trace("ksolve_create");
-    ksolve_status st = api.create(&d, &ko, &handle);
+    ksolve_status st = api.create(&d, &ko, &S->handle);
     trace("session tables");
     if (st != KSOLVE_OK) {
-      S->error = handle ? api.last_error(handle) : "ksolve_create failed";
+      S->error = S->handle ? api.last_error(S->handle) : "ksolve_create failed";
       S->error_kind = st == KSOLVE_ERR_UNSUPPORTED ? "unsupported" : st == KSOLVE_ERR_NO_DEVICE ? "no_device" : "create";
-      if (handle) { api.destroy(handle); handle = nullptr; }
+      if (S->handle) { api.destroy(S->handle); S->handle = nullptr; }
       return S;
     }
-    for (auto& p : pools) S->pool_names.push_back(p.name);
-    for (auto& n : nodes) { S->node_names.push_back(n.name); S->node_initialized.push_back(n.initialized ? 1 : 0); }
-    S->uid_text = uid_text; S->group_of_pod = group_of_pod; S->res_names = res_names; S->scale = scale;
-    for (int i = 0; i < n_its; ++i) S->it_names.push_back(its_json[i].at("name").s());
-    S->k_rid = k_rid;
-    S->n_pods = n_pods; S->n_rows = n_rows; S->n_its = n_its; S->n_res = n_res; S->it_words = it_words;
-    S->n_templates = n_templates; S->tmpl_lim = tmpl_lim; S->strict_shared = !strict_differs;
-    // what ksched_sweep needs: the node of every pod, its pending / deleting flags, offerings and requirement values per type
-    {
-      S->node_input_index = node_input_index;
-      S->pod_node = pod_node_sorted;
-      S->pod_pending_flag.assign(pod_pending.begin(), pod_pending.end());
-      S->pod_deleting_flag.assign(pod_from_deleting.begin(), pod_from_deleting.begin() + n_pods);
-      S->it_offerings.resize(n_its);
-      for (int i = 0; i < n_its; ++i) for (auto& o : it_offs[i]) S->it_offerings[i].push_back({o.zone, o.ct, o.rid, o.price, o.available});
-      S->it_exprs = it_exprs;
-      std::map<std::string, int> it_by_name;
-      for (int i = 0; i < n_its; ++i) it_by_name.emplace(S->it_names[i], i);
-      S->node_it.assign(nodes.size(), -1); S->node_price.assign(nodes.size(), 0.0); S->node_spot.assign(nodes.size(), 0);
-      for (size_t e = 0; e < nodes.size(); ++e) {
-        const Value& nl = nodes[e].v->at("labels");
-        auto label = [&](const char* k) { return nl.has(k) ? nl.at(k).s() : std::string(); };
-        const std::string ctl = label(kCapacityType), zl = label(kZone);
-        S->node_spot[e] = ctl == "spot" ? 1 : 0;
-        auto f = it_by_name.find(label(kInstanceType));
-        if (f == it_by_name.end()) continue;
-        S->node_it[e] = f->second;
-        auto zi = D.value_index[k_zone].find(zl); auto ci = D.value_index[k_ct].find(ctl);
-        if (zi == D.value_index[k_zone].end() || ci == D.value_index[k_ct].end()) continue;
-        for (auto& o : it_offs[f->second]) if (o.zone == zi->second && o.ct == ci->second) { S->node_price[e] = o.price != o.price ? 0.0 : o.price; break; }
-      }
-    }
+    b.fill_session(*S);
     trace("done");
     return S;
   } catch (const Unsupported& e) {
