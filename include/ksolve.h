@@ -162,7 +162,9 @@ typedef struct {
   /* ---- daemonset overhead (scheduler.go:963-1043): the instance types of a template are partitioned into groups that
    *      share the same set of compatible daemonset pods; a type must fit requests + its group's overhead
    *      (nodeclaim.go:558-566) and FinalizeScheduling adds the smallest overhead to the claim's requests
-   *      (nodeclaim.go:353-377). NULL tmpl_daemon_first = no daemonsets. At most 64 groups per problem. ---- */
+   *      (nodeclaim.go:353-377). NULL tmpl_daemon_first = no daemonsets. At most 64 groups per problem. Every engine solves them:
+   *      the cursor and spread engines test a claim against allocatable - overhead of the type's group in the claim's template,
+   *      tabulated once per handle (ksolve_fast_eff_alloc). Pods with host ports beside DaemonSets stay on the general engine. ---- */
   const uint32_t* tmpl_daemon_first;     /* n_templates+1 : CSR into the group arrays */
   const uint64_t* daemon_group_its;      /* n_groups * it_words */
   const int64_t* daemon_group_overhead;  /* n_groups * n_res, incl. pods = number of daemon pods */
@@ -268,7 +270,8 @@ typedef struct {
   uint32_t reserved_offering_strict; /* DisableReservedCapacityFallback / ReservedOfferingModeStrict (scheduler.go:103, nodeclaim.go:339-348) */
   uint32_t engine;                 /* which pack engine may run. 0 = automatic: the cursor engine (csrc/fast_engine.h) for problems whose
                                     * requirement algebra is purely positive (In sets only, no topology / existing nodes / minValues /
-                                    * reservations / daemon overhead), the general engine otherwise or whenever the cursor engine stops;
+                                    * reservations / host ports; DaemonSet overhead is handled), the general engine otherwise or whenever
+                                    * the cursor engine stops;
                                     * 1 = general engine only; 2 = cursor engine only (KSOLVE_ERR_UNSUPPORTED instead of the fallback:
                                     * tests use it to prove which engine produced a result); 3 = cursor engine only, with the claims' state
                                     * in HBM from the start (the plan the library moves to by itself when the LDS plan runs out of

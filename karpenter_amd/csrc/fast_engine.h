@@ -1,11 +1,14 @@
 // fast_engine.h — the cursor engine: Scheduler.Solve() (scheduler.go:440-519) for provisioning batches whose
 // requirement algebra is purely positive (every operator In — nodeSelector / node-affinity In terms, NodePool In
-// requirements, instance types that label themselves with In sets), no topology, no existing nodes, no daemon overhead,
-// no minValues, no reservations: BASELINE configs[0], [1] and [3]. One wavefront per scheduling problem, like engine.h,
+// requirements, instance types that label themselves with In sets), no topology, no existing nodes, no minValues, no reservations,
+// no host ports: BASELINE configs[0], [1] and [3], with or without DaemonSet overhead. One wavefront per scheduling problem, like engine.h,
 // but built on three facts that hold for this shape and make a step O(1) instead of a scan over the claims:
 //
 //  1. A claim's InstanceTypeOptions are a pure function of its requirement set and its requests:
-//         its = F(template, requirements) ∩ { it : allocatable(it) >= requests }          (nodeclaim.go:541-638)
+//         its = F(template, requirements) ∩ { it : allocatable(it) - overhead_t(it) >= requests }   (nodeclaim.go:541-638)
+//     overhead_t(it) = the overhead of it's daemon-overhead group in the claim's template (scheduler.go:963-1043): a constant of
+//     (template, type), tabulated once per handle as eff_t = allocatable - overhead_t (ksolve_fast_eff_alloc); a requirement set
+//     carries its template, so "allocatable" below reads eff_t and nothing else changes,
 //     because both only ever narrow / grow (NodeClaim.Add, nodeclaim.go:247-263) and with positive sets
 //     Intersects (requirements.go:254-274) is monotone. So CanAdd (nodeclaim.go:124-242) needs no per-claim instance-type
 //     mask: "some type of F still fits" is a dominance test against the Pareto-maximal allocatable vectors of F, which are
@@ -458,13 +461,14 @@ struct FastCold {
     int count = 0;
     const int poff = n_pool;
     int32_t f0 = -1, f1 = -1, f2 = -1, f3 = -1;
+    const int64_t* eff = eff_alloc(P, t);   // allocatable less the template's daemon overhead (ksp.h): the vectors a claim of template t is tested against
     for (;;) {
       const uint64_t any = W::reduce_or(iw, [&](int w) { return (uint64_t)rem[w]; });
       if (!any) break;
       W::for_n(iw, [&](int w) { cand[w] = rem[w]; });
       int64_t v0 = 0x3FFFFFFF, v1 = 0x3FFFFFFF, v2 = 0x3FFFFFFF, v3 = 0x3FFFFFFF;
       for (int r = 0; r < nr; ++r) {
-        const int64_t* al = P.it_alloc + (size_t)r * n_its;
+        const int64_t* al = eff + (size_t)r * n_its;
         const int64_t mx = W::reduce_max_i64(iw * 64, [&](int it) { return (it < n_its && ((cand[it >> 6] >> (it & 63)) & 1)) ? al[it] : INT64_MIN; });
         if (r == 0) v0 = mx; else if (r == 1) v1 = mx; else if (r == 2) v2 = mx; else v3 = mx;
         for (int j = 0; j < iw; ++j) {
@@ -486,10 +490,10 @@ struct FastCold {
         const uint64_t dom = in ? W::ballot([&](int l) {
           const int it = j * 64 + l;
           if (it >= n_its || !((in >> l) & 1)) return false;
-          bool le = Pv.it_alloc[it] <= v0;
-          if (nr > 1) le = le && Pv.it_alloc[(size_t)n_its + it] <= v1;
-          if (nr > 2) le = le && Pv.it_alloc[(size_t)2 * n_its + it] <= v2;
-          if (nr > 3) le = le && Pv.it_alloc[(size_t)3 * n_its + it] <= v3;
+          bool le = eff[it] <= v0;
+          if (nr > 1) le = le && eff[(size_t)n_its + it] <= v1;
+          if (nr > 2) le = le && eff[(size_t)2 * n_its + it] <= v2;
+          if (nr > 3) le = le && eff[(size_t)3 * n_its + it] <= v3;
           return le;
         }) : 0ull;
         W::store(&rem[j], in & ~dom);
@@ -551,6 +555,11 @@ struct FastCold {
     W::sync();
     // every quantity in 31 bits
     if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = Pv.it_alloc[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return 7;
+    for (int t = 0; t < T; ++t) {   // ... the effective allocatable too (negative where a type cannot even hold its daemons)
+      if (!((P.tmpl_ov >> t) & 1u)) continue;
+      const int64_t* eff = eff_alloc(P, t);
+      if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = eff[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return 7;
+    }
     if (W::reduce_or(nr * nc, [&](int i) { const int64_t a = Pv.cls_requests[i]; return (uint64_t)((a >= (1ll << 30) || a < 0) ? 1 : 0); })) return 7;
     // templates: packed form, and NewScheduler's prefilter (scheduler.go:156-171) with positive sets
     KS_LDS FastMisc& Mm = *Mp;
@@ -932,15 +941,16 @@ struct FastCold {
       }
       W::sync();
       if (lm) {
-        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m) ∩ fits(size)
+        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m) ∩ fits(size + daemon overhead)
         int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+        const int64_t* eff = eff_alloc(P, t);
         const uint64_t* eits = F.ent_its + (size_t)eh * iw;
         const ProblemView& Pv = P;
         const int n_its = P.n_its;
         for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) {
           const int64_t mx = W::reduce_max_i64(n_its, [&](int it) {
             if (!((eits[it >> 6] >> (it & 63)) & 1)) return INT64_MIN;
-            for (int z = 0; z < nr; ++z) if (Pv.it_alloc[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
+            for (int z = 0; z < nr; ++z) if (eff[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
             return Pv.it_cap[(size_t)q * n_its + it];
           });
           W::store(&rem[q], rem[q] - mx);
@@ -2077,7 +2087,7 @@ KS_FN void fast_scatter_body(int i, const FastQueueArgs& a) {
 
 // ksolve_fast_records — one wavefront per claim: materialises the hot claim record the finalize kernel and the result
 // download read (ksp.h RecLayout) from the cursor engine's compact state: requirement masks = the template's with the
-// variable keys' fields, InstanceTypeOptions = F(requirement set) ∩ { allocatable >= requests }.
+// variable keys' fields, InstanceTypeOptions = F(requirement set) ∩ { allocatable - daemon overhead >= requests }.
 struct FastRecordArgs {
   ProblemView pv;
   Workspace ws;
@@ -2106,13 +2116,14 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   });
   const int iw = ly.iw, nr = ly.nr, n_its = P.n_its;
   const uint64_t* eits = a.fw.ent_its + (size_t)a.fw.c_ent[c] * iw;
+  const int64_t* eff = eff_alloc(P, t);
   for (int j = 0; j < iw; ++j) {
     const uint64_t in = eits[j];
     const uint64_t okm = in ? W::ballot([&](int l) {
       const int it = j * 64 + l;
       if (it >= n_its || !((in >> l) & 1)) return false;
       bool f = true;
-      for (int r = 0; r < nr; ++r) f = f && (int64_t)st.req[r] <= P.it_alloc[(size_t)r * n_its + it];
+      for (int r = 0; r < nr; ++r) f = f && (int64_t)st.req[r] <= eff[(size_t)r * n_its + it];
       return f;
     }) : 0ull;
     W::store(&rec[ly.c_its() + j], okm);

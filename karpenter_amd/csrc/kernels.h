@@ -81,6 +81,34 @@ KS_FN void it_index_body(int it, const ItIndexArgs& a) {
   }
 }
 
+// ksolve_fast_eff_alloc — the fast engines' effective allocatable: eff[t][r][it] = allocatable[r][it] - overhead[g_t(it)][r], g_t(it)
+// the daemon-overhead group of type `it` in template t (scheduler.go:963-1043; nodeclaim.go:558-566: a type stays on a claim iff
+// requests + its group's overhead <= allocatable). One thread per (template, instance type); templates without a non-zero
+// overhead are skipped (their claims read it_alloc itself). A template with ONE group applies it to every type, as the general
+// engine does (engine.h filter_instance_types); a type of a template with several groups that is in none of them never fits.
+struct EffAllocArgs {
+  int n_templates, n_its, it_words, n_res;
+  uint32_t tmpl_ov;            // templates to write
+  const int64_t* it_alloc;     // [n_res][n_its]
+  const int* dg_first;         // [n_templates+1]
+  const int64_t* dg_ov;        // [n_dg][n_res]
+  const uint64_t* dg_its;      // [n_dg][it_words]
+  int64_t* it_eff;             // [n_templates][n_res][n_its]
+};
+constexpr int64_t kEffNever = -((1ll << 30) - 1);   // below every request, inside the cursor engine's 31-bit range
+KS_FN void eff_alloc_body(int t, int it, const EffAllocArgs& a) {
+  if (t >= a.n_templates || it >= a.n_its || !((a.tmpl_ov >> t) & 1u)) return;
+  const int g0 = a.dg_first[t], g1 = a.dg_first[t + 1];
+  int g = g0;
+  if (g1 - g0 > 1) {
+    g = -1;
+    for (int x = g0; x < g1 && g < 0; ++x) if ((a.dg_its[(size_t)x * a.it_words + (it >> 6)] >> (it & 63)) & 1) g = x;
+  }
+  int64_t* out = a.it_eff + (size_t)t * a.n_res * a.n_its;
+  for (int r = 0; r < a.n_res; ++r)
+    out[(size_t)r * a.n_its + it] = g < 0 ? kEffNever : a.it_alloc[(size_t)r * a.n_its + it] - a.dg_ov[(size_t)g * a.n_res + r];
+}
+
 // ------------------------------------------------------------------------------------------------ pod classes
 struct RowArgs {
   Dict dict;

@@ -548,7 +548,15 @@ __global__ void ksolve_fast_scatter(int n, ks::FastQueueArgs a) {
 __global__ void __launch_bounds__(64) ksolve_fast_records(ks::FastRecordArgs a) {
   ks::fast_record_body<ks::Wave>((int)blockIdx.x, a);
 }
+// The fast engines' effective allocatable (kernels.h eff_alloc_body): grid = instance types x templates, once per handle.
+__global__ void __launch_bounds__(256) ksolve_fast_eff_alloc(ks::EffAllocArgs a) {
+  ks::eff_alloc_body((int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x), a);
+}
 static dim3 grid_for(int n) { return dim3((unsigned)((n + 255) / 256)); }
+static void be_launch_eff_alloc(ksolve_handle* h, const ks::EffAllocArgs& a) {
+  hipLaunchKernelGGL(ksolve_fast_eff_alloc, dim3((unsigned)((a.n_its + 255) / 256), (unsigned)a.n_templates), dim3(256), 0, HB(h)->stream, a);
+  hip_check(h, hipGetLastError(), "ksolve_fast_eff_alloc launch");
+}
 static void be_launch_it_index(ksolve_handle* h, int n, const ks::ItIndexArgs& a) { hipLaunchKernelGGL(ksolve_it_index, grid_for(n), dim3(256), 0, HB(h)->stream, n, a); }
 static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a) {
   const int rw = a.dict.req_words;

@@ -80,6 +80,7 @@ struct ksolve_handle {
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
   ks::TopoArgs* d_topo_args = nullptr;
+  bool daemon_groups = false;   // the problem carries DaemonSets (ksolve_problem_desc.tmpl_daemon_first)
   // probes of a resident cluster (ksolve_probe_create): a probe handle shares the base's device tables
   ksolve_handle* base = nullptr;         // non-null: this handle is a probe of `base`
   bool prepared = false;                 // base: phases 1-3 have run and h_rank is valid
@@ -132,6 +133,12 @@ static void be_launch_pack_fast(ksolve_handle* h);                 // one wavefr
 static void be_launch_pack_topo(ksolve_handle* h);                 // one wavefront: TopoEngine::solve
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n);   // block b = the cursor engine on problem b; sets every handle's T_PACK timer
 static void be_launch_fast_records(ksolve_handle* h, int n_claims); // one wavefront per claim: fast_record_body; then fast_scatter_body per queue entry
+#ifdef KSOLVE_HOST_EMULATION
+// (the emulation's launch is the loop over the grid)
+static void be_launch_eff_alloc(ksolve_handle*, const ks::EffAllocArgs& a) { for (int t = 0; t < a.n_templates; ++t) for (int it = 0; it < a.n_its; ++it) ks::eff_alloc_body(t, it, a); }
+#else
+static void be_launch_eff_alloc(ksolve_handle* h, const ks::EffAllocArgs& a);   // ksolve_fast_eff_alloc: one thread per (template, instance type)
+#endif
 static void be_launch_fast_queue(ksolve_handle* h, bool count_live);   // one thread per queue entry: fast_queue_body (+ ksolve_fast_overlap when asked)
 static void be_launch_pack_batch(ksolve_handle** hs, int n);
 static void be_thread_init(ksolve_handle* h);   // makes the handle's device current on a worker thread   // one block per handle; sets every handle's T_PACK timer
@@ -356,6 +363,11 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     P.dg_ov = up(h, ov.data(), ov.size());
     P.dg_its = up(h, gits.data(), gits.size());
     P.dg_nonzero = nonzero; P.dg_nonempty = nonempty;
+    // templates with a group of non-zero overhead: the fast engines read their types' allocatable less that overhead (P.it_eff, built
+    // below once the engines' candidacy is known). Both engines take at most 32 templates (FastCold::setup), the width of this mask.
+    P.it_eff = nullptr; P.tmpl_ov = 0;
+    h->daemon_groups = d->tmpl_daemon_first != nullptr;
+    if (d->n_templates <= 32) for (uint32_t t = 0; t < d->n_templates; ++t) for (int g = first[t]; g < first[t + 1]; ++g) if ((nonzero >> g) & 1) P.tmpl_ov |= 1u << t;
     // host ports: only matter when some pod binds one
     P.node_removed = nullptr;
   P.hp_on = d->pod_host_ports ? 1 : 0; P.cls_hp = nullptr; P.dg_hp = nullptr; P.node_hp0 = nullptr;
@@ -682,9 +694,9 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     if (d->tmpl_reqs.min_values) for (size_t i = 0; i < (size_t)d->n_templates * d->n_keys; ++i) if (d->tmpl_reqs.min_values[i] >= 0) any_minv = true;
     const bool bounds = any_nonzero(d->pod_reqs.has_gte, d->n_pod_rows) || any_nonzero(d->pod_reqs.has_lte, d->n_pod_rows) ||
                         any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
-    P.plain = (d->topo.n == 0 && d->n_nodes == 0 && !d->tmpl_daemon_first && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
-    P.plain_topo = (d->n_nodes == 0 && !d->tmpl_daemon_first && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
-    P.lite = (P.plain && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
+    P.plain = (d->topo.n == 0 && d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
+    P.plain_topo = (d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
+    P.lite = (P.plain && !d->tmpl_daemon_first && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
 #ifdef KSOLVE_NO_LITE
     P.lite = 0;   // A/B builds only
 #endif
@@ -756,6 +768,12 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       tw.plan.total_bytes = off; fp.total_bytes = off;
       h->d_topo_args = dz<ks::TopoArgs>(h, 1);
     }
+    if ((fw.enabled || tw.enabled) && P.tmpl_ov) {
+      // the effective allocatable of the templates with daemon overhead: a function of catalogue, templates and DaemonSets only — once per handle
+      int64_t* eff = dz<int64_t>(h, (size_t)d->n_templates * d->n_res * d->n_its);
+      P.it_eff = eff;
+      if (d->n_its) be_launch_eff_alloc(h, ks::EffAllocArgs{(int)d->n_templates, (int)d->n_its, (int)it_words, (int)d->n_res, P.tmpl_ov, P.it_alloc, P.dg_first, P.dg_ov, P.dg_its, eff});
+    } else P.tmpl_ov = 0;   // (no fast engine will read it)
   }
   be_sync(h);
   be_toc(h, T_UPLOAD);
@@ -2064,7 +2082,11 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i] != KSOLVE_OK || !hs[i]->n_pods) continue;
     ksolve_handle* h = hs[i];
-    if (h->fw.enabled && !h->pv.big && h->n_classes) {
+    if (h->tw.enabled && h->daemon_groups && h->n_classes) {
+      // a DaemonSet problem of the spread engine's shape: alone through solve(), so that the batch runs the engine ksolve_solve would
+      be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1;
+    }
+    else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan; a handle whose claims live in HBM (an earlier Solve() moved it there, or engine =
       // cursor-wide / cursor-hbm) runs alone on the kernel of its plan
       if (h->fw.plan.global_state == 0) fast.push_back(h);

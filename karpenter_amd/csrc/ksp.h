@@ -222,11 +222,23 @@ struct ProblemView {
   const uint32_t* node_skip_prefix;   // [node_words + 1] how many of them precede each word
   TopoView topo;
   int big;                       // more in-flight claims than the LDS order holds: Engine<W, true, true> (order in HBM)
-  int plain;                     // no topology groups, existing nodes, daemon overhead, minValues, reservations or bounds (any size)
+  int plain;                     // no topology groups, existing nodes, minValues, reservations, bounds, override groups, host ports or volumes (any size); daemon
+                                 // overhead does not count: the fast engines solve it (it_eff below), and `lite` excludes it by itself
   int strict_same;               // PodData.StrictRequirements == Requirements for every pod row (no preferred terms): one table uploaded, two gathered
   int plain_topo;                // the same, but for topology groups: what the spread engine (topo_engine.h) looks at
-  int lite;                      // plain and small enough for the register tables:, existing nodes, daemon overhead, minValues or reservations: Engine<W, false>
+  int lite;                      // plain, no daemon overhead and small enough for the register tables: Engine<W, false>
+  // The fast engines' view of daemon overhead (fast_engine.h, topo_engine.h): a type stays on a claim of template t iff
+  // requests <= allocatable[it] - overhead[group of it in t] =: eff_t[it] (nodeclaim.go:558-566), so they read eff_t wherever they
+  // read a type's allocatable on behalf of a claim. Built once per handle by ksolve_fast_eff_alloc (kernels.h eff_alloc_body).
+  const int64_t* it_eff;         // [n_templates][n_res][n_its]; only the rows of the templates in tmpl_ov are written. null: no overhead
+  uint32_t tmpl_ov;              // templates with a group of non-zero overhead; the others read it_alloc itself. Bit t = template t: set by create() only for
+                                 // problems of at most 32 templates that a fast engine may run (both decline more, FastCold::setup); 0 otherwise
 };
+
+// allocatable of every instance type as a claim of template t sees it: [n_res][n_its]
+KS_FN const int64_t* eff_alloc(const ProblemView& P, int t) {
+  return ((P.tmpl_ov >> t) & 1u) ? P.it_eff + (size_t)t * P.n_res * P.n_its : P.it_alloc;
+}
 
 struct Counters {
   unsigned long long bin_evaluations, full_evaluations, it_evaluations, queue_pops, sorts, slow_sorts, relaxations, column_resets;

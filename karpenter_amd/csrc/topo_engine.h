@@ -6,7 +6,8 @@
 //
 //  1. InstanceTypeOptions are a function of (requirement set, requests) for positive sets (fast_engine.h, fact 1): CanAdd's
 //     filterInstanceTypesByRequirements (nodeclaim.go:541-638) is a dominance test against the cached Pareto-maximal allocatable
-//     vectors of F(requirement set) — the cursor engine's cache (FastCold::create_entry), one 32-byte LDS read per lane. The masks
+//     vectors of F(requirement set) — the cursor engine's cache (FastCold::create_entry), one 32-byte LDS read per lane; with
+//     DaemonSets the vectors are those of allocatable less the template's daemon overhead (ksp.h eff_alloc). The masks
 //     are materialised after the loop by ksolve_fast_records.
 //  2. The topology domain choice stands IN FRONT of that test. A group on a dictionary key has at most sixteen domains: its
 //     counters live in LDS, nextDomainTopologySpread / nextDomainAffinity (topologygroup.go:229-298, :324-388) are evaluated once
@@ -401,15 +402,16 @@ struct TopoEngine {
       if (track_fields) lists_add(nrq.hcnt, (uint32_t)c);
       W::sync();
       if (lm) {
-        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m2) ∩ fits(size)
+        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m2) ∩ fits(size + daemon overhead)
         int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+        const int64_t* eff = eff_alloc(P, t);
         const uint64_t* eits = F.ent_its + (size_t)eh * iw;
         const ProblemView& Pv = P;
         const int n_its = P.n_its;
         for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) {
           const int64_t mx = W::reduce_max_i64(n_its, [&](int it) {
             if (!((eits[it >> 6] >> (it & 63)) & 1)) return INT64_MIN;
-            for (int z = 0; z < nr; ++z) if (Pv.it_alloc[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
+            for (int z = 0; z < nr; ++z) if (eff[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
             return Pv.it_cap[(size_t)q * n_its + it];
           });
           W::store(&rem[q], rem[q] - mx);

@@ -588,3 +588,28 @@ def scale_problem(prob, pods):
     p["podGroups"] = [g for g in p["podGroups"] if g["count"]]
     assert sum(g["count"] for g in p["podGroups"]) == pods, total
     return p
+
+
+def with_daemonsets(prob, kind="c"):
+    """A copy of `prob` with a production-like set of DaemonSet pods (Provisioner.NewScheduler's daemonSetPods,
+    provisioner.go:265-360; overhead groups scheduler.go:963-1043):
+      kind "a": two DaemonSets that run on every node (kube-proxy / CNI style: they tolerate everything) — one overhead group per NodePool;
+      kind "b": plus one restricted to arm64 nodes and one restricted to one zone — several groups per NodePool, different overheads;
+      kind "c": plus one that tolerates no taint (not counted on a tainted NodePool) and one whose only compatible node-affinity
+                term is its second (isDaemonPodCompatible relaxes the terms one by one, scheduler.go:1029-1043)."""
+    if kind not in ("a", "b", "c"):
+        raise ValueError(f"with_daemonsets: kind {kind!r}")
+    p = copy.deepcopy(prob)
+    zones = sorted({v for it in p["instanceTypes"] for r in it["requirements"] if r["key"] == ZONE for v in r["values"]})
+    anything = [{"operator": "Exists"}]
+    ds = [pod(uid="daemonset-kube-proxy", requests={"cpu": "100m", "memory": "128Mi"}, tolerations=anything),
+          pod(uid="daemonset-cni", requests={"cpu": "50m", "memory": "64Mi"}, tolerations=anything)]
+    if kind in ("b", "c"):
+        ds.append(pod(uid="daemonset-arm-agent", requests={"cpu": "200m", "memory": "256Mi"}, node_selector={ARCH: "arm64"}, tolerations=anything))
+        ds.append(pod(uid="daemonset-zone-cache", requests={"cpu": "150m", "memory": "512Mi"}, node_selector={ZONE: zones[0]}, tolerations=anything))
+    if kind == "c":
+        ds.append(pod(uid="daemonset-intolerant", requests={"cpu": "250m", "memory": "100Mi"}))
+        ds.append(pod(uid="daemonset-second-term", requests={"cpu": "25m", "memory": "32Mi"}, tolerations=anything,
+                      node_requirements=[[req(ARCH, "In", "riscv64")], [req(ARCH, "In", "arm64")]]))
+    p["daemonSetPods"] = list(p.get("daemonSetPods", [])) + ds
+    return p
