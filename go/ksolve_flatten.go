@@ -959,8 +959,21 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 	f.opts.max_steps = C.int64_t(maxSteps)
 	f.opts.reserved_offering_strict = C.uint32_t(lo.Ternary(s.reservedOfferingMode == ReservedOfferingModeStrict, 1, 0))
 	f.opts.reserved_capacity = C.uint32_t(lo.Ternary(karpopts.FromContext(ctx).FeatureGates.ReservedCapacity, 1, 0))
+	f.opts.engine = C.uint32_t(KsolveEngine)
 	return f, nil
 }
+
+// KsolveEngine is ksolve_options.engine (include/ksolve.h) for every Scheduler flattened from here on. 0 = automatic;
+// KsolveEngineAutoNodes = automatic, and a problem with existing nodes that is otherwise of the cursor engine's shape runs on the
+// cursor engine with its existing-node stage (the general engine whenever the stage or the loop declines): the setting for
+// Provisioner.NewScheduler, which always passes stateNodes. KsolveEngineCursorNodes refuses instead of falling back (tests).
+var KsolveEngine uint32 = KsolveEngineAuto
+
+const (
+	KsolveEngineAuto        uint32 = 0
+	KsolveEngineAutoNodes   uint32 = 7
+	KsolveEngineCursorNodes uint32 = 8
+)
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).
 func uidWords(uid types.UID) (uint64, uint64) {

@@ -284,7 +284,14 @@ typedef struct {
                                     * pod affinity on dictionary keys and spread / anti-affinity on the hostname (BASELINE configs[2]);
                                     * KSOLVE_ERR_UNSUPPORTED when the problem is outside that shape. Automatic (0) tries it first on every
                                     * problem that is plain but for its topology groups and falls back to the general engine when it
-                                    * declines. All give identical Results. */
+                                    * declines;
+                                    * 7 = "auto-nodes": as automatic, but a problem WITH existing nodes that is otherwise of the cursor
+                                    * engine's shape runs on the cursor engine with its existing-node stage (csrc/node_stage.h: the pods
+                                    * existing nodes take are placed first, by a first fit with one cursor per pod class, the loop solves
+                                    * the rest); the general engine whenever the stage or the loop declines. The setting for
+                                    * Provisioner.NewScheduler, which always passes stateNodes; 8 = "cursor-nodes": the cursor engine with
+                                    * that stage only (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0 and 2 still hand every problem
+                                    * with an existing node to the general engine / refuse it. All give identical Results. */
 } ksolve_options;
 
 /* One NodeClaim of Results.NewNodeClaims (scheduler.go:282, nodeclaim.go:43-62), in the order the reference's
@@ -324,12 +331,18 @@ typedef struct {
   uint64_t ref_bin_evaluations;    /* V as the reference algorithm would count it: every claim up to the accepting one */
   uint64_t phase_cycles[24];       /* profiling builds only (-DKSOLVE_PHASE_TIMERS), zero otherwise: shader clocks per pack-engine phase
                                     * (queue, class fetch, sort, scan, record load, CanAdd, commit, new claim, dead mark, trySchedule,
-                                    * total, CanAdd and scan sub-phases) and a few diagnostic counts */
+                                    * total, CanAdd and scan sub-phases) and a few diagnostic counts; [19] in every build, when the
+                                    * cursor engine ran its existing-node stage: 1 = the nodes' remaining resources in LDS, 2 = in HBM (more than 96 KiB of them, or more than 4096 pod classes) */
   double us_upload, us_prepass, us_pack, us_finalize, us_download;
   double packing_cost;
   uint32_t engine_used;            /* 1 = general engine, 2 = cursor engine, 3 = spread engine */
   uint32_t engine_fallback_reason; /* non-zero: why the cursor / spread engine handed the problem to the general engine (csrc/fast_engine.h
-                                    * setup(): 1-8; run time: 20-28; csrc/topo_engine.h setup_topo(): 40-51, run time: 60-62) */
+                                    * setup(): 1-8; run time: 20-28; csrc/topo_engine.h setup_topo(): 40-51, run time: 60-62;
+                                    * the cursor engine's existing-node stage, engine 7 / 8 (csrc/node_stage.h): 30 = a node under
+                                    * consolidateAfter while some pod is neither pending nor from a deleting node, 31 = node requirement
+                                    * sets with bounds, 32 = a node label set that is not single-valued In, 33 = more pod classes than
+                                    * the stage keeps cursors for (12288), 34 = existing nodes, and otherwise outside the cursor engine's
+                                    * shape: topology, host ports, volumes, CSI volume limits, minValues, reservations, resident pods) */
   uint32_t cursor_wide;            /* engine_used == 2: the memory plan it ran with. 0 = claim state and order in LDS (~3,000 in-flight
                                     * NodeClaims); 1 = the claims' state in HBM (~15,000); 2 = their order too (65,472) */
   uint32_t cursor_attempts;        /* runs of the cursor engine this solve took: 1, or one more per plan it outgrew (a later solve of the

@@ -86,6 +86,17 @@ struct FastMisc {   // small LDS tables
 
 struct FastVar { int nv; uint8_t vkey[kFastMaxVar], voff[kFastMaxVar], vwidth[kFastMaxVar]; uint16_t vword[kFastMaxVar]; };   // the keys pods select on
 
+// What the existing-node stage leaves for the loop and for the counters (one record in HBM, written by ksolve_pack_nodes)
+struct FastNodes {
+  uint32_t n_left;        // queue entries no node took: the loop's queue
+  uint32_t n_placed;      // pods placed on existing nodes (queue pops of the stage that the loop does not see)
+  uint32_t limit_hit;     // the step limit ended the solve inside or right behind the stage's entries: the solve's status is "stopped" whatever the loop says
+  uint32_t variant;       // 1: `remaining` and the nodes' pod counts in LDS, 2: in the HBM workspace (reported as phase_cycles[19])
+  uint32_t bail;          // a reason of fast_engine.h setup() the stage found first (a class that is not positive: 4, 8): the loop stops with it
+  unsigned long long n_ref;     // candidate nodes the reference would have evaluated (scheduler.go:614-656)
+  unsigned long long n_tests;   // (class, node) resource tests of the stage
+};
+
 struct FastWork {   // HBM workspace of the cursor engine (host-allocated when the problem may qualify)
   FastVar* var;           // written by the pack kernel, read by ksolve_fast_records
   FastSlot* cls;          // [n_classes]
@@ -107,6 +118,11 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   uint32_t* cls_first;    // [n_classes] first / last queue entry of the class (ksolve_fast_queue)
   uint32_t* cls_last;
   uint32_t* max_active;   // [1] the most classes live at once: max over classes c of #{c' : first(c') <= first(c) <= last(c')} (ksolve_fast_overlap)
+  // The existing-node stage (node_stage.h, ksolve_pack_nodes) in front of the loop; null without it. The loop then solves the pods
+  // the stage left: q_class / q_claim / q_cnt are the COMPACTED queue (nodes->n_left entries), nd_pod the pod of each entry.
+  FastNodes* nodes;       // [1] what the stage hands to the loop
+  uint32_t* nd_pod;       // [n_pods] pod index of compacted queue entry j (sorted_pods of the queue the loop sees)
+  const uint64_t* nd_dead0;   // [n_classes][node_words] the static (class, node) verdicts (ksolve_node_dead0) for this solve's class ids
   FastPlan plan;
   int enabled;
 };
@@ -519,7 +535,7 @@ struct FastCold {
     const Dict& d = P.dict;
     const int nk = d.n_keys, iw = P.it_words, nr = P.n_res, n_its = P.n_its, nc = P.n_classes, T = P.n_templates;
     const ProblemView& Pv = P;
-    if (!(topo ? P.plain_topo : P.plain) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return 1;
+    if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return 1;
     // (instance types may use any operator: with positive sets on the claim side the NotIn / DoesNotExist escape of
     // requirements.go:260-265 never applies, so compatible() stays monotone)
     // templates: only In sets
@@ -982,16 +998,20 @@ struct FastCold {
       });
       W::store(S.n_claims_out, n_claims);
     }
+    FastNodes nd{};   // the existing-node stage in front of the loop: its pops and evaluations count, and its step limit stands
+    if (F.nodes) nd = *F.nodes;
+    if (status == 0 && nd.limit_hit) status = 2;
     if (status) W::store(S.status_out, status);
     Counters c{};
-    c.bin_evaluations = n_tests + n_cold_tests; c.full_evaluations = n_steps; c.queue_pops = steps; c.sorts = steps; c.slow_sorts = order.slow_sorts;
-    c.column_resets = (unsigned long long)n_evict; c.ref_bin_evaluations = n_ref + n_ref_extra;
+    c.bin_evaluations = n_tests + n_cold_tests + nd.n_tests; c.full_evaluations = n_steps; c.queue_pops = steps + nd.n_placed; c.sorts = steps; c.slow_sorts = order.slow_sorts;
+    c.column_resets = (unsigned long long)n_evict; c.ref_bin_evaluations = n_ref + n_ref_extra + nd.n_ref;
     c.cycles[20] = (unsigned long long)(bail_code > 0 ? bail_code : 0);
     if (tc) for (int i = 0; i < 16; ++i) c.cycles[i] = tc[i];
 #ifdef KSOLVE_PHASE_TIMERS
     for (int i = 0; i < 4; ++i) c.cycles[16 + i] = hs->hw[i];
     c.cycles[18] = (hs->hw[2] << 32) | (unsigned long long)(hs->mail.simd[0] | (hs->mail.simd[1] << 8) | (hs->mail.simd[2] << 16) | (hs->mail.simd[3] << 24));
 #endif
+    if (F.nodes) c.cycles[19] = (unsigned long long)nd.variant;
     if (W::leader()) *S.counters = c;
     W::sync();
   }
@@ -1966,11 +1986,15 @@ struct FastEngine {
       const int why = (int)W::uniform((uint64_t)(uint32_t)cold.setup());
       if (why) { cold.bail_code = why; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
     }
-    const int np = fast_uniform(cold.Pk->n_pods);
+    // (behind the existing-node stage the queue is what the stage left, and a step limit has been applied to the stage's entries:
+    // every entry it left is inside the limit)
+    const FastNodes* const nds = fast_uniform(cold.Fk->nodes);
+    if (nds && fast_uniform((int)nds->bail) != 0) { cold.bail_code = fast_uniform((int)nds->bail); cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
+    const int np = nds ? fast_uniform((int)nds->n_left) : fast_uniform(cold.Pk->n_pods);
     if (W::leader()) {
       h->base = 0; h->bi = 0; h->bn = 0; h->n = 0; h->np = np; h->steps = 0; h->status = 0;
       const long long ms_ = cold.Sk->max_steps;
-      h->max_steps = ms_ < 0 ? -1 : (int)(ms_ > 0x7FFFFFFF ? 0x7FFFFFFF : ms_);
+      h->max_steps = ms_ < 0 ? -1 : (nds || ms_ > 0x7FFFFFFF) ? 0x7FFFFFFF : (int)ms_;
       h->pend_a = -1; h->pend_x = 0; h->pend_mv = 0; h->pend_new = 0; h->ev_arg = 0; h->rf_x = -1; h->rf_x2 = -1;
       h->n_steps = 0; h->n_tests = 0; h->n_ref = 0; h->hot_cycles = 0;
       for (int i = 0; i < 8; ++i) h->tsec[i] = 0;

@@ -540,6 +540,14 @@ __global__ void ksolve_fast_mark(int n, ks::FastQueueArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ks::fast_mark_body(i, a);
 }
+__global__ void ksolve_fast_requeue(int n, ks::FastRequeueArgs a) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ks::fast_requeue_body(i, a);
+}
+__global__ void ksolve_fast_remark(int n, ks::FastRequeueArgs a) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ks::fast_remark_body(i, a);
+}
 __global__ void ksolve_fast_scatter(int n, ks::FastQueueArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ks::fast_scatter_body(i, a);
@@ -732,6 +740,21 @@ static void be_launch_fast_records(ksolve_handle* h, int n_claims) {
   const int n = (int)h->n_pods;
   hipLaunchKernelGGL(ksolve_fast_scatter, grid_for(n), dim3(256), 0, HB(h)->stream, n, fast_queue_args(h));
   hip_check(h, hipGetLastError(), "ksolve_fast_scatter launch");
+}
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
+  const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
+  const ksolve_pack_fast_fn fn = hbm ? ksolve_pack_nodes_hbm : ksolve_pack_nodes_lds;
+  if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
+  ks::FastArgs a{h->pv, h->ws, h->fw};
+  be_h2d(h, h->d_fast_args, &a, sizeof(a));
+  hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::FastArgs*)h->d_fast_args);
+  hip_check(h, hipGetLastError(), "ksolve_pack_nodes launch");
+  const int n = (int)h->n_pods;
+  const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
+  hipLaunchKernelGGL(ksolve_fast_requeue, grid_for(n), dim3(256), 0, HB(h)->stream, n, q);
+  hip_check(h, hipGetLastError(), "ksolve_fast_requeue launch");
+  hipLaunchKernelGGL(ksolve_fast_remark, grid_for(n), dim3(256), 0, HB(h)->stream, n, q);
+  hip_check(h, hipGetLastError(), "ksolve_fast_remark launch");
 }
 static void be_launch_fast_queue(ksolve_handle* h, bool count_live) {
   const int n = (int)h->n_pods;

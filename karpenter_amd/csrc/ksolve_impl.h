@@ -18,6 +18,7 @@
 #include "engine.h"
 #include "kernels.h"
 #include "fast_engine.h"
+#include "node_stage.h"
 #include "topo_types.h"
 
 // Backend contract (provided by the including TU):
@@ -78,6 +79,8 @@ struct ksolve_handle {
   ks::FastWork fw{};            // cursor engine (fast_engine.h): workspace + LDS plan; fw.enabled while the problem may qualify
   uint32_t engine_used = 0, fast_reason = 0, fast_attempts = 0;
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
+  bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
+  uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
   ks::TopoArgs* d_topo_args = nullptr;
   bool daemon_groups = false;   // the problem carries DaemonSets (ksolve_problem_desc.tmpl_daemon_first)
@@ -147,6 +150,7 @@ static int be_device_available();
 static int be_device_of(const ksolve_handle* h);     // the device ordinal the handle lives on
 static void be_free(ksolve_handle* h, void* p);   // releases one be_alloc'ed block before the handle goes
 static void be_launch_node_dead0(ksolve_handle* h, int n_blocks, const ks::NodeDeadArgs& a);   // one wavefront per 64 nodes
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
 static void be_launch_sweep_items(ksolve_handle* h, int n, const ks::SweepItemArgs& a);
@@ -228,6 +232,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   }
   if (o) h->opts = *o;
   else { h->opts = ksolve_options{}; h->opts.max_steps = -1; }
+  if (h->opts.engine == 7 || h->opts.engine == 8) { h->opt_nodes = true; h->opts.engine = h->opts.engine == 7 ? 0u : 2u; }   // automatic / cursor only, existing nodes allowed
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -697,6 +702,35 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     P.plain = (d->topo.n == 0 && d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
     P.plain_topo = (d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
     P.lite = (P.plain && !d->tmpl_daemon_first && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
+    // plain but for existing nodes the cursor engine's node stage can place pods on (node_stage.h); otherwise the reason (30-34)
+    P.plain_nodes = 0;
+    if (h->opt_nodes && d->n_nodes > 0) {
+      uint32_t why = 0;
+      if (!(d->topo.n == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = 34;
+      if (!why && d->node_under_consolidate_after) {
+        // a node under consolidateAfter is skipped for pods that are neither pending nor from a deleting node (scheduler.go:628)
+        bool under = false, bound = false;
+        for (uint32_t e = 0; e < d->n_nodes; ++e) under = under || d->node_under_consolidate_after[e];
+        for (uint32_t p = 0; p < d->n_pods && under; ++p) bound = bound || !((d->pod_is_pending && d->pod_is_pending[p]) || (d->pod_from_deleting_node && d->pod_from_deleting_node[p]));
+        if (under && bound) why = 30;
+      }
+      if (!why && (any_nonzero(d->node_reqs.has_gte, d->n_nodes) || any_nonzero(d->node_reqs.has_lte, d->n_nodes))) why = 31;
+      if (!why) {
+        // labels as single-valued In sets: ExistingNode.Add then leaves a node's requirements as they were
+        for (uint32_t e = 0; e < d->n_nodes && !why; ++e) {
+          if (d->node_reqs.complement[e]) { why = 32; break; }
+          const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
+          for (uint32_t k = 0; k < d->n_keys; ++k) {
+            if (!((d->node_reqs.defined[e] >> k) & 1u)) continue;
+            int vals = 0;
+            for (uint32_t x = P.dict.key_word_off[k]; x < P.dict.key_word_off[k + 1]; ++x) vals += __builtin_popcountll(nm[x]);
+            if (vals != 1) { why = 32; break; }
+          }
+        }
+      }
+      P.plain_nodes = why ? 0 : 1;
+      h->fast_reason = why;
+    }
 #ifdef KSOLVE_NO_LITE
     P.lite = 0;   // A/B builds only
 #endif
@@ -705,7 +739,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     // cursor engine (fast_engine.h): candidate when the problem is lite and has no relaxation rows; the kernel itself checks the
     // rest (positive operators only, packed variable keys, 31-bit quantities) and hands the problem back otherwise
     ks::FastWork& fw = h->fw;
-    fw.enabled = (P.plain && d->n_res <= 4 && h->opts.engine != 1 && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
+    fw.enabled = ((P.plain || P.plain_nodes) && d->n_res <= 4 && h->opts.engine != 1 && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
     if (fw.enabled) {
       h->fast_mc = mc;
       fast_plan_set(h, h->opts.engine == 4 ? 2 : h->opts.engine == 3 ? 1 : 0, 1);
@@ -737,6 +771,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       fw.q_class = dz<uint32_t>(h, d->n_pods); fw.q_claim = dz<uint32_t>(h, d->n_pods); fw.q_cnt = dz<uint32_t>(h, d->n_pods);
       { const size_t oc = std::min<size_t>(65472, ((size_t)mc + 63) & ~(size_t)63) + 64; fw.o_key = dz<uint16_t>(h, oc); fw.o_ord = dz<uint16_t>(h, oc); fw.o_snap = dz<uint16_t>(h, oc); }
       h->d_fast_args = dz<ks::FastArgs>(h, 1);
+      if (P.plain_nodes) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the
@@ -1949,6 +1984,40 @@ static void fast_plan_set(ksolve_handle* h, int plan, int rows) {
   fp.total_bytes = off;
 }
 
+// ksolve_fast_requeue / ksolve_fast_remark behind ksolve_pack_nodes: the compacted queue's tables, the full queue's pods
+static ks::FastRequeueArgs fast_requeue_args(ksolve_handle* h) {
+  return ks::FastRequeueArgs{ks::FastQueueArgs{h->fw.nd_pod, h->pv.row_class, h->fw.q_class, h->fw.q_claim, h->fw.q_cnt, h->ws.assign, h->ws.slot, h->fw.cls_first, h->fw.cls_last, h->fw.max_active},
+                             h->pv.sorted_pods, h->fw.nodes};
+}
+
+// The cursor engine's existing-node stage (node_stage.h) between the queue kernels and the loop: the static (class, node) rows,
+// ksolve_pack_nodes, and the compacted queue the loop then reads. The rows are a function of the problem, but they are indexed by
+// class id, and class ids are drawn from an atomic counter by the rows that open a hash slot (kernels.h row_hash_body): the numbering
+// differs from solve to solve on the device. So the rows are computed with every solve's classes (one wavefront per 64 nodes x 32
+// classes: microseconds); the handle keeps the buffer.
+static void fast_nodes_stage(ksolve_handle* h) {
+  ks::ProblemView& P = h->pv;
+  const uint32_t ne = h->n_nodes, nw = (uint32_t)P.node_words, nc = h->n_classes;
+  if (!h->nd_dead0 || h->nd_dead0_classes < nc) { h->nd_dead0 = dz<uint64_t>(h, (size_t)nc * nw); h->nd_dead0_classes = nc; }
+  {
+    uint64_t* dead0 = h->nd_dead0;
+    ks::NodeDeadArgs a{};
+    a.dict = P.dict; a.lay = P.lay; a.n_nodes = (int)ne; a.node_words = (int)nw; a.n_classes = (int)nc; a.hp_on = 0;
+    a.cls_hot = P.cls_hot; a.cls_cold = P.cls_cold; a.cls_hp = nullptr; a.node_taints = P.node_taints;
+    a.pristine.mask = h->ws.n_mask0; a.pristine.defined = h->ws.n_defined0; a.pristine.complement = h->ws.n_complement0;
+    a.pristine.hg = nullptr; a.pristine.hl = nullptr; a.pristine.gte = nullptr; a.pristine.lte = nullptr;
+    a.pristine.remaining = h->ws.n_remaining0; a.pristine.hp = nullptr; a.pristine.stride = ne;
+    a.dead0 = dead0;
+    be_launch_node_dead0(h, (int)nw, a);
+  }
+  h->fw.nd_dead0 = h->nd_dead0;
+  be_fill(h, h->fw.cls_first, 0xFF, (size_t)nc * 4); be_fill(h, h->fw.cls_last, 0, (size_t)nc * 4);   // (the compacted queue's, rebuilt behind the stage)
+  be_launch_pack_nodes(h, ks::node_stage_hbm((int)nc, (int)ne, (int)h->n_res));
+  // From here to the end of the solve the queue IS the compacted one: entry j is pod nd_pod[j]. The loop's record and the scatter of
+  // its results (be_launch_fast_records) read the queue's pods through the view; solve_prepare sorts the queue anew for every solve.
+  P.sorted_pods = h->fw.nd_pod;
+}
+
 static void be_results_drop(ksolve_results* r) { if (r && r->impl) { delete (ResultsImpl*)r->impl; r->impl = nullptr; } }
 static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_context = true) {
   memset(out, 0, sizeof(*out));
@@ -1959,7 +2028,14 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
   if (h->opts.engine == 6 && !(h->tw.enabled && h->n_pods && h->n_classes))
     return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)");
   if (h->opts.engine >= 2 && h->opts.engine != 6 && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
-    return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)");
+    return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
+                (h->opt_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
+  if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
+    // more pod classes than the node stage keeps cursors for: the general engine (nothing has run yet)
+    h->fast_reason = 33;
+    if (h->opts.engine >= 2) return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason 33)");
+    h->fw.enabled = 0;
+  }
   if (h->tw.enabled && h->n_pods && h->n_classes) {
     // the spread engine first; status 3 = "not my shape / stopped before any result": the general engine takes over
     alloc_run_order(h);
@@ -1994,6 +2070,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
     for (;;) {
       h->fast_attempts++;
       be_tic(h, T_PACK);
+      if (h->fw.nodes) fast_nodes_stage(h);   // existing nodes first (scheduler.go:594); the loop solves the pods they left
       be_launch_pack_fast(h);
       be_toc(h, T_PACK);
       int status = 0, n_claims = 0;
@@ -2089,7 +2166,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan; a handle whose claims live in HBM (an earlier Solve() moved it there, or engine =
       // cursor-wide / cursor-hbm) runs alone on the kernel of its plan
-      if (h->fw.plan.global_state == 0) fast.push_back(h);
+      if (h->fw.plan.global_state == 0 && !h->fw.nodes) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop)
       else { be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1; }
     }
     else if (h->opts.engine >= 2) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");
@@ -2193,3 +2270,18 @@ static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksol
 }
 
 }  // namespace ksi
+
+#ifdef KSOLVE_HOST_EMULATION
+// The host emulation's launch of the stage (the other launches of the emulation live with its backend): a kernel launch is a loop over its grid.
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
+  const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
+  std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
+  ks::FastArgs a{h->pv, h->ws, h->fw};
+  be_h2d(h, h->d_fast_args, &a, sizeof(a));
+  if (hbm) ks::pack_nodes_body<ks::Wave, true>(h->d_fast_args, lds.data());
+  else ks::pack_nodes_body<ks::Wave, false>(h->d_fast_args, lds.data());
+  const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
+  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_requeue_body(i, q);
+  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_remark_body(i, q);
+}
+#endif

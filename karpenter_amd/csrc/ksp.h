@@ -227,6 +227,8 @@ struct ProblemView {
   int strict_same;               // PodData.StrictRequirements == Requirements for every pod row (no preferred terms): one table uploaded, two gathered
   int plain_topo;                // the same, but for topology groups: what the spread engine (topo_engine.h) looks at
   int lite;                      // plain, no daemon overhead and small enough for the register tables: Engine<W, false>
+  int plain_nodes;               // plain but for its existing nodes, and those are what the cursor engine's node stage (node_stage.h) places pods on:
+                                 // single-valued In labels, no bounds, no CSI volume limits, no node under consolidateAfter that a pod must skip
   // The fast engines' view of daemon overhead (fast_engine.h, topo_engine.h): a type stays on a claim of template t iff
   // requests <= allocatable[it] - overhead[group of it in t] =: eff_t[it] (nodeclaim.go:558-566), so they read eff_t wherever they
   // read a type's allocatable on behalf of a claim. Built once per handle by ksolve_fast_eff_alloc (kernels.h eff_alloc_body).

@@ -613,3 +613,33 @@ def with_daemonsets(prob, kind="c"):
                       node_requirements=[[req(ARCH, "In", "riscv64")], [req(ARCH, "In", "arm64")]]))
     p["daemonSetPods"] = list(p.get("daemonSetPods", [])) + ds
     return p
+
+
+def with_existing_nodes(prob, n_nodes, seed=0, fill=(0.2, 0.9), small=False):
+    """A copy of `prob` with `n_nodes` state nodes (Provisioner.NewScheduler's stateNodes, provisioner.go:265-360) launched from the
+    problem's own catalogue and NodePools, as a cluster that has been running for a while looks to the scheduler: each node is an
+    instance type a NodePool admits, in one of the type's available offerings (zone, capacity type), carries the pool's labels and
+    taints, and a fraction of its cpu / memory / pods drawn from `fill` (low, high) is in use. `small`: only the smaller half of
+    the catalogue (by cpu), for tests that want many nodes that each hold few pods."""
+    p = copy.deepcopy(prob)
+    rng = random.Random(77000 + seed)
+    types = sorted(p["instanceTypes"], key=lambda t: (quantity_float(t["capacity"]["cpu"]), t["name"]))
+    if small:
+        types = types[:max(1, len(types) // 2)]
+    nodes = list(p.get("stateNodes", []))
+    for i in range(n_nodes):
+        pool = rng.choice(p["nodePools"])
+        allowed = [t for t in types if "instanceTypes" not in pool or t["name"] in pool["instanceTypes"]] or types
+        it = rng.choice(allowed)
+        off = rng.choice([o for o in it["offerings"] if o.get("available", True)])
+        where = {r["key"]: r["values"][0] for r in off["requirements"]}
+        f = rng.uniform(*fill)
+        used = {"cpu": f"{int(quantity_float(it['capacity']['cpu']) * 1000 * f)}m",
+                "memory": f"{int(quantity_float(it['capacity']['memory']) / 2**20 * f)}Mi",
+                "pods": str(int(quantity_float(it["capacity"]["pods"]) * f))}
+        extra = dict(pool.get("labels", {}))
+        extra[pool["nodeClassLabelKey"]] = pool["nodeClassName"]
+        nodes.append(state_node(f"existing-{len(nodes):05d}", it, where[ZONE], where[CAPACITY_TYPE], pool["name"], used=used,
+                                taints=[dict(t) for t in pool.get("taints", [])], extra_labels=extra))
+    p["stateNodes"] = nodes
+    return p
