@@ -967,12 +967,18 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // KsolveEngineAutoNodes = automatic, and a problem with existing nodes that is otherwise of the cursor engine's shape runs on the
 // cursor engine with its existing-node stage (the general engine whenever the stage or the loop declines): the setting for
 // Provisioner.NewScheduler, which always passes stateNodes. KsolveEngineCursorNodes refuses instead of falling back (tests).
+// KsolveEngineAutoNodesSpread = KsolveEngineAutoNodes, and a problem with existing nodes AND topology groups that is otherwise of
+// the spread engine's shape runs on the spread engine, which offers every pod to the nodes first: the setting for a cluster whose
+// pods carry spread constraints. KsolveEngineSpreadNodes refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
 	KsolveEngineAuto        uint32 = 0
 	KsolveEngineAutoNodes   uint32 = 7
 	KsolveEngineCursorNodes uint32 = 8
+
+	KsolveEngineAutoNodesSpread uint32 = 9
+	KsolveEngineSpreadNodes     uint32 = 10
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

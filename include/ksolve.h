@@ -291,7 +291,13 @@ typedef struct {
                                     * the rest); the general engine whenever the stage or the loop declines. The setting for
                                     * Provisioner.NewScheduler, which always passes stateNodes; 8 = "cursor-nodes": the cursor engine with
                                     * that stage only (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0 and 2 still hand every problem
-                                    * with an existing node to the general engine / refuse it. All give identical Results. */
+                                    * with an existing node to the general engine / refuse it;
+                                    * 9 = "auto-nodes-spread": as 7, and a problem with existing nodes AND topology groups that is
+                                    * otherwise of the spread engine's shape runs on the spread engine, whose per-pod step offers the
+                                    * pod to the nodes first (csrc/topo_nodes.h, kernel ksolve_pack_topo_nodes); the general engine
+                                    * whenever the spread engine declines or stops; 10 = "spread-nodes": the spread engine only, nodes
+                                    * allowed (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 7 still answers a problem with nodes
+                                    * and topology groups with reason 34. All give identical Results. */
 } ksolve_options;
 
 /* One NodeClaim of Results.NewNodeClaims (scheduler.go:282, nodeclaim.go:43-62), in the order the reference's
@@ -342,7 +348,11 @@ typedef struct {
                                     * consolidateAfter while some pod is neither pending nor from a deleting node, 31 = node requirement
                                     * sets with bounds, 32 = a node label set that is not single-valued In, 33 = more pod classes than
                                     * the stage keeps cursors for (12288), 34 = existing nodes, and otherwise outside the cursor engine's
-                                    * shape: topology, host ports, volumes, CSI volume limits, minValues, reservations, resident pods) */
+                                    * shape: topology, host ports, volumes, CSI volume limits, minValues, reservations, resident pods);
+                                    * the spread engine's existing-node path, engine 9 / 10 (csrc/topo_nodes.h): 30-32 and 34 as
+                                    * above (34 without "topology"), 35 = a node without a label for a dictionary key some topology
+                                    * group uses, 36 = a node whose value of such a key lies beyond the sixteen domains a group's
+                                    * counters hold, 43 = a group honours nodeTaintsPolicy and a node (not only a template) is tainted) */
   uint32_t cursor_wide;            /* engine_used == 2: the memory plan it ran with. 0 = claim state and order in LDS (~3,000 in-flight
                                     * NodeClaims); 1 = the claims' state in HBM (~15,000); 2 = their order too (65,472) */
   uint32_t cursor_attempts;        /* runs of the cursor engine this solve took: 1, or one more per plan it outgrew (a later solve of the

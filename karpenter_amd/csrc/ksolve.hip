@@ -694,14 +694,16 @@ static void be_launch_pack_fast(ksolve_handle* h) {
   hipLaunchKernelGGL(fn, dim3(1), dim3(two ? 256 : 64), (size_t)lds_bytes, HB(h)->stream, (const ks::FastArgs*)h->d_fast_args);
   hip_check(h, hipGetLastError(), "ksolve_pack_fast launch");
 }
-static void be_launch_pack_topo(ksolve_handle* h) {
+static void launch_pack_topo(ksolve_handle* h, void (*fn)(const ks::TopoArgs*), const char* what) {
   const int lds_bytes = h->tw.plan.total_bytes;
-  if (!hip_check(h, hipFuncSetAttribute((const void*)ksolve_pack_topo, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
+  if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
   be_h2d(h, h->d_topo_args, &a, sizeof(a));
-  hipLaunchKernelGGL(ksolve_pack_topo, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::TopoArgs*)h->d_topo_args);
-  hip_check(h, hipGetLastError(), "ksolve_pack_topo launch");
+  hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::TopoArgs*)h->d_topo_args);
+  hip_check(h, hipGetLastError(), what);
 }
+static void be_launch_pack_topo(ksolve_handle* h) { launch_pack_topo(h, ksolve_pack_topo, "ksolve_pack_topo launch"); }
+static void be_launch_pack_topo_nodes(ksolve_handle* h) { launch_pack_topo(h, ksolve_pack_topo_nodes, "ksolve_pack_topo_nodes launch"); }
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {
   if (n <= 0) return;
   ksolve_handle* h0 = hs[0];
@@ -734,9 +736,11 @@ static ks::FastQueueArgs fast_queue_args(ksolve_handle* h) {
   return ks::FastQueueArgs{h->pv.sorted_pods, h->pv.row_class, h->fw.q_class, h->fw.q_claim, h->fw.q_cnt, h->ws.assign, h->ws.slot, h->fw.cls_first, h->fw.cls_last, h->fw.max_active};
 }
 static void be_launch_fast_records(ksolve_handle* h, int n_claims) {
-  ks::FastRecordArgs a{h->pv, h->ws, h->fw};
-  hipLaunchKernelGGL(ksolve_fast_records, dim3((unsigned)n_claims), dim3(64), 0, HB(h)->stream, a);
-  hip_check(h, hipGetLastError(), "ksolve_fast_records launch");
+  if (n_claims > 0) {   // (none: every pod went to an existing node — only the scatter of the queue's results)
+    ks::FastRecordArgs a{h->pv, h->ws, h->fw};
+    hipLaunchKernelGGL(ksolve_fast_records, dim3((unsigned)n_claims), dim3(64), 0, HB(h)->stream, a);
+    hip_check(h, hipGetLastError(), "ksolve_fast_records launch");
+  }
   const int n = (int)h->n_pods;
   hipLaunchKernelGGL(ksolve_fast_scatter, grid_for(n), dim3(256), 0, HB(h)->stream, n, fast_queue_args(h));
   hip_check(h, hipGetLastError(), "ksolve_fast_scatter launch");

@@ -80,6 +80,7 @@ struct ksolve_handle {
   uint32_t engine_used = 0, fast_reason = 0, fast_attempts = 0;
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
   bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
+  bool opt_spread_nodes = false;   // engine = auto-nodes-spread / spread-nodes (9 / 10; opts.engine holds 0 / 6 from then on): the spread engine may take a problem with existing nodes (topo_nodes.h)
   uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
   ks::TopoArgs* d_topo_args = nullptr;
@@ -150,6 +151,7 @@ static int be_device_available();
 static int be_device_of(const ksolve_handle* h);     // the device ordinal the handle lives on
 static void be_free(ksolve_handle* h, void* p);   // releases one be_alloc'ed block before the handle goes
 static void be_launch_node_dead0(ksolve_handle* h, int n_blocks, const ks::NodeDeadArgs& a);   // one wavefront per 64 nodes
+static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: TopoEngine<W, true>::solve (existing nodes: topo_nodes.h)
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
@@ -207,6 +209,32 @@ static bool any_nonzero(const uint32_t* p, uint32_t n) {
 }
 
 static void fast_plan_set(ksolve_handle* h, int plan, int rows);   // the cursor engine's memory plan (0 LDS / 1 claim state in HBM / 2 order arrays too)
+// The existing-node conditions the cursor engine's stage (node_stage.h) and the spread engine's node path (topo_nodes.h) share;
+// 0, or the fallback reason: 30 = a node under consolidateAfter that some pod must skip, 31 = node requirement sets with bounds,
+// 32 = a node label set that is not single-valued In.
+static uint32_t node_stage_declines(const ksolve_problem_desc* d, const ks::Dict& dict, uint32_t req_words) {
+  if (d->node_under_consolidate_after) {
+    // a node under consolidateAfter is skipped for pods that are neither pending nor from a deleting node (scheduler.go:628)
+    bool under = false, bound = false;
+    for (uint32_t e = 0; e < d->n_nodes; ++e) under = under || d->node_under_consolidate_after[e];
+    for (uint32_t p = 0; p < d->n_pods && under; ++p) bound = bound || !((d->pod_is_pending && d->pod_is_pending[p]) || (d->pod_from_deleting_node && d->pod_from_deleting_node[p]));
+    if (under && bound) return 30;
+  }
+  if (any_nonzero(d->node_reqs.has_gte, d->n_nodes) || any_nonzero(d->node_reqs.has_lte, d->n_nodes)) return 31;
+  // labels as single-valued In sets: ExistingNode.Add then leaves a node's requirements as they were
+  for (uint32_t e = 0; e < d->n_nodes; ++e) {
+    if (d->node_reqs.complement[e]) return 32;
+    const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
+    for (uint32_t k = 0; k < d->n_keys; ++k) {
+      if (!((d->node_reqs.defined[e] >> k) & 1u)) continue;
+      int vals = 0;
+      for (uint32_t x = dict.key_word_off[k]; x < dict.key_word_off[k + 1]; ++x) vals += __builtin_popcountll(nm[x]);
+      if (vals != 1) return 32;
+    }
+  }
+  return 0;
+}
+
 static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* o, ksolve_handle* h) {
   if (!d || d->abi_version != KSOLVE_ABI_VERSION) return fail(h, KSOLVE_ERR_INVALID, "abi version mismatch");
   if (d->n_keys == 0 || d->n_keys > KSOLVE_MAX_KEYS) return fail(h, KSOLVE_ERR_INVALID, "n_keys out of range");
@@ -233,6 +261,8 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   if (o) h->opts = *o;
   else { h->opts = ksolve_options{}; h->opts.max_steps = -1; }
   if (h->opts.engine == 7 || h->opts.engine == 8) { h->opt_nodes = true; h->opts.engine = h->opts.engine == 7 ? 0u : 2u; }   // automatic / cursor only, existing nodes allowed
+  else if (h->opts.engine == 9) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opts.engine = 0u; }   // as 7, and the spread engine may take nodes too
+  else if (h->opts.engine == 10) { h->opt_spread_nodes = true; h->opts.engine = 6u; }                        // spread only, existing nodes allowed
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -707,29 +737,37 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     if (h->opt_nodes && d->n_nodes > 0) {
       uint32_t why = 0;
       if (!(d->topo.n == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = 34;
-      if (!why && d->node_under_consolidate_after) {
-        // a node under consolidateAfter is skipped for pods that are neither pending nor from a deleting node (scheduler.go:628)
-        bool under = false, bound = false;
-        for (uint32_t e = 0; e < d->n_nodes; ++e) under = under || d->node_under_consolidate_after[e];
-        for (uint32_t p = 0; p < d->n_pods && under; ++p) bound = bound || !((d->pod_is_pending && d->pod_is_pending[p]) || (d->pod_from_deleting_node && d->pod_from_deleting_node[p]));
-        if (under && bound) why = 30;
-      }
-      if (!why && (any_nonzero(d->node_reqs.has_gte, d->n_nodes) || any_nonzero(d->node_reqs.has_lte, d->n_nodes))) why = 31;
-      if (!why) {
-        // labels as single-valued In sets: ExistingNode.Add then leaves a node's requirements as they were
-        for (uint32_t e = 0; e < d->n_nodes && !why; ++e) {
-          if (d->node_reqs.complement[e]) { why = 32; break; }
-          const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
-          for (uint32_t k = 0; k < d->n_keys; ++k) {
-            if (!((d->node_reqs.defined[e] >> k) & 1u)) continue;
-            int vals = 0;
-            for (uint32_t x = P.dict.key_word_off[k]; x < P.dict.key_word_off[k + 1]; ++x) vals += __builtin_popcountll(nm[x]);
-            if (vals != 1) { why = 32; break; }
-          }
-        }
-      }
+      if (!why) why = node_stage_declines(d, P.dict, req_words);
       P.plain_nodes = why ? 0 : 1;
       h->fast_reason = why;
+    }
+    // plain_topo_nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
+    // engine's node path rests on (topo_nodes.h): every node carries ONE value of every dictionary key a group uses (35), among the
+    // sixteen a group's counters hold (36), and no group honours nodeTaintsPolicy while a node is tainted (43, extended to nodes:
+    // TopologyNodeFilter.Matches must be true for every node as it is for every claim). The view's plain_topo says it: a handle
+    // with nodes runs ksolve_pack_topo_nodes.
+    if (h->opt_spread_nodes && d->n_nodes > 0 && d->topo.n > 0) {
+      uint32_t why = 0;
+      if (!(!any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = 34;
+      if (!why) why = node_stage_declines(d, P.dict, req_words);
+      std::vector<uint8_t> dom((size_t)d->n_keys * d->n_nodes, 0xFF);
+      bool any_taint = false;
+      for (uint32_t e = 0; e < d->n_nodes; ++e) any_taint = any_taint || d->node_taints[e] != 0;
+      for (uint32_t g = 0; g < d->topo.n && !why; ++g) {
+        if (d->topo.filter_taint_honor[g] && any_taint) { why = 43; break; }
+        const int32_t k = d->topo.key[g];
+        if (k < 0 || dom[(size_t)k * d->n_nodes] != 0xFF) continue;   // the hostname, or a key an earlier group filled in
+        for (uint32_t e = 0; e < d->n_nodes && !why; ++e) {
+          if (!((d->node_reqs.defined[e] >> k) & 1u)) { why = 35; break; }
+          const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
+          int z = -1;
+          for (uint32_t x = P.dict.key_word_off[k]; x < P.dict.key_word_off[k + 1]; ++x) if (nm[x]) { z = (int)(x - P.dict.key_word_off[k]) * 64 + __builtin_ctzll(nm[x]); break; }
+          if (z < 0 || z >= ks::kTopoMaxDom) { why = 36; break; }
+          dom[(size_t)k * d->n_nodes + e] = (uint8_t)z;
+        }
+      }
+      h->fast_reason = why;
+      if (!why) { P.plain_topo = 1; h->tw.nd.dom = up(h, dom.data(), dom.size()); h->tw.nd.hword = dz<uint64_t>(h, d->n_nodes); }
     }
 #ifdef KSOLVE_NO_LITE
     P.lite = 0;   // A/B builds only
@@ -1990,15 +2028,17 @@ static ks::FastRequeueArgs fast_requeue_args(ksolve_handle* h) {
                              h->pv.sorted_pods, h->fw.nodes};
 }
 
-// The cursor engine's existing-node stage (node_stage.h) between the queue kernels and the loop: the static (class, node) rows,
-// ksolve_pack_nodes, and the compacted queue the loop then reads. The rows are a function of the problem, but they are indexed by
-// class id, and class ids are drawn from an atomic counter by the rows that open a hash slot (kernels.h row_hash_body): the numbering
-// differs from solve to solve on the device. So the rows are computed with every solve's classes (one wavefront per 64 nodes x 32
-// classes: microseconds); the handle keeps the buffer.
-static void fast_nodes_stage(ksolve_handle* h) {
+// The static (class, node) rows of the fast engines' node paths (node_stage.h, topo_nodes.h). They are a function of the problem, but
+// they are indexed by class id, and class ids are drawn from an atomic counter by the rows that open a hash slot (kernels.h
+// row_hash_body): the numbering differs from solve to solve on the device. So the rows are computed with every solve's classes (one
+// wavefront per 64 nodes x 32 classes: microseconds); the handle keeps the buffer.
+static void node_static_rows(ksolve_handle* h) {
   ks::ProblemView& P = h->pv;
   const uint32_t ne = h->n_nodes, nw = (uint32_t)P.node_words, nc = h->n_classes;
-  if (!h->nd_dead0 || h->nd_dead0_classes < nc) { h->nd_dead0 = dz<uint64_t>(h, (size_t)nc * nw); h->nd_dead0_classes = nc; }
+  if (!h->nd_dead0 || h->nd_dead0_classes < nc) {
+    h->nd_dead0 = dz<uint64_t>(h, (size_t)nc * nw); h->nd_dead0_classes = nc;
+    if (h->tw.nd.dom) { h->tw.nd.alive = dz<uint64_t>(h, (size_t)nc * nw); h->tw.nd.cursor = dz<uint32_t>(h, nc); }   // (the spread engine's node path: per class too)
+  }
   {
     uint64_t* dead0 = h->nd_dead0;
     ks::NodeDeadArgs a{};
@@ -2010,9 +2050,16 @@ static void fast_nodes_stage(ksolve_handle* h) {
     a.dead0 = dead0;
     be_launch_node_dead0(h, (int)nw, a);
   }
+}
+// The cursor engine's existing-node stage (node_stage.h) between the queue kernels and the loop: the static rows, ksolve_pack_nodes,
+// and the compacted queue the loop then reads.
+static void fast_nodes_stage(ksolve_handle* h) {
+  ks::ProblemView& P = h->pv;
+  const uint32_t nc = h->n_classes;
+  node_static_rows(h);
   h->fw.nd_dead0 = h->nd_dead0;
   be_fill(h, h->fw.cls_first, 0xFF, (size_t)nc * 4); be_fill(h, h->fw.cls_last, 0, (size_t)nc * 4);   // (the compacted queue's, rebuilt behind the stage)
-  be_launch_pack_nodes(h, ks::node_stage_hbm((int)nc, (int)ne, (int)h->n_res));
+  be_launch_pack_nodes(h, ks::node_stage_hbm((int)nc, (int)h->n_nodes, (int)h->n_res));
   // From here to the end of the solve the queue IS the compacted one: entry j is pod nd_pod[j]. The loop's record and the scatter of
   // its results (be_launch_fast_records) read the queue's pods through the view; solve_prepare sorts the queue anew for every solve.
   P.sorted_pods = h->fw.nd_pod;
@@ -2026,7 +2073,8 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
   ksolve_status st = solve_prepare(h, fresh_context);
   if (st != KSOLVE_OK) return st;
   if (h->opts.engine == 6 && !(h->tw.enabled && h->n_pods && h->n_classes))
-    return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)");
+    return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)" +
+                (h->opt_spread_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
   if (h->opts.engine >= 2 && h->opts.engine != 6 && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
     return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
                 (h->opt_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
@@ -2040,7 +2088,13 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
     // the spread engine first; status 3 = "not my shape / stopped before any result": the general engine takes over
     alloc_run_order(h);
     be_tic(h, T_PACK);
-    be_launch_pack_topo(h);
+    if (h->tw.nd.dom) {
+      // existing nodes (engine 9 / 10): the static (class, node) rows for this solve's classes, then the kernel with the node path.
+      // It resets the nodes' remaining resources, pod counts and counters from the pristine tables itself.
+      node_static_rows(h);
+      h->tw.nd.dead0 = h->nd_dead0;
+      be_launch_pack_topo_nodes(h);
+    } else be_launch_pack_topo(h);
     be_toc(h, T_PACK);
     int status = 0, n_claims = 0;
     be_d2h(h, &status, h->ws.status_out, 4);
@@ -2049,7 +2103,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
     if (be_ok(h) && status != 3 && status != 1) {
       h->engine_used = 3;
       h->fast_reason = 0; h->fast_attempts = 1;
-      if (n_claims) be_launch_fast_records(h, n_claims);
+      if (n_claims || h->tw.nd.dom) be_launch_fast_records(h, n_claims);   // (pods on existing nodes are scattered with the queue's results even when no claim was opened)
       return solve_finish(h, out);
     }
     if (be_ok(h) && status == 3) {
@@ -2159,8 +2213,8 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i] != KSOLVE_OK || !hs[i]->n_pods) continue;
     ksolve_handle* h = hs[i];
-    if (h->tw.enabled && h->daemon_groups && h->n_classes) {
-      // a DaemonSet problem of the spread engine's shape: alone through solve(), so that the batch runs the engine ksolve_solve would
+    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom) && h->n_classes) {
+      // a DaemonSet problem of the spread engine's shape, or one with existing nodes (engine 9 / 10): alone through solve(), so that the batch runs the engine ksolve_solve would
       be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1;
     }
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
@@ -2272,7 +2326,8 @@ static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksol
 }  // namespace ksi
 
 #ifdef KSOLVE_HOST_EMULATION
-// The host emulation's launch of the stage (the other launches of the emulation live with its backend): a kernel launch is a loop over its grid.
+#include "topo_engine.h"
+// The host emulation's launches of the node kernels (the other launches of the emulation live with its backend): a kernel launch is a loop over its grid.
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
   const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
   std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
@@ -2283,5 +2338,13 @@ static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
   const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
   for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_requeue_body(i, q);
   for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_remark_body(i, q);
+}
+static void be_launch_pack_topo_nodes(ksolve_handle* h) {
+  std::vector<char> lds((size_t)h->tw.plan.total_bytes + 64, (char)0xA5);
+  ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
+  be_h2d(h, h->d_topo_args, &a, sizeof(a));
+  const ks::TopoArgs* a_ = h->d_topo_args;
+  ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data());
+  eng.solve();
 }
 #endif

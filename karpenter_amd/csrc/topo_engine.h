@@ -35,10 +35,13 @@
 #include "fast_engine.h"
 #include "run_order.h"
 #include "topo_types.h"
+#include "topo_nodes.h"
 
 namespace ks {
 
-template <class W>
+// NODES: the problem has existing nodes, and every pod is offered to them first (topo_nodes.h; kernel ksolve_pack_topo_nodes). The
+// code of the plain instantiation is what it was: every line of the node path stands behind `if constexpr (NODES)`.
+template <class W, bool NODES = false>
 struct TopoEngine {
   FastCold<W, 2, 1> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
   RunOrder<W> order;        // Go's sort.Slice permutation as one ring per pod count
@@ -302,10 +305,7 @@ struct TopoEngine {
       if (W::leader()) { const int32_t c = Z->cnt[z]; Z->cnt[z] = c + 1; if (c == 0) Z->nonzero = Z->nonzero + 1; Z->dom = Z->dom | f; }
     }
   }
-  KS_FN static uint64_t host_add(uint64_t hcnt, uint64_t hinc) {   // per-field +1, saturating at 7
-    const uint64_t full = hcnt & (hcnt >> 1) & (hcnt >> 2) & kTopoOnes;
-    return hcnt + (hinc & ~full);
-  }
+  KS_FN static uint64_t host_add(uint64_t hcnt, uint64_t hinc) { return topo_host_add(hcnt, hinc); }
   // a claim that now holds a member of the anti-affinity groups in `fields` leaves their lists
   KS_COLD void lists_remove(uint64_t fields, uint32_t x) {
     KS_LDS TopoState& S_ = *st;
@@ -585,6 +585,16 @@ struct TopoEngine {
     return list_t >= 0 ? scan_list(list_t, kc, zc, zkv, zd, zkw) : scan_order(kc, zc, zkv, zd, zkw);
   }
   KS_COLD void sort_cold() { order.sort(); }
+  // NODES: addToExistingNode (scheduler.go:614-656) for a pod of class k — the candidate domains of the groups it is tested against,
+  // as the claim test below evaluates them, then the node scan and the commit (topo_nodes.h). node < 0: no node takes the pod.
+  KS_COLD TopoNodePick node_step(uint32_t k, uint64_t cvmask, uint64_t hlim, uint64_t hinc, uint64_t zsel, int zg0, int zg1, uint32_t zselfw) {
+    LaneVar<uint64_t> zkv;
+    bool p0 = true, p1 = true;
+    const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, cvmask, zkv, p0);
+    const ZChoice zd = choose_domains(zg1, (zselfw & 2u) != 0, cvmask, zkv, p1);
+    if (!p0 || !p1) { TopoNodePick none; none.node = -1; none.slot = 0; return none; }   // (no domain anywhere: the claim path stops with reason 27)
+    return topo_nodes_place<W>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm);
+  }
 
   KS_COLD void finish(int status, unsigned long long steps) {
     const Workspace& S = *Sk; const FastWork& F = *Fk;
@@ -648,6 +658,7 @@ struct TopoEngine {
       const int why2 = (int)W::uniform((uint64_t)(uint32_t)setup_topo());
       if (why2) { bail = why2; finish(3, 0); return; }
     }
+    if constexpr (NODES) topo_nodes_init<W>(Pk, Sk, Tk);
     const int np = fast_uniform(Pk->n_pods);
     const int max_claims = fast_uniform(Sk->max_claims);
     KS_GLOBAL TopoRec* const rec = (KS_GLOBAL TopoRec*)fast_uniform(Tk->rec);
@@ -741,6 +752,16 @@ struct TopoEngine {
         c_tok.at(l) = (uint32_t)v4;
         oclaim.at(l) = 0xFFFFFFFFu; ocntv.at(l) = 0;
       });
+      // NODES: the class id of each pod, bit 31: no node can take the class any more (its cursor is at the end, and cursors only grow)
+      [[maybe_unused]] LaneVar<uint32_t> c_node;
+      if constexpr (NODES) {
+        const KS_GLOBAL uint32_t* const gcur = (const KS_GLOBAL uint32_t*)fast_uniform(Tk->nd.cursor);
+        const uint32_t nwn = (uint32_t)fast_uniform(Pk->node_words);
+        W::each([&](int l) {
+          const uint32_t k = gqcls[base + (l < bn ? l : bn - 1)] & ~kFastLastBit;
+          c_node.at(l) = k | (gcur[k] >= nwn ? 0x80000000u : 0u);
+        });
+      }
       if (cancel) {
         // > 0: ksolve_cancel / the deadline; < 0 (tests only, KSOLVE_TEST_CANCEL_AT): as if the cancel landed once -flag pods were placed
         const int cv = fast_uniform((int)W::poll_flag(cancel));
@@ -752,6 +773,23 @@ struct TopoEngine {
         steps++;
         unsigned long long tq = W::clock();
 #define KS_TSEC(acc) { const unsigned long long tn_ = W::clock(); acc += tn_ - tq; tq = tn_; }
+        if constexpr (NODES) {
+          // ---- addToExistingNode (scheduler.go:594, :614-656): the nodes first. A pod that lands on one never reaches sort.Slice
+          // (scheduler.go:598): a move that is pending in `order` stays pending, and the last move stays the last ----
+          const uint32_t kn = c_node.bcast(bi);
+          if (!(kn >> 31)) {
+            const int zgn = c_zg.bcast(bi);
+            const TopoNodePick pk = node_step(kn, c_cvm.bcast(bi), c_hlim.bcast(bi), c_hinc.bcast(bi), c_zsel.bcast(bi),
+                                              (int)(int16_t)(uint16_t)(uint32_t)zgn, (int)(int16_t)(uint16_t)((uint32_t)zgn >> 16), c_zself.bcast(bi));
+            const int node = fast_uniform(pk.node);   // (the node path reads and writes tables of its own and ends with a fence: nothing of the loop's state to hand over)
+            if (node >= 0) {
+              ref += (unsigned long long)node + 1;
+              oclaim.set(bi, (uint32_t)(-2 - node)); ocntv.set(bi, (uint32_t)fast_uniform((int)pk.slot));   // Results.pod_assignment = -2 - node
+              continue;
+            }
+          }
+          ref += (unsigned long long)Pk->n_nodes;   // every node was evaluated
+        }
         if (pending) {   // scheduler.go:598: a move pdqsort makes the long way
           fence(); push(); sort_cold(); pull(); wvalid = false;
           if (fast_uniform((int)order.overflow)) { status = 1; break; }

@@ -1,5 +1,5 @@
 // topo_types.h — what the host side (ksolve_impl.h: buffers, LDS plan, kernel arguments) shares with the spread engine
-// (topo_engine.h, compiled into ksolve_pack_topo.hip and the test emulation only).
+// (topo_engine.h, compiled into ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip and the test emulation only).
 #pragma once
 #include "fast_engine.h"
 #include "run_order.h"
@@ -14,6 +14,10 @@ constexpr int kTopoTrack = 4;         // anti-affinity counters with a list of t
 constexpr int kTopoFreeCap = 1024;    // entries of such a list (more: the list is dropped, its classes scan the order)
 constexpr uint64_t kTopoGuard = 0x8888888888888888ull, kTopoOnes = 0x1111111111111111ull;
 
+KS_FN uint64_t topo_host_add(uint64_t hcnt, uint64_t hinc) {   // per-field +1, saturating at 7
+  const uint64_t full = hcnt & (hcnt >> 1) & (hcnt >> 2) & kTopoOnes;
+  return hcnt + (hinc & ~full);
+}
 struct TopoRec { uint64_t vmask; int32_t req[4]; uint64_t hcnt; };   // 32 B: an in-flight claim (requirement set, requests, hostname-group counters)
 // a pod class's topology: limits on the hostname counters it is tested against (field = 8 | limit; 8 | 7 where it has none),
 // the counters and dictionary-key groups a pod of the class is counted by, the dictionary-key group it owns
@@ -39,7 +43,16 @@ struct TopoState {   // LDS
   int32_t last[4];                    // the move of the last step: kind (1: a claim gained a pod, 2: a new claim, 0: pending in the order / none), claim, position it left
 };
 struct TopoPlan { int total_bytes, off_run, off_state; };   // (the cursor engine's tables sit where FastWork::plan says)
-struct TopoWork { TopoClass* cls; TopoRec* rec; TopoPlan plan; int enabled; };
+// The existing-node path of the spread engine (topo_nodes.h, kernel ksolve_pack_topo_nodes), all in HBM; dom == null: the problem has
+// no nodes (or the engine may not take them: engines 0 and 6). Reset by the kernel at the start of every solve.
+struct TopoNodes {
+  uint64_t* alive;        // [n_classes][node_words] nodes that have not failed the class on a test that only moves towards rejection
+  uint32_t* cursor;       // [n_classes] first 64-node block whose alive word is not zero (node_words: none)
+  uint64_t* hword;        // [n_nodes] the node's hostname-group counters, laid out like TopoRec::hcnt
+  const uint8_t* dom;     // [n_keys][n_nodes] the node's domain on a dictionary key some group uses: the value's bit inside the key's words
+  const uint64_t* dead0;  // [n_classes][node_words] the static (class, node) verdicts (ksolve_node_dead0) for this solve's class ids
+};
+struct TopoWork { TopoClass* cls; TopoRec* rec; TopoPlan plan; int enabled; TopoNodes nd; };
 struct TopoArgs { ProblemView pv; Workspace ws; FastWork fw; TopoWork tw; };
 
 }  // namespace ks

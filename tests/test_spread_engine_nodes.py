@@ -1,0 +1,237 @@
+"""CPU tests of the spread engine's existing-node path (csrc/topo_nodes.h, engine "spread-nodes" / "auto-nodes-spread"): through
+the host emulation of the device code (tests/emu, test infrastructure only), the real C ABI and the real flattener, against the
+oracle claim by claim, node by node and in the reference-equivalent evaluation count. The device run is
+tests/test_gpu_spread_nodes.py."""
+import pytest
+
+import parity
+import spread_node_cases as sn
+from karpenter_amd import fixtures as fx
+from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported
+from test_device_algorithm import emu  # noqa: F401  (fixture)
+
+
+@pytest.mark.parametrize("daemonsets", [False, True])
+@pytest.mark.parametrize("cfg,n_nodes,plain,with_ds", sn.MIX)
+def test_the_benchmark_mix_with_nodes(oracle, emu, cfg, n_nodes, plain, with_ds, daemonsets):
+    got, want = sn.check_engine(oracle, emu, sn.mix_problem(cfg, n_nodes, daemonsets))
+    assert not want["podErrors"]
+    assert (sn.on_nodes(want), len(want["newNodeClaims"])) == (with_ds if daemonsets else plain)
+    assert sn.on_nodes(got) > 0 and got["newNodeClaims"]
+
+
+@pytest.mark.parametrize("n_nodes", sn.BLOCK_EDGES)
+def test_block_edges(oracle, emu, n_nodes):
+    got, want = sn.check_engine(oracle, emu, sn.block_edge_problem(n_nodes))
+    assert not want["podErrors"] and want["newNodeClaims"]
+    assert f"node-{n_nodes - 1:04d}" in {e["name"] for e in want["existingNodes"] if e["pods"]}   # the last block's last node holds a pod
+    assert sn.on_nodes(want) == 2 * n_nodes                                                        # hostname spread, maxSkew 2
+
+
+def test_a_node_refuses_and_later_accepts(oracle, emu):
+    prob = sn.refuse_then_accept_problem()
+    got, want = sn.check_engine(oracle, emu, prob)
+    assert not want["podErrors"] and sn.node_then_claim_then_node(want, prob)
+
+
+def _by_node(res):
+    return {e["name"]: len(e["pods"]) for e in res["existingNodes"]}
+
+
+def test_hostname_spread_counts_bound_pods(oracle, emu):
+    """node-0 already holds two matching pods: with maxSkew 2 it takes none, node-1 takes two, the rest go to NodeClaims."""
+    lab = {"app": "h"}
+    its = fx.fake_instance_types(8)
+    nodes = [fx.state_node(f"node-{i}", its[5], "test-zone-1", "on-demand", "default") for i in range(2)]
+    bound = [fx.pod(labels=lab, requests={"cpu": "100m"}, phase="Running", node_name="node-0") for _ in range(2)]
+    pods = [fx.pod(labels=lab, requests={"cpu": "200m"}, topology_spread=[fx.spread(fx.HOSTNAME, lab, max_skew=2)]) for _ in range(5)]
+    prob = fx.problem(its, [fx.node_pool()], pods, state_nodes=nodes, cluster_pods=bound)
+    want = oracle.solve(prob)
+    assert _by_node(want).get("node-0", 0) == 0 and _by_node(want)["node-1"] == 2 and want["newNodeClaims"] and not want["podErrors"]
+    sn.check_engine(oracle, emu, prob)
+
+
+def test_hostname_anti_affinity(oracle, emu):
+    """A node with a member repels, empty nodes take one each."""
+    lab = {"app": "aa"}
+    its = fx.fake_instance_types(8)
+    nodes = [fx.state_node(f"node-{i}", its[5], "test-zone-1", "on-demand", "default") for i in range(3)]
+    bound = [fx.pod(labels=lab, requests={"cpu": "100m"}, phase="Running", node_name="node-1")]
+    pods = [fx.pod(labels=lab, requests={"cpu": "200m"}, pod_anti_requirements=[fx.affinity_term(fx.HOSTNAME, lab)]) for _ in range(4)]
+    prob = fx.problem(its, [fx.node_pool()], pods, state_nodes=nodes, cluster_pods=bound)
+    want = oracle.solve(prob)
+    assert {k: v for k, v in _by_node(want).items() if v} == {"node-0": 1, "node-2": 1}
+    assert len(want["newNodeClaims"]) == 2 and not want["podErrors"]
+    sn.check_engine(oracle, emu, prob)
+
+
+def test_zonal_affinity_follows_a_bound_pod(oracle, emu):
+    """The pod to be affine to is bound in zone 2: the pods go to the zone-2 node first, then to NodeClaims in zone 2."""
+    lab = {"app": "af"}
+    its = fx.fake_instance_types(8)
+    nodes = [fx.state_node(f"node-{i}", its[2], f"test-zone-{1 + i}", "on-demand", "default") for i in range(3)]
+    bound = [fx.pod(labels=lab, requests={"cpu": "100m"}, phase="Running", node_name="node-1")]
+    pods = [fx.pod(labels=lab, requests={"cpu": "1"}, pod_requirements=[fx.affinity_term(fx.ZONE, lab)]) for _ in range(6)]
+    prob = fx.problem(its, [fx.node_pool()], pods, state_nodes=nodes, cluster_pods=bound)
+    want = oracle.solve(prob)
+    took = {k: v for k, v in _by_node(want).items() if v}
+    assert set(took) == {"node-1"} and want["newNodeClaims"] and not want["podErrors"]
+    for c in want["newNodeClaims"]:
+        assert [r["values"] for r in c["requirements"] if r["key"] == fx.ZONE] == [["test-zone-2"]]
+    sn.check_engine(oracle, emu, prob)
+
+
+def test_zonal_anti_affinity_with_its_inverse(oracle, emu):
+    """A pod with zonal anti-affinity against app=z lands on the zone-1 node and blocks the zone; the app=z pods (selected by the
+    inverse group) then avoid the zone-1 nodes and take the zone-2 node."""
+    its = fx.fake_instance_types(8)
+    nodes = [fx.state_node("node-0", its[5], "test-zone-1", "on-demand", "default"),
+             fx.state_node("node-1", its[5], "test-zone-1", "on-demand", "default"),
+             fx.state_node("node-2", its[2], "test-zone-2", "on-demand", "default")]
+    lonely = fx.pod(labels={"role": "lonely"}, requests={"cpu": "2"}, pod_anti_requirements=[fx.affinity_term(fx.ZONE, {"app": "z"})])
+    others = [fx.pod(labels={"app": "z"}, requests={"cpu": "500m"}) for _ in range(5)]
+    prob = fx.problem(its, [fx.node_pool()], [lonely] + others, state_nodes=nodes)
+    want = oracle.solve(prob)
+    took = {k: v for k, v in _by_node(want).items() if v}
+    assert took.get("node-0") == 1 and "node-1" not in took and took.get("node-2", 0) >= 1 and not want["podErrors"]
+    sn.check_engine(oracle, emu, prob)
+
+
+def test_two_passes_through_launch(oracle, emu):
+    """The first pass's NodeClaims become nodes with their pods bound; the second pass spreads against them."""
+    its = fx.fake_instance_types(8)
+    lab = {"app": "two"}
+    mk = lambda n, cpu: [fx.pod(labels=lab, requests={"cpu": cpu}, topology_spread=[fx.spread(fx.ZONE, lab), fx.spread(fx.HOSTNAME, lab, max_skew=3)]) for _ in range(n)]
+    first_pods = mk(3, "400m")    # one NodeClaim per zone, each launched as the cheapest type that holds its pod: room for one more
+    first = oracle.solve(fx.problem(its, [fx.node_pool()], first_pods))
+    assert not first["podErrors"]
+    nodes, bound = fx.launch(first, its, first_pods)
+    prob = fx.problem(its, [fx.node_pool()], mk(12, "300m"), state_nodes=nodes, cluster_pods=bound)
+    want = oracle.solve(prob)
+    assert sn.on_nodes(want) > 0 and want["newNodeClaims"] and not want["podErrors"]
+    sn.check_engine(oracle, emu, prob)
+
+
+def _declined(oracle, emu, prob, reason):
+    with pytest.raises(Unsupported, match="spread engine"):
+        sn.solve(prob, "spread-nodes", emu)
+    auto = sn.solve(prob, "auto-nodes-spread", emu)
+    assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == reason, auto["counters"]
+    sn.same(auto, oracle.solve(prob), prob)
+
+
+TAINT = {"key": "dedicated", "value": "batch", "effect": "NoSchedule"}
+
+
+def test_declines(oracle, emu):
+    its = fx.fake_instance_types(8)
+    lab = {"app": "d"}
+    node = fx.state_node("node-0", its[5], "test-zone-1", "on-demand", "default", used={"cpu": "500m", "pods": "1"})
+    zonal = [fx.pod(labels=lab, requests={"cpu": "300m"}, topology_spread=[fx.spread(fx.ZONE, lab)]) for _ in range(6)]
+    # a node without the zone label under zonal spread
+    bare = fx.state_node("node-1", its[5], "test-zone-1", "on-demand", "default")
+    del bare["labels"][fx.ZONE]
+    _declined(oracle, emu, fx.problem(its, [fx.node_pool()], zonal, state_nodes=[node, bare]), 35)
+    # a tainted node while a group honours nodeTaintsPolicy
+    tainted = fx.state_node("node-2", its[5], "test-zone-2", "on-demand", "default", taints=[TAINT])
+    honor = [fx.pod(labels=lab, requests={"cpu": "300m"}, topology_spread=[fx.spread(fx.ZONE, lab, taints_policy="Honor")]) for _ in range(6)]
+    _declined(oracle, emu, fx.problem(its, [fx.node_pool()], honor, state_nodes=[node, tainted]), 43)
+    # a host port: outside the spread engine's shape with or without nodes
+    ported = zonal + [fx.pod(requests={"cpu": "1"}, host_ports=[8080]) for _ in range(2)]
+    _declined(oracle, emu, fx.problem(its, [fx.node_pool()], ported, state_nodes=[node]), 34)
+    # an unschedulable pod: the engine stops at run time (27), the general engine re-solves from pristine nodes
+    huge = zonal + [fx.pod(requests={"cpu": "1000"})]
+    prob = fx.problem(its, [fx.node_pool()], huge, state_nodes=[node])
+    _declined(oracle, emu, prob, 27)
+    want = oracle.solve(prob)
+    assert len(want["podErrors"]) == 1 and sn.on_nodes(want) > 0
+
+
+def test_the_decline_mix(oracle, emu):
+    """The benchmark mix the issue keeps for this test: 130 nearly full nodes leave pods unschedulable — the spread engine stops, the
+    general engine's answer from pristine nodes equals the oracle."""
+    prob = fx.with_existing_nodes(fx.config3(pods=2500, n_types=60, seed=9), 130, seed=3, fill=(0.5, 1.0))
+    want = oracle.solve(prob)
+    assert want["podErrors"] and sn.on_nodes(want) > 0
+    auto = sn.solve(prob, "auto-nodes-spread", emu)
+    assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == 27
+    sn.same(auto, want, prob)
+
+
+def test_other_engines_are_unchanged(oracle, emu):
+    prob = sn.block_edge_problem(5)
+    with pytest.raises(Unsupported, match="spread engine"):                 # 6 still refuses a problem with nodes
+        sn.solve(prob, "spread", emu)
+    c = sn.solve(prob, "auto-nodes", emu)["counters"]                       # 7 still answers nodes + topology with general / 34
+    assert c["engine"] == "general" and c["engineFallbackReason"] == 34
+    assert sn.solve(prob, "auto", emu)["counters"]["engine"] == "general"
+    # nodes and no topology: the cursor engine with its node stage under 9, as under 7
+    plain = fx.with_existing_nodes(fx.config2(pods=600, n_types=60, seed=4), 20, seed=3)
+    got = sn.solve(plain, "auto-nodes-spread", emu)
+    assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0 and sn.on_nodes(got) > 0
+    sn.same(got, oracle.solve(plain), plain)
+    with pytest.raises(Unsupported, match="spread engine"):
+        sn.solve(plain, "spread-nodes", emu)
+    # topology and no nodes: the kernel without the node path, the same counters as under 0 / 6
+    topo = fx.config3(pods=600, n_types=60, seed=2)
+    keys = ("binEvaluations", "slowSorts", "referenceBinEvaluations", "pops")
+    for new, old in (("auto-nodes-spread", "auto"), ("spread-nodes", "spread")):
+        a, b = sn.solve(topo, new, emu), sn.solve(topo, old, emu)
+        assert a["counters"]["engine"] == b["counters"]["engine"] == "spread"
+        assert [a["counters"][k] for k in keys] == [b["counters"][k] for k in keys]
+        assert parity.results_digest(a)[0] == parity.results_digest(b)[0]
+
+
+def test_step_limit(oracle, emu):
+    """maxSteps (the ctx deadline's stand-in): a step is a queue pop, whether the pod lands on a node or on a NodeClaim."""
+    prob = sn.mix_problem((1500, 144, 5), 40)
+    full = sn.solve(prob, "spread-nodes", emu)
+    assert 200 < sn.on_nodes(full) < 1400
+    for steps in (1, 5, 63, 64, 65, 200, 777, 1499):     # (the queue's first pods land on nodes: the small limits lie inside a run of node placements)
+        opts = dict(prob, options=dict(prob["options"], maxSteps=steps))
+        s, g = sn.solve(opts, "spread-nodes", emu), sn.solve(opts, "general", emu)
+        assert s["counters"]["engine"] == "spread" and s["timedOut"] and g["timedOut"], steps
+        parity.assert_same_results(s, g)
+        assert s["scheduledPods"] == g["scheduledPods"] == steps and s["counters"]["pops"] == g["counters"]["pops"]
+        assert s["counters"]["referenceBinEvaluations"] == g["counters"]["referenceBinEvaluations"]
+    assert sn.on_nodes(sn.solve(dict(prob, options=dict(prob["options"], maxSteps=5)), "spread-nodes", emu)) == 5
+    s = sn.solve(dict(prob, options=dict(prob["options"], maxSteps=1500)), "spread-nodes", emu)
+    assert not s["timedOut"]
+    sn.same(s, oracle.solve(prob), prob)
+
+
+def test_repeated_solves_and_batches(oracle, emu):
+    prob = sn.mix_problem((1500, 144, 5), 40, daemonsets=True)
+    s = NewScheduler(dict(prob, options=dict(prob["options"], engine="auto-nodes-spread")), solver_lib=emu)
+    digests = set()
+    for _ in range(5):
+        r = s.Solve()
+        assert r["counters"]["engine"] == "spread" and r["counters"]["engineFallbackReason"] == 0
+        digests.add(parity.results_digest(r)[0])
+    s.close()
+    assert len(digests) == 1
+    sn.same(r, oracle.solve(prob), prob)
+    # ksolve_solve_batch: nodes + topology and nodes only run alone through solve(), plain ones in the batched cursor kernel
+    probs = [sn.mix_problem((300, 144, 1), 5), fx.with_existing_nodes(fx.config2(pods=800, n_types=60, seed=91), 30, seed=1),
+             fx.config2(pods=800, n_types=60, seed=92), sn.block_edge_problem(65), fx.config2(pods=500, n_types=60, seed=93)]
+    engines = ["spread", "cursor", "cursor", "spread", "cursor"]
+    scheds = [NewScheduler(dict(p, options=dict(p["options"], engine="auto-nodes-spread")), solver_lib=emu) for p in probs]
+    for _ in range(2):
+        got = SolveBatch(scheds)
+        assert [g["counters"]["engine"] for g in got] == engines
+        for g, p in zip(got, probs):
+            assert parity.results_digest(g)[0] == parity.results_digest(sn.solve(p, "auto-nodes-spread", emu))[0]
+            sn.same(g, oracle.solve(p), p)
+            assert (sn.on_nodes(g) > 0) == bool(p["stateNodes"])
+    for s in scheds:
+        s.close()
+
+
+SEEDS = list(range(48))
+
+
+def test_seeded_fuzz(oracle, emu):
+    cands, ran, placed, _ = sn.run_fuzz(oracle, emu, SEEDS)
+    assert cands >= 20, cands
+    assert ran * 3 >= cands * 2, (ran, cands)      # at least two thirds of the candidates on the spread engine, reason 0
+    assert placed > 0
