@@ -342,17 +342,10 @@ typedef struct {
   double us_upload, us_prepass, us_pack, us_finalize, us_download;
   double packing_cost;
   uint32_t engine_used;            /* 1 = general engine, 2 = cursor engine, 3 = spread engine */
-  uint32_t engine_fallback_reason; /* non-zero: why the cursor / spread engine handed the problem to the general engine (csrc/fast_engine.h
-                                    * setup(): 1-8; run time: 20-28; csrc/topo_engine.h setup_topo(): 40-51, run time: 60-62;
-                                    * the cursor engine's existing-node stage, engine 7 / 8 (csrc/node_stage.h): 30 = a node under
-                                    * consolidateAfter while some pod is neither pending nor from a deleting node, 31 = node requirement
-                                    * sets with bounds, 32 = a node label set that is not single-valued In, 33 = more pod classes than
-                                    * the stage keeps cursors for (12288), 34 = existing nodes, and otherwise outside the cursor engine's
-                                    * shape: topology, host ports, volumes, CSI volume limits, minValues, reservations, resident pods);
-                                    * the spread engine's existing-node path, engine 9 / 10 (csrc/topo_nodes.h): 30-32 and 34 as
-                                    * above (34 without "topology"), 35 = a node without a label for a dictionary key some topology
-                                    * group uses, 36 = a node whose value of such a key lies beyond the sixteen domains a group's
-                                    * counters hold, 43 = a group honours nodeTaintsPolicy and a node (not only a template) is tainted) */
+  uint32_t engine_fallback_reason; /* non-zero: why the cursor / spread engine handed the problem to the general engine. DESIGN.md, "Decline
+                                    * reasons", lists every value: 1-8 the engines' shape check, 20-28 the cursor engine's loop, 30-36 existing
+                                    * nodes (engines 7-10), 40-51 the spread engine's shape check, 60-62 its loop, 100 = more NodeClaims than
+                                    * max_claims */
   uint32_t cursor_wide;            /* engine_used == 2: the memory plan it ran with. 0 = claim state and order in LDS (~3,000 in-flight
                                     * NodeClaims); 1 = the claims' state in HBM (~15,000); 2 = their order too (65,472) */
   uint32_t cursor_attempts;        /* runs of the cursor engine this solve took: 1, or one more per plan it outgrew (a later solve of the

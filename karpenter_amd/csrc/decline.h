@@ -1,0 +1,58 @@
+// decline.h — why a fast engine (cursor: fast_engine.h, node_stage.h; spread: topo_engine.h, topo_nodes.h) handed a problem to the
+// general engine: the values of ksolve_results::engine_fallback_reason. The numbers are public output and do not change; DESIGN.md
+// ("Decline reasons") has the table with who raises each and what the handle does afterwards. Device and host code.
+#pragma once
+
+namespace ks {
+
+enum Decline : int {
+  DECLINE_KERNEL_CAPACITY = -1,        // inside a kernel only: more claims than Workspace::max_claims — the kernel ends with status 1, not 3, and the host reports DECLINE_CAPACITY
+  DECLINE_NONE = 0,                    // the fast engine solved the problem
+  // FastCold::setup(), for both engines
+  DECLINE_NOT_PLAIN = 1,               // outside the view's plain / plain_topo / plain_nodes, relaxation rows, more than 4 resources, 32 templates or kMaxItWords words of types
+  DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, DoesNotExist, Gt, Lt)
+  DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply)
+  DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
+  DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits
+  DECLINE_QUANTITY_RANGE = 7,          // an allocatable, effective allocatable or request outside 31 bits
+  DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive)
+  // the cursor engine's loop
+  DECLINE_CACHE_FULL = 20,             // no room for a requirement set's cache entry or Pareto vectors (a claim's acceptance words, a new class slot)
+  DECLINE_REFRESH_FAILED = 21,         // the same while the driver recomputed a claim's acceptance words
+  DECLINE_UNKNOWN_EVENT = 22,          // the loop returned an event the driver does not know
+  DECLINE_LIMIT_NODES = 23,            // a NodePool's `nodes` limit is used up (filterByRemainingResources, scheduler.go:1069-1085); both engines
+  DECLINE_LIMIT_EXCLUDES_TYPE = 24,    // a NodePool limit excludes an instance type of the template (scheduler.go:1069-1085); both engines
+  DECLINE_CACHE_FULL_NEW_CLAIM = 25,   // no room for the cache entry of a new claim's requirement set (addToNewNodeClaim, scheduler.go:695-790); both engines
+  DECLINE_CLAIM_SLOTS = 26,            // more in-flight claims than the cursor engine's memory plan holds: the host moves to the next plan
+  DECLINE_UNSCHEDULABLE_POD = 27,      // a pod no claim and no template takes: error codes and diagnostics are the general engine's; both engines
+  DECLINE_REFRESHER_DEAD = 28,         // two-wavefront kernel: the refresher wavefront does not answer
+  // existing nodes, decided by create() (cursor: engines 7 / 8, spread: engines 9 / 10)
+  DECLINE_NODE_CONSOLIDATE_AFTER = 30, // a node under consolidateAfter that some pod must skip (scheduler.go:628)
+  DECLINE_NODE_BOUNDS = 31,            // node requirement sets with Gt / Lt bounds
+  DECLINE_NODE_LABELS = 32,            // a node label set that is not single-valued In (existingnode.go:172-185 would change it)
+  DECLINE_NODE_CLASSES = 33,           // more pod classes than the node stage keeps cursors for (kNodeStageMaxClasses); decided by solve()
+  DECLINE_NODES_NOT_PLAIN = 34,        // existing nodes, and otherwise outside the engine's shape (host ports, volumes, minValues, reservations, resident pods ...)
+  DECLINE_NODE_LACKS_KEY = 35,         // spread: a node without a label for a dictionary key some topology group uses
+  DECLINE_NODE_DOMAIN_RANGE = 36,      // spread: a node whose value of such a key lies beyond the kTopoMaxDom domains a group's counters hold
+  // TopoEngine::setup_topo()
+  DECLINE_TOPO_GROUPS = 40,            // no topology group, more than kTopoMaxGroups, or aliased groups
+  DECLINE_TOPO_PREFERENCES = 41,       // a pod with preferences: podDomains = StrictRequirements differs from its requirements (topology.go:230)
+  DECLINE_TOPO_RELAXATION_GROUP = 42,  // a group created by a relaxing pod (topology.go:162-194)
+  DECLINE_TOPO_NODE_FILTER = 43,       // a group's TopologyNodeFilter can reject a claim or node (topologynodefilter.go:68-96); create() raises it for tainted nodes
+  DECLINE_TOPO_SKEW_RANGE = 44,        // dictionary-key spread: maxSkew outside 1..30000, or minDomains above 30000
+  DECLINE_TOPO_HOST_AFFINITY = 45,     // pod affinity on the hostname
+  DECLINE_TOPO_HOST_GROUPS = 46,       // more hostname groups than kTopoMaxHost
+  DECLINE_TOPO_HOST_SKEW = 47,         // hostname spread with maxSkew outside 1..6 (the counters saturate at 7)
+  DECLINE_TOPO_INVERSE_KIND = 48,      // an inverse group on a dictionary key that is not anti-affinity
+  DECLINE_TOPO_KEY_GROUPS = 49,        // more dictionary-key groups than kTopoMaxZg
+  DECLINE_TOPO_DOMAINS = 50,           // a group's key is not a packed variable key, or has more than kTopoMaxDom domains
+  DECLINE_TOPO_CLASS = 51,             // a pod class with a hostname limit outside 0..6 or three dictionary-key groups
+  // the spread engine's loop
+  DECLINE_TOPO_CACHE_FULL = 60,        // no room for a requirement set's cache entry (resolve)
+  DECLINE_TOPO_LIST_BEYOND_RINGS = 61, // a listed claim holds more pods than the LDS ring tables cover (kRunMaxCount)
+  DECLINE_TOPO_RUN_BEYOND_RINGS = 62,  // a run at the front of the order lies beyond the LDS ring tables
+  // the host
+  DECLINE_CAPACITY = 100,              // the kernel ended with status 1: more claims than max_claims — the general engine reports it (or moves to BIG)
+};
+
+}  // namespace ks

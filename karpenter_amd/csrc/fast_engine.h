@@ -92,7 +92,7 @@ struct FastNodes {
   uint32_t n_placed;      // pods placed on existing nodes (queue pops of the stage that the loop does not see)
   uint32_t limit_hit;     // the step limit ended the solve inside or right behind the stage's entries: the solve's status is "stopped" whatever the loop says
   uint32_t variant;       // 1: `remaining` and the nodes' pod counts in LDS, 2: in the HBM workspace (reported as phase_cycles[19])
-  uint32_t bail;          // a reason of fast_engine.h setup() the stage found first (a class that is not positive: 4, 8): the loop stops with it
+  uint32_t bail;          // a reason of fast_engine.h setup() the stage found first (a class that is not positive: DECLINE_CLASS_NOT_POSITIVE, DECLINE_CLASS_EMPTY_IN): the loop stops with it
   unsigned long long n_ref;     // candidate nodes the reference would have evaluated (scheduler.go:614-656)
   unsigned long long n_tests;   // (class, node) resource tests of the stage
 };
@@ -334,6 +334,50 @@ KS_FN bool fast_sampled(int n, int p) {   // choosePivot's nine positions (pdq_e
   return u - (q - 1) <= 2u || u - (2 * q - 1) <= 2u || u - (3 * q - 1) <= 2u;
 }
 
+// The NodePool-limit steps of addToNewNodeClaim (scheduler.go:695-790) for a claim of template t with limits lm =
+// tmpl_limit_mask[t] != 0, wave-level, shared by the new_claim of both engines (FastCold below, topo_engine.h). The callers read
+// lm once and skip both steps for a template without limits: a load here is a microsecond of the lone wavefront, per claim.
+// filterByRemainingResources (scheduler.go:1069-1085): the engines only continue while no type is excluded -> 0, or the reason
+template <class W>
+KS_FN int limits_exclude(const ProblemView& P, const Workspace& S, int t, uint32_t lm) {
+  const int nr = P.n_res, iw = P.it_words, n_its = P.n_its;
+  const int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+  if (((lm >> nr) & 1) && rem[nr] <= 0) return DECLINE_LIMIT_NODES;
+  const ProblemView& Pv = P;
+  const uint64_t* tits = S.t_its + (size_t)t * iw;
+  uint64_t excluded = 0;
+  for (int w = 0; w < iw; ++w) {
+    const uint64_t in = tits[w];
+    if (!in) continue;
+    excluded |= W::ballot([&](int l) {
+      const int it = w * 64 + l;
+      if (it >= n_its || !((in >> l) & 1)) return false;
+      bool v = true;
+      for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
+      return !v;
+    });
+  }
+  return excluded ? DECLINE_LIMIT_EXCLUDES_TYPE : DECLINE_NONE;
+}
+// subtractMax (scheduler.go:1049-1066) over the new claim's instance types: F(requirement set of cache entry eh) ∩ fits(size + daemon overhead)
+template <class W>
+KS_FN void subtract_max(const ProblemView& P, const Workspace& S, const FastWork& F, int t, uint32_t lm, int eh, const int32_t size[4]) {
+  const int nr = P.n_res, n_its = P.n_its;
+  int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+  const int64_t* eff = eff_alloc(P, t);
+  const uint64_t* eits = F.ent_its + (size_t)eh * P.it_words;
+  const ProblemView& Pv = P;
+  for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) {
+    const int64_t mx = W::reduce_max_i64(n_its, [&](int it) {
+      if (!((eits[it >> 6] >> (it & 63)) & 1)) return INT64_MIN;
+      for (int z = 0; z < nr; ++z) if (eff[(size_t)z * n_its + it] < (int64_t)size[z]) return INT64_MIN;
+      return Pv.it_cap[(size_t)q * n_its + it];
+    });
+    W::store(&rem[q], rem[q] - mx);
+  }
+  W::sync();
+}
+
 // Everything that happens rarely (a new requirement set, a new claim, a new class slot, pdqsort leaving its single-move
 // path): real function calls, so that their code and registers stay out of the loop that places a pod.
 // The loop's state between two events (LDS): scalars, the class slots (lane = slot: class id, cursor) and the 64-entry queue block
@@ -528,32 +572,32 @@ struct FastCold {
     return (int)h;
   }
 
-  // Returns 0 when the problem is of the shape this engine solves, a reason code otherwise. topo: on behalf of the spread engine
+  // Returns 0 when the problem is of the shape this engine solves, a reason (decline.h) otherwise. topo: on behalf of the spread engine
   // (topo_engine.h) — topology groups are its business, and the dictionary keys they spread over are variable keys too.
   KS_COLD int setup(bool topo = false) {
     const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
     const Dict& d = P.dict;
     const int nk = d.n_keys, iw = P.it_words, nr = P.n_res, n_its = P.n_its, nc = P.n_classes, T = P.n_templates;
     const ProblemView& Pv = P;
-    if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return 1;
+    if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
     // (instance types may use any operator: with positive sets on the claim side the NotIn / DoesNotExist escape of
     // requirements.go:260-265 never applies, so compatible() stays monotone)
     // templates: only In sets
-    if (W::reduce_or(T, [&](int t) { return (uint64_t)(Pv.tmpl_reqs.complement[t] | (Pv.tmpl_reqs.has_gte ? Pv.tmpl_reqs.has_gte[t] : 0) | (Pv.tmpl_reqs.has_lte ? Pv.tmpl_reqs.has_lte[t] : 0)); })) return 3;
+    if (W::reduce_or(T, [&](int t) { return (uint64_t)(Pv.tmpl_reqs.complement[t] | (Pv.tmpl_reqs.has_gte ? Pv.tmpl_reqs.has_gte[t] : 0) | (Pv.tmpl_reqs.has_lte ? Pv.tmpl_reqs.has_lte[t] : 0)); })) return DECLINE_TEMPLATE_NOT_POSITIVE;
     // classes: only In sets; the keys they define are the variable keys
-    if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return 4;
+    if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return DECLINE_CLASS_NOT_POSITIVE;
     uint32_t vk = (uint32_t)W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.defined[c]; });
     if (topo) vk |= (uint32_t)W::reduce_or(P.topo.n_groups, [&](int g) { return Pv.topo.key[g] >= 0 ? (uint64_t)1 << Pv.topo.key[g] : (uint64_t)0; });
-    if (d.key_hostname >= 0 && ((vk >> d.key_hostname) & 1u)) return 5;
-    if (d.key_it >= 0 && ((vk >> d.key_it) & 1u)) return 5;
+    if (d.key_hostname >= 0 && ((vk >> d.key_hostname) & 1u)) return DECLINE_SELECTS_HOST_OR_TYPE;
+    if (d.key_it >= 0 && ((vk >> d.key_it) & 1u)) return DECLINE_SELECTS_HOST_OR_TYPE;
     int bits = 0;
     nv = 0;
     for (int k = 0; k < nk; ++k) {
       if (!((vk >> k) & 1u)) continue;
-      if (d.key_word_off[k + 1] - d.key_word_off[k] != 1 || nv >= kFastMaxVar) return 6;
+      if (d.key_word_off[k + 1] - d.key_word_off[k] != 1 || nv >= kFastMaxVar) return DECLINE_KEYS_DO_NOT_PACK;
       const uint64_t valid = d.value_valid[d.key_word_off[k]];
       const int width = valid ? 64 - __builtin_clzll(valid) : 1;
-      if (bits + width + 1 > kFastVarBits) return 6;
+      if (bits + width + 1 > kFastVarBits) return DECLINE_KEYS_DO_NOT_PACK;
       if (W::leader()) {
         Mp->vkey[nv] = (uint8_t)k; Mp->voff[nv] = (uint8_t)bits; Mp->vwidth[nv] = (uint8_t)width; Mp->vword[nv] = (uint16_t)d.key_word_off[k];
         Mp->fmask[nv] = ((1ull << width) - 1) << bits;
@@ -570,13 +614,13 @@ struct FastCold {
     }
     W::sync();
     // every quantity in 31 bits
-    if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = Pv.it_alloc[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return 7;
+    if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = Pv.it_alloc[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return DECLINE_QUANTITY_RANGE;
     for (int t = 0; t < T; ++t) {   // ... the effective allocatable too (negative where a type cannot even hold its daemons)
       if (!((P.tmpl_ov >> t) & 1u)) continue;
       const int64_t* eff = eff_alloc(P, t);
-      if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = eff[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return 7;
+      if (W::reduce_or(nr * n_its, [&](int i) { const int64_t a = eff[i]; return (uint64_t)((a >= (1ll << 30) || a <= -(1ll << 30)) ? 1 : 0); })) return DECLINE_QUANTITY_RANGE;
     }
-    if (W::reduce_or(nr * nc, [&](int i) { const int64_t a = Pv.cls_requests[i]; return (uint64_t)((a >= (1ll << 30) || a < 0) ? 1 : 0); })) return 7;
+    if (W::reduce_or(nr * nc, [&](int i) { const int64_t a = Pv.cls_requests[i]; return (uint64_t)((a >= (1ll << 30) || a < 0) ? 1 : 0); })) return DECLINE_QUANTITY_RANGE;
     // templates: packed form, and NewScheduler's prefilter (scheduler.go:156-171) with positive sets
     KS_LDS FastMisc& Mm = *Mp;
     const int nvv = nv;
@@ -652,9 +696,9 @@ struct FastCold {
       fc[c] = s;
       return badc;
     });
-    if (bad) return 8;
+    if (bad) return DECLINE_CLASS_EMPTY_IN;
     W::for_n(kFastEnt, [&](int i) { ent[i].info = 0; ent[i].vmask = ~0ull; });   // (no requirement set is all ones: the top byte is a template id < 32)
-    return 0;
+    return DECLINE_NONE;
   }
 
   // CanAdd (nodeclaim.go:124-242) of a claim in state `st` for the classes in the 64 slots of row j, one lane each -> the claim's
@@ -682,7 +726,7 @@ struct FastCold {
       }, okb, miss, d0, d1);
       accm |= okb;
       todo = miss;
-      if (miss && create_entry(missv.bcast(ctz64(miss))) < 0) { bail_code = 20; return 0; }
+      if (miss && create_entry(missv.bcast(ctz64(miss))) < 0) { bail_code = DECLINE_CACHE_FULL; return 0; }
     }
     return accm;
   }
@@ -789,7 +833,7 @@ struct FastCold {
         }, okb, miss, d0, d1);
         accm |= okb;
         todo = miss;
-        if (miss && create_entry(missv.bcast(ctz64(miss))) < 0) { bail_code = 20; return -1; }
+        if (miss && create_entry(missv.bcast(ctz64(miss))) < 0) { bail_code = DECLINE_CACHE_FULL; return -1; }
       }
       W::each([&](int l) {
         if (x0 + l < nc) {
@@ -897,37 +941,17 @@ struct FastCold {
   }
 
   // addToNewNodeClaim (scheduler.go:695-790) for a pod no in-flight claim accepted: 1 = claim n created (appended to the
-  // order with one pod; its acceptance words computed), 0 = the engine must stop (bail_code; -1 = capacity).
+  // order with one pod; its acceptance words computed), 0 = the engine must stop (bail_code; DECLINE_KERNEL_CAPACITY = capacity).
   KS_COLD int new_claim(int slot, int bi, int n) {
     slot = (int)W::uniform((uint64_t)(uint32_t)slot); bi = (int)W::uniform((uint64_t)(uint32_t)bi); n = (int)W::uniform((uint64_t)(uint32_t)n);
     const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
     const FastSlot cs = lds_get(&aslot[slot]);
-    const int T = P.n_templates, nr = P.n_res, iw = P.it_words, cap = F.plan.cap;
+    const int T = P.n_templates, cap = F.plan.cap;
     n_ref_extra += (unsigned long long)n;
     for (int t = 0; t < T; ++t) {
       if (!((active_templates >> t) & 1u)) continue;
       const uint32_t lm = P.tmpl_limit_mask[t];
-      if (lm) {
-        // filterByRemainingResources (scheduler.go:1069-1085): this engine only continues while no type is excluded
-        int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
-        if (((lm >> nr) & 1) && rem[nr] <= 0) { bail_code = 23; return 0; }
-        const ProblemView& Pv = P;
-        const uint64_t* tits = S.t_its + (size_t)t * iw;
-        const int n_its = P.n_its;
-        uint64_t excluded = 0;
-        for (int w = 0; w < iw; ++w) {
-          const uint64_t in = tits[w];
-          if (!in) continue;
-          excluded |= W::ballot([&](int l) {
-            const int it = w * 64 + l;
-            if (it >= n_its || !((in >> l) & 1)) return false;
-            bool v = true;
-            for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
-            return !v;
-          });
-        }
-        if (excluded) { bail_code = 24; return 0; }
-      }
+      if (lm) { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail_code = why; return 0; } }
       host_seq++;
       n_ref_extra++;
       if (!((cs.tmplok >> t) & 1u)) continue;
@@ -935,11 +959,11 @@ struct FastCold {
       if (!fast_fields_ok(m, cs.dmask)) continue;
       FastEnt e;
       int eh = fast_lookup(ent, m, e);
-      if (eh < 0) { eh = create_entry(m); if (eh < 0) { bail_code = 25; return 0; } e = lds_get(&ent[eh]); }
+      if (eh < 0) { eh = create_entry(m); if (eh < 0) { bail_code = DECLINE_CACHE_FULL_NEW_CLAIM; return 0; } e = lds_get(&ent[eh]); }
       const int32_t zero[4] = {0, 0, 0, 0};
       if (!fast_fits(pool, e, zero, cs.size)) continue;
-      if (n_claims >= S.max_claims) { bail_code = -1; return 0; }   // capacity: reported as such
-      if (n_claims >= cap) { bail_code = 26; return 0; }
+      if (n_claims >= S.max_claims) { bail_code = DECLINE_KERNEL_CAPACITY; return 0; }   // capacity: reported as such
+      if (n_claims >= cap) { bail_code = DECLINE_CLAIM_SLOTS; return 0; }
       const int c = n_claims++;
       FastClaim ns;
       ns.vmask = m;
@@ -956,26 +980,10 @@ struct FastCold {
         if (W::leader()) { cst.put_acc((uint32_t)c, j, aw); Mp->acc[j] = aw; }
       }
       W::sync();
-      if (lm) {
-        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m) ∩ fits(size + daemon overhead)
-        int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
-        const int64_t* eff = eff_alloc(P, t);
-        const uint64_t* eits = F.ent_its + (size_t)eh * iw;
-        const ProblemView& Pv = P;
-        const int n_its = P.n_its;
-        for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) {
-          const int64_t mx = W::reduce_max_i64(n_its, [&](int it) {
-            if (!((eits[it >> 6] >> (it & 63)) & 1)) return INT64_MIN;
-            for (int z = 0; z < nr; ++z) if (eff[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
-            return Pv.it_cap[(size_t)q * n_its + it];
-          });
-          W::store(&rem[q], rem[q] - mx);
-        }
-        W::sync();
-      }
+      if (lm) subtract_max<W>(P, S, F, t, lm, eh, cs.size);
       return 1;
     }
-    bail_code = 27;   // an unschedulable pod: error codes and diagnostics come from the general engine
+    bail_code = DECLINE_UNSCHEDULABLE_POD;   // error codes and diagnostics come from the general engine
     return 0;
   }
 
@@ -1005,7 +1013,7 @@ struct FastCold {
     Counters c{};
     c.bin_evaluations = n_tests + n_cold_tests + nd.n_tests; c.full_evaluations = n_steps; c.queue_pops = steps + nd.n_placed; c.sorts = steps; c.slow_sorts = order.slow_sorts;
     c.column_resets = (unsigned long long)n_evict; c.ref_bin_evaluations = n_ref + n_ref_extra + nd.n_ref;
-    c.cycles[20] = (unsigned long long)(bail_code > 0 ? bail_code : 0);
+    c.decline = (unsigned long long)(bail_code > 0 ? bail_code : 0);
     if (tc) for (int i = 0; i < 16; ++i) c.cycles[i] = tc[i];
 #ifdef KSOLVE_PHASE_TIMERS
     for (int i = 0; i < 4; ++i) c.cycles[16 + i] = hs->hw[i];
@@ -2021,13 +2029,13 @@ struct FastEngine {
       const bool place_now = use_fast && fast_uniform(h->pend_new) != 0 && fast_uniform(h->bi) < fast_uniform(h->bn) && fast_uniform(h->status) == 0;
       int ev = place_now ? (int)FEV_PLACE : use_fast ? fast_uniform(fast_hot_run<W, GS, R, HP>(cx)) : (int)FEV_SLOW;
       t_fast += W::clock() - tf0; n_fast++;
-      if (HP && ev == FEV_DEAD) { cold.bail_code = 28; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }   // (the refresher wavefront does not answer)
+      if (HP && ev == FEV_DEAD) { cold.bail_code = DECLINE_REFRESHER_DEAD; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }   // (the refresher wavefront does not answer)
       if (use_fast && fast_uniform(h->rf_x) >= 0) {
         const int rx = fast_uniform(h->rf_x), rx2 = HP ? fast_uniform(h->rf_x2) : -1;
         if (W::leader()) { h->rf_x = -1; h->rf_x2 = -1; }
         W::sync();
-        if (fast_uniform(cold.refresh_claim(rx)) < 0) { cold.bail_code = 21; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
-        if (rx2 >= 0 && fast_uniform(cold.refresh_claim(rx2)) < 0) { cold.bail_code = 21; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
+        if (fast_uniform(cold.refresh_claim(rx)) < 0) { cold.bail_code = DECLINE_REFRESH_FAILED; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
+        if (rx2 >= 0 && fast_uniform(cold.refresh_claim(rx2)) < 0) { cold.bail_code = DECLINE_REFRESH_FAILED; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
         continue;
       }
       if (ev == FEV_SLOW) { const unsigned long long ts0 = W::clock(); ev = fast_uniform(fast_slow_run<W, GS, R>(cx, use_fast ? 1 : 0x7FFFFFFF)); t_slow += W::clock() - ts0; n_slow++; }
@@ -2035,7 +2043,7 @@ struct FastEngine {
       if (ev == FEV_DONE) break;
       const unsigned long long te0 = W::clock();
       if (ev == FEV_REFRESH) {
-        if (fast_uniform(cold.refresh_claim(fast_uniform(h->ev_arg))) < 0) { cold.bail_code = 21; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
+        if (fast_uniform(cold.refresh_claim(fast_uniform(h->ev_arg))) < 0) { cold.bail_code = DECLINE_REFRESH_FAILED; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
       } else if (ev == FEV_SLOT) {
         if (fast_uniform(cold.new_slot(fast_uniform(h->ev_arg))) < 0) { cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
       } else if (ev == FEV_SLOWSORT || ev == FEV_PLACE) {
@@ -2058,10 +2066,10 @@ struct FastEngine {
       } else if (ev == FEV_NEWCLAIM) {
         const int n = fast_uniform(h->n), bi = fast_uniform(h->bi);
         const int made = fast_uniform(cold.new_claim(fast_uniform(h->ev_arg), bi, n));
-        if (!made) { cold.finish(fast_uniform(cold.bail_code) < 0 ? 1 : 3, 0, (unsigned long long)fast_uniform(h->steps), 0, 0, 0, nullptr); return; }
+        if (!made) { cold.finish(fast_uniform(cold.bail_code) == DECLINE_KERNEL_CAPACITY ? 1 : 3, 0, (unsigned long long)fast_uniform(h->steps), 0, 0, 0, nullptr); return; }
         if (W::leader()) { h->oclaim[bi] = (uint32_t)n; h->ocnt[bi] = 0; h->n = n + 1; h->pend_new = 1; h->pend_a = 0x7FFFFFFF; h->bi = bi + 1; }   // (pend_a: the loop tests one flag)   // claim ids are handed out in creation order
         W::sync();
-      } else { cold.bail_code = 22; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
+      } else { cold.bail_code = DECLINE_UNKNOWN_EVENT; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
       if (ev >= 1 && ev <= 5) { tev[ev] += W::clock() - te0; nev[ev]++; }
     }
     // profiling builds (-DKSOLVE_PHASE_TIMERS): cycles inside the loop function, per event kind, in total; event counts

@@ -210,26 +210,26 @@ static bool any_nonzero(const uint32_t* p, uint32_t n) {
 
 static void fast_plan_set(ksolve_handle* h, int plan, int rows);   // the cursor engine's memory plan (0 LDS / 1 claim state in HBM / 2 order arrays too)
 // The existing-node conditions the cursor engine's stage (node_stage.h) and the spread engine's node path (topo_nodes.h) share;
-// 0, or the fallback reason: 30 = a node under consolidateAfter that some pod must skip, 31 = node requirement sets with bounds,
-// 32 = a node label set that is not single-valued In.
+// 0, or the fallback reason (decline.h): 30 = a node under consolidateAfter that some pod must skip, 31 = node requirement sets with
+// bounds, 32 = a node label set that is not single-valued In.
 static uint32_t node_stage_declines(const ksolve_problem_desc* d, const ks::Dict& dict, uint32_t req_words) {
   if (d->node_under_consolidate_after) {
     // a node under consolidateAfter is skipped for pods that are neither pending nor from a deleting node (scheduler.go:628)
     bool under = false, bound = false;
     for (uint32_t e = 0; e < d->n_nodes; ++e) under = under || d->node_under_consolidate_after[e];
     for (uint32_t p = 0; p < d->n_pods && under; ++p) bound = bound || !((d->pod_is_pending && d->pod_is_pending[p]) || (d->pod_from_deleting_node && d->pod_from_deleting_node[p]));
-    if (under && bound) return 30;
+    if (under && bound) return ks::DECLINE_NODE_CONSOLIDATE_AFTER;
   }
-  if (any_nonzero(d->node_reqs.has_gte, d->n_nodes) || any_nonzero(d->node_reqs.has_lte, d->n_nodes)) return 31;
+  if (any_nonzero(d->node_reqs.has_gte, d->n_nodes) || any_nonzero(d->node_reqs.has_lte, d->n_nodes)) return ks::DECLINE_NODE_BOUNDS;
   // labels as single-valued In sets: ExistingNode.Add then leaves a node's requirements as they were
   for (uint32_t e = 0; e < d->n_nodes; ++e) {
-    if (d->node_reqs.complement[e]) return 32;
+    if (d->node_reqs.complement[e]) return ks::DECLINE_NODE_LABELS;
     const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
     for (uint32_t k = 0; k < d->n_keys; ++k) {
       if (!((d->node_reqs.defined[e] >> k) & 1u)) continue;
       int vals = 0;
       for (uint32_t x = dict.key_word_off[k]; x < dict.key_word_off[k + 1]; ++x) vals += __builtin_popcountll(nm[x]);
-      if (vals != 1) return 32;
+      if (vals != 1) return ks::DECLINE_NODE_LABELS;
     }
   }
   return 0;
@@ -736,7 +736,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     P.plain_nodes = 0;
     if (h->opt_nodes && d->n_nodes > 0) {
       uint32_t why = 0;
-      if (!(d->topo.n == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = 34;
+      if (!(d->topo.n == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = ks::DECLINE_NODES_NOT_PLAIN;
       if (!why) why = node_stage_declines(d, P.dict, req_words);
       P.plain_nodes = why ? 0 : 1;
       h->fast_reason = why;
@@ -748,21 +748,21 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     // with nodes runs ksolve_pack_topo_nodes.
     if (h->opt_spread_nodes && d->n_nodes > 0 && d->topo.n > 0) {
       uint32_t why = 0;
-      if (!(!any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = 34;
+      if (!(!any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = ks::DECLINE_NODES_NOT_PLAIN;
       if (!why) why = node_stage_declines(d, P.dict, req_words);
       std::vector<uint8_t> dom((size_t)d->n_keys * d->n_nodes, 0xFF);
       bool any_taint = false;
       for (uint32_t e = 0; e < d->n_nodes; ++e) any_taint = any_taint || d->node_taints[e] != 0;
       for (uint32_t g = 0; g < d->topo.n && !why; ++g) {
-        if (d->topo.filter_taint_honor[g] && any_taint) { why = 43; break; }
+        if (d->topo.filter_taint_honor[g] && any_taint) { why = ks::DECLINE_TOPO_NODE_FILTER; break; }
         const int32_t k = d->topo.key[g];
         if (k < 0 || dom[(size_t)k * d->n_nodes] != 0xFF) continue;   // the hostname, or a key an earlier group filled in
         for (uint32_t e = 0; e < d->n_nodes && !why; ++e) {
-          if (!((d->node_reqs.defined[e] >> k) & 1u)) { why = 35; break; }
+          if (!((d->node_reqs.defined[e] >> k) & 1u)) { why = ks::DECLINE_NODE_LACKS_KEY; break; }
           const uint64_t* nm = d->node_reqs.mask + (size_t)e * req_words;
           int z = -1;
           for (uint32_t x = P.dict.key_word_off[k]; x < P.dict.key_word_off[k + 1]; ++x) if (nm[x]) { z = (int)(x - P.dict.key_word_off[k]) * 64 + __builtin_ctzll(nm[x]); break; }
-          if (z < 0 || z >= ks::kTopoMaxDom) { why = 36; break; }
+          if (z < 0 || z >= ks::kTopoMaxDom) { why = ks::DECLINE_NODE_DOMAIN_RANGE; break; }
           dom[(size_t)k * d->n_nodes + e] = (uint8_t)z;
         }
       }
@@ -2065,6 +2065,26 @@ static void fast_nodes_stage(ksolve_handle* h) {
   P.sorted_pods = h->fw.nd_pod;
 }
 
+// What a fast engine's kernel left behind: done = it solved the problem (or was stopped by a step limit / cancel flag) and its results
+// stand; otherwise `reason` says why not (decline.h) — the kernel's own for status 3, DECLINE_CAPACITY for status 1, the handle's as
+// it was after a device error — and `pops` how far a status-3 run got. The counters are downloaded for status 3 only.
+struct FastOutcome { bool done; int status, n_claims; uint32_t reason; unsigned long long pops; };
+static FastOutcome fast_outcome(ksolve_handle* h) {
+  FastOutcome o{false, 0, 0, h->fast_reason, 0};
+  be_d2h(h, &o.status, h->ws.status_out, 4);
+  be_d2h(h, &o.n_claims, h->ws.n_claims_out, 4);
+  be_sync(h);
+  o.done = be_ok(h) && o.status != 3 && o.status != 1;
+  if (be_ok(h) && o.status == 3) {
+    ks::Counters ctr{};
+    be_d2h(h, &ctr, h->ws.counters, sizeof(ctr));
+    be_sync(h);
+    o.reason = (uint32_t)ctr.decline;
+    o.pops = ctr.queue_pops;
+  } else if (be_ok(h) && o.status == 1) o.reason = ks::DECLINE_CAPACITY;
+  return o;
+}
+
 static void be_results_drop(ksolve_results* r) { if (r && r->impl) { delete (ResultsImpl*)r->impl; r->impl = nullptr; } }
 static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_context = true) {
   memset(out, 0, sizeof(*out));
@@ -2080,8 +2100,8 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
                 (h->opt_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
   if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
     // more pod classes than the node stage keeps cursors for: the general engine (nothing has run yet)
-    h->fast_reason = 33;
-    if (h->opts.engine >= 2) return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason 33)");
+    h->fast_reason = ks::DECLINE_NODE_CLASSES;
+    if (h->opts.engine >= 2) return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")");
     h->fw.enabled = 0;
   }
   if (h->tw.enabled && h->n_pods && h->n_classes) {
@@ -2096,30 +2116,22 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
       be_launch_pack_topo_nodes(h);
     } else be_launch_pack_topo(h);
     be_toc(h, T_PACK);
-    int status = 0, n_claims = 0;
-    be_d2h(h, &status, h->ws.status_out, 4);
-    be_d2h(h, &n_claims, h->ws.n_claims_out, 4);
-    be_sync(h);
-    if (be_ok(h) && status != 3 && status != 1) {
+    const FastOutcome o = fast_outcome(h);
+    if (o.done) {
       h->engine_used = 3;
       h->fast_reason = 0; h->fast_attempts = 1;
-      if (n_claims || h->tw.nd.dom) be_launch_fast_records(h, n_claims);   // (pods on existing nodes are scattered with the queue's results even when no claim was opened)
+      if (o.n_claims || h->tw.nd.dom) be_launch_fast_records(h, o.n_claims);   // (pods on existing nodes are scattered with the queue's results even when no claim was opened)
       return solve_finish(h, out);
     }
-    if (be_ok(h) && status == 3) {
-      ks::Counters ctr{};
-      be_d2h(h, &ctr, h->ws.counters, sizeof(ctr));
-      be_sync(h);
-      h->fast_reason = (uint32_t)ctr.cycles[20];
-    } else if (be_ok(h)) h->fast_reason = 100;
+    h->fast_reason = o.reason;
     if (h->opts.engine == 6) return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine declined the problem (reason " + std::to_string(h->fast_reason) + ")");
-    if (h->fast_reason != 27 && h->fast_reason != 100) h->tw.enabled = 0;   // not its shape: later solves of this handle go straight to the general engine
+    if (h->fast_reason != ks::DECLINE_UNSCHEDULABLE_POD && h->fast_reason != ks::DECLINE_CAPACITY) h->tw.enabled = 0;   // not its shape: later solves of this handle go straight to the general engine
     st = solve_prepare(h, false);
     if (st != KSOLVE_OK) return st;
   }
   if (h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes) {
     // the cursor engine first; status 3 = "not my shape / stopped before any result": the general engine takes over — unless all
-    // that stopped it was the number of claims its LDS plan holds (reason 26): then once more with the claims' state in HBM
+    // that stopped it was the number of claims its LDS plan holds (DECLINE_CLAIM_SLOTS, reason 26): then once more with the claims' state in HBM
     h->fast_attempts = 0;
     for (;;) {
       h->fast_attempts++;
@@ -2127,32 +2139,22 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
       if (h->fw.nodes) fast_nodes_stage(h);   // existing nodes first (scheduler.go:594); the loop solves the pods they left
       be_launch_pack_fast(h);
       be_toc(h, T_PACK);
-      int status = 0, n_claims = 0;
-      be_d2h(h, &status, h->ws.status_out, 4);
-      be_d2h(h, &n_claims, h->ws.n_claims_out, 4);
-      be_sync(h);
-      if (be_ok(h) && status != 3 && status != 1) {
+      const FastOutcome o = fast_outcome(h);
+      if (o.done) {
         h->engine_used = 2;
         h->fast_reason = 0;   // (a first attempt that ran out of LDS claim slots is not a fallback to the general engine)
-        if (n_claims) be_launch_fast_records(h, n_claims);
+        if (o.n_claims) be_launch_fast_records(h, o.n_claims);
         return solve_finish(h, out);
       }
-      unsigned long long ctr_pops = 0;
-      if (be_ok(h) && status == 3) {
-        ks::Counters ctr{};
-        be_d2h(h, &ctr, h->ws.counters, sizeof(ctr));
-        be_sync(h);
-        h->fast_reason = (uint32_t)ctr.cycles[20];
-        ctr_pops = ctr.queue_pops;
-      } else if (be_ok(h)) h->fast_reason = 100;   // more claims than max_claims: the general engine reports it (or moves to BIG)
-      if (be_ok(h) && h->fast_reason == 26 && h->fw.plan.global_state < 2 && !h->opts.lds_claim_cap) {
+      h->fast_reason = o.reason;   // (DECLINE_CAPACITY, 100 = more claims than max_claims: the general engine reports it, or moves to BIG)
+      if (be_ok(h) && h->fast_reason == ks::DECLINE_CLAIM_SLOTS && h->fw.plan.global_state < 2 && !h->opts.lds_claim_cap) {
         // out of claim slots: the next plan (later solves of this handle start there). The attempt says how many pods its
         // claims took: when the whole queue, at that rate and a quarter more, would not fit plan 1 either, go to plan 2 at once.
         const int had = h->fw.plan.cap;
         int next = h->fw.plan.global_state + 1;
         if (next == 1) {
           fast_plan_set(h, 1, h->fw.plan.rows);
-          const double placed = (double)(ctr_pops > 0 ? ctr_pops : 1);
+          const double placed = (double)(o.pops > 0 ? o.pops : 1);
           const bool holds_all = h->fw.plan.cap >= (int)((h->fast_mc + 63) & ~63u);   // plan 1 has a slot for every claim the problem may open
           if (!holds_all && (double)had * (double)h->n_pods / placed * 1.25 > (double)h->fw.plan.cap) next = 2;
         }
@@ -2231,13 +2233,9 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
     std::vector<int> handed_back(fast.size(), 0);
     for (size_t k = 0; k < fast.size(); ++k) {
       ksolve_handle* h = fast[k];
-      int status = 0, n_claims = 0;
-      be_d2h(h, &status, h->ws.status_out, 4);
-      be_d2h(h, &n_claims, h->ws.n_claims_out, 4);
-      be_sync(h);
-      if (be_ok(h) && status != 3 && status != 1) { h->engine_used = 2; if (n_claims) be_launch_fast_records(h, n_claims); continue; }
-      if (be_ok(h) && status == 3) { ks::Counters ctr{}; be_d2h(h, &ctr, h->ws.counters, sizeof(ctr)); be_sync(h); h->fast_reason = (uint32_t)ctr.cycles[20]; }
-      else if (be_ok(h)) h->fast_reason = 100;
+      const FastOutcome o = fast_outcome(h);
+      if (o.done) { h->engine_used = 2; if (o.n_claims) be_launch_fast_records(h, o.n_claims); continue; }
+      h->fast_reason = o.reason;
       handed_back[k] = 1;
     }
     for (size_t k = 0; k < fast.size(); ++k) {
@@ -2245,7 +2243,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
       ksolve_handle* h = fast[k];
       uint32_t idx = 0;
       while (hs[idx] != h) ++idx;
-      if (h->fast_reason == 26 && !h->opts.lds_claim_cap) {
+      if (h->fast_reason == ks::DECLINE_CLAIM_SLOTS && !h->opts.lds_claim_cap) {
         // more in-flight claims than the LDS plan holds: alone, on the plans that keep them in HBM (solve() escalates further)
         fast_plan_set(h, 1, h->fw.plan.rows);
         be_results_drop(&outs[idx]); st[idx] = solve(h, &outs[idx], false); outs[idx].status = st[idx]; alone[idx] = 1;

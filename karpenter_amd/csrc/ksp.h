@@ -3,6 +3,7 @@
 // kernel streams over many entities (pods) and AoS-by-entity where one wave touches one entity at a time (claims).
 #pragma once
 #include "reqalg.h"
+#include "decline.h"
 
 namespace ks {
 
@@ -245,10 +246,11 @@ KS_FN const int64_t* eff_alloc(const ProblemView& P, int t) {
 struct Counters {
   unsigned long long bin_evaluations, full_evaluations, it_evaluations, queue_pops, sorts, slow_sorts, relaxations, column_resets;
   unsigned long long ref_bin_evaluations;  // V: candidate bins the reference would have evaluated
-  unsigned long long cycles[24];           // shader clock spent per engine phase (profiling aid)
+  unsigned long long cycles[24];           // slots 0-23: shader clock spent per engine phase and a few diagnostic counts (profiling aid) — timers only, no status or reason
   unsigned long long full_filters;         // filterInstanceTypesByRequirements runs that had to re-evaluate compatibility + offerings
   unsigned long long node_block_steps;     // probes: 64-word steps over a class's n_dead0 row (512 B each) in the existing-node scan
   unsigned long long node_evaluations;     // existing nodes whose tables a scan actually read (the live bits of the blocks it stopped at)
+  unsigned long long decline;              // fast engines, status 3: why they stopped (decline.h); the last member, so that every other keeps its offset
 };
 
 struct Workspace {

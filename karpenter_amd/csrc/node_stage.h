@@ -28,7 +28,7 @@ namespace ks {
 
 constexpr int kNodeStageLdsRem = 96 * 1024;   // bytes of `remaining` ([n_res][n_nodes] int64) the LDS variant holds; beyond: the HBM variant
 constexpr int kNodeStageLdsClasses = 4096;    // cursor + alive word per class in LDS (12 B each) beside `remaining`; with more classes `remaining` goes to HBM ...
-constexpr int kNodeStageMaxClasses = 12288;   // ... and the classes have the LDS to themselves; beyond: reason 33
+constexpr int kNodeStageMaxClasses = 12288;   // ... and the classes have the LDS to themselves; beyond: DECLINE_NODE_CLASSES (33)
 
 // LDS layout (bytes): alive words [nc] u64 | cursors [nc] u32 | (LDS variant) pod counts [nn] u32 | remaining [nr][nn] i64
 struct NodeStagePlan { int off_word, off_cur, off_npods, off_rem, total_bytes; };
@@ -73,7 +73,7 @@ KS_DEV void pack_nodes_body(const FastArgs* a, char* lds) {
   // reasons are those of fast_engine.h setup(), which would find the same classes behind the stage ----
   {
     const ProblemView& Pv = P;
-    if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) out.bail = 4;
+    if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) out.bail = DECLINE_CLASS_NOT_POSITIVE;
     else if (W::reduce_or(nc, [&](int c) {
       const uint64_t* cm = Pv.cls_reqs.mask + (size_t)c * d.req_words;
       uint64_t bad = 0;
@@ -84,7 +84,7 @@ KS_DEV void pack_nodes_body(const FastArgs* a, char* lds) {
         if (!any) bad = 1;   // In [] == DoesNotExist
       }
       return bad;
-    })) out.bail = 8;
+    })) out.bail = DECLINE_CLASS_EMPTY_IN;
   }
   if (out.bail) {
     if (W::leader()) *F.nodes = out;

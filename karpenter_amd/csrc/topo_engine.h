@@ -67,8 +67,8 @@ struct TopoEngine {
   KS_COLD int setup_topo() {
     const ProblemView& P = *Pk; const TopoView& T = P.topo; const Dict& d = P.dict;
     const int G = T.n_groups;
-    if (G <= 0 || G > kTopoMaxGroups || T.n_alias) return 40;
-    if (!P.strict_same) return 41;   // podDomains = StrictRequirements (topology.go:230): one table when no pod has a preference
+    if (G <= 0 || G > kTopoMaxGroups || T.n_alias) return DECLINE_TOPO_GROUPS;
+    if (!P.strict_same) return DECLINE_TOPO_PREFERENCES;   // podDomains = StrictRequirements (topology.go:230): one table when no pod has a preference
     KS_LDS TopoState& S_ = *st;
     const int nvv = cold.nv;
     n_zg = 0; n_host = 0; n_track = 0; track_fields = 0;
@@ -76,20 +76,20 @@ struct TopoEngine {
     const bool any_taint = W::reduce_or(P.n_templates, [&](int t) { return P.tmpl_taints[t]; }) != 0;
     for (int g = 0; g < G; ++g) {
       const bool inv = (T.inverse_mask[g >> 6] >> (g & 63)) & 1;
-      if (!((T.initially_active[g >> 6] >> (g & 63)) & 1)) return 42;             // created by a relaxing pod (topology.go:162-194)
+      if (!((T.initially_active[g >> 6] >> (g & 63)) & 1)) return DECLINE_TOPO_RELAXATION_GROUP;             // created by a relaxing pod (topology.go:162-194)
       {
         // TopologyNodeFilter.Matches (topologynodefilter.go:68-96) must be true for every claim: no taint policy to honor (or no
         // tainted template), and no node-affinity terms — or one that requires nothing (a pod without nodeSelector / node affinity)
-        if (T.f_taint[g] && any_taint) return 43;
+        if (T.f_taint[g] && any_taint) return DECLINE_TOPO_NODE_FILTER;
         bool open = !T.f_affinity[g] || T.f_first[g] == T.f_first[g + 1];
         for (uint32_t i = T.f_first[g]; i < T.f_first[g + 1]; ++i) if (T.f_reqs.defined[i] == 0) open = true;
-        if (!open) return 43;
+        if (!open) return DECLINE_TOPO_NODE_FILTER;
       }
       const int key = T.key[g], type = T.type[g];
       if (key < 0) {
-        if (type == 1 || (inv && type != 2)) return 45;                           // affinity on the hostname
-        if (n_host >= kTopoMaxHost) return 46;
-        if (type == 0 && (T.max_skew[g] < 1 || T.max_skew[g] > 6)) return 47;     // counters saturate at 7
+        if (type == 1 || (inv && type != 2)) return DECLINE_TOPO_HOST_AFFINITY;                           // affinity on the hostname
+        if (n_host >= kTopoMaxHost) return DECLINE_TOPO_HOST_GROUPS;
+        if (type == 0 && (T.max_skew[g] < 1 || T.max_skew[g] > 6)) return DECLINE_TOPO_HOST_SKEW;     // counters saturate at 7
         if (type == 2 && n_track < kTopoTrack) {
           W::store(&S_.track_field[n_track], (uint32_t)n_host);
           track_fields |= 1ull << (4 * n_host);
@@ -98,12 +98,12 @@ struct TopoEngine {
         W::store(&S_.gmap[g], (int16_t)n_host);
         n_host++;
       } else {
-        if (inv && type != 2) return 48;
-        if (type == 0 && (T.max_skew[g] < 1 || T.max_skew[g] > 30000 || T.min_domains[g] > 30000)) return 44;
-        if (n_zg >= kTopoMaxZg) return 49;
+        if (inv && type != 2) return DECLINE_TOPO_INVERSE_KIND;
+        if (type == 0 && (T.max_skew[g] < 1 || T.max_skew[g] > 30000 || T.min_domains[g] > 30000)) return DECLINE_TOPO_SKEW_RANGE;
+        if (n_zg >= kTopoMaxZg) return DECLINE_TOPO_KEY_GROUPS;
         int var = -1;
         for (int j = 0; j < nvv; ++j) if (Mp->vkey[j] == key) var = j;
-        if (var < 0 || Mp->vwidth[var] > kTopoMaxDom) return 50;
+        if (var < 0 || Mp->vwidth[var] > kTopoMaxDom) return DECLINE_TOPO_DOMAINS;
         const uint32_t w0 = d.key_word_off[key];
         KS_LDS TopoZg& Z = S_.zg[n_zg];
         const int32_t* c0 = T.counts0 + (size_t)g * T.dom_words * 64;
@@ -114,7 +114,7 @@ struct TopoEngine {
           Z.type = (uint8_t)type; Z.var = (uint8_t)var; Z.off = Mp->voff[var]; Z.width = Mp->vwidth[var];
         }
         // (domains beyond the sixteen the field holds cannot exist: the field's width is the key's highest valid value)
-        if (T.domains0[(size_t)g * T.dom_words] >> kTopoMaxDom) return 50;
+        if (T.domains0[(size_t)g * T.dom_words] >> kTopoMaxDom) return DECLINE_TOPO_DOMAINS;
         W::store(&S_.gmap[g], (int16_t)(0x100 + n_zg));
         n_zg++;
       }
@@ -161,8 +161,8 @@ struct TopoEngine {
       tc[c] = k;
       return b;
     });
-    if (bad) return 51;
-    return 0;
+    if (bad) return DECLINE_TOPO_CLASS;
+    return DECLINE_NONE;
   }
 
   // ---- the pod's domain choice on the dictionary-key group it owns, before any claim is looked at ----
@@ -282,7 +282,7 @@ struct TopoEngine {
       }, okb, miss);
       acc |= okb;
       todo = miss;
-      if (miss && cold.create_entry(m2v.bcast(ctz64(miss))) < 0) { bail = 60; return 0; }
+      if (miss && cold.create_entry(m2v.bcast(ctz64(miss))) < 0) { bail = DECLINE_TOPO_CACHE_FULL; return 0; }
     }
     return acc;
   }
@@ -335,43 +335,23 @@ struct TopoEngine {
   }
 
   // addToNewNodeClaim (scheduler.go:695-790) for a pod no in-flight claim accepted, every case: several templates, NodePool limits,
-  // requirement sets that are not cached yet, pdqsort's other paths. The claim's id, or -1: stop (bail; -1 = capacity).
+  // requirement sets that are not cached yet, pdqsort's other paths. The claim's id, or -1: stop (bail; DECLINE_KERNEL_CAPACITY = capacity).
   // (solve() places the common case itself: one template without limits, the set cached, the single stable move.)
   KS_COLD int new_claim(TopoClass tc, FastSlot cs) {
     const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
-    const int T = P.n_templates, nr = P.n_res, iw = P.it_words;
+    const int T = P.n_templates;
     const int n = order.n;
     n_ref += (unsigned long long)n;
     LaneVar<uint64_t> zkv, zkw;
     bool possible = true, possible2 = true;
     const ZChoice zc = choose_domains(tc.zg[0], (tc.zself & 1u) != 0, cs.cvmask, zkv, possible);
     const ZChoice zd = choose_domains(tc.zg[1], (tc.zself & 2u) != 0, cs.cvmask, zkw, possible2);
-    if (!possible || !possible2) { bail = 27; return -1; }
+    if (!possible || !possible2) { bail = DECLINE_UNSCHEDULABLE_POD; return -1; }
     KClass kc; kc.hlim = tc.hlim; kc.cvmask = cs.cvmask; kc.dmask = cs.dmask; kc.s0 = cs.size[0]; kc.s1 = cs.size[1]; kc.s2 = cs.size[2]; kc.s3 = cs.size[3]; kc.tmplok = cs.tmplok;
     for (int t = 0; t < T; ++t) {
       if (!((cold.active_templates >> t) & 1u)) continue;
       const uint32_t lm = P.tmpl_limit_mask[t];
-      if (lm) {
-        // filterByRemainingResources (scheduler.go:1069-1085): this engine only continues while no type is excluded
-        int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
-        if (((lm >> nr) & 1) && rem[nr] <= 0) { bail = 23; return -1; }
-        const ProblemView& Pv = P;
-        const uint64_t* tits = S.t_its + (size_t)t * iw;
-        const int n_its = P.n_its;
-        uint64_t excluded = 0;
-        for (int w = 0; w < iw; ++w) {
-          const uint64_t in = tits[w];
-          if (!in) continue;
-          excluded |= W::ballot([&](int l) {
-            const int it = w * 64 + l;
-            if (it >= n_its || !((in >> l) & 1)) return false;
-            bool v = true;
-            for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
-            return !v;
-          });
-        }
-        if (excluded) { bail = 24; return -1; }
-      }
+      if (lm) { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail = why; return -1; } }
       cold.host_seq++;
       n_ref++;
       // CanAdd on the fresh claim: the template's set, no requests, every hostname counter zero (the limits are >= 0)
@@ -382,10 +362,10 @@ struct TopoEngine {
       if (v == 0) continue;
       FastEnt e;
       int eh = fast_lookup(cold.ent, m2, e);
-      if (eh < 0) { eh = cold.create_entry(m2); if (eh < 0) { bail = 25; return -1; } e = lds_get(&cold.ent[eh]); }
+      if (eh < 0) { eh = cold.create_entry(m2); if (eh < 0) { bail = DECLINE_CACHE_FULL_NEW_CLAIM; return -1; } e = lds_get(&cold.ent[eh]); }
       const int32_t zero[4] = {0, 0, 0, 0};
       if (!fast_fits(cold.pool, e, zero, cs.size)) continue;
-      if (cold.n_claims >= S.max_claims) { bail = -1; return -1; }
+      if (cold.n_claims >= S.max_claims) { bail = DECLINE_KERNEL_CAPACITY; return -1; }
       const int c = cold.n_claims++;
       TopoRec nrq;
       nrq.vmask = m2;
@@ -401,26 +381,10 @@ struct TopoEngine {
       record_zonal(tc.zsel, m2);
       if (track_fields) lists_add(nrq.hcnt, (uint32_t)c);
       W::sync();
-      if (lm) {
-        // subtractMax (scheduler.go:1049-1066) over the claim's instance types: F(m2) ∩ fits(size + daemon overhead)
-        int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
-        const int64_t* eff = eff_alloc(P, t);
-        const uint64_t* eits = F.ent_its + (size_t)eh * iw;
-        const ProblemView& Pv = P;
-        const int n_its = P.n_its;
-        for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) {
-          const int64_t mx = W::reduce_max_i64(n_its, [&](int it) {
-            if (!((eits[it >> 6] >> (it & 63)) & 1)) return INT64_MIN;
-            for (int z = 0; z < nr; ++z) if (eff[(size_t)z * n_its + it] < (int64_t)cs.size[z]) return INT64_MIN;
-            return Pv.it_cap[(size_t)q * n_its + it];
-          });
-          W::store(&rem[q], rem[q] - mx);
-        }
-        W::sync();
-      }
+      if (lm) subtract_max<W>(P, S, F, t, lm, eh, cs.size);
       return c;
     }
-    bail = 27;   // an unschedulable pod: error codes, diagnostics and the relaxation ladder are the general engine's
+    bail = DECLINE_UNSCHEDULABLE_POD;   // error codes, diagnostics and the relaxation ladder are the general engine's
     return -1;
   }
   // a claim gained a pod and pdqsort's repair is not the single stable move (or its run lies beyond the LDS tables): through RunOrder
@@ -469,7 +433,7 @@ struct TopoEngine {
         q0.at(l) = r.req[0]; q1.at(l) = r.req[1]; q2.at(l) = r.req[2]; q3.at(l) = r.req[3];
         return f0 + l < nf ? v : 0;
       }, okm, und);
-      if (W::ballot([&](int l) { return f0 + l < nf && cv.at(l) >= (uint32_t)kRunMaxCount; })) { bail = 61; return A; }   // (a claim beyond the LDS ring tables in a list: not this engine's shape)
+      if (W::ballot([&](int l) { return f0 + l < nf && cv.at(l) >= (uint32_t)kRunMaxCount; })) { bail = DECLINE_TOPO_LIST_BEYOND_RINGS; return A; }   // (a claim beyond the LDS ring tables in a list: not this engine's shape)
       if (und) { okm |= resolve(und, m2v, q0, q1, q2, q3, kc.s0, kc.s1, kc.s2, kc.s3); if (bail) return A; }
       if (okm) {
         int who = -1;
@@ -494,7 +458,7 @@ struct TopoEngine {
     bool done = false;
     W::each([&](int l) { xv.at(l) = 0; });
     while (!done && filled < 64 && k <= max_cnt) {
-      if (k + 16 >= kRunMaxCount) { bail = 62; return filled; }   // (a run beyond the LDS ring tables at the front of the order: not this engine's shape)
+      if (k + 16 >= kRunMaxCount) { bail = DECLINE_TOPO_RUN_BEYOND_RINGS; return filled; }   // (a run beyond the LDS ring tables at the front of the order: not this engine's shape)
       LaneVar<uint32_t> eh, es, eo, em;
       const int kb = k;
       W::each([&](int l) {
@@ -581,7 +545,7 @@ struct TopoEngine {
     LaneVar<uint64_t> zkw;
     bool p2 = true;
     const ZChoice zd = choose_domains(zg1, self1, kc.cvmask, zkw, p2);
-    if (!p2) { bail = 27; Accept A; A.found = 0; A.x = 0; A.pos = 0; A.cnt = 0; A.m2 = 0; A.hcnt = 0; A.q0 = A.q1 = A.q2 = A.q3 = 0; return A; }
+    if (!p2) { bail = DECLINE_UNSCHEDULABLE_POD; Accept A; A.found = 0; A.x = 0; A.pos = 0; A.cnt = 0; A.m2 = 0; A.hcnt = 0; A.q0 = A.q1 = A.q2 = A.q3 = 0; return A; }
     return list_t >= 0 ? scan_list(list_t, kc, zc, zkv, zd, zkw) : scan_order(kc, zc, zkv, zd, zkw);
   }
   KS_COLD void sort_cold() { order.sort(); }
@@ -592,7 +556,7 @@ struct TopoEngine {
     bool p0 = true, p1 = true;
     const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, cvmask, zkv, p0);
     const ZChoice zd = choose_domains(zg1, (zselfw & 2u) != 0, cvmask, zkv, p1);
-    if (!p0 || !p1) { TopoNodePick none; none.node = -1; none.slot = 0; return none; }   // (no domain anywhere: the claim path stops with reason 27)
+    if (!p0 || !p1) { TopoNodePick none; none.node = -1; none.slot = 0; return none; }   // (no domain anywhere: the claim path stops with DECLINE_UNSCHEDULABLE_POD)
     return topo_nodes_place<W>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm);
   }
 
@@ -629,7 +593,7 @@ struct TopoEngine {
     Counters c{};
     c.bin_evaluations = n_tests; c.full_evaluations = n_windows; c.queue_pops = steps; c.sorts = steps; c.slow_sorts = order.slow_sorts;
     c.ref_bin_evaluations = n_ref; c.it_evaluations = n_listed;
-    c.cycles[20] = (unsigned long long)(bail > 0 ? bail : 0);
+    c.decline = (unsigned long long)(bail > 0 ? bail : 0);
     c.cycles[0] = tc0; c.cycles[1] = tc1; c.cycles[2] = tc2; c.cycles[3] = tc3; c.cycles[4] = tc4; c.cycles[5] = tc5; c.cycles[6] = tc6; c.cycles[7] = tc7; c.cycles[8] = tc8; c.cycles[9] = tc9;
     if (W::leader()) *S.counters = c;
     W::sync();
@@ -808,7 +772,7 @@ struct TopoEngine {
         LaneVar<uint64_t> zkv;
         bool possible = true;
         const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, kc.cvmask, zkv, possible);
-        if (!possible) { bail = 27; status = 3; break; }
+        if (!possible) { bail = DECLINE_UNSCHEDULABLE_POD; status = 3; break; }
         const bool two = zg1 >= 0;   // a second group on a dictionary key (rare): its pods take the out-of-line paths all the way
         KS_TSEC(t2)
         // ---- addToInflightNode (scheduler.go:658-692): the first claim of the order that accepts ----
@@ -941,7 +905,7 @@ struct TopoEngine {
             fence();
             const int c = fast_uniform(new_claim(tcc, csc));
             pull(); wvalid = false;
-            if (c < 0) { status = fast_uniform(bail) < 0 ? 1 : 3; break; }
+            if (c < 0) { status = fast_uniform(bail) == DECLINE_KERNEL_CAPACITY ? 1 : 3; break; }
             oclaim.set(bi, (uint32_t)c); ocntv.set(bi, 0u);
           }
           KS_TSEC(t6)

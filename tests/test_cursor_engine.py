@@ -276,7 +276,7 @@ def test_declined_shapes_fall_back_loudly(oracle, emu):
     # a pod that selects on the instance type (a 500-value key does not pack into the claim word)
     check_declined(oracle, emu, fx.problem(its, [pool], [fx.pod(node_selector={fx.INSTANCE_TYPE: "fake-it-3"}) for _ in range(5)]), reason=5)
     # NodePool limits that exclude instance types
-    check_declined(oracle, emu, fx.problem(its, [fx.node_pool(limits={"cpu": "20"})], [fx.pod(requests={"cpu": "1"}) for _ in range(40)]))
+    check_declined(oracle, emu, fx.problem(its, [fx.node_pool(limits={"cpu": "20"})], [fx.pod(requests={"cpu": "1"}) for _ in range(40)]), reason=24)
     # more than four resource dimensions (the fake provider's default catalogue carries two GPU resources)
     got = NewScheduler(fx.problem(fx.fake_default_instance_types(), [pool], [fx.pod(requests={"cpu": "1"}) for _ in range(9)]), solver_lib=emu).Solve()
     assert got["counters"]["engine"] == "general"
