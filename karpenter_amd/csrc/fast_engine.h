@@ -152,7 +152,7 @@ KS_FN void lds_put(KS_LDS T* p, const T& v) {
 // ... and as 16-byte pieces for records that are multiples of 16 bytes at 16-byte-aligned addresses (FastEnt, FastRec<1>; the plan
 // aligns every table to 16): ds_read_b128 takes 4 LDS cycles per wave-instruction where ds_read2_b64 takes 8, ds_write_b128 13 where
 // two ds_write_b64 take 12 + 12 (MI355X_MICROARCH.md, LDS table).
-typedef uint32_t __attribute__((vector_size(16), may_alias)) u32x4_alias;
+// (u32x4_alias: wave.h)
 template <class T>
 KS_FN T lds_get16(const KS_LDS T* p) {
   static_assert(sizeof(T) % 16 == 0, "lds_get16: 16-byte multiples");
@@ -431,7 +431,7 @@ struct FastCold {
   const Workspace* Sk;
   const FastWork* Fk;
   typedef typename FastMem<GS, R>::o16 o16;
-  ClaimOrder<W, o16, false> order;
+  ClaimOrder<W, o16, false, !FastMem<GS, R>::kOrderHbm> order;   // (an order in LDS: the sort's scans read it in 16-byte pieces)
   typename FastMem<GS, R>::s16 snap;   // [cap] order snapshot around a slow sort (HBM on plans 1 and 2)
   typename FastMem<GS, R>::States cst;
   KS_LDS FastEnt* ent;
@@ -444,6 +444,9 @@ struct FastCold {
   int bail_code = 0;
   int lo_ = 0, hi_ = -1;    // positions a slow sort permuted
   unsigned long long n_ref_extra = 0, n_cold_tests = 0;
+#ifdef KSOLVE_PHASE_TIMERS
+  unsigned long long t_small = 0, n_small = 0;   // shader clock inside slow_sort with n <= 64 and its calls (phase_cycles[20]: cycles | calls << 44)
+#endif
 
   KS_DEV void init(const ProblemView* p, const Workspace* s, const FastWork* f, char* lds) {
     Pk = p; Sk = s; Fk = f;
@@ -851,7 +854,27 @@ struct FastCold {
   KS_COLD void slow_sort(int n, int defect, int app) {
     order.n = (int)W::uniform((uint64_t)(uint32_t)n); order.defect = (int)W::uniform((uint64_t)(uint32_t)defect); order.defect_append = W::uniform((uint64_t)app) != 0;
     n = order.n;
+#ifdef KSOLVE_PHASE_TIMERS
+    const unsigned long long t_in = W::clock();
+#endif
     const o16 oo = order.ord; const typename FastMem<GS, R>::s16 sn = snap;
+    if (n <= 64) {
+      // The whole order fits one wavefront's lanes (pdq_emul.h RegOrder): one load, the sort in registers, one store. The positions
+      // whose claim changed are one ballot over the claim ids before and after: no snapshot, no searches.
+      RegOrder<W> r;
+      r.load(order.key, oo, n);
+      r.defect = order.defect; r.defect_append = order.defect_append;
+      const LaneVar<uint32_t> before = r.o;
+      r.sort();
+      order.slow_sorts += r.slow_sorts; order.defect = -1;
+      const uint64_t moved = W::ballot([&](int l) { return l < n && before.v_of(l) != r.o.v_of(l); });
+      r.store(order.key, oo);
+      lo_ = moved ? ctz64(moved) : 0; hi_ = moved ? 63 - __builtin_clzll(moved) : -1;
+#ifdef KSOLVE_PHASE_TIMERS
+      t_small += W::clock() - t_in; n_small++;
+#endif
+      return;
+    }
     if constexpr (FastMem<GS, R>::kSnapHbm) {
       W::copy8(sn, oo, n);
       order.sort();
@@ -1017,6 +1040,7 @@ struct FastCold {
     if (tc) for (int i = 0; i < 16; ++i) c.cycles[i] = tc[i];
 #ifdef KSOLVE_PHASE_TIMERS
     for (int i = 0; i < 4; ++i) c.cycles[16 + i] = hs->hw[i];
+    c.cycles[20] = t_small | (n_small << 44);
     c.cycles[18] = (hs->hw[2] << 32) | (unsigned long long)(hs->mail.simd[0] | (hs->mail.simd[1] << 8) | (hs->mail.simd[2] << 16) | (hs->mail.simd[3] << 24));
 #endif
     if (F.nodes) c.cycles[19] = (unsigned long long)nd.variant;

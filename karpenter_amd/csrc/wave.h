@@ -384,6 +384,10 @@ struct LaneVar {
 #endif
 };
 
+// A 16-byte piece of an array (one ds_read_b128 / ds_write_b128 in LDS), whatever the array's element type
+typedef uint32_t __attribute__((vector_size(16), may_alias)) u32x4_alias;
+KS_FN const KS_LDS u32x4_alias* pieces16(const KS_LDS uint16_t* p) { return (const KS_LDS u32x4_alias*)p; }
+
 KS_FN int popc64(uint64_t x) { return __builtin_popcountll(x); }
 KS_FN int ctz64(uint64_t x) { return __builtin_ctzll(x); }
 
