@@ -608,10 +608,21 @@ static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a) {
     else if (same) hipLaunchKernelGGL((ksolve_row_hash_coop2<false, true>), grid, dim3(64), lds2, HB(h)->stream, n, a, rw, magic, kmagic, rpb);
     else if (nr4) hipLaunchKernelGGL((ksolve_row_hash_coop2<false, false, 4>), grid, dim3(64), lds2, HB(h)->stream, n, a, rw, magic, kmagic, rpb);
     else hipLaunchKernelGGL((ksolve_row_hash_coop2<false, false>), grid, dim3(64), lds2, HB(h)->stream, n, a, rw, magic, kmagic, rpb);
+#ifdef KSOLVE_TEST_HOOKS   // the instantiation the chain above picked, in its order (ksolve_test_classify reports it)
+    h->test_row_kernel = (uint32_t)(minv ? (same ? KSOLVE_TEST_ROW_KERNEL_COOP2_MINV_SAME : KSOLVE_TEST_ROW_KERNEL_COOP2_MINV)
+                                         : same ? (nr4 ? KSOLVE_TEST_ROW_KERNEL_COOP2_SAME_4 : KSOLVE_TEST_ROW_KERNEL_COOP2_SAME_8)
+                                                : (nr4 ? KSOLVE_TEST_ROW_KERNEL_COOP2_4 : KSOLVE_TEST_ROW_KERNEL_COOP2_8)) | ((uint32_t)rpb << 8);
+#endif
   } else if (!plain && rw >= 1 && nk >= 1 && lds1 <= 64 * 1024) {
     hipLaunchKernelGGL(ksolve_row_hash_coop, dim3((unsigned)((n + 63) / 64)), dim3(64), lds1, HB(h)->stream, n, a, rw, magic, kmagic);
+#ifdef KSOLVE_TEST_HOOKS
+    h->test_row_kernel = (uint32_t)KSOLVE_TEST_ROW_KERNEL_COOP1 | (64u << 8);
+#endif
   } else {
     hipLaunchKernelGGL(ksolve_row_hash, grid_for(n), dim3(256), 0, HB(h)->stream, n, a);
+#ifdef KSOLVE_TEST_HOOKS
+    h->test_row_kernel = (uint32_t)KSOLVE_TEST_ROW_KERNEL_PLAIN;
+#endif
   }
 }
 static void be_launch_row_class(ksolve_handle* h, int n, const ks::RowArgs& a) { hipLaunchKernelGGL(ksolve_row_class, grid_for(n), dim3(256), 0, HB(h)->stream, n, a); }
@@ -867,6 +878,23 @@ ksolve_status ksolve_create(const ksolve_problem_desc* desc, const ksolve_option
   for (int i = 0; i < 8; ++i) { hip_check(h, hipEventCreate(&b->ev0[i]), "hipEventCreate"); hip_check(h, hipEventCreate(&b->ev1[i]), "hipEventCreate"); }
   return ksi::create(desc, opts, h);
 }
+#ifdef KSOLVE_TEST_HOOKS
+// the classing phase alone, on a bare handle made the way ksolve_create makes one (ksolve_impl.h test_classify; test builds only)
+ksolve_status ksolve_test_classify(const ksolve_test_classify_in* in, ksolve_test_classify_out* out) {
+  ksolve_handle* h = new ksolve_handle();
+  HipBackend* b = new HipBackend();
+  h->backend = b;
+  ksolve_status st = KSOLVE_ERR_DEVICE;
+  if (!be_device_available()) st = KSOLVE_ERR_NO_DEVICE;
+  else if (hip_check(h, hipSetDevice(b->device), "hipSetDevice") && hip_check(h, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    for (int i = 0; i < 8; ++i) { hip_check(h, hipEventCreate(&b->ev0[i]), "hipEventCreate"); hip_check(h, hipEventCreate(&b->ev1[i]), "hipEventCreate"); }
+    st = ksi::test_classify(h, in, out);
+  }
+  if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_classify: %s\n", h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
+#endif
 ksolve_status ksolve_probe_create(ksolve_handle* base, const ksolve_probe* probe, ksolve_handle** out) {
   if (!out) return KSOLVE_ERR_INVALID;
   ksolve_handle* h = new ksolve_handle();

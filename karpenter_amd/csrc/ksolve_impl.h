@@ -110,7 +110,54 @@ struct ksolve_handle {
   bool sweep_arena_refused = false;   // the last sweep_run stopped because the device refused its arena (sweep() then halves the launch)
   size_t sweep_last_total = 0;   // arena bytes the last sweep_run laid out (held against sweep_probe_bytes by the test builds)
   char* sweep_fin = nullptr; size_t sweep_fin_bytes = 0;     // finalize outputs + gathered claim records of a sweep
+#ifdef KSOLVE_TEST_HOOKS
+  uint32_t test_row_kernel = 0;   // which classing kernel be_launch_row_hash launched last (KSOLVE_TEST_ROW_KERNEL_*) | rows per block << 8
+#endif
 };
+
+#ifdef KSOLVE_TEST_HOOKS
+// ksolve_test_classify — TEST BUILDS ONLY (tests/emu/libksolve_hooks.so, tests/emu/libksolve_emu.so; not in include/ksolve.h, not in
+// the product): the classing phase alone on raw host tables, ONE attempt without the re-seed loop, everything it produced downloaded.
+// tests/classing_cases.py holds the definition the answers are compared with.
+enum {
+  KSOLVE_TEST_ROW_KERNEL_COOP2_MINV_SAME = 1,   // ksolve_row_hash_coop2<true, true, 8>
+  KSOLVE_TEST_ROW_KERNEL_COOP2_MINV = 2,        // <true, false, 8>
+  KSOLVE_TEST_ROW_KERNEL_COOP2_SAME_4 = 3,      // <false, true, 4>
+  KSOLVE_TEST_ROW_KERNEL_COOP2_SAME_8 = 4,      // <false, true, 8>
+  KSOLVE_TEST_ROW_KERNEL_COOP2_4 = 5,           // <false, false, 4>
+  KSOLVE_TEST_ROW_KERNEL_COOP2_8 = 6,           // <false, false, 8>
+  KSOLVE_TEST_ROW_KERNEL_COOP1 = 7,             // ksolve_row_hash_coop
+  KSOLVE_TEST_ROW_KERNEL_PLAIN = 8,             // ksolve_row_hash
+  KSOLVE_TEST_ROW_KERNEL_HOST = 9               // the emulation's loop over row_hash_body
+};
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;   // [n_keys + 1]; req_words = key_word_off[n_keys]
+  uint32_t n_rows, n_res;
+  const int64_t* requests;                         // [n_res][n_rows]
+  const ksolve_reqsets* reqs; const ksolve_reqsets* strict;   // strict: null or the same tables = shared with reqs
+  const uint64_t* tolerates;                       // [n_rows]
+  const uint64_t* host_ports;                      // [n_rows][2] or null
+  const uint64_t* vol;                             // [n_rows] or null
+  const uint64_t *topo_owned, *topo_selected;      // [n_rows][topo_words] or null
+  uint32_t topo_words;
+  uint64_t hash_keep, seed;
+} ksolve_test_classify_in;
+// every table is the caller's, sized for n_rows classes (there are never more classes than rows)
+typedef struct {
+  uint32_t n_classes, collision, kernel, rows_per_block;
+  uint32_t *row_class, *class_rep;                 // [n_rows], [n_classes]
+  int64_t* min_request;                            // [n_res]
+  int64_t* cls_requests;                           // [n_classes][n_res]
+  uint64_t* cls_tolerates;
+  uint64_t *reqs_mask, *strict_mask;               // the two MutReqTables, field by field
+  uint32_t *reqs_flags, *strict_flags;             // [4][n_classes]: defined | complement | has_gte | has_lte
+  int64_t *reqs_gte, *reqs_lte, *strict_gte, *strict_lte;
+  int32_t *reqs_minv, *strict_minv;
+  uint64_t *cls_host_ports, *cls_vol, *cls_topo;   // filled when the input has the table
+  uint64_t *cls_hot, *cls_cold;                    // [n_classes][k_hot_words], [n_classes][cold_words]
+  int32_t lay[8];                                  // RecLayout: k_mask, k_req, k_f0, k_f1, k_tol, k_meta, k_hot_words, cold_words
+} ksolve_test_classify_out;
+#endif
 
 // ---- backend hooks (defined by the including TU before this point is instantiated) ----
 static void* be_alloc(ksolve_handle* h, size_t bytes);
@@ -897,6 +944,106 @@ struct ResultsImpl {
 };
 
 // Phases 1-3 (instance-type index, pod classes, queue order) and the resets the pack kernel needs.
+#ifdef KSOLVE_TEST_HOOKS
+// The classing phase alone (see ksolve_test_classify_in): RowArgs filled through the helpers create() uses, the table sized as
+// create() sizes it, then the fills and launches of ONE attempt of solve_prepare's phase 2 and the downloads. The caller owns the
+// (bare) handle and destroys it.
+static ksolve_status test_classify(ksolve_handle* h, const ksolve_test_classify_in* in, ksolve_test_classify_out* out) {
+  if (!in || !out || !in->key_word_off || !in->requests || !in->reqs || !in->reqs->mask || !in->tolerates) return fail(h, KSOLVE_ERR_INVALID, "test_classify: missing table");
+  const uint32_t nk = in->n_keys, n = in->n_rows, nr = in->n_res;
+  if (nk < 1 || nk > (uint32_t)kMaxKeys || nr < 1 || nr > (uint32_t)kMaxRes || n < 1) return fail(h, KSOLVE_ERR_INVALID, "test_classify: sizes out of range");
+  const uint32_t rw = in->key_word_off[nk];
+  if (rw < 1 || rw > (uint32_t)kMaxReqWords || in->key_word_off[0] != 0) return fail(h, KSOLVE_ERR_INVALID, "test_classify: req_words out of range");
+  for (uint32_t k = 0; k < nk; ++k) if (in->key_word_off[k] > in->key_word_off[k + 1]) return fail(h, KSOLVE_ERR_INVALID, "test_classify: key_word_off decreases");
+  if ((in->topo_owned != nullptr) != (in->topo_selected != nullptr) || (in->topo_owned && (in->topo_words < 1 || in->topo_words > (uint32_t)kMaxTopoWords))) return fail(h, KSOLVE_ERR_INVALID, "test_classify: topology tables");
+  ks::RowArgs& R = h->row_args;
+  ks::Dict dict{};
+  dict.n_keys = (int)nk; dict.req_words = (int)rw;
+  for (uint32_t k = 0; k <= nk; ++k) dict.key_word_off[k] = in->key_word_off[k];
+  dict.key_it = dict.key_zone = dict.key_ct = dict.key_hostname = -1;
+  R.dict = dict; R.n_rows = (int)n; R.n_res = (int)nr;
+  R.requests = up(h, in->requests, (size_t)nr * n);
+  auto all_nil = [&](const ksolve_reqsets& r) {
+    if (!r.min_values) return true;
+    for (size_t i = 0; i < (size_t)n * nk; ++i) if (r.min_values[i] >= 0) return false;
+    return true;
+  };
+  const bool strict_same = !in->strict || in->strict == in->reqs || in->strict->mask == in->reqs->mask || in->strict->mask == nullptr;
+  const bool rows_nil = all_nil(*in->reqs) && (strict_same || all_nil(*in->strict));   // minValues tables for both sets or for neither
+  R.reqs = upload_reqs(h, *in->reqs, n, rw, nk, !rows_nil);
+  if (strict_same) R.strict = R.reqs;
+  else R.strict = upload_reqs(h, *in->strict, n, rw, nk, !rows_nil);
+  R.tolerates = up(h, in->tolerates, n);
+  R.vol = in->vol ? up(h, in->vol, n) : nullptr;
+  R.host_ports = in->host_ports ? up(h, in->host_ports, (size_t)n * 2) : nullptr;
+  R.topo_words = in->topo_owned ? (int)in->topo_words : 0;
+  R.topo_owned = in->topo_owned ? up(h, in->topo_owned, (size_t)n * in->topo_words) : nullptr;
+  R.topo_selected = in->topo_owned ? up(h, in->topo_selected, (size_t)n * in->topo_words) : nullptr;
+  uint32_t ts = 64;
+  while (ts < 2 * n) ts <<= 1;
+  R.table_size = ts; R.seed = in->seed; R.hash_keep = in->hash_keep;
+  R.table_hash = dz<uint64_t>(h, ts); R.table_rep = dz<uint32_t>(h, ts); R.table_class = dz<uint32_t>(h, ts);
+  R.row_slot = dz<uint32_t>(h, n); R.row_class = dz<uint32_t>(h, n);
+  R.n_classes = dz<uint32_t>(h, 1); R.collision = dz<uint32_t>(h, 1);
+  R.min_request = dz<int64_t>(h, nr);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  // ---- one attempt of solve_prepare's phase 2 ----
+  be_fill(h, R.table_hash, 0, (size_t)R.table_size * 8);
+  be_fill(h, R.table_rep, 0xFF, (size_t)R.table_size * 4);
+  be_fill(h, R.n_classes, 0, 4);
+  be_fill(h, R.collision, 0, 4);
+  h->test_row_kernel = 0;
+  be_launch_row_hash(h, (int)n, R);
+  uint32_t n_classes = 0, coll = 0;
+  be_d2h(h, &n_classes, R.n_classes, 4);
+  be_d2h(h, &coll, R.collision, 4);
+  be_sync(h);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  if (n_classes < 1 || n_classes > n) return fail(h, KSOLVE_ERR_DEVICE, "test_classify: class count outside [1, n_rows]");
+  const ks::RecLayout lay{(int)rw, 1, (int)nr, (int)nk};
+  const size_t nc = n_classes;
+  R.class_rep = dz<uint32_t>(h, nc);
+  R.cls_requests = dz<int64_t>(h, nc * nr);
+  h->d_cls_reqs = alloc_reqs(h, n_classes, rw, nk);
+  h->d_cls_strict = alloc_reqs(h, n_classes, rw, nk);
+  R.cls_reqs = h->d_cls_reqs; R.cls_strict = h->d_cls_strict;
+  R.cls_tolerates = dz<uint64_t>(h, nc);
+  R.cls_host_ports = R.host_ports ? dz<uint64_t>(h, nc * 2) : nullptr;
+  R.cls_vol = R.vol ? dz<uint64_t>(h, nc) : nullptr;
+  R.cls_hot = dz<uint64_t>(h, nc * lay.k_hot_words());
+  R.cls_cold = dz<uint64_t>(h, nc * lay.cold_words());
+  R.cls_topo = R.topo_owned ? dz<uint64_t>(h, nc * 2 * R.topo_words) : nullptr;
+  R.lay = lay;
+  be_fill(h, R.min_request, 0x7F, (size_t)nr * 8);
+  be_launch_row_class(h, (int)n, R);
+  be_launch_class_gather(h, (int)n_classes, R);
+  // ---- downloads ----
+  out->n_classes = n_classes; out->collision = coll;
+  out->kernel = h->test_row_kernel & 0xFFu; out->rows_per_block = h->test_row_kernel >> 8;
+  const int lw[8] = {lay.k_mask(), lay.k_req(), lay.k_f0(), lay.k_f1(), lay.k_tol(), lay.k_meta(), lay.k_hot_words(), lay.cold_words()};
+  for (int i = 0; i < 8; ++i) out->lay[i] = lw[i];
+  be_d2h(h, out->row_class, R.row_class, (size_t)n * 4);
+  be_d2h(h, out->class_rep, R.class_rep, nc * 4);
+  be_d2h(h, out->min_request, R.min_request, (size_t)nr * 8);
+  be_d2h(h, out->cls_requests, R.cls_requests, nc * nr * 8);
+  be_d2h(h, out->cls_tolerates, R.cls_tolerates, nc * 8);
+  auto down_reqs = [&](const ks::MutReqTable& t, uint64_t* mask, uint32_t* flags, int64_t* gte, int64_t* lte, int32_t* minv) {
+    be_d2h(h, mask, t.mask, nc * rw * 8);
+    if (flags) { be_d2h(h, flags, t.defined, nc * 4); be_d2h(h, flags + nc, t.complement, nc * 4); be_d2h(h, flags + 2 * nc, t.has_gte, nc * 4); be_d2h(h, flags + 3 * nc, t.has_lte, nc * 4); }
+    be_d2h(h, gte, t.gte, nc * nk * 8); be_d2h(h, lte, t.lte, nc * nk * 8); be_d2h(h, minv, t.minv, nc * nk * 4);
+  };
+  down_reqs(R.cls_reqs, out->reqs_mask, out->reqs_flags, out->reqs_gte, out->reqs_lte, out->reqs_minv);
+  down_reqs(R.cls_strict, out->strict_mask, out->strict_flags, out->strict_gte, out->strict_lte, out->strict_minv);
+  if (R.cls_host_ports) be_d2h(h, out->cls_host_ports, R.cls_host_ports, nc * 2 * 8);
+  if (R.cls_vol) be_d2h(h, out->cls_vol, R.cls_vol, nc * 8);
+  if (R.cls_topo) be_d2h(h, out->cls_topo, R.cls_topo, nc * 2 * R.topo_words * 8);
+  be_d2h(h, out->cls_hot, R.cls_hot, nc * lay.k_hot_words() * 8);
+  be_d2h(h, out->cls_cold, R.cls_cold, nc * lay.cold_words() * 8);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+#endif
+
 // fresh_context: this is the start of a Solve() call (not the re-run of one on the BIG engine): every Solve starts with
 // a context that is not cancelled. The flag is cleared synchronously, so a ksolve_cancel that arrives at any later
 // moment of the call — during classification, the queue sort or the pack kernel — is kept.

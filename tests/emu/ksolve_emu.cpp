@@ -37,7 +37,7 @@ static void be_toc(ksolve_handle* h, int slot) {
   h->timers.ms[slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ((EmuBackend*)h->backend)->t0[slot]).count();
 }
 static void be_launch_it_index(ksolve_handle*, int n, const ks::ItIndexArgs& a) { for (int i = 0; i < n; ++i) ks::it_index_body(i, a); }
-static void be_launch_row_hash(ksolve_handle*, int n, const ks::RowArgs& a) { for (int i = 0; i < n; ++i) ks::row_hash_body(i, a); }
+static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a) { h->test_row_kernel = KSOLVE_TEST_ROW_KERNEL_HOST; for (int i = 0; i < n; ++i) ks::row_hash_body(i, a); }
 static void be_launch_row_class(ksolve_handle*, int n, const ks::RowArgs& a) { for (int i = 0; i < n; ++i) ks::row_class_body(i, a); }
 static void be_launch_class_gather(ksolve_handle*, int n, const ks::RowArgs& a) { for (int i = 0; i < n; ++i) ks::class_gather_body(i, a); }
 static void be_launch_finalize(ksolve_handle*, int n, const ks::FinalizeArgs& a) { for (int i = 0; i < n; ++i) ks::finalize_body(i, a); }
@@ -266,6 +266,15 @@ double ksolve_last_kernel_ms(const ksolve_handle* h, const char* name) {
   return -1;
 }
 int ksolve_is_emulation(void) { return 1; }
+// the classing phase alone, on a bare handle (ksolve_impl.h test_classify)
+ksolve_status ksolve_test_classify(const ksolve_test_classify_in* in, ksolve_test_classify_out* out) {
+  ksolve_handle* h = new ksolve_handle();
+  h->backend = new EmuBackend();
+  const ksolve_status st = ksi::test_classify(h, in, out);
+  if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_classify: %s\n", h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
 // The product's Go-sort (csrc/go_sort.h, used by the finalize kernel for OrderByPrice) on an array of integer keys:
 // out_perm receives the original indices in sorted order, ties as Go's sort.Slice leaves them.
 void ksolve_emu_go_sort(const long long* keys, int n, int* out_perm) {
