@@ -297,7 +297,14 @@ typedef struct {
                                     * pod to the nodes first (csrc/topo_nodes.h, kernel ksolve_pack_topo_nodes); the general engine
                                     * whenever the spread engine declines or stops; 10 = "spread-nodes": the spread engine only, nodes
                                     * allowed (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 7 still answers a problem with nodes
-                                    * and topology groups with reason 34. All give identical Results. */
+                                    * and topology groups with reason 34;
+                                    * 11 = "auto-limits": as 7, and the cursor engine goes on when a NodePool limit binds — a template
+                                    * whose pool has no node left or whose limit-filtered type list is empty is skipped for the pod, a
+                                    * shorter list opens the NodeClaim with that list (scheduler.go:706-727; csrc/fast_engine.h
+                                    * FastLimits) — instead of declining with reason 23 / 24; reason 29 when the lists narrowed more
+                                    * often than there are free template ids; 12 = "cursor-limits": the cursor engine only, with that
+                                    * (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0-10 still decline with 23 / 24; the spread
+                                    * engine does under every setting. All give identical Results. */
 } ksolve_options;
 
 /* One NodeClaim of Results.NewNodeClaims (scheduler.go:282, nodeclaim.go:43-62), in the order the reference's
@@ -338,7 +345,9 @@ typedef struct {
   uint64_t phase_cycles[24];       /* profiling builds only (-DKSOLVE_PHASE_TIMERS), zero otherwise: shader clocks per pack-engine phase
                                     * (queue, class fetch, sort, scan, record load, CanAdd, commit, new claim, dead mark, trySchedule,
                                     * total, CanAdd and scan sub-phases) and a few diagnostic counts; [19] in every build, when the
-                                    * cursor engine ran its existing-node stage: 1 = the nodes' remaining resources in LDS, 2 = in HBM (more than 96 KiB of them, or more than 4096 pod classes) */
+                                    * cursor engine ran its existing-node stage: 1 = the nodes' remaining resources in LDS, 2 = in HBM (more than 96 KiB of them, or more than 4096 pod classes);
+                                    * [23] in every build, when the cursor engine ran under engine 11 / 12: limit stages created | rows of class
+                                    * slots << 16 | NodeClaims open when a limit first excluded a type << 32 (0xFFFFFFFF: never) */
   double us_upload, us_prepass, us_pack, us_finalize, us_download;
   double packing_cost;
   uint32_t engine_used;            /* 1 = general engine, 2 = cursor engine, 3 = spread engine */

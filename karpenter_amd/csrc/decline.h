@@ -26,6 +26,7 @@ enum Decline : int {
   DECLINE_CLAIM_SLOTS = 26,            // more in-flight claims than the cursor engine's memory plan holds: the host moves to the next plan
   DECLINE_UNSCHEDULABLE_POD = 27,      // a pod no claim and no template takes: error codes and diagnostics are the general engine's; both engines
   DECLINE_REFRESHER_DEAD = 28,         // two-wavefront kernel: the refresher wavefront does not answer
+  DECLINE_LIMIT_STAGES = 29,           // engines 11 / 12: NodePool limits narrowed the templates' type lists more often than there are free template ids (limit stages)
   // existing nodes, decided by create() (cursor: engines 7 / 8, spread: engines 9 / 10)
   DECLINE_NODE_CONSOLIDATE_AFTER = 30, // a node under consolidateAfter that some pod must skip (scheduler.go:628)
   DECLINE_NODE_BOUNDS = 31,            // node requirement sets with Gt / Lt bounds

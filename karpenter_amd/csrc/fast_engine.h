@@ -28,7 +28,8 @@
 // The hot loop touches LDS and registers only (claim state, order, requirement-set cache, class slots); HBM sees the
 // queue (64 pods per fetch) and the two result stores per pod.
 //
-// Everything this engine does not handle (an unschedulable pod, NodePool limits that actually exclude a type, more claims
+// Everything this engine does not handle (an unschedulable pod, NodePool limits that actually exclude a type — unless the handle
+// asked for limit stages, FastLimits below —, more claims
 // than the LDS plan holds, non-positive operators, ...) makes it stop with status 3 before it has written a result;
 // the host then runs the general engine (engine.h) on the same problem. There is no CPU path.
 #pragma once
@@ -97,6 +98,18 @@ struct FastNodes {
   unsigned long long n_tests;   // (class, node) resource tests of the stage
 };
 
+// Binding NodePool limits (engines 11 / 12, FastCold::limit_stage): every distinct limit-filtered type list L of a template is a
+// LIMIT STAGE with a template id of its own (the ids the problem's templates leave free, below 32): row `id` of Workspace::t_its
+// holds L, FastMisc::tvmask / tdef [id] are the template's, and the claims opened under L carry `id` in the top byte of their
+// requirement set — so the requirement-set cache, CanAdd and the claims' records filter inside L without knowing about limits.
+// One record in HBM, reset by setup(), read and written by cold code only.
+struct FastLimits {
+  uint8_t real[32];       // template id or stage id -> the template (the identity below n_templates)
+  uint8_t cur[32];        // template -> its current stage (itself while no limit has excluded a type)
+  uint32_t n_ids;         // ids handed out: n_templates + the stages created
+  uint32_t first_claim;   // claims open when a limit first excluded a type (0xFFFFFFFF: no limit bound)
+};
+
 struct FastWork {   // HBM workspace of the cursor engine (host-allocated when the problem may qualify)
   FastVar* var;           // written by the pack kernel, read by ksolve_fast_records
   FastSlot* cls;          // [n_classes]
@@ -123,6 +136,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   FastNodes* nodes;       // [1] what the stage hands to the loop
   uint32_t* nd_pod;       // [n_pods] pod index of compacted queue entry j (sorted_pods of the queue the loop sees)
   const uint64_t* nd_dead0;   // [n_classes][node_words] the static (class, node) verdicts (ksolve_node_dead0) for this solve's class ids
+  FastLimits* lim;        // [1] engines 11 / 12: the engine goes on when a NodePool limit binds (Workspace::t_its has 32 rows then); null otherwise
   FastPlan plan;
   int enabled;
 };
@@ -469,6 +483,7 @@ struct FastCold {
     vm = W::uniform(vm);
     const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
     const int t = (int)(vm >> 56);
+    const int tr = F.lim ? (int)F.lim->real[t] : t;   // t may be a limit stage (FastLimits): its row of t_its, the template's requirements and overhead
     const int iw = P.it_words, n_its = P.n_its, nr = P.n_res;
     const Dict& d = P.dict;
     const ProblemView& Pv = P;
@@ -494,7 +509,7 @@ struct FastCold {
     // a compatible available offering (nodeclaim.go:624-638, types.go:553-570)
     uint32_t zones = (1u << P.n_zones) - 1, cts = (1u << P.n_cts) - 1;
     {
-      const uint64_t* tm = P.tmpl_reqs.mask + (size_t)t * d.req_words;
+      const uint64_t* tm = P.tmpl_reqs.mask + (size_t)tr * d.req_words;
       const uint32_t tdef = Mp->tdef[t];
       if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)tm[d.key_word_off[d.key_zone]];
       if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)tm[d.key_word_off[d.key_ct]];
@@ -524,7 +539,7 @@ struct FastCold {
     int count = 0;
     const int poff = n_pool;
     int32_t f0 = -1, f1 = -1, f2 = -1, f3 = -1;
-    const int64_t* eff = eff_alloc(P, t);   // allocatable less the template's daemon overhead (ksp.h): the vectors a claim of template t is tested against
+    const int64_t* eff = eff_alloc(P, tr);   // allocatable less the template's daemon overhead (ksp.h): the vectors a claim of template t is tested against
     for (;;) {
       const uint64_t any = W::reduce_or(iw, [&](int w) { return (uint64_t)rem[w]; });
       if (!any) break;
@@ -582,6 +597,12 @@ struct FastCold {
     const Dict& d = P.dict;
     const int nk = d.n_keys, iw = P.it_words, nr = P.n_res, n_its = P.n_its, nc = P.n_classes, T = P.n_templates;
     const ProblemView& Pv = P;
+    if (F.lim) {   // no limit stage yet: every id stands for itself
+      FastLimits* const lim = F.lim;
+      W::for_n(32, [&](int i) { lim->real[i] = (uint8_t)i; lim->cur[i] = (uint8_t)i; });
+      if (W::leader()) { lim->n_ids = (uint32_t)T; lim->first_claim = 0xFFFFFFFFu; }
+      W::sync();
+    }
     if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
     // (instance types may use any operator: with positive sets on the claim side the NotIn / DoesNotExist escape of
     // requirements.go:260-265 never applies, so compatible() stays monotone)
@@ -963,6 +984,59 @@ struct FastCold {
     }
   }
 
+  // Engines 11 / 12 (FastWork::lim), the limit steps of addToNewNodeClaim (scheduler.go:706-727) for template t with limits lm:
+  // the id the new claim's requirement set carries — t itself while the limits exclude no type of the template, else the limit
+  // stage (FastLimits) whose row of t_its is L = t_its[t] less the types that no longer fit `remaining`, created here when L is
+  // narrower than the template's current stage. -1: the reference skips the template for this pod (no node left, :711-715, or L
+  // empty, :717-719), -2: no id left (DECLINE_LIMIT_STAGES). Remaining resources only shrink, so a template's stages form a
+  // chain that only narrows; a claim keeps the stage it was opened in (limits are consulted at creation only).
+  KS_COLD int limit_stage(int t, uint32_t lm) {
+    const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
+    const int nr = P.n_res, iw = P.it_words, n_its = P.n_its;
+    const int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+    if (((lm >> nr) & 1) && rem[nr] <= 0) return -1;
+    FastLimits* const lim = F.lim;
+    const int cur = (int)lim->cur[t];
+    const ProblemView& Pv = P;
+    const uint64_t* tits = S.t_its + (size_t)t * iw;
+    const uint64_t* cits = S.t_its + (size_t)cur * iw;
+    KS_LDS uint64_t* L = Mp->its;
+    uint64_t any = 0, differs = 0;
+    for (int w = 0; w < iw; ++w) {
+      const uint64_t in = tits[w];
+      const uint64_t okm = in ? W::ballot([&](int l) {
+        const int it = w * 64 + l;
+        if (it >= n_its || !((in >> l) & 1)) return false;
+        bool v = true;
+        for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
+        return v;
+      }) : 0ull;
+      W::store(&L[w], okm);
+      any |= okm; differs |= okm ^ cits[w];
+    }
+    W::sync();
+    if (differs && W::leader() && lim->first_claim == 0xFFFFFFFFu) lim->first_claim = (uint32_t)n_claims;   // the first exclusion of the solve
+    if (!any) return -1;
+    if (!differs) return cur;
+    const int s = (int)lim->n_ids;
+    if (s >= 32) return -2;
+    uint64_t* srow = S.t_its + (size_t)s * iw;
+    W::for_n(iw, [&](int w) { srow[w] = L[w]; });
+    if (W::leader()) {
+      lim->real[s] = (uint8_t)t; lim->cur[t] = (uint8_t)s; lim->n_ids = (uint32_t)(s + 1);
+      Mp->tvmask[s] = (Mp->tvmask[t] & ~(0xFFull << 56)) | ((uint64_t)s << 56);
+      Mp->tdef[s] = Mp->tdef[t];
+    }
+    // a class takes claims of the stage exactly when it takes claims of the template: bit t of every class's tmplok, copied to
+    // bit s — in the class records and in the slots' copies (the loops read theirs from the slots whenever the driver calls them)
+    FastSlot* fc = F.cls;
+    W::for_n(P.n_classes, [&](int c) { const uint32_t k = fc[c].tmplok; fc[c].tmplok = k | (((k >> t) & 1u) << s); });
+    KS_LDS FastSlot* as = aslot;
+    W::for_n(64 * R, [&](int i) { const uint32_t k = as[i].tmplok; as[i].tmplok = k | (((k >> t) & 1u) << s); });
+    W::sync();
+    return s;
+  }
+
   // addToNewNodeClaim (scheduler.go:695-790) for a pod no in-flight claim accepted: 1 = claim n created (appended to the
   // order with one pod; its acceptance words computed), 0 = the engine must stop (bail_code; DECLINE_KERNEL_CAPACITY = capacity).
   KS_COLD int new_claim(int slot, int bi, int n) {
@@ -974,11 +1048,18 @@ struct FastCold {
     for (int t = 0; t < T; ++t) {
       if (!((active_templates >> t) & 1u)) continue;
       const uint32_t lm = P.tmpl_limit_mask[t];
-      if (lm) { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail_code = why; return 0; } }
+      int ts = t;   // the id the claim's requirement set carries: the template, or its limit stage
+      if (lm) {
+        if (F.lim) {
+          ts = (int)W::uniform((uint64_t)(uint32_t)limit_stage(t, lm));
+          if (ts == -1) continue;   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
+          if (ts < 0) { bail_code = DECLINE_LIMIT_STAGES; return 0; }
+        } else { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail_code = why; return 0; } }
+      }
       host_seq++;
       n_ref_extra++;
       if (!((cs.tmplok >> t) & 1u)) continue;
-      const uint64_t m = Mp->tvmask[t] & cs.cvmask;
+      const uint64_t m = Mp->tvmask[ts] & cs.cvmask;
       if (!fast_fields_ok(m, cs.dmask)) continue;
       FastEnt e;
       int eh = fast_lookup(ent, m, e);
@@ -1044,6 +1125,10 @@ struct FastCold {
     c.cycles[18] = (hs->hw[2] << 32) | (unsigned long long)(hs->mail.simd[0] | (hs->mail.simd[1] << 8) | (hs->mail.simd[2] << 16) | (hs->mail.simd[3] << 24));
 #endif
     if (F.nodes) c.cycles[19] = (unsigned long long)nd.variant;
+    // engines 11 / 12: limit stages created | rows of class slots << 16 | claims open at the first exclusion << 32. Reported as
+    // phase_cycles[23] through full_filters, a count of the general engine's that this engine leaves at zero: every slot of `cycles`
+    // holds a timer in profiling builds
+    if (F.lim) c.full_filters = (unsigned long long)(F.lim->n_ids - (uint32_t)Pk->n_templates) | ((unsigned long long)R << 16) | ((unsigned long long)F.lim->first_claim << 32);
     if (W::leader()) *S.counters = c;
     W::sync();
   }
@@ -2155,7 +2240,8 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   const RecLayout ly = P.lay;
   const Dict& d = P.dict;
   const FastClaim st = a.fw.c_state[c];
-  const int t = (int)(st.vmask >> 56);
+  const int ts = (int)(st.vmask >> 56);
+  const int t = a.fw.lim ? (int)a.fw.lim->real[ts] : ts;   // the claim's template (its requirement set may carry a limit stage, FastLimits; the cache entry below is the stage's)
   const FastVar fv = *a.fw.var;
   // keys the requirement set defines: the template's, and of the keys pods select on those whose guard bit is clear
   uint32_t vdef = P.tmpl_reqs.defined[t];

@@ -80,6 +80,7 @@ struct ksolve_handle {
   uint32_t engine_used = 0, fast_reason = 0, fast_attempts = 0;
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
   bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
+  bool opt_limits = false;      // engine = auto-limits / cursor-limits (11 / 12: as 7 / 8, opt_nodes included): the cursor engine goes on when a NodePool limit binds (fast_engine.h FastLimits)
   bool opt_spread_nodes = false;   // engine = auto-nodes-spread / spread-nodes (9 / 10; opts.engine holds 0 / 6 from then on): the spread engine may take a problem with existing nodes (topo_nodes.h)
   uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
@@ -310,6 +311,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   if (h->opts.engine == 7 || h->opts.engine == 8) { h->opt_nodes = true; h->opts.engine = h->opts.engine == 7 ? 0u : 2u; }   // automatic / cursor only, existing nodes allowed
   else if (h->opts.engine == 9) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opts.engine = 0u; }   // as 7, and the spread engine may take nodes too
   else if (h->opts.engine == 10) { h->opt_spread_nodes = true; h->opts.engine = 6u; }                        // spread only, existing nodes allowed
+  else if (h->opts.engine == 11 || h->opts.engine == 12) { h->opt_nodes = true; h->opt_limits = true; h->opts.engine = h->opts.engine == 11 ? 0u : 2u; }   // as 7 / 8, and binding NodePool limits do not stop the cursor engine
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -620,7 +622,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   W.c_hp = P.hp_on ? dz<uint64_t>(h, mc) : nullptr;
   W.o_key = dz<uint32_t>(h, mc); W.o_ord = dz<uint32_t>(h, mc); W.o_pos = dz<uint32_t>(h, mc);
   W.queue = dz<uint32_t>(h, (size_t)d->n_pods + 1); W.last_len = dz<uint32_t>(h, d->n_pods);
-  W.t_its = dz<uint64_t>(h, (size_t)d->n_templates * it_words);
+  W.t_its = dz<uint64_t>(h, (size_t)(h->opt_limits ? 32u : d->n_templates) * it_words);   // (engines 11 / 12: a row for every limit stage too, fast_engine.h FastLimits)
   W.t_remaining = dz<int64_t>(h, (size_t)d->n_templates * (d->n_res + 1));
   W.assign = dz<int32_t>(h, d->n_pods); W.err = dz<uint8_t>(h, d->n_pods); W.diag = dz<uint8_t>(h, d->n_pods); W.slot = dz<uint32_t>(h, d->n_pods);
   W.n_claims_out = dz<int>(h, 1); W.status_out = dz<int>(h, 1);
@@ -857,6 +859,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       { const size_t oc = std::min<size_t>(65472, ((size_t)mc + 63) & ~(size_t)63) + 64; fw.o_key = dz<uint16_t>(h, oc); fw.o_ord = dz<uint16_t>(h, oc); fw.o_snap = dz<uint16_t>(h, oc); }
       h->d_fast_args = dz<ks::FastArgs>(h, 1);
       if (P.plain_nodes) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
+      if (h->opt_limits) fw.lim = dz<ks::FastLimits>(h, 1);
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the
@@ -2369,7 +2372,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan; a handle whose claims live in HBM (an earlier Solve() moved it there, or engine =
       // cursor-wide / cursor-hbm) runs alone on the kernel of its plan
-      if (h->fw.plan.global_state == 0 && !h->fw.nodes) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop)
+      if (h->fw.plan.global_state == 0 && !h->fw.nodes && !h->fw.lim) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop; so does one of engines 11 / 12)
       else { be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1; }
     }
     else if (h->opts.engine >= 2) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");
