@@ -304,7 +304,13 @@ typedef struct {
                                     * FastLimits) — instead of declining with reason 23 / 24; reason 29 when the lists narrowed more
                                     * often than there are free template ids; 12 = "cursor-limits": the cursor engine only, with that
                                     * (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0-10 still decline with 23 / 24; the spread
-                                    * engine does under every setting. All give identical Results. */
+                                    * engine does under 0-12;
+                                    * 13 = "auto-limits-spread": 9 and 11 together, and the spread engine goes on when a NodePool limit
+                                    * binds too (csrc/topo_engine.h limit_stage: the same limit stages, reason 29 when the ids run out);
+                                    * the general engine whenever either engine declines or stops; 14 = "spread-limits": the spread
+                                    * engine only, existing nodes allowed as under 10, with limit stages (KSOLVE_ERR_UNSUPPORTED with
+                                    * "spread engine declined the problem (reason N)" instead of the fallback).
+                                    * All give identical Results. */
 } ksolve_options;
 
 /* One NodeClaim of Results.NewNodeClaims (scheduler.go:282, nodeclaim.go:43-62), in the order the reference's

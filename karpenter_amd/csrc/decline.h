@@ -20,13 +20,13 @@ enum Decline : int {
   DECLINE_CACHE_FULL = 20,             // no room for a requirement set's cache entry or Pareto vectors (a claim's acceptance words, a new class slot)
   DECLINE_REFRESH_FAILED = 21,         // the same while the driver recomputed a claim's acceptance words
   DECLINE_UNKNOWN_EVENT = 22,          // the loop returned an event the driver does not know
-  DECLINE_LIMIT_NODES = 23,            // a NodePool's `nodes` limit is used up (filterByRemainingResources, scheduler.go:1069-1085); both engines
-  DECLINE_LIMIT_EXCLUDES_TYPE = 24,    // a NodePool limit excludes an instance type of the template (scheduler.go:1069-1085); both engines
+  DECLINE_LIMIT_NODES = 23,            // a NodePool's `nodes` limit is used up (filterByRemainingResources, scheduler.go:1069-1085); both engines — not under the settings with limit stages (cursor: 11-13, spread: 13 / 14)
+  DECLINE_LIMIT_EXCLUDES_TYPE = 24,    // a NodePool limit excludes an instance type of the template (scheduler.go:1069-1085); both engines, as 23
   DECLINE_CACHE_FULL_NEW_CLAIM = 25,   // no room for the cache entry of a new claim's requirement set (addToNewNodeClaim, scheduler.go:695-790); both engines
   DECLINE_CLAIM_SLOTS = 26,            // more in-flight claims than the cursor engine's memory plan holds: the host moves to the next plan
   DECLINE_UNSCHEDULABLE_POD = 27,      // a pod no claim and no template takes: error codes and diagnostics are the general engine's; both engines
   DECLINE_REFRESHER_DEAD = 28,         // two-wavefront kernel: the refresher wavefront does not answer
-  DECLINE_LIMIT_STAGES = 29,           // engines 11 / 12: NodePool limits narrowed the templates' type lists more often than there are free template ids (limit stages)
+  DECLINE_LIMIT_STAGES = 29,           // engines 11-14, both engines: NodePool limits narrowed the templates' type lists more often than there are free template ids (limit stages)
   // existing nodes, decided by create() (cursor: engines 7 / 8, spread: engines 9 / 10)
   DECLINE_NODE_CONSOLIDATE_AFTER = 30, // a node under consolidateAfter that some pod must skip (scheduler.go:628)
   DECLINE_NODE_BOUNDS = 31,            // node requirement sets with Gt / Lt bounds

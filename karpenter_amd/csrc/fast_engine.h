@@ -98,7 +98,7 @@ struct FastNodes {
   unsigned long long n_tests;   // (class, node) resource tests of the stage
 };
 
-// Binding NodePool limits (engines 11 / 12, FastCold::limit_stage): every distinct limit-filtered type list L of a template is a
+// Binding NodePool limits (engines 11 / 12 on the cursor engine, 13 / 14 on the spread engine; limit_stage_id): every distinct limit-filtered type list L of a template is a
 // LIMIT STAGE with a template id of its own (the ids the problem's templates leave free, below 32): row `id` of Workspace::t_its
 // holds L, FastMisc::tvmask / tdef [id] are the template's, and the claims opened under L carry `id` in the top byte of their
 // requirement set — so the requirement-set cache, CanAdd and the claims' records filter inside L without knowing about limits.
@@ -136,7 +136,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   FastNodes* nodes;       // [1] what the stage hands to the loop
   uint32_t* nd_pod;       // [n_pods] pod index of compacted queue entry j (sorted_pods of the queue the loop sees)
   const uint64_t* nd_dead0;   // [n_classes][node_words] the static (class, node) verdicts (ksolve_node_dead0) for this solve's class ids
-  FastLimits* lim;        // [1] engines 11 / 12: the engine goes on when a NodePool limit binds (Workspace::t_its has 32 rows then); null otherwise
+  FastLimits* lim;        // [1] engines 11-14: the engine goes on when a NodePool limit binds (Workspace::t_its has 32 rows then); null otherwise
   FastPlan plan;
   int enabled;
 };
@@ -390,6 +390,55 @@ KS_FN void subtract_max(const ProblemView& P, const Workspace& S, const FastWork
     W::store(&rem[q], rem[q] - mx);
   }
   W::sync();
+}
+// Engines 11-14 (FastWork::lim), the limit steps of addToNewNodeClaim (scheduler.go:706-727) for template t with limits lm, the part
+// both engines share: the id the new claim's requirement set carries — t itself while the limits exclude no type of the template,
+// else the limit stage (FastLimits) whose row of t_its is L = t_its[t] less the types that no longer fit `remaining`, created here
+// when L is narrower than the template's current stage (its row, tvmask / tdef, the first exclusion's claim count). -1: the
+// reference skips the template for this pod (no node left, :711-715, or L empty, :717-719), -2: no id left (DECLINE_LIMIT_STAGES).
+// fresh: the id was created by this call — the caller copies bit t of every class's tmplok to bit id, in F.cls and in whatever
+// copies its loop holds, and fences. Remaining resources only shrink, so a template's stages form a chain that only narrows; a
+// claim keeps the stage it was opened in (limits are consulted at creation only).
+template <class W>
+KS_FN int limit_stage_id(const ProblemView& P, const Workspace& S, const FastWork& F, KS_LDS FastMisc* Mp, int t, uint32_t lm, int n_claims, bool& fresh) {
+  fresh = false;
+  const int nr = P.n_res, iw = P.it_words, n_its = P.n_its;
+  const int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
+  if (((lm >> nr) & 1) && rem[nr] <= 0) return -1;
+  FastLimits* const lim = F.lim;
+  const int cur = (int)lim->cur[t];
+  const ProblemView& Pv = P;
+  const uint64_t* tits = S.t_its + (size_t)t * iw;
+  const uint64_t* cits = S.t_its + (size_t)cur * iw;
+  KS_LDS uint64_t* L = Mp->its;
+  uint64_t any = 0, differs = 0;
+  for (int w = 0; w < iw; ++w) {
+    const uint64_t in = tits[w];
+    const uint64_t okm = in ? W::ballot([&](int l) {
+      const int it = w * 64 + l;
+      if (it >= n_its || !((in >> l) & 1)) return false;
+      bool v = true;
+      for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
+      return v;
+    }) : 0ull;
+    W::store(&L[w], okm);
+    any |= okm; differs |= okm ^ cits[w];
+  }
+  W::sync();
+  if (differs && W::leader() && lim->first_claim == 0xFFFFFFFFu) lim->first_claim = (uint32_t)n_claims;   // the first exclusion of the solve
+  if (!any) return -1;
+  if (!differs) return cur;
+  const int s = (int)lim->n_ids;
+  if (s >= 32) return -2;
+  uint64_t* srow = S.t_its + (size_t)s * iw;
+  W::for_n(iw, [&](int w) { srow[w] = L[w]; });
+  if (W::leader()) {
+    lim->real[s] = (uint8_t)t; lim->cur[t] = (uint8_t)s; lim->n_ids = (uint32_t)(s + 1);
+    Mp->tvmask[s] = (Mp->tvmask[t] & ~(0xFFull << 56)) | ((uint64_t)s << 56);
+    Mp->tdef[s] = Mp->tdef[t];
+  }
+  fresh = true;
+  return s;
 }
 
 // Everything that happens rarely (a new requirement set, a new claim, a new class slot, pdqsort leaving its single-move
@@ -984,49 +1033,13 @@ struct FastCold {
     }
   }
 
-  // Engines 11 / 12 (FastWork::lim), the limit steps of addToNewNodeClaim (scheduler.go:706-727) for template t with limits lm:
-  // the id the new claim's requirement set carries — t itself while the limits exclude no type of the template, else the limit
-  // stage (FastLimits) whose row of t_its is L = t_its[t] less the types that no longer fit `remaining`, created here when L is
-  // narrower than the template's current stage. -1: the reference skips the template for this pod (no node left, :711-715, or L
-  // empty, :717-719), -2: no id left (DECLINE_LIMIT_STAGES). Remaining resources only shrink, so a template's stages form a
-  // chain that only narrows; a claim keeps the stage it was opened in (limits are consulted at creation only).
+  // Engines 11 / 12 (FastWork::lim): the id the new claim's requirement set carries (limit_stage_id above: the template, its limit
+  // stage, -1: skip the template for this pod, -2: no id left), and this engine's share of a new stage.
   KS_COLD int limit_stage(int t, uint32_t lm) {
-    const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
-    const int nr = P.n_res, iw = P.it_words, n_its = P.n_its;
-    const int64_t* rem = S.t_remaining + (size_t)t * (nr + 1);
-    if (((lm >> nr) & 1) && rem[nr] <= 0) return -1;
-    FastLimits* const lim = F.lim;
-    const int cur = (int)lim->cur[t];
-    const ProblemView& Pv = P;
-    const uint64_t* tits = S.t_its + (size_t)t * iw;
-    const uint64_t* cits = S.t_its + (size_t)cur * iw;
-    KS_LDS uint64_t* L = Mp->its;
-    uint64_t any = 0, differs = 0;
-    for (int w = 0; w < iw; ++w) {
-      const uint64_t in = tits[w];
-      const uint64_t okm = in ? W::ballot([&](int l) {
-        const int it = w * 64 + l;
-        if (it >= n_its || !((in >> l) & 1)) return false;
-        bool v = true;
-        for (int q = 0; q < nr; ++q) if ((lm >> q) & 1) v = v && Pv.it_cap[(size_t)q * n_its + it] <= rem[q];
-        return v;
-      }) : 0ull;
-      W::store(&L[w], okm);
-      any |= okm; differs |= okm ^ cits[w];
-    }
-    W::sync();
-    if (differs && W::leader() && lim->first_claim == 0xFFFFFFFFu) lim->first_claim = (uint32_t)n_claims;   // the first exclusion of the solve
-    if (!any) return -1;
-    if (!differs) return cur;
-    const int s = (int)lim->n_ids;
-    if (s >= 32) return -2;
-    uint64_t* srow = S.t_its + (size_t)s * iw;
-    W::for_n(iw, [&](int w) { srow[w] = L[w]; });
-    if (W::leader()) {
-      lim->real[s] = (uint8_t)t; lim->cur[t] = (uint8_t)s; lim->n_ids = (uint32_t)(s + 1);
-      Mp->tvmask[s] = (Mp->tvmask[t] & ~(0xFFull << 56)) | ((uint64_t)s << 56);
-      Mp->tdef[s] = Mp->tdef[t];
-    }
+    const ProblemView& P = *Pk; const FastWork& F = *Fk;
+    bool fresh = false;
+    const int s = limit_stage_id<W>(P, *Sk, F, Mp, t, lm, n_claims, fresh);
+    if (!fresh) return s;
     // a class takes claims of the stage exactly when it takes claims of the template: bit t of every class's tmplok, copied to
     // bit s — in the class records and in the slots' copies (the loops read theirs from the slots whenever the driver calls them)
     FastSlot* fc = F.cls;

@@ -81,6 +81,7 @@ struct ksolve_handle {
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
   bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
   bool opt_limits = false;      // engine = auto-limits / cursor-limits (11 / 12: as 7 / 8, opt_nodes included): the cursor engine goes on when a NodePool limit binds (fast_engine.h FastLimits)
+  bool opt_spread_limits = false;  // engine = auto-limits-spread / spread-limits (13 / 14: as 9 + 11 / as 10): the spread engine goes on when a NodePool limit binds (topo_engine.h limit_stage)
   bool opt_spread_nodes = false;   // engine = auto-nodes-spread / spread-nodes (9 / 10; opts.engine holds 0 / 6 from then on): the spread engine may take a problem with existing nodes (topo_nodes.h)
   uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
@@ -312,6 +313,8 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   else if (h->opts.engine == 9) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opts.engine = 0u; }   // as 7, and the spread engine may take nodes too
   else if (h->opts.engine == 10) { h->opt_spread_nodes = true; h->opts.engine = 6u; }                        // spread only, existing nodes allowed
   else if (h->opts.engine == 11 || h->opts.engine == 12) { h->opt_nodes = true; h->opt_limits = true; h->opts.engine = h->opts.engine == 11 ? 0u : 2u; }   // as 7 / 8, and binding NodePool limits do not stop the cursor engine
+  else if (h->opts.engine == 13) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opt_limits = true; h->opt_spread_limits = true; h->opts.engine = 0u; }   // 9 and 11 together, and binding limits do not stop the spread engine either
+  else if (h->opts.engine == 14) { h->opt_spread_nodes = true; h->opt_spread_limits = true; h->opts.engine = 6u; }   // as 10, with limit stages
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -622,7 +625,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   W.c_hp = P.hp_on ? dz<uint64_t>(h, mc) : nullptr;
   W.o_key = dz<uint32_t>(h, mc); W.o_ord = dz<uint32_t>(h, mc); W.o_pos = dz<uint32_t>(h, mc);
   W.queue = dz<uint32_t>(h, (size_t)d->n_pods + 1); W.last_len = dz<uint32_t>(h, d->n_pods);
-  W.t_its = dz<uint64_t>(h, (size_t)(h->opt_limits ? 32u : d->n_templates) * it_words);   // (engines 11 / 12: a row for every limit stage too, fast_engine.h FastLimits)
+  W.t_its = dz<uint64_t>(h, (size_t)(h->opt_limits || h->opt_spread_limits ? 32u : d->n_templates) * it_words);   // (engines 11-14: a row for every limit stage too, fast_engine.h FastLimits)
   W.t_remaining = dz<int64_t>(h, (size_t)d->n_templates * (d->n_res + 1));
   W.assign = dz<int32_t>(h, d->n_pods); W.err = dz<uint8_t>(h, d->n_pods); W.diag = dz<uint8_t>(h, d->n_pods); W.slot = dz<uint32_t>(h, d->n_pods);
   W.n_claims_out = dz<int>(h, 1); W.status_out = dz<int>(h, 1);
@@ -876,6 +879,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       fw.q_class = dz<uint32_t>(h, d->n_pods); fw.q_claim = dz<uint32_t>(h, d->n_pods); fw.q_cnt = dz<uint32_t>(h, d->n_pods);
       fw.o_key = nullptr; fw.o_ord = nullptr; fw.o_snap = nullptr;
       tw.rec = dz<ks::TopoRec>(h, mc);
+      if (h->opt_spread_limits) fw.lim = dz<ks::FastLimits>(h, 1);
       auto align = [](int x) { return (x + 15) & ~15; };
       ks::FastPlan& fp = fw.plan;
       int off = 0;

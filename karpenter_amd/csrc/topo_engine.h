@@ -29,7 +29,8 @@
 // dictionary key with its inverse groups (every domain the pod could land in is blocked, topology.go:203-206, :213-219).
 //
 // Whatever it does not handle (node filters, groups created by relaxation, affinity on the hostname, three or more dictionary-key
-// groups on one pod, maxSkew beyond a counter's range, an unschedulable pod, NodePool limits that exclude a type ...) makes it stop
+// groups on one pod, maxSkew beyond a counter's range, an unschedulable pod, NodePool limits that exclude a type — unless the handle
+// asked for limit stages, engines 13 / 14, fast_engine.h FastLimits — ...) makes it stop
 // with status 3 before it has written a result; the host runs the general engine on the same problem. There is no CPU path.
 #pragma once
 #include "fast_engine.h"
@@ -52,6 +53,7 @@ struct TopoEngine {
   uint64_t track_fields = 0;   // bit 4 f: counter f has a list
   unsigned long long n_ref = 0, n_tests = 0, n_windows = 0, n_listed = 0;
   int bail = 0;
+  int tok_stale = 0;   // a limit stage was created: the classes' tmplok words changed in FastWork::cls, the loop's lane copies are behind
   unsigned long long tc0 = 0, tc1 = 0, tc2 = 0, tc3 = 0, tc4 = 0, tc5 = 0, tc6 = 0, tc7 = 0, tc8 = 0, tc9 = 0;   // profiling builds (-DKSOLVE_PHASE_TIMERS): shader clock per phase of a step
   int last_kind = 0, last_x = 0, last_p = 0;   // the move of the last step (1: a claim gained a pod, from position last_p; 2: a new claim), 0: pending in `order` / none
 
@@ -334,6 +336,29 @@ struct TopoEngine {
     }
   }
 
+  // Engines 13 / 14 (FastWork::lim): the id the new claim's requirement set carries (fast_engine.h limit_stage_id: the template, its
+  // limit stage, -1: skip the template for this pod, -2: no id left), and this engine's share of a new stage: bit t of every
+  // class's tmplok copied to bit s in the class records. The loop's copies — the block's classes in lane registers — are read
+  // again by reload_tok once new_claim has returned (tok_stale); lane_test finds the stage's id in the claim's requirement set.
+  KS_COLD int limit_stage(int t, uint32_t lm) {
+    const ProblemView& P = *Pk; const FastWork& F = *Fk;
+    bool fresh = false;
+    const int s = limit_stage_id<W>(P, *Sk, F, Mp, t, lm, cold.n_claims, fresh);
+    if (!fresh) return s;
+    FastSlot* fc = F.cls;
+    W::for_n(P.n_classes, [&](int c) { const uint32_t k = fc[c].tmplok; fc[c].tmplok = k | (((k >> t) & 1u) << s); });
+    W::sync();
+    tok_stale = 1;
+    return s;
+  }
+  // the tmplok words of the classes of the block's pods, one per lane, as the loop's gather reads them
+  KS_COLD LaneVar<uint32_t> reload_tok(int base, int bn) {
+    LaneVar<uint32_t> tok;
+    const uint32_t* qc = Fk->q_class; const FastSlot* fc = Fk->cls;
+    W::each([&](int l) { tok.at(l) = fc[qc[base + (l < bn ? l : bn - 1)] & ~kFastLastBit].tmplok; });
+    tok_stale = 0;
+    return tok;
+  }
   // addToNewNodeClaim (scheduler.go:695-790) for a pod no in-flight claim accepted, every case: several templates, NodePool limits,
   // requirement sets that are not cached yet, pdqsort's other paths. The claim's id, or -1: stop (bail; DECLINE_KERNEL_CAPACITY = capacity).
   // (solve() places the common case itself: one template without limits, the set cached, the single stable move.)
@@ -351,12 +376,20 @@ struct TopoEngine {
     for (int t = 0; t < T; ++t) {
       if (!((cold.active_templates >> t) & 1u)) continue;
       const uint32_t lm = P.tmpl_limit_mask[t];
-      if (lm) { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail = why; return -1; } }
+      int ts = t;   // the id the claim's requirement set carries: the template, or its limit stage
+      if (lm) {
+        if (F.lim) {
+          ts = (int)W::uniform((uint64_t)(uint32_t)limit_stage(t, lm));
+          if (ts == -1) continue;   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
+          if (ts < 0) { bail = DECLINE_LIMIT_STAGES; return -1; }
+          kc.tmplok |= ((kc.tmplok >> t) & 1u) << ts;   // (this pod's copy of the class came from the loop's registers)
+        } else { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail = why; return -1; } }
+      }
       cold.host_seq++;
       n_ref++;
-      // CanAdd on the fresh claim: the template's set, no requests, every hostname counter zero (the limits are >= 0)
+      // CanAdd on the fresh claim: the template's (or the stage's) set, no requests, every hostname counter zero (the limits are >= 0)
       uint64_t m2 = 0;
-      int v = lane_test(Mp->tvmask[t], 0, 0, 0, 0, 0ull, kc, zc, zkv, zd, zkw, cold.ent, m2);   // (every lane computes the same verdict: the state is wave-uniform)
+      int v = lane_test(Mp->tvmask[ts], 0, 0, 0, 0, 0ull, kc, zc, zkv, zd, zkw, cold.ent, m2);   // (every lane computes the same verdict: the state is wave-uniform)
       v = fast_uniform(v);
       m2 = W::uniform(m2);
       if (v == 0) continue;
@@ -594,6 +627,9 @@ struct TopoEngine {
     c.bin_evaluations = n_tests; c.full_evaluations = n_windows; c.queue_pops = steps; c.sorts = steps; c.slow_sorts = order.slow_sorts;
     c.ref_bin_evaluations = n_ref; c.it_evaluations = n_listed;
     c.decline = (unsigned long long)(bail > 0 ? bail : 0);
+    // engines 13 / 14: limit stages created | claims open at the first exclusion << 32 — the cursor engine's word (phase_cycles[23],
+    // FastCold::finish) with its rows field left at zero
+    if (F.lim) c.full_filters = (unsigned long long)(F.lim->n_ids - (uint32_t)Pk->n_templates) | ((unsigned long long)F.lim->first_claim << 32);
     c.cycles[0] = tc0; c.cycles[1] = tc1; c.cycles[2] = tc2; c.cycles[3] = tc3; c.cycles[4] = tc4; c.cycles[5] = tc5; c.cycles[6] = tc6; c.cycles[7] = tc7; c.cycles[8] = tc8; c.cycles[9] = tc9;
     if (W::leader()) *S.counters = c;
     W::sync();
@@ -906,6 +942,7 @@ struct TopoEngine {
             const int c = fast_uniform(new_claim(tcc, csc));
             pull(); wvalid = false;
             if (c < 0) { status = fast_uniform(bail) == DECLINE_KERNEL_CAPACITY ? 1 : 3; break; }
+            if (fast_uniform(tok_stale)) c_tok = reload_tok(base, bn);   // a limit stage was created: the classes accept one more template id
             oclaim.set(bi, (uint32_t)c); ocntv.set(bi, 0u);
           }
           KS_TSEC(t6)
