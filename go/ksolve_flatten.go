@@ -970,6 +970,9 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // KsolveEngineAutoNodesSpread = KsolveEngineAutoNodes, and a problem with existing nodes AND topology groups that is otherwise of
 // the spread engine's shape runs on the spread engine, which offers every pod to the nodes first: the setting for a cluster whose
 // pods carry spread constraints. KsolveEngineSpreadNodes refuses instead of falling back (tests).
+// KsolveEngineAutoOperators = "auto-operators" (15): existing nodes and binding NodePool limits on both fast engines, and the cursor
+// engine takes NodePools whose requirements use NotIn, Exists, DoesNotExist, Gt or Lt — what the NodePool examples carry.
+// KsolveEngineCursorOperators (16) is the cursor engine alone with that acceptance and refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -979,6 +982,9 @@ const (
 
 	KsolveEngineAutoNodesSpread uint32 = 9
 	KsolveEngineSpreadNodes     uint32 = 10
+
+	KsolveEngineAutoOperators   uint32 = 15
+	KsolveEngineCursorOperators uint32 = 16
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

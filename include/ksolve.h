@@ -309,7 +309,16 @@ typedef struct {
                                     * binds too (csrc/topo_engine.h limit_stage: the same limit stages, reason 29 when the ids run out);
                                     * the general engine whenever either engine declines or stops; 14 = "spread-limits": the spread
                                     * engine only, existing nodes allowed as under 10, with limit stages (KSOLVE_ERR_UNSUPPORTED with
-                                    * "spread engine declined the problem (reason N)" instead of the fallback).
+                                    * "spread engine declined the problem (reason N)" instead of the fallback);
+                                    * 15 = "auto-operators": as 13, and the cursor engine also takes NodePools whose requirements are
+                                    * not In sets — NotIn, Exists, DoesNotExist, Gt, Lt (csrc/fast_engine.h, "Complement templates":
+                                    * the values such a requirement admits fill the template's field of the packed requirement set,
+                                    * and the guard bit above the field says whether a NodeClaim still holds the NodePool's own
+                                    * requirement or a concrete set) — instead of declining with reason 3 (1 for Gt / Lt); pods with
+                                    * such operators (reason 4; 1 for Gt / Lt) and minValues (1) still go to the general engine, and
+                                    * so does every topology batch over such a NodePool: the spread engine declines as before;
+                                    * 16 = "cursor-operators": as 12 with the same acceptance (KSOLVE_ERR_UNSUPPORTED with "cursor
+                                    * engine declined the problem (reason N)" instead of the fallback). 0-14 still decline with 3 / 1.
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -9,8 +9,9 @@ enum Decline : int {
   DECLINE_KERNEL_CAPACITY = -1,        // inside a kernel only: more claims than Workspace::max_claims — the kernel ends with status 1, not 3, and the host reports DECLINE_CAPACITY
   DECLINE_NONE = 0,                    // the fast engine solved the problem
   // FastCold::setup(), for both engines
-  DECLINE_NOT_PLAIN = 1,               // outside the view's plain / plain_topo / plain_nodes, relaxation rows, more than 4 resources, 32 templates or kMaxItWords words of types
-  DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, DoesNotExist, Gt, Lt)
+  DECLINE_NOT_PLAIN = 1,               // outside the view's plain / plain_topo / plain_nodes (/ plain_ops under engines 15 / 16), relaxation rows, more than 4 resources, 32 templates or kMaxItWords
+                                       // words of types; the host raises it for a batch that Gt / Lt NodePools alone keep from the cursor engine (ksolve_impl.h, plain_ops)
+  DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, Exists, DoesNotExist; Gt, Lt on the spread engine) — not the cursor engine under engines 15 / 16
   DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply)
   DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
   DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits

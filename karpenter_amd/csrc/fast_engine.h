@@ -30,7 +30,8 @@
 //
 // Everything this engine does not handle (an unschedulable pod, NodePool limits that actually exclude a type — unless the handle
 // asked for limit stages, FastLimits below —, more claims
-// than the LDS plan holds, non-positive operators, ...) makes it stop with status 3 before it has written a result;
+// than the LDS plan holds, non-positive operators — on pods; on NodePools unless the handle asked for complement templates, setup()
+// below —, ...) makes it stop with status 3 before it has written a result;
 // the host then runs the general engine (engine.h) on the same problem. There is no CPU path.
 #pragma once
 #include <type_traits>
@@ -139,6 +140,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   FastLimits* lim;        // [1] engines 11-14: the engine goes on when a NodePool limit binds (Workspace::t_its has 32 rows then); null otherwise
   FastPlan plan;
   int enabled;
+  int ops;                // engines 15 / 16: setup() accepts NodePool requirements that are not In sets (NotIn, Exists, DoesNotExist, Gt, Lt) — "Complement templates" below
 };
 
 // whole-record moves between LDS and registers (a struct behind an address-space-3 pointer has no implicit copy)
@@ -546,9 +548,10 @@ struct FastCold {
       for (int j = 0; j < nvv; ++j) {
         const int k = Mm.vkey[j];
         if (!((Pv.it_keys >> k) & 1u)) continue;
-        if ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1) continue;   // guard bit set: the requirement set does not define the key
+        if ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1) continue;   // guard bit set: the requirement set does not define the key, or holds the template's own complement set — in t_its already
         uint64_t field = (vm >> Mm.voff[j]) & (Mm.fmask[j] >> Mm.voff[j]);
         uint64_t r = Pv.key_undef[(size_t)k * iw + w];
+        if (!field) r |= Pv.key_neg[(size_t)k * iw + w];   // an empty set is the template's DoesNotExist (a pod's In never leaves one): the escape of requirements.go:260-265
         const size_t base = (size_t)Mm.vword[j] * 64;
         while (field) { const int b = ctz64(field); field &= field - 1; r |= Pv.kv_has[(base + b) * iw + w]; }
         acc &= r;
@@ -558,10 +561,10 @@ struct FastCold {
     // a compatible available offering (nodeclaim.go:624-638, types.go:553-570)
     uint32_t zones = (1u << P.n_zones) - 1, cts = (1u << P.n_cts) - 1;
     {
-      const uint64_t* tm = P.tmpl_reqs.mask + (size_t)tr * d.req_words;
+      const ReqRef tq = P.tmpl_reqs.at(d, tr);   // (the values the template's requirement Has(): a NotIn zone is not a zone set)
       const uint32_t tdef = Mp->tdef[t];
-      if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)tm[d.key_word_off[d.key_zone]];
-      if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)tm[d.key_word_off[d.key_ct]];
+      if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)req_values_word(d, tq, d.key_zone, d.key_word_off[d.key_zone]);
+      if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)req_values_word(d, tq, d.key_ct, d.key_word_off[d.key_ct]);
       for (int j = 0; j < nv; ++j) {
         const uint32_t field = (uint32_t)((vm >> Mp->voff[j]) & (Mp->fmask[j] >> Mp->voff[j]));
         if (Mp->vkey[j] == d.key_zone) zones &= field;
@@ -652,11 +655,18 @@ struct FastCold {
       if (W::leader()) { lim->n_ids = (uint32_t)T; lim->first_claim = 0xFFFFFFFFu; }
       W::sync();
     }
-    if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
-    // (instance types may use any operator: with positive sets on the claim side the NotIn / DoesNotExist escape of
-    // requirements.go:260-265 never applies, so compatible() stays monotone)
-    // templates: only In sets
-    if (W::reduce_or(T, [&](int t) { return (uint64_t)(Pv.tmpl_reqs.complement[t] | (Pv.tmpl_reqs.has_gte ? Pv.tmpl_reqs.has_gte[t] : 0) | (Pv.tmpl_reqs.has_lte ? Pv.tmpl_reqs.has_lte[t] : 0)); })) return DECLINE_TEMPLATE_NOT_POSITIVE;
+    const bool ops = F.ops && !topo;   // engines 15 / 16, the cursor engine only: complement templates (below)
+    if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes) || (ops && P.plain_ops))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
+    // Instance types may use any operator. Pods are positive, so a claim's set on a key is either concrete — against it the NotIn /
+    // DoesNotExist escape of requirements.go:260-265 never applies — or still the template's own requirement, and that one meets the
+    // instance types once, below, where the escape does apply (a DoesNotExist type passes a NotIn pool and fails an Exists or Gt
+    // pool). Either way a claim's types only shrink: compatible() stays monotone.
+    // templates: only In sets, but for engines 15 / 16
+    if (!ops && W::reduce_or(T, [&](int t) {
+      const ReqRef tr = Pv.tmpl_reqs.at(d, t);
+      uint64_t neg = (uint64_t)(tr.complement | tr.has_gte | tr.has_lte);
+      for (uint32_t ks_ = tr.defined & ~tr.complement; ks_; ks_ &= ks_ - 1) if (!key_nonempty(d, tr.mask, __builtin_ctz(ks_))) neg |= 1;   // In [] == DoesNotExist
+      return neg; })) return DECLINE_TEMPLATE_NOT_POSITIVE;
     // classes: only In sets; the keys they define are the variable keys
     if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return DECLINE_CLASS_NOT_POSITIVE;
     uint32_t vk = (uint32_t)W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.defined[c]; });
@@ -697,38 +707,59 @@ struct FastCold {
     // templates: packed form, and NewScheduler's prefilter (scheduler.go:156-171) with positive sets
     KS_LDS FastMisc& Mm = *Mp;
     const int nvv = nv;
+    // Complement templates (engines 15 / 16). The intersection of a pod's In Q with a template's NotIn S, Exists, Gt or Lt is the
+    // concrete set Q ∩ E, E = the dictionary values of the key outside S and inside the bounds (requirement.go:181-214), so the
+    // template's field holds E and the loop's AND and fast_fields_ok stay what they are. The guard bit above the field — "the set does
+    // not define the key", which a template that defines the key never uses — is set for such a template and then means "the claim
+    // still holds the template's own requirement, not a concrete set": a class that selects on the key has the bit clear and clears
+    // it by the same AND. The two states print differently (NotIn [a] against In [b, c]: ksolve_fast_records) and meet the instance
+    // types differently (t_its below against create_entry's fields). In and DoesNotExist (field 0: every selecting pod fails
+    // fast_fields_ok, requirements.go:254-274) keep the bit clear.
     W::for_n(T, [&](int t) {
-      const uint64_t* tm = Pv.tmpl_reqs.mask + (size_t)t * d.req_words;
-      const uint32_t tdef = Pv.tmpl_reqs.defined[t];
+      const ReqRef tr = Pv.tmpl_reqs.at(d, t);
+      const uint32_t tdef = tr.defined;
       uint64_t vm = (uint64_t)t << 56;
       for (int j = 0; j < nvv; ++j) {
-        if ((tdef >> Mm.vkey[j]) & 1u) vm |= (tm[Mm.vword[j]] << Mm.voff[j]) & Mm.fmask[j];
-        else vm |= Mm.fmask[j] | (1ull << (Mm.voff[j] + Mm.vwidth[j]));   // undefined: every value, and the guard bit says so
+        const int k = Mm.vkey[j];
+        const uint64_t guard = 1ull << (Mm.voff[j] + Mm.vwidth[j]);
+        if ((tdef >> k) & 1u) vm |= ((req_values_word(d, tr, k, Mm.vword[j]) << Mm.voff[j]) & Mm.fmask[j]) | (bit(tr.complement, k) ? guard : 0ull);
+        else vm |= Mm.fmask[j] | guard;   // undefined: every value, and the guard bit says so
       }
       Mm.tvmask[t] = vm; Mm.tdef[t] = tdef;
     });
     active_templates = 0;
     for (int t = 0; t < T; ++t) {
-      const uint64_t* tm = P.tmpl_reqs.mask + (size_t)t * d.req_words;
+      const ReqRef tr = Pv.tmpl_reqs.at(d, t);
+      const uint64_t* tm = tr.mask;
       const uint32_t tdef = Mp->tdef[t];
       uint64_t* tits = S.t_its + (size_t)t * iw;
       const uint64_t* tin = P.tmpl_its + (size_t)t * iw;
+      // InstanceType.Requirements.Intersects(template) (requirements.go:254-274, requirement.go:220-254) for every type at once, whichever
+      // operator the template's key has (only In below engines 15 / 16; engine.h compat_mask is the general engine's form of this)
       W::for_n(iw, [&](int w) {
         uint64_t acc = tin[w] & Pv.it_alloc_ok[w];
         for (int k = 0; k < nk; ++k) {
           if (!((tdef >> k) & 1u)) continue;
           const uint32_t w0 = d.key_word_off[k], w1 = d.key_word_off[k + 1];
-          if (k == d.key_it) { acc &= tm[w0 + w]; continue; }
+          const bool comp = bit(tr.complement, k);
+          if (k == d.key_it) {   // the key's dictionary is the type list and every type requires In [own name]
+            acc &= comp ? inbounds_word(d, w0 + w, ~tm[w0 + w], bit(tr.has_gte, k), bit(tr.has_gte, k) ? tr.gte[k] : 0, bit(tr.has_lte, k), bit(tr.has_lte, k) ? tr.lte[k] : 0) : tm[w0 + w];
+            continue;
+          }
           if (!((Pv.it_keys >> k) & 1u)) continue;
           uint64_t r = Pv.key_undef[(size_t)k * iw + w];
-          for (uint32_t x = w0; x < w1; ++x) for (uint64_t b = tm[x]; b; b &= b - 1) r |= Pv.kv_has[((size_t)x * 64 + ctz64(b)) * iw + w];
+          // concrete types: some value of theirs that the template Has(); complement types by kv_has too (In), or always (two complements
+          // intersect, requirement.go:226-228: instance types carry no bounds)
+          for (uint32_t x = w0; x < w1; ++x) for (uint64_t b = req_values_word(d, tr, k, x); b; b &= b - 1) r |= Pv.kv_has[((size_t)x * 64 + ctz64(b)) * iw + w];
+          if (comp) r |= Pv.key_compl[(size_t)k * iw + w];
+          if (op_negative(req_op(d, tr, k))) r |= Pv.key_neg[(size_t)k * iw + w];   // NotIn / DoesNotExist on both sides: the escape of requirements.go:260-265
           acc &= r;
         }
         tits[w] = acc;
       });
       uint32_t zones = (1u << P.n_zones) - 1, cts = (1u << P.n_cts) - 1;
-      if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)tm[d.key_word_off[d.key_zone]];
-      if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)tm[d.key_word_off[d.key_ct]];
+      if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)req_values_word(d, tr, d.key_zone, d.key_word_off[d.key_zone]);
+      if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)req_values_word(d, tr, d.key_ct, d.key_word_off[d.key_ct]);
       uint64_t cells = 0;
       for (uint32_t z = zones; z; z &= z - 1) cells |= (uint64_t)cts << (__builtin_ctz(z) * 4);
       uint64_t any = 0;
@@ -2256,19 +2287,29 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   const int ts = (int)(st.vmask >> 56);
   const int t = a.fw.lim ? (int)a.fw.lim->real[ts] : ts;   // the claim's template (its requirement set may carry a limit stage, FastLimits; the cache entry below is the stage's)
   const FastVar fv = *a.fw.var;
-  // keys the requirement set defines: the template's, and of the keys pods select on those whose guard bit is clear
-  uint32_t vdef = P.tmpl_reqs.defined[t];
+  // Keys the requirement set defines: the template's, and of the keys pods select on those whose guard bit is clear — a concrete
+  // set: the field, complement off, bounds dropped (requirement.go:209-212). A set guard bit on a key the template defines (a
+  // complement template, engines 15 / 16) says the claim still holds the template's own requirement: its raw mask words, its
+  // complement flag and its bounds, as the general engine's claims carry them (engine.h, the template records).
+  const ReqRef tr = P.tmpl_reqs.at(d, t);
+  uint32_t vdef = tr.defined, vcompl = tr.complement, vhg = tr.has_gte, vhl = tr.has_lte, concrete = 0;
   for (int j = 0; j < fv.nv; ++j) {
     const uint32_t kb = 1u << fv.vkey[j];
-    vdef = ((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) ? (vdef & ~kb) : (vdef | kb);
+    if ((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) { if (!(tr.defined & kb)) vdef &= ~kb; }
+    else { vdef |= kb; concrete |= kb; vcompl &= ~kb; vhg &= ~kb; vhl &= ~kb; }
   }
   uint64_t* rec = a.ws.c_hot + (size_t)c * ly.c_hot_words();
-  const uint64_t* tm = P.tmpl_reqs.mask + (size_t)t * d.req_words;
+  const uint64_t* tm = tr.mask;
   W::for_n(ly.rw, [&](int w) {
     uint64_t v = tm[w];
-    for (int j = 0; j < fv.nv; ++j) if (fv.vword[j] == w && ((vdef >> fv.vkey[j]) & 1u)) v = (st.vmask >> fv.voff[j]) & ((1ull << fv.vwidth[j]) - 1);
+    for (int j = 0; j < fv.nv; ++j) if (fv.vword[j] == w && ((concrete >> fv.vkey[j]) & 1u)) v = (st.vmask >> fv.voff[j]) & ((1ull << fv.vwidth[j]) - 1);
     rec[ly.c_mask() + w] = v;
   });
+  if (vhg | vhl) {   // the cold record is read only then (decode_claim, finalize_body)
+    uint64_t* cold = a.ws.c_cold + (size_t)c * ly.cold_words();
+    int64_t* cg = (int64_t*)cold; int64_t* cl = cg + ly.nk; int32_t* cv = (int32_t*)(cold + 2 * ly.nk);
+    W::for_n(ly.nk, [&](int k) { cg[k] = bit(vhg, k) ? tr.gte[k] : 0; cl[k] = bit(vhl, k) ? tr.lte[k] : 0; cv[k] = -1; });
+  }
   const int iw = ly.iw, nr = ly.nr, n_its = P.n_its;
   const uint64_t* eits = a.fw.ent_its + (size_t)a.fw.c_ent[c] * iw;
   const int64_t* eff = eff_alloc(P, t);
@@ -2285,8 +2326,8 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   }
   W::for_n(nr, [&](int r) { rec[ly.c_total() + r] = (uint64_t)(int64_t)st.req[r]; rec[ly.c_head() + r] = 0; });
   if (W::leader()) {
-    rec[ly.c_f0()] = (uint64_t)vdef;
-    rec[ly.c_f1()] = 0;
+    rec[ly.c_f0()] = (uint64_t)vdef | ((uint64_t)vcompl << 32);
+    rec[ly.c_f1()] = (uint64_t)vhg | ((uint64_t)vhl << 32);
     rec[ly.c_meta()] = (uint64_t)(uint32_t)t | ((uint64_t)a.fw.c_npods[c] << 32);
     rec[ly.c_meta2()] = (uint64_t)a.fw.c_hostseq[c];
   }

@@ -82,6 +82,7 @@ struct ksolve_handle {
   bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
   bool opt_limits = false;      // engine = auto-limits / cursor-limits (11 / 12: as 7 / 8, opt_nodes included): the cursor engine goes on when a NodePool limit binds (fast_engine.h FastLimits)
   bool opt_spread_limits = false;  // engine = auto-limits-spread / spread-limits (13 / 14: as 9 + 11 / as 10): the spread engine goes on when a NodePool limit binds (topo_engine.h limit_stage)
+  bool opt_ops = false;         // engine = auto-operators / cursor-operators (15 / 16: as 13 / 12): the cursor engine takes NodePools whose requirements are not In sets (fast_engine.h, "Complement templates")
   bool opt_spread_nodes = false;   // engine = auto-nodes-spread / spread-nodes (9 / 10; opts.engine holds 0 / 6 from then on): the spread engine may take a problem with existing nodes (topo_nodes.h)
   uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
@@ -315,6 +316,8 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   else if (h->opts.engine == 11 || h->opts.engine == 12) { h->opt_nodes = true; h->opt_limits = true; h->opts.engine = h->opts.engine == 11 ? 0u : 2u; }   // as 7 / 8, and binding NodePool limits do not stop the cursor engine
   else if (h->opts.engine == 13) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opt_limits = true; h->opt_spread_limits = true; h->opts.engine = 0u; }   // 9 and 11 together, and binding limits do not stop the spread engine either
   else if (h->opts.engine == 14) { h->opt_spread_nodes = true; h->opt_spread_limits = true; h->opts.engine = 6u; }   // as 10, with limit stages
+  else if (h->opts.engine == 15) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opt_limits = true; h->opt_spread_limits = true; h->opt_ops = true; h->opts.engine = 0u; }   // as 13, and the cursor engine takes NotIn / Exists / DoesNotExist / Gt / Lt NodePools
+  else if (h->opts.engine == 16) { h->opt_nodes = true; h->opt_limits = true; h->opt_ops = true; h->opts.engine = 2u; }   // as 12, with the same acceptance
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -779,8 +782,9 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   {
     bool any_minv = false;
     if (d->tmpl_reqs.min_values) for (size_t i = 0; i < (size_t)d->n_templates * d->n_keys; ++i) if (d->tmpl_reqs.min_values[i] >= 0) any_minv = true;
-    const bool bounds = any_nonzero(d->pod_reqs.has_gte, d->n_pod_rows) || any_nonzero(d->pod_reqs.has_lte, d->n_pod_rows) ||
-                        any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
+    const bool pod_bounds = any_nonzero(d->pod_reqs.has_gte, d->n_pod_rows) || any_nonzero(d->pod_reqs.has_lte, d->n_pod_rows);
+    const bool tmpl_bounds = any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
+    const bool bounds = pod_bounds || tmpl_bounds;
     P.plain = (d->topo.n == 0 && d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
     P.plain_topo = (d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
     P.lite = (P.plain && !d->tmpl_daemon_first && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
@@ -792,6 +796,20 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       if (!why) why = node_stage_declines(d, P.dict, req_words);
       P.plain_nodes = why ? 0 : 1;
       h->fast_reason = why;
+    }
+    // plain_ops: plain / plain_nodes without the templates' share of `bounds` — what alone keeps a batch with a Gt / Lt NodePool from
+    // the cursor engine, which takes it under engines 15 / 16 only. Whatever else is outside the shape (pod-side bounds, minValues,
+    // ...) stays outside, and those two settings name it as FastCold::setup() would: DECLINE_NOT_PLAIN. So does every other setting
+    // for the batch that only the templates' bounds keep out (without existing nodes: they have reasons of their own, above).
+    P.plain_ops = 0;
+    if (h->opts.engine != 1 && d->topo.n == 0 && !P.plain && !P.plain_nodes) {
+      const bool rest = !any_minv && !P.reserved_on && !pod_bounds && !d->n_override_groups && !P.hp_on && !P.vol_on;
+      if (h->opt_ops) {
+        uint32_t why = rest ? 0u : (uint32_t)(d->n_nodes > 0 ? ks::DECLINE_NODES_NOT_PLAIN : ks::DECLINE_NOT_PLAIN);
+        if (!why && d->n_nodes > 0) why = (P.pv_on || d->pod_node) ? (uint32_t)ks::DECLINE_NODES_NOT_PLAIN : node_stage_declines(d, P.dict, req_words);
+        P.plain_ops = why ? 0 : 1;
+        h->fast_reason = why;
+      } else if (rest && tmpl_bounds && d->n_nodes == 0) h->fast_reason = ks::DECLINE_NOT_PLAIN;
     }
     // plain_topo_nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
     // engine's node path rests on (topo_nodes.h): every node carries ONE value of every dictionary key a group uses (35), among the
@@ -829,7 +847,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     // cursor engine (fast_engine.h): candidate when the problem is lite and has no relaxation rows; the kernel itself checks the
     // rest (positive operators only, packed variable keys, 31-bit quantities) and hands the problem back otherwise
     ks::FastWork& fw = h->fw;
-    fw.enabled = ((P.plain || P.plain_nodes) && d->n_res <= 4 && h->opts.engine != 1 && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
+    fw.enabled = ((P.plain || P.plain_nodes || P.plain_ops) && d->n_res <= 4 && h->opts.engine != 1 && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
     if (fw.enabled) {
       h->fast_mc = mc;
       fast_plan_set(h, h->opts.engine == 4 ? 2 : h->opts.engine == 3 ? 1 : 0, 1);
@@ -861,8 +879,9 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       fw.q_class = dz<uint32_t>(h, d->n_pods); fw.q_claim = dz<uint32_t>(h, d->n_pods); fw.q_cnt = dz<uint32_t>(h, d->n_pods);
       { const size_t oc = std::min<size_t>(65472, ((size_t)mc + 63) & ~(size_t)63) + 64; fw.o_key = dz<uint16_t>(h, oc); fw.o_ord = dz<uint16_t>(h, oc); fw.o_snap = dz<uint16_t>(h, oc); }
       h->d_fast_args = dz<ks::FastArgs>(h, 1);
-      if (P.plain_nodes) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
+      if (P.plain_nodes || (P.plain_ops && d->n_nodes > 0)) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
       if (h->opt_limits) fw.lim = dz<ks::FastLimits>(h, 1);
+      fw.ops = h->opt_ops ? 1 : 0;
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the
@@ -2250,8 +2269,9 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
     return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)" +
                 (h->opt_spread_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
   if (h->opts.engine >= 2 && h->opts.engine != 6 && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
-    return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
-                (h->opt_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
+    return fail(h, KSOLVE_ERR_UNSUPPORTED, h->opt_ops && h->fast_reason ? "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")" :
+                "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
+                (h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
   if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
     // more pod classes than the node stage keeps cursors for: the general engine (nothing has run yet)
     h->fast_reason = ks::DECLINE_NODE_CLASSES;

@@ -236,6 +236,8 @@ struct ProblemView {
   const int64_t* it_eff;         // [n_templates][n_res][n_its]; only the rows of the templates in tmpl_ov are written. null: no overhead
   uint32_t tmpl_ov;              // templates with a group of non-zero overhead; the others read it_alloc itself. Bit t = template t: set by create() only for
                                  // problems of at most 32 templates that a fast engine may run (both decline more, FastCold::setup); 0 otherwise
+  int plain_ops;                 // engines 15 / 16 only: `plain` (no existing nodes) or `plain_nodes` (with them) but for Gt / Lt bounds on NodePool requirements, which
+                                 // the cursor engine then solves itself (fast_engine.h, "complement templates"); pod-side bounds and minValues still clear it
 };
 
 // allocatable of every instance type as a claim of template t sees it: [n_res][n_its]

@@ -121,6 +121,16 @@ KS_FN bool req_has(const Dict& d, const ReqRef& r, int k, uint32_t w, int b) {
   return bit(r.complement, k) ? !in : in;
 }
 
+// The dictionary values of word w of key k that r's requirement on k Has() (requirement.go:275-280), as a mask: the set itself
+// for In, for a complement set (NotIn, Exists, Gt, Lt) the dictionary's values outside it and inside the bounds.
+KS_FN uint64_t req_values_word(const Dict& d, const ReqRef& r, int k, uint32_t w) {
+  const bool hg = bit(r.has_gte, k) && r.gte, hl = bit(r.has_lte, k) && r.lte;
+  const int64_t g = hg ? r.gte[k] : 0, l = hl ? r.lte[k] : 0;
+  if (hg && hl && g > l) return 0;
+  const uint64_t base = bit(r.complement, k) ? (~r.mask[w] & d.value_valid[w]) : r.mask[w];
+  return inbounds_word(d, w, base, hg, g, hl, l);
+}
+
 enum { COMPAT_OK = 0, COMPAT_UNDEFINED_KEY = 1, COMPAT_NO_INTERSECTION = 2 };
 
 // Intersects — requirements.go:254-274 (existing = r, incoming = q)

@@ -2155,7 +2155,7 @@ struct ProblemBuilder {
     ko.truncate_instance_types = (uint32_t)opts.at("truncateInstanceTypes").i(0);
     ko.reserved_capacity = opts.at("reservedCapacity").boolean_or(false) ? 1 : 0;
     ko.reserved_offering_strict = opts.at("reservedOfferingMode").s("Fallback") == "Strict" ? 1 : 0;
-    { const std::string eng = opts.at("engine").s("auto"); ko.engine = eng == "general" ? 1u : eng == "cursor" ? 2u : eng == "cursor-wide" ? 3u : eng == "cursor-hbm" ? 4u : eng == "cursor-pair" ? 5u : eng == "spread" ? 6u : eng == "auto-nodes" ? 7u : eng == "cursor-nodes" ? 8u : eng == "auto-nodes-spread" ? 9u : eng == "spread-nodes" ? 10u : eng == "auto-limits" ? 11u : eng == "cursor-limits" ? 12u : eng == "auto-limits-spread" ? 13u : eng == "spread-limits" ? 14u : 0u; }
+    { const std::string eng = opts.at("engine").s("auto"); ko.engine = eng == "general" ? 1u : eng == "cursor" ? 2u : eng == "cursor-wide" ? 3u : eng == "cursor-hbm" ? 4u : eng == "cursor-pair" ? 5u : eng == "spread" ? 6u : eng == "auto-nodes" ? 7u : eng == "cursor-nodes" ? 8u : eng == "auto-nodes-spread" ? 9u : eng == "spread-nodes" ? 10u : eng == "auto-limits" ? 11u : eng == "cursor-limits" ? 12u : eng == "auto-limits-spread" ? 13u : eng == "spread-limits" ? 14u : eng == "auto-operators" ? 15u : eng == "cursor-operators" ? 16u : 0u; }
     return ko;
   }
 
