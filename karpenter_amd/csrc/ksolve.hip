@@ -181,6 +181,13 @@ __global__ void ksolve_it_index(int n, ks::ItIndexArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ks::it_index_body(i, a);
 }
+#ifdef KSOLVE_TEST_HOOKS
+// the requirement algebra on pairs of rows (ksolve_impl.h reqalg_test_body; test builds only): one thread per pair
+__global__ void ksolve_reqalg_test(int n, ks::ReqalgTestArgs a) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ks::reqalg_test_body(i, a);
+}
+#endif
 __global__ void ksolve_row_hash(int n, ks::RowArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ks::row_hash_body(i, a);
@@ -566,6 +573,9 @@ static void be_launch_eff_alloc(ksolve_handle* h, const ks::EffAllocArgs& a) {
   hip_check(h, hipGetLastError(), "ksolve_fast_eff_alloc launch");
 }
 static void be_launch_it_index(ksolve_handle* h, int n, const ks::ItIndexArgs& a) { hipLaunchKernelGGL(ksolve_it_index, grid_for(n), dim3(256), 0, HB(h)->stream, n, a); }
+#ifdef KSOLVE_TEST_HOOKS
+static void be_launch_reqalg_test(ksolve_handle* h, int n, const ks::ReqalgTestArgs& a) { hipLaunchKernelGGL(ksolve_reqalg_test, grid_for(n), dim3(256), 0, HB(h)->stream, n, a); }
+#endif
 static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a) {
   const int rw = a.dict.req_words;
   const int nk = a.dict.n_keys;
@@ -863,6 +873,24 @@ static int be_device_available() {
   return std::string(p.gcnArchName).rfind("gfx950", 0) == 0 ? 1 : 0;
 }
 
+#ifdef KSOLVE_TEST_HOOKS
+// a test-only entry point's run on a bare handle made the way ksolve_create makes one (ksolve_test_reqalg, ksolve_test_it_index)
+template <class F>
+static ksolve_status test_on_bare_handle(const char* who, F run) {
+  ksolve_handle* h = new ksolve_handle();
+  HipBackend* b = new HipBackend();
+  h->backend = b;
+  ksolve_status st = KSOLVE_ERR_DEVICE;
+  if (!be_device_available()) st = KSOLVE_ERR_NO_DEVICE;
+  else if (hip_check(h, hipSetDevice(b->device), "hipSetDevice") && hip_check(h, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking), "hipStreamCreate")) {
+    for (int i = 0; i < 8; ++i) { hip_check(h, hipEventCreate(&b->ev0[i]), "hipEventCreate"); hip_check(h, hipEventCreate(&b->ev1[i]), "hipEventCreate"); }
+    st = run(h);
+  }
+  if (st != KSOLVE_OK) fprintf(stderr, "%s: %s\n", who, h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
+#endif
 extern "C" {
 
 ksolve_status ksolve_create(const ksolve_problem_desc* desc, const ksolve_options* opts, ksolve_handle** out) {
@@ -893,6 +921,13 @@ ksolve_status ksolve_test_classify(const ksolve_test_classify_in* in, ksolve_tes
   if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_classify: %s\n", h->error.c_str());
   ksolve_destroy(h);
   return st;
+}
+// the requirement algebra on pairs of rows, and the instance-type index alone (ksolve_impl.h test_reqalg, test_it_index; test builds only)
+ksolve_status ksolve_test_reqalg(const ksolve_test_reqalg_in* in, ksolve_test_reqalg_out* out) {
+  return test_on_bare_handle("ksolve_test_reqalg", [&](ksolve_handle* h) { return ksi::test_reqalg(h, in, out); });
+}
+ksolve_status ksolve_test_it_index(const ksolve_test_it_index_in* in, ksolve_test_it_index_out* out) {
+  return test_on_bare_handle("ksolve_test_it_index", [&](ksolve_handle* h) { return ksi::test_it_index(h, in, out); });
 }
 #endif
 ksolve_status ksolve_probe_create(ksolve_handle* base, const ksolve_probe* probe, ksolve_handle** out) {

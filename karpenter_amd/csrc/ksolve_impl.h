@@ -160,6 +160,97 @@ typedef struct {
   uint64_t *cls_hot, *cls_cold;                    // [n_classes][k_hot_words], [n_classes][cold_words]
   int32_t lay[8];                                  // RecLayout: k_mask, k_req, k_f0, k_f1, k_tol, k_meta, k_hot_words, cold_words
 } ksolve_test_classify_out;
+
+// ksolve_test_reqalg — TEST BUILDS ONLY, like ksolve_test_classify: the requirement algebra of reqalg.h on n pairs of requirement
+// sets (row i of `a` with row i of `b`), one device thread per pair, every function's answer downloaded. The tables go to the device
+// as they come: a NULL has_gte / has_lte / gte / lte / min_values column stays NULL in the ReqRef the functions see.
+// tests/reqalg_cases.py holds the definition the answers are compared with.
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;   // [n_keys + 1]; req_words = key_word_off[n_keys]
+  uint32_t well_known_mask;
+  const int64_t* value_int;                        // [req_words * 64]
+  const uint64_t *value_is_int, *value_valid;      // [req_words]
+  uint32_t n;                                      // pairs
+  const ksolve_reqsets *a, *b;                     // n rows each
+} ksolve_test_reqalg_in;
+// every table is the caller's
+typedef struct {
+  uint32_t* has_intersection;        // [n] key bits: has_intersection(A, B, k) over the keys both sets define
+  uint8_t* intersects;               // [n] reqs_intersect(A, B)
+  uint8_t* compatible;               // [2][n] reqs_compatible(A, B, allow_undefined = false | true)
+  uint8_t* op;                       // [n][n_keys] req_op(A, k); 0xFF where A does not define k
+  uint64_t *values_word, *has_word;  // [n][req_words] req_values_word(A, k, w) | req_has(A, k, w, b) over the value_valid bits; zero on keys A does not define
+  uint64_t* buf_mask;                // [n][req_words]  the ReqBuf after reqbuf_load(A), reqbuf_add(B), field by field
+  uint32_t* buf_flags;               // [6][n]: defined | complement | has_gte | has_lte | has_minv | the `changed` reqbuf_add returned
+  int64_t *buf_gte, *buf_lte;        // [n][n_keys]
+  int32_t* buf_minv;                 // [n][n_keys]
+} ksolve_test_reqalg_out;
+
+// ksolve_test_it_index — TEST BUILDS ONLY: the instance-type index (kernels.h it_index_body) alone on raw host tables: uploaded and
+// cleared as create() and solve_prepare() do, one be_launch_it_index, everything it wrote downloaded. it_words = ceil(n_its / 64).
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;
+  int32_t key_it;                                  // the instance-type key: its dictionary is the type list
+  const int64_t* value_int;
+  const uint64_t *value_is_int, *value_valid;
+  uint32_t n_its, n_res;
+  const ksolve_reqsets* it_reqs;                   // n_its rows
+  const int64_t* it_allocatable;                   // [n_res][n_its]
+} ksolve_test_it_index_in;
+typedef struct {
+  uint64_t* kv_has;                                // [req_words * 64][it_words]
+  uint64_t *key_undef, *key_compl, *key_neg;       // [n_keys][it_words]
+  uint64_t* it_alloc_ok;                           // [it_words]
+  uint32_t error, it_words;
+} ksolve_test_it_index_out;
+
+namespace ks {
+struct ReqalgTestArgs {
+  Dict dict;
+  int n;
+  ReqTable a, b;
+  uint32_t* has_intersection; uint8_t* intersects; uint8_t* compatible; uint8_t* op;
+  uint64_t *values_word, *has_word, *buf_mask;
+  uint32_t* buf_flags;
+  int64_t *buf_gte, *buf_lte;
+  int32_t* buf_minv;
+};
+// one thread per pair
+KS_FN void reqalg_test_body(int i, const ReqalgTestArgs& t) {
+  const Dict& d = t.dict;
+  const ReqRef a = t.a.at(d, i), b = t.b.at(d, i);
+  const size_t n = (size_t)t.n, rw = (size_t)d.req_words, nk = (size_t)d.n_keys;
+  uint32_t hi = 0;
+  for (int k = 0; k < d.n_keys; ++k)
+    if (bit(a.defined & b.defined, k) && has_intersection(d, a, b, k)) hi |= 1u << k;
+  t.has_intersection[i] = hi;
+  t.intersects[i] = reqs_intersect(d, a, b) ? 1 : 0;
+  t.compatible[i] = (uint8_t)reqs_compatible(d, a, b, false);
+  t.compatible[n + i] = (uint8_t)reqs_compatible(d, a, b, true);
+  for (int k = 0; k < d.n_keys; ++k) {
+    const bool def = bit(a.defined, k);
+    t.op[(size_t)i * nk + k] = def ? (uint8_t)req_op(d, a, k) : (uint8_t)0xFF;
+    for (uint32_t w = d.key_word_off[k]; w < d.key_word_off[k + 1]; ++w) {
+      uint64_t vw = 0, hw = 0;
+      if (def) {
+        vw = req_values_word(d, a, k, w);
+        for (uint64_t c = d.value_valid[w]; c; c &= c - 1) { const int x = ctz64(c); if (req_has(d, a, k, w, x)) hw |= 1ull << x; }
+      }
+      t.values_word[(size_t)i * rw + w] = vw;
+      t.has_word[(size_t)i * rw + w] = hw;
+    }
+  }
+  ReqBuf buf;
+  reqbuf_load(d, buf, a);
+  const bool changed = reqbuf_add(d, buf, b);
+  for (size_t w = 0; w < rw; ++w) t.buf_mask[(size_t)i * rw + w] = buf.mask[w];
+  t.buf_flags[i] = buf.defined; t.buf_flags[n + i] = buf.complement; t.buf_flags[2 * n + i] = buf.has_gte; t.buf_flags[3 * n + i] = buf.has_lte;
+  t.buf_flags[4 * n + i] = buf.has_minv; t.buf_flags[5 * n + i] = changed ? 1u : 0u;
+  for (size_t k = 0; k < nk; ++k) {
+    t.buf_gte[(size_t)i * nk + k] = buf.gte[k]; t.buf_lte[(size_t)i * nk + k] = buf.lte[k]; t.buf_minv[(size_t)i * nk + k] = buf.minv[k];
+  }
+}
+}  // namespace ks
 #endif
 
 // ---- backend hooks (defined by the including TU before this point is instantiated) ----
@@ -178,6 +269,9 @@ static void be_range_drop(ksolve_handle* h);   // closes the trace range of a be
 // for the rest of the process after a failed sweep)
 struct PhaseRange { ksolve_handle* h; bool open; ~PhaseRange() { if (open) be_range_drop(h); } };
 static void be_launch_it_index(ksolve_handle* h, int n, const ks::ItIndexArgs& a);
+#ifdef KSOLVE_TEST_HOOKS
+static void be_launch_reqalg_test(ksolve_handle* h, int n, const ks::ReqalgTestArgs& a);   // one thread per pair: reqalg_test_body
+#endif
 static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a);
 static void be_launch_row_class(ksolve_handle* h, int n, const ks::RowArgs& a);
 static void be_launch_class_gather(ksolve_handle* h, int n, const ks::RowArgs& a);
@@ -1065,6 +1159,113 @@ static ksolve_status test_classify(ksolve_handle* h, const ksolve_test_classify_
   if (R.cls_topo) be_d2h(h, out->cls_topo, R.cls_topo, nc * 2 * R.topo_words * 8);
   be_d2h(h, out->cls_hot, R.cls_hot, nc * lay.k_hot_words() * 8);
   be_d2h(h, out->cls_cold, R.cls_cold, nc * lay.cold_words() * 8);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+
+// the dictionary of the two hooks below, checked and uploaded as create() uploads it (value_valid is the caller's here)
+static ksolve_status test_dict(ksolve_handle* h, const char* who, uint32_t nk, const uint32_t* key_word_off, const int64_t* value_int, const uint64_t* value_is_int,
+                               const uint64_t* value_valid, ks::Dict& dict) {
+  const std::string w(who);
+  if (!key_word_off || !value_int || !value_is_int || !value_valid) return fail(h, KSOLVE_ERR_INVALID, w + ": missing dictionary table");
+  if (nk < 1 || nk > (uint32_t)kMaxKeys) return fail(h, KSOLVE_ERR_INVALID, w + ": n_keys out of range");
+  const uint32_t rw = key_word_off[nk];
+  if (rw < 1 || rw > (uint32_t)kMaxReqWords || key_word_off[0] != 0) return fail(h, KSOLVE_ERR_INVALID, w + ": req_words out of range");
+  for (uint32_t k = 0; k < nk; ++k) if (key_word_off[k] > key_word_off[k + 1]) return fail(h, KSOLVE_ERR_INVALID, w + ": key_word_off decreases");
+  dict = ks::Dict{};
+  dict.n_keys = (int)nk; dict.req_words = (int)rw;
+  for (uint32_t k = 0; k <= nk; ++k) dict.key_word_off[k] = key_word_off[k];
+  dict.key_it = dict.key_zone = dict.key_ct = dict.key_hostname = -1;
+  dict.value_int = up(h, value_int, (size_t)rw * 64);
+  dict.value_is_int = up(h, value_is_int, rw);
+  dict.value_valid = up(h, value_valid, rw);
+  return KSOLVE_OK;
+}
+// a ksolve_reqsets on the device column by column: what is NULL with the caller is NULL for the algebra (upload_reqs puts zero columns there)
+static ReqTable upload_reqs_as_given(ksolve_handle* h, const ksolve_reqsets& r, uint32_t n, uint32_t req_words, uint32_t n_keys) {
+  ReqTable t{};
+  t.mask = up(h, r.mask, (size_t)n * req_words);
+  t.defined = up(h, r.defined, n);
+  t.complement = up(h, r.complement, n);
+  t.has_gte = r.has_gte ? up(h, r.has_gte, n) : nullptr;
+  t.has_lte = r.has_lte ? up(h, r.has_lte, n) : nullptr;
+  t.gte = r.gte ? up(h, r.gte, (size_t)n * n_keys) : nullptr;
+  t.lte = r.lte ? up(h, r.lte, (size_t)n * n_keys) : nullptr;
+  t.minv = r.min_values ? up(h, r.min_values, (size_t)n * n_keys) : nullptr;
+  return t;
+}
+// The requirement algebra on pairs of rows (see ksolve_test_reqalg_in). The caller owns the (bare) handle and destroys it.
+static ksolve_status test_reqalg(ksolve_handle* h, const ksolve_test_reqalg_in* in, ksolve_test_reqalg_out* out) {
+  if (!in || !out || !in->a || !in->b) return fail(h, KSOLVE_ERR_INVALID, "test_reqalg: missing table");
+  const uint32_t nk = in->n_keys, n = in->n;
+  if (n < 1) return fail(h, KSOLVE_ERR_INVALID, "test_reqalg: no pairs");
+  for (const ksolve_reqsets* r : {in->a, in->b}) {
+    if (!r->mask || !r->defined || !r->complement) return fail(h, KSOLVE_ERR_INVALID, "test_reqalg: missing mask / defined / complement");
+    if ((!r->gte && any_nonzero(r->has_gte, n)) || (!r->lte && any_nonzero(r->has_lte, n))) return fail(h, KSOLVE_ERR_INVALID, "test_reqalg: a has_gte / has_lte bit without the bounds column");
+  }
+  ks::ReqalgTestArgs A{};
+  if (ksolve_status st = test_dict(h, "test_reqalg", nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, A.dict)) return st;
+  A.dict.well_known_mask = in->well_known_mask;
+  const uint32_t rw = (uint32_t)A.dict.req_words;
+  A.n = (int)n;
+  A.a = upload_reqs_as_given(h, *in->a, n, rw, nk);
+  A.b = upload_reqs_as_given(h, *in->b, n, rw, nk);
+  A.has_intersection = dz<uint32_t>(h, n); A.intersects = dz<uint8_t>(h, n); A.compatible = dz<uint8_t>(h, (size_t)2 * n); A.op = dz<uint8_t>(h, (size_t)n * nk);
+  A.values_word = dz<uint64_t>(h, (size_t)n * rw); A.has_word = dz<uint64_t>(h, (size_t)n * rw); A.buf_mask = dz<uint64_t>(h, (size_t)n * rw);
+  A.buf_flags = dz<uint32_t>(h, (size_t)6 * n);
+  A.buf_gte = dz<int64_t>(h, (size_t)n * nk); A.buf_lte = dz<int64_t>(h, (size_t)n * nk); A.buf_minv = dz<int32_t>(h, (size_t)n * nk);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_launch_reqalg_test(h, (int)n, A);
+  be_d2h(h, out->has_intersection, A.has_intersection, (size_t)n * 4);
+  be_d2h(h, out->intersects, A.intersects, n);
+  be_d2h(h, out->compatible, A.compatible, (size_t)2 * n);
+  be_d2h(h, out->op, A.op, (size_t)n * nk);
+  be_d2h(h, out->values_word, A.values_word, (size_t)n * rw * 8);
+  be_d2h(h, out->has_word, A.has_word, (size_t)n * rw * 8);
+  be_d2h(h, out->buf_mask, A.buf_mask, (size_t)n * rw * 8);
+  be_d2h(h, out->buf_flags, A.buf_flags, (size_t)6 * n * 4);
+  be_d2h(h, out->buf_gte, A.buf_gte, (size_t)n * nk * 8);
+  be_d2h(h, out->buf_lte, A.buf_lte, (size_t)n * nk * 8);
+  be_d2h(h, out->buf_minv, A.buf_minv, (size_t)n * nk * 4);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The instance-type index alone (see ksolve_test_it_index_in): create()'s uploads and sizes, solve_prepare()'s phase 1.
+static ksolve_status test_it_index(ksolve_handle* h, const ksolve_test_it_index_in* in, ksolve_test_it_index_out* out) {
+  if (!in || !out || !in->it_reqs || !in->it_reqs->mask || !in->it_reqs->defined || !in->it_reqs->complement || !in->it_allocatable) return fail(h, KSOLVE_ERR_INVALID, "test_it_index: missing table");
+  const uint32_t nk = in->n_keys, n_its = in->n_its, nr = in->n_res;
+  if (n_its < 1 || nr < 1 || nr > (uint32_t)kMaxRes) return fail(h, KSOLVE_ERR_INVALID, "test_it_index: sizes out of range");
+  const uint32_t it_words = (n_its + 63) / 64;
+  if (it_words > (uint32_t)kMaxItWords) return fail(h, KSOLVE_ERR_UNSUPPORTED, "test_it_index: more than 2048 instance types");
+  ks::Dict dict{};
+  if (ksolve_status st = test_dict(h, "test_it_index", nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, dict)) return st;
+  if (in->key_it < 0 || in->key_it >= (int32_t)nk || dict.key_word_off[in->key_it + 1] - dict.key_word_off[in->key_it] != it_words)
+    return fail(h, KSOLVE_ERR_INVALID, "test_it_index: instance-type key dictionary must be the instance type list");
+  dict.key_it = in->key_it;
+  const uint32_t rw = (uint32_t)dict.req_words;
+  const ReqTable it_reqs = upload_reqs(h, *in->it_reqs, n_its, rw, nk);
+  const int64_t* it_alloc = up(h, in->it_allocatable, (size_t)nr * n_its);
+  uint64_t* kv_has = dz<uint64_t>(h, (size_t)rw * 64 * it_words);
+  uint64_t* key_undef = dz<uint64_t>(h, (size_t)nk * it_words);
+  uint64_t* key_compl = dz<uint64_t>(h, (size_t)nk * it_words);
+  uint64_t* key_neg = dz<uint64_t>(h, (size_t)nk * it_words);
+  uint64_t* alloc_ok = dz<uint64_t>(h, it_words);
+  const ks::ItIndexArgs A{dict, (int)n_its, (int)it_words, (int)nr, it_reqs, it_alloc, kv_has, key_undef, key_compl, key_neg, alloc_ok, dz<uint32_t>(h, 1)};
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_fill(h, kv_has, 0, (size_t)rw * 64 * it_words * 8);
+  be_fill(h, key_undef, 0, (size_t)nk * it_words * 8);
+  be_fill(h, key_compl, 0, (size_t)nk * it_words * 8);
+  be_fill(h, key_neg, 0, (size_t)nk * it_words * 8);
+  be_fill(h, alloc_ok, 0, (size_t)it_words * 8);
+  be_fill(h, A.error, 0, 4);
+  be_launch_it_index(h, (int)n_its, A);
+  out->it_words = it_words; out->error = 0;
+  be_d2h(h, out->kv_has, kv_has, (size_t)rw * 64 * it_words * 8);
+  be_d2h(h, out->key_undef, key_undef, (size_t)nk * it_words * 8);
+  be_d2h(h, out->key_compl, key_compl, (size_t)nk * it_words * 8);
+  be_d2h(h, out->key_neg, key_neg, (size_t)nk * it_words * 8);
+  be_d2h(h, out->it_alloc_ok, alloc_ok, (size_t)it_words * 8);
+  be_d2h(h, &out->error, A.error, 4);
   be_sync(h);
   return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
 }

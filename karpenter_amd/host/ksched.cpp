@@ -403,7 +403,7 @@ struct Flattener {
     if (e.op == "Gt") {
       if (v == LLONG_MAX) { b.complement = 0; b.minv[k] = -1; b.has_minv = 0; return; }  // Gt MaxInt matches nothing (requirement.go:85-88)
       b.has_gte = kb; b.gte[k] = v + 1;
-    } else if (e.op == "Lt") { b.has_lte = kb; b.lte[k] = v - 1; }
+    } else if (e.op == "Lt") { b.has_lte = kb; b.lte[k] = (long long)((unsigned long long)v - 1ULL); }   // Go's value-- wraps at MinInt (requirement.go:98)
     else if (e.op == "Gte") { b.has_gte = kb; b.gte[k] = v; }
     else if (e.op == "Lte") { b.has_lte = kb; b.lte[k] = v; }
     else throw std::runtime_error("bad operator " + e.op);

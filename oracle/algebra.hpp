@@ -298,7 +298,7 @@ struct Requirement {
       if (v == LLONG_MAX) return make(key, Op::DoesNotExist, std::nullopt, nullptr, 0);  // requirement.go:85-88 (minValues dropped)
       r.gte = v + 1;
     }
-    if (op == Op::Lt) { long long v = n_vals == 0 ? 0 : atoi0(vals[0]); r.lte = v - 1; }
+    if (op == Op::Lt) { long long v = n_vals == 0 ? 0 : atoi0(vals[0]); r.lte = (long long)((unsigned long long)v - 1ULL); }   // value-- wraps at MinInt, as Go's does
     if (op == Op::Gte) r.gte = n_vals == 0 ? 0 : atoi0(vals[0]);
     if (op == Op::Lte) r.lte = n_vals == 0 ? 0 : atoi0(vals[0]);
     return r;

@@ -37,6 +37,7 @@ static void be_toc(ksolve_handle* h, int slot) {
   h->timers.ms[slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ((EmuBackend*)h->backend)->t0[slot]).count();
 }
 static void be_launch_it_index(ksolve_handle*, int n, const ks::ItIndexArgs& a) { for (int i = 0; i < n; ++i) ks::it_index_body(i, a); }
+static void be_launch_reqalg_test(ksolve_handle*, int n, const ks::ReqalgTestArgs& a) { for (int i = 0; i < n; ++i) ks::reqalg_test_body(i, a); }
 static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a) { h->test_row_kernel = KSOLVE_TEST_ROW_KERNEL_HOST; for (int i = 0; i < n; ++i) ks::row_hash_body(i, a); }
 static void be_launch_row_class(ksolve_handle*, int n, const ks::RowArgs& a) { for (int i = 0; i < n; ++i) ks::row_class_body(i, a); }
 static void be_launch_class_gather(ksolve_handle*, int n, const ks::RowArgs& a) { for (int i = 0; i < n; ++i) ks::class_gather_body(i, a); }
@@ -272,6 +273,23 @@ ksolve_status ksolve_test_classify(const ksolve_test_classify_in* in, ksolve_tes
   h->backend = new EmuBackend();
   const ksolve_status st = ksi::test_classify(h, in, out);
   if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_classify: %s\n", h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
+// the requirement algebra on pairs of rows, and the instance-type index alone (ksolve_impl.h test_reqalg, test_it_index)
+ksolve_status ksolve_test_reqalg(const ksolve_test_reqalg_in* in, ksolve_test_reqalg_out* out) {
+  ksolve_handle* h = new ksolve_handle();
+  h->backend = new EmuBackend();
+  const ksolve_status st = ksi::test_reqalg(h, in, out);
+  if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_reqalg: %s\n", h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
+ksolve_status ksolve_test_it_index(const ksolve_test_it_index_in* in, ksolve_test_it_index_out* out) {
+  ksolve_handle* h = new ksolve_handle();
+  h->backend = new EmuBackend();
+  const ksolve_status st = ksi::test_it_index(h, in, out);
+  if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_it_index: %s\n", h->error.c_str());
   ksolve_destroy(h);
   return st;
 }
