@@ -268,57 +268,66 @@ typedef struct {
                                     * ksolve_claims.truncation_failed */
   uint32_t reserved_capacity;      /* FeatureGates.ReservedCapacity (nodeclaim.go:308) */
   uint32_t reserved_offering_strict; /* DisableReservedCapacityFallback / ReservedOfferingModeStrict (scheduler.go:103, nodeclaim.go:339-348) */
-  uint32_t engine;                 /* which pack engine may run. 0 = automatic: the cursor engine (csrc/fast_engine.h) for problems whose
-                                    * requirement algebra is purely positive (In sets only, no topology / existing nodes / minValues /
-                                    * reservations / host ports; DaemonSet overhead is handled), the general engine otherwise or whenever
-                                    * the cursor engine stops;
-                                    * 1 = general engine only; 2 = cursor engine only (KSOLVE_ERR_UNSUPPORTED instead of the fallback:
-                                    * tests use it to prove which engine produced a result); 3 = cursor engine only, with the claims' state
-                                    * in HBM from the start (the plan the library moves to by itself when the LDS plan runs out of
-                                    * claims); 4 = cursor engine only, claim state AND claim order in HBM from the start (the plan above
-                                    * ~15,000 in-flight NodeClaims, up to 65,472); 5 = cursor engine only, LDS plan with one row of class slots on
-                                    * TWO wavefronts (ksolve_pack_fast2: a second wavefront recomputes a NodeClaim's acceptance words
-                                    * while the first places the next pod; kept for measurements — on the MI355X it is 5.7% slower than
-                                    * the one-wavefront kernel every other setting runs, profiles/round5/pass_i);
-                                    * 6 = spread engine only (csrc/topo_engine.h, round 6): the cursor engine's shape plus topology spread /
-                                    * pod affinity on dictionary keys and spread / anti-affinity on the hostname (BASELINE configs[2]);
-                                    * KSOLVE_ERR_UNSUPPORTED when the problem is outside that shape. Automatic (0) tries it first on every
-                                    * problem that is plain but for its topology groups and falls back to the general engine when it
-                                    * declines;
-                                    * 7 = "auto-nodes": as automatic, but a problem WITH existing nodes that is otherwise of the cursor
-                                    * engine's shape runs on the cursor engine with its existing-node stage (csrc/node_stage.h: the pods
-                                    * existing nodes take are placed first, by a first fit with one cursor per pod class, the loop solves
-                                    * the rest); the general engine whenever the stage or the loop declines. The setting for
-                                    * Provisioner.NewScheduler, which always passes stateNodes; 8 = "cursor-nodes": the cursor engine with
-                                    * that stage only (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0 and 2 still hand every problem
-                                    * with an existing node to the general engine / refuse it;
-                                    * 9 = "auto-nodes-spread": as 7, and a problem with existing nodes AND topology groups that is
-                                    * otherwise of the spread engine's shape runs on the spread engine, whose per-pod step offers the
-                                    * pod to the nodes first (csrc/topo_nodes.h, kernel ksolve_pack_topo_nodes); the general engine
-                                    * whenever the spread engine declines or stops; 10 = "spread-nodes": the spread engine only, nodes
-                                    * allowed (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 7 still answers a problem with nodes
-                                    * and topology groups with reason 34;
-                                    * 11 = "auto-limits": as 7, and the cursor engine goes on when a NodePool limit binds — a template
-                                    * whose pool has no node left or whose limit-filtered type list is empty is skipped for the pod, a
-                                    * shorter list opens the NodeClaim with that list (scheduler.go:706-727; csrc/fast_engine.h
-                                    * FastLimits) — instead of declining with reason 23 / 24; reason 29 when the lists narrowed more
-                                    * often than there are free template ids; 12 = "cursor-limits": the cursor engine only, with that
-                                    * (KSOLVE_ERR_UNSUPPORTED instead of the fallback). 0-10 still decline with 23 / 24; the spread
-                                    * engine does under 0-12;
-                                    * 13 = "auto-limits-spread": 9 and 11 together, and the spread engine goes on when a NodePool limit
-                                    * binds too (csrc/topo_engine.h limit_stage: the same limit stages, reason 29 when the ids run out);
-                                    * the general engine whenever either engine declines or stops; 14 = "spread-limits": the spread
-                                    * engine only, existing nodes allowed as under 10, with limit stages (KSOLVE_ERR_UNSUPPORTED with
-                                    * "spread engine declined the problem (reason N)" instead of the fallback);
-                                    * 15 = "auto-operators": as 13, and the cursor engine also takes NodePools whose requirements are
-                                    * not In sets — NotIn, Exists, DoesNotExist, Gt, Lt (csrc/fast_engine.h, "Complement templates":
-                                    * the values such a requirement admits fill the template's field of the packed requirement set,
-                                    * and the guard bit above the field says whether a NodeClaim still holds the NodePool's own
-                                    * requirement or a concrete set) — instead of declining with reason 3 (1 for Gt / Lt); pods with
-                                    * such operators (reason 4; 1 for Gt / Lt) and minValues (1) still go to the general engine, and
-                                    * so does every topology batch over such a NodePool: the spread engine declines as before;
-                                    * 16 = "cursor-operators": as 12 with the same acceptance (KSOLVE_ERR_UNSUPPORTED with "cursor
-                                    * engine declined the problem (reason N)" instead of the fallback). 0-14 still decline with 3 / 1.
+  uint32_t engine;                 /* which pack engine may run, and with which switches. One line per value (the table the library decodes
+                                    * the value with is csrc/engine_setting.h; the name is what the host library's options.engine takes).
+                                    * "falls back": the general engine takes over whenever a fast engine declines or stops, and
+                                    * engine_fallback_reason says why; "refuses": KSOLVE_ERR_UNSUPPORTED instead, with "cursor / spread
+                                    * engine declined the problem (reason N)" or "... requested for a problem outside its shape".
+                                    * Switches: nodes / s-nodes = the cursor / spread engine may take a problem with existing nodes;
+                                    * limits / s-limits = the cursor / spread engine goes on when a NodePool limit binds; operators = the
+                                    * cursor engine takes NodePools whose requirements are not In sets.
+                                    *
+                                    *    value  name                 engines that may run       a decline     switches
+                                    *      0    auto                 cursor, spread, general    falls back    -
+                                    *      1    general              general                    -             -
+                                    *      2    cursor               cursor                     refuses       -
+                                    *      3    cursor-wide          cursor                     refuses       - (starts with the claims' state in HBM)
+                                    *      4    cursor-hbm           cursor                     refuses       - (claim state AND claim order in HBM)
+                                    *      5    cursor-pair          cursor                     refuses       - (LDS plan on TWO wavefronts)
+                                    *      6    spread               spread                     refuses       -
+                                    *      7    auto-nodes           cursor, spread, general    falls back    nodes
+                                    *      8    cursor-nodes         cursor                     refuses       nodes
+                                    *      9    auto-nodes-spread    cursor, spread, general    falls back    nodes, s-nodes
+                                    *     10    spread-nodes         spread                     refuses       s-nodes
+                                    *     11    auto-limits          cursor, spread, general    falls back    nodes, limits
+                                    *     12    cursor-limits        cursor                     refuses       nodes, limits
+                                    *     13    auto-limits-spread   cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits
+                                    *     14    spread-limits        spread                     refuses       s-nodes, s-limits
+                                    *     15    auto-operators       cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators
+                                    *     16    cursor-operators     cursor                     refuses       nodes, limits, operators
+                                    *   above 16: no name; as 2, except that the library does not choose the first memory plan by the problem's size.
+                                    *
+                                    * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
+                                    * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
+                                    * handled). Tests pin it (2) to prove which engine produced a result. It moves by itself from the LDS
+                                    * plan to the plan with the claims' state in HBM when it runs out of claims (3 starts there), and to
+                                    * the one with the claim order in HBM too (4 starts there: the plan above ~15,000 in-flight NodeClaims,
+                                    * up to 65,472). 5 runs ksolve_pack_fast2: a second wavefront recomputes a NodeClaim's acceptance words
+                                    * while the first places the next pod; kept for measurements — on the MI355X it is 5.7% slower than the
+                                    * one-wavefront kernel every other setting runs, profiles/round5/pass_i.
+                                    * The spread engine (csrc/topo_engine.h, round 6) takes the cursor engine's shape plus topology spread /
+                                    * pod affinity on dictionary keys and spread / anti-affinity on the hostname (BASELINE configs[2]). An
+                                    * "auto" value tries it first on every problem that is plain but for its topology groups.
+                                    * nodes: a problem WITH existing nodes that is otherwise of the cursor engine's shape runs on the cursor
+                                    * engine with its existing-node stage (csrc/node_stage.h: the pods existing nodes take are placed first,
+                                    * by a first fit with one cursor per pod class, the loop solves the rest). 7 is the setting for
+                                    * Provisioner.NewScheduler, which always passes stateNodes. Without the switch every problem with an
+                                    * existing node goes to the general engine / is refused; 7 still answers a problem with nodes and
+                                    * topology groups with reason 34.
+                                    * s-nodes: a problem with existing nodes AND topology groups that is otherwise of the spread engine's
+                                    * shape runs on the spread engine, whose per-pod step offers the pod to the nodes first
+                                    * (csrc/topo_nodes.h, kernel ksolve_pack_topo_nodes).
+                                    * limits: a template whose pool has no node left or whose limit-filtered type list is empty is skipped for
+                                    * the pod, a shorter list opens the NodeClaim with that list (scheduler.go:706-727; csrc/fast_engine.h
+                                    * FastLimits) — instead of declining with reason 23 / 24; reason 29 when the lists narrowed more often
+                                    * than there are free template ids. s-limits: the same limit stages in the spread engine
+                                    * (csrc/topo_engine.h limit_stage). Without the switch an engine still declines with 23 / 24.
+                                    * operators: NotIn, Exists, DoesNotExist, Gt, Lt NodePools (csrc/fast_engine.h, "Complement templates": the
+                                    * values such a requirement admits fill the template's field of the packed requirement set, and the
+                                    * guard bit above the field says whether a NodeClaim still holds the NodePool's own requirement or a
+                                    * concrete set) — instead of declining with reason 3 (1 for Gt / Lt); pods with such operators (reason
+                                    * 4; 1 for Gt / Lt) and minValues (1) still go to the general engine, and so does every topology batch
+                                    * over such a NodePool: the spread engine declines as before.
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -1,0 +1,68 @@
+// engine_setting.h — ksolve_options.engine decoded ONCE: one table with a row per public value, and the policy a row stands for.
+// Host-only plain C++, no device code: ksolve_impl.h looks a handle's value up in create() and reads the policy from then on
+// (ksolve_handle::eng; the options keep what the caller passed); the host library (host/ksched.cpp) looks the option's NAME up in the
+// same table. include/ksolve.h documents the values for callers; a new value is a new row here and a new line there.
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+namespace ksi {
+
+struct EnginePolicy {
+  enum Run : uint8_t {
+    Auto,      // the fast engine whose shape the problem has, the general engine otherwise or whenever a fast engine declines (a fallback, with a reason)
+    General,   // the general engine only
+    Cursor,    // the cursor engine only: a problem it cannot take, or declines, is KSOLVE_ERR_UNSUPPORTED
+    Spread     // the spread engine only, likewise
+  };
+  Run run;
+  uint8_t first_plan;   // the cursor engine's memory plan a handle starts on (fast_plan_set): 0 = LDS, 1 = the claims' state in HBM, 2 = their order too
+  bool pick_plan;       // ... unless the problem's size says that a later plan is needed anyway (create(), "Which plan will hold ...")
+  bool pair;            // the two-wavefront kernel of the LDS plan (ksolve_pack_fast2; measurements only)
+  bool nodes;           // the cursor engine may take a problem with existing nodes (node_stage.h)
+  bool spread_nodes;    // the spread engine may (topo_nodes.h)
+  bool limits;          // the cursor engine goes on when a NodePool limit binds (fast_engine.h FastLimits)
+  bool spread_limits;   // the spread engine does (topo_engine.h limit_stage)
+  bool operators;       // the cursor engine takes NodePools whose requirements are not In sets (fast_engine.h, "Complement templates")
+  const char* name;     // options.engine of the host library's problem document; nullptr = no name
+
+  constexpr bool general_only() const { return run == General; }
+  constexpr bool cursor_only() const { return run == Cursor; }
+  constexpr bool spread_only() const { return run == Spread; }
+  constexpr bool refuses() const { return run == Cursor || run == Spread; }    // a decline is an error, not a fallback
+  constexpr bool may_spread() const { return run == Auto || run == Spread; }   // (a cursor-only handle never tries the spread engine)
+};
+
+//                                              run                    plan pick   pair   nodes  s-nodes limits s-lim  ops    name
+inline constexpr EnginePolicy kEngineSettings[] = {
+  /*  0 */ {EnginePolicy::Auto,    0, true,  false, false, false, false, false, false, "auto"},
+  /*  1 */ {EnginePolicy::General, 0, false, false, false, false, false, false, false, "general"},
+  /*  2 */ {EnginePolicy::Cursor,  0, true,  false, false, false, false, false, false, "cursor"},
+  /*  3 */ {EnginePolicy::Cursor,  1, false, false, false, false, false, false, false, "cursor-wide"},
+  /*  4 */ {EnginePolicy::Cursor,  2, false, false, false, false, false, false, false, "cursor-hbm"},
+  /*  5 */ {EnginePolicy::Cursor,  0, false, true,  false, false, false, false, false, "cursor-pair"},
+  /*  6 */ {EnginePolicy::Spread,  0, false, false, false, false, false, false, false, "spread"},
+  /*  7 */ {EnginePolicy::Auto,    0, true,  false, true,  false, false, false, false, "auto-nodes"},
+  /*  8 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, false, false, false, "cursor-nodes"},
+  /*  9 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  false, false, false, "auto-nodes-spread"},
+  /* 10 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, false, false, "spread-nodes"},
+  /* 11 */ {EnginePolicy::Auto,    0, true,  false, true,  false, true,  false, false, "auto-limits"},
+  /* 12 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, false, "cursor-limits"},
+  /* 13 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  false, "auto-limits-spread"},
+  /* 14 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, "spread-limits"},
+  /* 15 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  "auto-operators"},
+  /* 16 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  "cursor-operators"},
+};
+inline constexpr uint32_t kEngineSettingCount = (uint32_t)(sizeof(kEngineSettings) / sizeof(kEngineSettings[0]));
+// A value past the table is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch.
+inline constexpr EnginePolicy kEngineSettingPastTable = {EnginePolicy::Cursor, 0, false, false, false, false, false, false, false, nullptr};
+
+inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineSettingCount ? kEngineSettings[value] : kEngineSettingPastTable; }
+
+// The value an option name stands for; 0 ("auto") for a name the table does not hold.
+inline uint32_t engine_value(const char* name) {
+  for (uint32_t v = 0; v < kEngineSettingCount; ++v) if (!strcmp(kEngineSettings[v].name, name)) return v;
+  return 0;
+}
+
+}  // namespace ksi

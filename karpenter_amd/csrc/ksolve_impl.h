@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ksolve.h"
+#include "engine_setting.h"
 #include "engine.h"
 #include "kernels.h"
 #include "fast_engine.h"
@@ -46,7 +47,8 @@ enum { T_UPLOAD = 0, T_INDEX = 1, T_CLASSIFY = 2, T_SORT = 3, T_PACK = 4, T_FINA
 
 struct ksolve_handle {
   std::string error;
-  ksolve_options opts{};
+  ksolve_options opts{};        // as the caller passed them
+  ksi::EnginePolicy eng = ksi::engine_policy(0);   // the engine option decoded (engine_setting.h): every question about the setting is asked here
   ksi::Timers timers;
   // problem sizes
   uint32_t n_keys = 0, req_words = 0, n_res = 0, n_its = 0, it_words = 0, n_templates = 0, n_pods = 0, n_rows = 0, n_classes = 0;
@@ -79,11 +81,6 @@ struct ksolve_handle {
   ks::FastWork fw{};            // cursor engine (fast_engine.h): workspace + LDS plan; fw.enabled while the problem may qualify
   uint32_t engine_used = 0, fast_reason = 0, fast_attempts = 0;
   ks::FastArgs* d_fast_args = nullptr;   // the record ksolve_pack_fast reads its problem from
-  bool opt_nodes = false;       // engine = auto-nodes / cursor-nodes (7 / 8; opts.engine holds 0 / 2 from then on): the cursor engine may take a problem with existing nodes (node_stage.h)
-  bool opt_limits = false;      // engine = auto-limits / cursor-limits (11 / 12: as 7 / 8, opt_nodes included): the cursor engine goes on when a NodePool limit binds (fast_engine.h FastLimits)
-  bool opt_spread_limits = false;  // engine = auto-limits-spread / spread-limits (13 / 14: as 9 + 11 / as 10): the spread engine goes on when a NodePool limit binds (topo_engine.h limit_stage)
-  bool opt_ops = false;         // engine = auto-operators / cursor-operators (15 / 16: as 13 / 12): the cursor engine takes NodePools whose requirements are not In sets (fast_engine.h, "Complement templates")
-  bool opt_spread_nodes = false;   // engine = auto-nodes-spread / spread-nodes (9 / 10; opts.engine holds 0 / 6 from then on): the spread engine may take a problem with existing nodes (topo_nodes.h)
   uint64_t* nd_dead0 = nullptr; uint32_t nd_dead0_classes = 0;   // node stage: the static (class, node) rows (buffer kept, sized for that many classes; filled with every solve's classes)
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
   ks::TopoArgs* d_topo_args = nullptr;
@@ -353,6 +350,42 @@ static bool any_nonzero(const uint32_t* p, uint32_t n) {
 }
 
 static void fast_plan_set(ksolve_handle* h, int plan, int rows);   // the cursor engine's memory plan (0 LDS / 1 claim state in HBM / 2 order arrays too)
+// The head of a fast engine's LDS plan, which the cursor and the spread engine share (`rows` rows of 64 class slots); returns the offset behind it.
+static int fast_plan_head(ks::FastPlan& fp, int rows) {
+  auto align = [](int x) { return (x + 15) & ~15; };
+  int off = 0;
+  fp.off_ent = off; off = align(off + ks::kFastEnt * (int)sizeof(ks::FastEnt));
+  fp.off_pool = off; off = align(off + ks::kFastPool * 16);
+  fp.off_slot = off; off = align(off + rows * 64 * (int)sizeof(ks::FastSlot));
+  fp.off_misc = off; off = align(off + (int)sizeof(ks::FastMisc));
+  fp.off_hot = off; off = align(off + (int)sizeof(ks::FastHot));
+  return off;
+}
+// The workspace both fast engines use, zero-filled. rec_words: 64-bit words of a claim record in c_rec, 0 = none (the spread engine keeps its own, TopoWork::rec).
+static void fast_shared_alloc(ksolve_handle* h, uint32_t mc, size_t rec_words) {
+  ks::FastWork& fw = h->fw;
+  fw.var = dz<ks::FastVar>(h, 1);
+  fw.c_hostseq = dz<uint32_t>(h, mc); fw.c_ent = dz<uint16_t>(h, mc);
+  fw.c_state = dz<ks::FastClaim>(h, mc); fw.c_npods = dz<uint32_t>(h, mc);
+  fw.c_rec = rec_words ? dz<uint64_t>(h, (size_t)mc * rec_words) : nullptr;
+  fw.max_active = dz<uint32_t>(h, 1);
+  fw.ent_its = dz<uint64_t>(h, (size_t)ks::kFastEnt * h->it_words);
+  fw.q_class = dz<uint32_t>(h, h->n_pods); fw.q_claim = dz<uint32_t>(h, h->n_pods); fw.q_cnt = dz<uint32_t>(h, h->n_pods);
+}
+// The texts of a refusal (KSOLVE_ERR_UNSUPPORTED under a setting that names one engine), built here and nowhere else.
+static std::string reason_text(ksolve_handle* h) { return " (reason " + std::to_string(h->fast_reason) + ")"; }
+// the engine, or the host on its behalf, handed the problem back: the handle's fast_reason says why (decline.h)
+static ksolve_status declined(ksolve_handle* h, const char* engine) {
+  return fail(h, KSOLVE_ERR_UNSUPPORTED, std::string(engine) + " engine declined the problem" + reason_text(h));
+}
+// create() found the problem outside the shape of the one engine the setting names; the reason create() left, where it leaves one
+static ksolve_status outside_shape(ksolve_handle* h, EnginePolicy::Run engine) {
+  if (engine == EnginePolicy::Spread)
+    return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)" +
+                (h->eng.spread_nodes && h->fast_reason ? reason_text(h) : std::string()));
+  return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
+              (h->fast_reason ? reason_text(h) : std::string()));
+}
 // The existing-node conditions the cursor engine's stage (node_stage.h) and the spread engine's node path (topo_nodes.h) share;
 // 0, or the fallback reason (decline.h): 30 = a node under consolidateAfter that some pod must skip, 31 = node requirement sets with
 // bounds, 32 = a node label set that is not single-valued In.
@@ -398,20 +431,9 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   }
   if (d->topo.n > KSOLVE_MAX_TOPO_GROUPS) return fail(h, KSOLVE_ERR_UNSUPPORTED, "more than 1024 topology groups");
   if (d->topo.n && (!d->pod_topo_owned || !d->pod_topo_selected)) return fail(h, KSOLVE_ERR_INVALID, "topology groups without pod_topo_owned / pod_topo_selected");
-  for (uint32_t i = 0; i < d->n_its; ++i) {
-    // reserved offerings would need the ReservationManager; capacity type index >= n_captypes never occurs by construction
-    (void)i;
-  }
   if (o) h->opts = *o;
   else { h->opts = ksolve_options{}; h->opts.max_steps = -1; }
-  if (h->opts.engine == 7 || h->opts.engine == 8) { h->opt_nodes = true; h->opts.engine = h->opts.engine == 7 ? 0u : 2u; }   // automatic / cursor only, existing nodes allowed
-  else if (h->opts.engine == 9) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opts.engine = 0u; }   // as 7, and the spread engine may take nodes too
-  else if (h->opts.engine == 10) { h->opt_spread_nodes = true; h->opts.engine = 6u; }                        // spread only, existing nodes allowed
-  else if (h->opts.engine == 11 || h->opts.engine == 12) { h->opt_nodes = true; h->opt_limits = true; h->opts.engine = h->opts.engine == 11 ? 0u : 2u; }   // as 7 / 8, and binding NodePool limits do not stop the cursor engine
-  else if (h->opts.engine == 13) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opt_limits = true; h->opt_spread_limits = true; h->opts.engine = 0u; }   // 9 and 11 together, and binding limits do not stop the spread engine either
-  else if (h->opts.engine == 14) { h->opt_spread_nodes = true; h->opt_spread_limits = true; h->opts.engine = 6u; }   // as 10, with limit stages
-  else if (h->opts.engine == 15) { h->opt_nodes = true; h->opt_spread_nodes = true; h->opt_limits = true; h->opt_spread_limits = true; h->opt_ops = true; h->opts.engine = 0u; }   // as 13, and the cursor engine takes NotIn / Exists / DoesNotExist / Gt / Lt NodePools
-  else if (h->opts.engine == 16) { h->opt_nodes = true; h->opt_limits = true; h->opt_ops = true; h->opts.engine = 2u; }   // as 12, with the same acceptance
+  h->eng = engine_policy(h->opts.engine);
   h->n_keys = d->n_keys; h->req_words = req_words; h->n_res = d->n_res; h->n_its = d->n_its; h->it_words = it_words;
   h->n_templates = d->n_templates; h->n_pods = d->n_pods; h->n_rows = d->n_pod_rows;
   if (h->n_rows < h->n_pods) return fail(h, KSOLVE_ERR_INVALID, "n_pod_rows < n_pods");
@@ -722,7 +744,7 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
   W.c_hp = P.hp_on ? dz<uint64_t>(h, mc) : nullptr;
   W.o_key = dz<uint32_t>(h, mc); W.o_ord = dz<uint32_t>(h, mc); W.o_pos = dz<uint32_t>(h, mc);
   W.queue = dz<uint32_t>(h, (size_t)d->n_pods + 1); W.last_len = dz<uint32_t>(h, d->n_pods);
-  W.t_its = dz<uint64_t>(h, (size_t)(h->opt_limits || h->opt_spread_limits ? 32u : d->n_templates) * it_words);   // (engines 11-14: a row for every limit stage too, fast_engine.h FastLimits)
+  W.t_its = dz<uint64_t>(h, (size_t)(h->eng.limits || h->eng.spread_limits ? 32u : d->n_templates) * it_words);   // (with limit stages: a row for every stage too, fast_engine.h FastLimits)
   W.t_remaining = dz<int64_t>(h, (size_t)d->n_templates * (d->n_res + 1));
   W.assign = dz<int32_t>(h, d->n_pods); W.err = dz<uint8_t>(h, d->n_pods); W.diag = dz<uint8_t>(h, d->n_pods); W.slot = dz<uint32_t>(h, d->n_pods);
   W.n_claims_out = dz<int>(h, 1); W.status_out = dz<int>(h, 1);
@@ -874,46 +896,45 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     lp.total_bytes = off;
   }
   {
-    bool any_minv = false;
-    if (d->tmpl_reqs.min_values) for (size_t i = 0; i < (size_t)d->n_templates * d->n_keys; ++i) if (d->tmpl_reqs.min_values[i] >= 0) any_minv = true;
+    // The fast engines' shape, each term named once. What a predicate below leaves out is what its engine handles.
+    bool min_values = false;
+    if (d->tmpl_reqs.min_values) for (size_t i = 0; i < (size_t)d->n_templates * d->n_keys; ++i) if (d->tmpl_reqs.min_values[i] >= 0) min_values = true;
     const bool pod_bounds = any_nonzero(d->pod_reqs.has_gte, d->n_pod_rows) || any_nonzero(d->pod_reqs.has_lte, d->n_pod_rows);
     const bool tmpl_bounds = any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
-    const bool bounds = pod_bounds || tmpl_bounds;
-    P.plain = (d->topo.n == 0 && d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
-    P.plain_topo = (d->n_nodes == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on) ? 1 : 0;
+    const bool topology = d->topo.n > 0, nodes = d->n_nodes > 0;
+    const bool node_only = P.pv_on || d->pod_node;   // CSI volume limits, a resident cluster: they concern existing nodes alone
+    const bool common = !min_values && !P.reserved_on && !d->n_override_groups && !P.hp_on && !P.vol_on;   // no minValues, reservations, override groups, host ports, volumes: every predicate asks this
+    const bool no_bounds = !pod_bounds && !tmpl_bounds;
+    // with existing nodes: the stage's own reasons (30-33) behind the one for everything else
+    auto nodes_decline = [&](bool rest) { return rest && !node_only ? node_stage_declines(d, P.dict, req_words) : (uint32_t)ks::DECLINE_NODES_NOT_PLAIN; };
+    P.plain = (common && no_bounds && !topology && !nodes) ? 1 : 0;
+    P.plain_topo = (common && no_bounds && !nodes) ? 1 : 0;
     P.lite = (P.plain && !d->tmpl_daemon_first && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
-    // plain but for existing nodes the cursor engine's node stage can place pods on (node_stage.h); otherwise the reason (30-34)
+    // plain_nodes: plain but for existing nodes the cursor engine's node stage can place pods on (node_stage.h); otherwise the reason (30-34)
     P.plain_nodes = 0;
-    if (h->opt_nodes && d->n_nodes > 0) {
-      uint32_t why = 0;
-      if (!(d->topo.n == 0 && !any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = ks::DECLINE_NODES_NOT_PLAIN;
-      if (!why) why = node_stage_declines(d, P.dict, req_words);
-      P.plain_nodes = why ? 0 : 1;
-      h->fast_reason = why;
+    if (h->eng.nodes && nodes) {
+      h->fast_reason = nodes_decline(common && no_bounds && !topology);
+      P.plain_nodes = h->fast_reason ? 0 : 1;
     }
-    // plain_ops: plain / plain_nodes without the templates' share of `bounds` — what alone keeps a batch with a Gt / Lt NodePool from
-    // the cursor engine, which takes it under engines 15 / 16 only. Whatever else is outside the shape (pod-side bounds, minValues,
-    // ...) stays outside, and those two settings name it as FastCold::setup() would: DECLINE_NOT_PLAIN. So does every other setting
+    // plain_ops: plain / plain_nodes without the templates' share of the bounds — what alone keeps a batch with a Gt / Lt NodePool from
+    // the cursor engine, which takes it under the operators switch only. Whatever else is outside the shape (pod-side bounds, minValues,
+    // ...) stays outside, and that switch names it as FastCold::setup() would: DECLINE_NOT_PLAIN. So does every other setting
     // for the batch that only the templates' bounds keep out (without existing nodes: they have reasons of their own, above).
     P.plain_ops = 0;
-    if (h->opts.engine != 1 && d->topo.n == 0 && !P.plain && !P.plain_nodes) {
-      const bool rest = !any_minv && !P.reserved_on && !pod_bounds && !d->n_override_groups && !P.hp_on && !P.vol_on;
-      if (h->opt_ops) {
-        uint32_t why = rest ? 0u : (uint32_t)(d->n_nodes > 0 ? ks::DECLINE_NODES_NOT_PLAIN : ks::DECLINE_NOT_PLAIN);
-        if (!why && d->n_nodes > 0) why = (P.pv_on || d->pod_node) ? (uint32_t)ks::DECLINE_NODES_NOT_PLAIN : node_stage_declines(d, P.dict, req_words);
-        P.plain_ops = why ? 0 : 1;
-        h->fast_reason = why;
-      } else if (rest && tmpl_bounds && d->n_nodes == 0) h->fast_reason = ks::DECLINE_NOT_PLAIN;
+    if (!h->eng.general_only() && !topology && !P.plain && !P.plain_nodes) {
+      const bool rest = common && !pod_bounds;
+      if (h->eng.operators) {
+        h->fast_reason = nodes ? nodes_decline(rest) : rest ? 0u : (uint32_t)ks::DECLINE_NOT_PLAIN;
+        P.plain_ops = h->fast_reason ? 0 : 1;
+      } else if (rest && tmpl_bounds && !nodes) h->fast_reason = ks::DECLINE_NOT_PLAIN;
     }
-    // plain_topo_nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
+    // plain_topo with nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
     // engine's node path rests on (topo_nodes.h): every node carries ONE value of every dictionary key a group uses (35), among the
     // sixteen a group's counters hold (36), and no group honours nodeTaintsPolicy while a node is tainted (43, extended to nodes:
     // TopologyNodeFilter.Matches must be true for every node as it is for every claim). The view's plain_topo says it: a handle
     // with nodes runs ksolve_pack_topo_nodes.
-    if (h->opt_spread_nodes && d->n_nodes > 0 && d->topo.n > 0) {
-      uint32_t why = 0;
-      if (!(!any_minv && !P.reserved_on && !bounds && !d->n_override_groups && !P.hp_on && !P.vol_on && !P.pv_on && !d->pod_node)) why = ks::DECLINE_NODES_NOT_PLAIN;
-      if (!why) why = node_stage_declines(d, P.dict, req_words);
+    if (h->eng.spread_nodes && nodes && topology) {
+      uint32_t why = nodes_decline(common && no_bounds);
       std::vector<uint8_t> dom((size_t)d->n_keys * d->n_nodes, 0xFF);
       bool any_taint = false;
       for (uint32_t e = 0; e < d->n_nodes; ++e) any_taint = any_taint || d->node_taints[e] != 0;
@@ -941,11 +962,11 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     // cursor engine (fast_engine.h): candidate when the problem is lite and has no relaxation rows; the kernel itself checks the
     // rest (positive operators only, packed variable keys, 31-bit quantities) and hands the problem back otherwise
     ks::FastWork& fw = h->fw;
-    fw.enabled = ((P.plain || P.plain_nodes || P.plain_ops) && d->n_res <= 4 && h->opts.engine != 1 && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
+    fw.enabled = ((P.plain || P.plain_nodes || P.plain_ops) && d->n_res <= 4 && !h->eng.general_only() && d->n_pod_rows == d->n_pods && d->n_pods > 0) ? 1 : 0;
     if (fw.enabled) {
       h->fast_mc = mc;
-      fast_plan_set(h, h->opts.engine == 4 ? 2 : h->opts.engine == 3 ? 1 : 0, 1);
-      if ((h->opts.engine == 0 || h->opts.engine == 2) && !h->opts.lds_claim_cap) {
+      fast_plan_set(h, h->eng.first_plan, 1);
+      if (h->eng.pick_plan && !h->opts.lds_claim_cap) {
         // Which plan will hold the problem's NodeClaims is predictable from the rows themselves: no packing needs fewer claims than
         // the batch's total requests over the largest allocatable of any type, per resource (round-5 review: the exact configs[3]
         // batch — 27,345 claims — spent a whole attempt on the LDS plan before it moved to plan 2). A problem whose bound already
@@ -964,44 +985,28 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
         int plan = 0;
         while (plan < 2 && need > (double)h->fw.plan.cap) { ++plan; fast_plan_set(h, plan, h->fw.plan.rows); }
       }
-      fw.var = dz<ks::FastVar>(h, 1);
-      fw.c_hostseq = dz<uint32_t>(h, mc); fw.c_ent = dz<uint16_t>(h, mc);
-      fw.c_state = dz<ks::FastClaim>(h, mc); fw.c_npods = dz<uint32_t>(h, mc);
-      fw.c_rec = dz<uint64_t>(h, (size_t)mc * (sizeof(ks::FastRec<ks::kFastRows>) / 8));
-      fw.max_active = dz<uint32_t>(h, 1);
-      fw.ent_its = dz<uint64_t>(h, (size_t)ks::kFastEnt * it_words);
-      fw.q_class = dz<uint32_t>(h, d->n_pods); fw.q_claim = dz<uint32_t>(h, d->n_pods); fw.q_cnt = dz<uint32_t>(h, d->n_pods);
+      fast_shared_alloc(h, mc, sizeof(ks::FastRec<ks::kFastRows>) / 8);
       { const size_t oc = std::min<size_t>(65472, ((size_t)mc + 63) & ~(size_t)63) + 64; fw.o_key = dz<uint16_t>(h, oc); fw.o_ord = dz<uint16_t>(h, oc); fw.o_snap = dz<uint16_t>(h, oc); }
       h->d_fast_args = dz<ks::FastArgs>(h, 1);
       if (P.plain_nodes || (P.plain_ops && d->n_nodes > 0)) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
-      if (h->opt_limits) fw.lim = dz<ks::FastLimits>(h, 1);
-      fw.ops = h->opt_ops ? 1 : 0;
+      if (h->eng.limits) fw.lim = dz<ks::FastLimits>(h, 1);
+      fw.ops = h->eng.operators ? 1 : 0;
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the
     // cursor engine's tables (requirement-set cache, class records, queue-order arrays) and on the BIG engine's claim order (run_order.h).
     ks::TopoWork& tw = h->tw;
-    tw.enabled = (!fw.enabled && P.plain_topo && d->topo.n > 0 && d->topo.n <= (uint32_t)ks::kTopoMaxGroups && d->n_res <= 4 && (h->opts.engine == 0 || h->opts.engine == 6) &&
+    tw.enabled = (!fw.enabled && P.plain_topo && d->topo.n > 0 && d->topo.n <= (uint32_t)ks::kTopoMaxGroups && d->n_res <= 4 && h->eng.may_spread() &&
                   d->n_pod_rows == d->n_pods && d->n_pods > 0 && !d->pod_node) ? 1 : 0;
     if (tw.enabled) {
-      fw.var = dz<ks::FastVar>(h, 1);
-      fw.c_hostseq = dz<uint32_t>(h, mc); fw.c_ent = dz<uint16_t>(h, mc);
-      fw.c_state = dz<ks::FastClaim>(h, mc); fw.c_npods = dz<uint32_t>(h, mc);
-      fw.c_rec = nullptr; fw.max_active = dz<uint32_t>(h, 1);
-      fw.ent_its = dz<uint64_t>(h, (size_t)ks::kFastEnt * it_words);
-      fw.q_class = dz<uint32_t>(h, d->n_pods); fw.q_claim = dz<uint32_t>(h, d->n_pods); fw.q_cnt = dz<uint32_t>(h, d->n_pods);
+      fast_shared_alloc(h, mc, 0);
       fw.o_key = nullptr; fw.o_ord = nullptr; fw.o_snap = nullptr;
       tw.rec = dz<ks::TopoRec>(h, mc);
-      if (h->opt_spread_limits) fw.lim = dz<ks::FastLimits>(h, 1);
+      if (h->eng.spread_limits) fw.lim = dz<ks::FastLimits>(h, 1);
       auto align = [](int x) { return (x + 15) & ~15; };
       ks::FastPlan& fp = fw.plan;
-      int off = 0;
       fp.rows = 1; fp.helper = 0; fp.global_state = 2; fp.cap = 0;
-      fp.off_ent = off; off = align(off + ks::kFastEnt * (int)sizeof(ks::FastEnt));
-      fp.off_pool = off; off = align(off + ks::kFastPool * 16);
-      fp.off_slot = off; off = align(off + 64 * (int)sizeof(ks::FastSlot));
-      fp.off_misc = off; off = align(off + (int)sizeof(ks::FastMisc));
-      fp.off_hot = off; off = align(off + (int)sizeof(ks::FastHot));
+      int off = fast_plan_head(fp, fp.rows);
       fp.off_state = fp.off_key = fp.off_ord = fp.off_snap = off;
       tw.plan.off_run = off; off = align(off + (int)sizeof(ks::RunTables));
       tw.plan.off_state = off; off = align(off + (int)sizeof(ks::TopoState));
@@ -1041,7 +1046,7 @@ static ksolve_status probe_create(ksolve_handle* base, const ksolve_probe* pr, k
   for (uint32_t e = 0; e < base->n_nodes; ++e) if ((pr->removed_nodes[e >> 6] >> (e & 63)) & 1) h->pr_nodes.push_back(e);
   if (pr->tmpl_limits) h->pr_limits.assign(pr->tmpl_limits, pr->tmpl_limits + (size_t)base->n_templates * (base->n_res + 1));
   h->base = base;
-  h->opts = base->opts;
+  h->opts = base->opts; h->eng = base->eng;
   h->n_keys = base->n_keys; h->req_words = base->req_words; h->n_res = base->n_res; h->n_its = base->n_its; h->it_words = base->it_words;
   h->n_templates = base->n_templates; h->n_pods = base->n_pods; h->n_rows = base->n_rows; h->n_classes = base->n_classes;
   h->n_nodes = base->n_nodes; h->has_topology = base->has_topology;
@@ -1378,7 +1383,7 @@ static ksolve_status solve_prepare(ksolve_handle* h, bool fresh_context = true) 
     const int rows = live <= 64 ? 1 : ks::kFastRows;
     if (rows != h->fw.plan.rows) {
       fast_plan_set(h, h->fw.plan.global_state, rows);
-      if ((h->opts.engine == 0 || h->opts.engine == 2) && !h->opts.lds_claim_cap)   // (a plan's capacity depends on the rows of class slots: the bound of create() once more)
+      if (h->eng.pick_plan && !h->opts.lds_claim_cap)   // (a plan's capacity depends on the rows of class slots: the bound of create() once more)
         while (h->fw.plan.global_state < 2 && h->fast_need > (double)h->fw.plan.cap) fast_plan_set(h, h->fw.plan.global_state + 1, rows);
     }
   }
@@ -2369,14 +2374,9 @@ static void fast_plan_set(ksolve_handle* h, int plan, int rows) {
   ks::FastPlan& fp = h->fw.plan;
   rows = rows <= 1 ? 1 : ks::kFastRows;
   fp.rows = rows;
-  fp.helper = (plan == 0 && rows == 1 && h->opts.engine == 5) ? 1 : 0;   // the two-wavefront kernel: on request only (engine 5) — measured 5.7% SLOWER than one wavefront on the headline problem (profiles/round5/pass_i)
+  fp.helper = (plan == 0 && rows == 1 && h->eng.pair) ? 1 : 0;   // the two-wavefront kernel: on request only (engine 5) — measured 5.7% SLOWER than one wavefront on the headline problem (profiles/round5/pass_i)
   const int rec_bytes = rows == 1 ? (int)sizeof(ks::FastRec<1>) : (int)sizeof(ks::FastRec<ks::kFastRows>);
-  int off = 0;
-  fp.off_ent = off; off = align(off + ks::kFastEnt * (int)sizeof(ks::FastEnt));
-  fp.off_pool = off; off = align(off + ks::kFastPool * 16);
-  fp.off_slot = off; off = align(off + rows * 64 * (int)sizeof(ks::FastSlot));
-  fp.off_misc = off; off = align(off + (int)sizeof(ks::FastMisc));
-  fp.off_hot = off; off = align(off + (int)sizeof(ks::FastHot));
+  int off = fast_plan_head(fp, rows);
   const int budget = 160 * 1024 - 512;
   const int per_claim = wide ? 4 : rec_bytes + 6;   // plan 1: the order's keys and ids; plan 0: the record, the order and the order's snapshot
   int cap = plan >= 2 ? 65472 : ((budget - off - 64) / per_claim) & ~63;
@@ -2466,17 +2466,13 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
   if (h->base) { ksolve_status st = KSOLVE_OK; solve_probes(&h, 1, out, &st, fresh_context); return st; }
   ksolve_status st = solve_prepare(h, fresh_context);
   if (st != KSOLVE_OK) return st;
-  if (h->opts.engine == 6 && !(h->tw.enabled && h->n_pods && h->n_classes))
-    return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine requested for a problem outside its shape (no topology groups / existing nodes / minValues / reservations / relaxation rows)" +
-                (h->opt_spread_nodes && h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
-  if (h->opts.engine >= 2 && h->opts.engine != 6 && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
-    return fail(h, KSOLVE_ERR_UNSUPPORTED, h->opt_ops && h->fast_reason ? "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")" :
-                "cursor engine requested for a problem outside its shape (topology / existing nodes / minValues / reservations / relaxation rows)" +
-                (h->fast_reason ? " (reason " + std::to_string(h->fast_reason) + ")" : std::string()));
+  if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes)) return outside_shape(h, EnginePolicy::Spread);
+  if (h->eng.cursor_only() && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
+    return h->eng.operators && h->fast_reason ? declined(h, "cursor") : outside_shape(h, EnginePolicy::Cursor);
   if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
     // more pod classes than the node stage keeps cursors for: the general engine (nothing has run yet)
     h->fast_reason = ks::DECLINE_NODE_CLASSES;
-    if (h->opts.engine >= 2) return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")");
+    if (h->eng.refuses()) return declined(h, "cursor");
     h->fw.enabled = 0;
   }
   if (h->tw.enabled && h->n_pods && h->n_classes) {
@@ -2499,7 +2495,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
       return solve_finish(h, out);
     }
     h->fast_reason = o.reason;
-    if (h->opts.engine == 6) return fail(h, KSOLVE_ERR_UNSUPPORTED, "spread engine declined the problem (reason " + std::to_string(h->fast_reason) + ")");
+    if (h->eng.spread_only()) return declined(h, "spread");
     if (h->fast_reason != ks::DECLINE_UNSCHEDULABLE_POD && h->fast_reason != ks::DECLINE_CAPACITY) h->tw.enabled = 0;   // not its shape: later solves of this handle go straight to the general engine
     st = solve_prepare(h, false);
     if (st != KSOLVE_OK) return st;
@@ -2542,7 +2538,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
       }
       break;
     }
-    if (h->opts.engine >= 2) return fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")");
+    if (h->eng.refuses()) return declined(h, "cursor");
     h->fw.enabled = 0;   // later solves of this handle go straight to the general engine
     st = solve_prepare(h, false);
     if (st != KSOLVE_OK) return st;
@@ -2600,7 +2596,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
       if (h->fw.plan.global_state == 0 && !h->fw.nodes && !h->fw.lim) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop; so does one of engines 11 / 12)
       else { be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1; }
     }
-    else if (h->opts.engine >= 2) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");
+    else if (h->eng.refuses()) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");   // (the batch path's short form; a spread-only handle gets the cursor wording too: a known wart)
     else run.push_back(h);
   }
   if (!fast.empty()) {
@@ -2624,7 +2620,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
         be_results_drop(&outs[idx]); st[idx] = solve(h, &outs[idx], false); outs[idx].status = st[idx]; alone[idx] = 1;
         continue;
       }
-      if (h->opts.engine >= 2) { st[idx] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine declined the problem (reason " + std::to_string(h->fast_reason) + ")"); continue; }
+      if (h->eng.refuses()) { st[idx] = declined(h, "cursor"); continue; }
       h->fw.enabled = 0;
       st[idx] = solve_prepare(h, false);
       if (st[idx] == KSOLVE_OK) { be_sync(h); run.push_back(h); }

@@ -57,6 +57,7 @@
 #include <vector>
 
 #include "../../include/ksolve.h"
+#include "../csrc/engine_setting.h"
 #include "../csrc/reqalg.h"
 #include "json_mini.hpp"
 
@@ -2155,7 +2156,8 @@ struct ProblemBuilder {
     ko.truncate_instance_types = (uint32_t)opts.at("truncateInstanceTypes").i(0);
     ko.reserved_capacity = opts.at("reservedCapacity").boolean_or(false) ? 1 : 0;
     ko.reserved_offering_strict = opts.at("reservedOfferingMode").s("Fallback") == "Strict" ? 1 : 0;
-    { const std::string eng = opts.at("engine").s("auto"); ko.engine = eng == "general" ? 1u : eng == "cursor" ? 2u : eng == "cursor-wide" ? 3u : eng == "cursor-hbm" ? 4u : eng == "cursor-pair" ? 5u : eng == "spread" ? 6u : eng == "auto-nodes" ? 7u : eng == "cursor-nodes" ? 8u : eng == "auto-nodes-spread" ? 9u : eng == "spread-nodes" ? 10u : eng == "auto-limits" ? 11u : eng == "cursor-limits" ? 12u : eng == "auto-limits-spread" ? 13u : eng == "spread-limits" ? 14u : eng == "auto-operators" ? 15u : eng == "cursor-operators" ? 16u : 0u; }
+    const Value& eng = opts.at("engine");   // a name of csrc/engine_setting.h's table (0 for one it does not hold), or the value itself as a number
+    ko.engine = eng.kind == Value::Num ? (uint32_t)eng.i(0) : ksi::engine_value(eng.s("auto").c_str());
     return ko;
   }
 
