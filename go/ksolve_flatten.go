@@ -973,6 +973,9 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // KsolveEngineAutoOperators = "auto-operators" (15): existing nodes and binding NodePool limits on both fast engines, and the cursor
 // engine takes NodePools whose requirements use NotIn, Exists, DoesNotExist, Gt or Lt — what the NodePool examples carry.
 // KsolveEngineCursorOperators (16) is the cursor engine alone with that acceptance and refuses instead of falling back (tests).
+// KsolveEngineAutoOperatorsSpread = "auto-operators-spread" (18): KsolveEngineAutoOperators, and the spread engine takes such
+// NodePools too — topology batches over them no longer go to the general engine. KsolveEngineSpreadOperators (19) is the spread
+// engine alone with that acceptance and refuses instead of falling back (tests). 17 has no name.
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -985,6 +988,9 @@ const (
 
 	KsolveEngineAutoOperators   uint32 = 15
 	KsolveEngineCursorOperators uint32 = 16
+
+	KsolveEngineAutoOperatorsSpread uint32 = 18
+	KsolveEngineSpreadOperators     uint32 = 19
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

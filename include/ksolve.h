@@ -275,7 +275,7 @@ typedef struct {
                                     * engine declined the problem (reason N)" or "... requested for a problem outside its shape".
                                     * Switches: nodes / s-nodes = the cursor / spread engine may take a problem with existing nodes;
                                     * limits / s-limits = the cursor / spread engine goes on when a NodePool limit binds; operators = the
-                                    * cursor engine takes NodePools whose requirements are not In sets.
+                                    * cursor engine takes NodePools whose requirements are not In sets; s-operators = the spread engine does.
                                     *
                                     *    value  name                 engines that may run       a decline     switches
                                     *      0    auto                 cursor, spread, general    falls back    -
@@ -295,7 +295,10 @@ typedef struct {
                                     *     14    spread-limits        spread                     refuses       s-nodes, s-limits
                                     *     15    auto-operators       cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators
                                     *     16    cursor-operators     cursor                     refuses       nodes, limits, operators
-                                    *   above 16: no name; as 2, except that the library does not choose the first memory plan by the problem's size.
+                                    *     17    (no name)            cursor                     refuses       - (as 2, except that the library does not choose the first memory plan by the problem's size)
+                                    *     18    auto-operators-spread cursor, spread, general   falls back    nodes, s-nodes, limits, s-limits, operators, s-operators
+                                    *     19    spread-operators     spread                     refuses       s-nodes, s-limits, s-operators
+                                    *   above 19: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
@@ -327,7 +330,12 @@ typedef struct {
                                     * guard bit above the field says whether a NodeClaim still holds the NodePool's own requirement or a
                                     * concrete set) — instead of declining with reason 3 (1 for Gt / Lt); pods with such operators (reason
                                     * 4; 1 for Gt / Lt) and minValues (1) still go to the general engine, and so does every topology batch
-                                    * over such a NodePool: the spread engine declines as before.
+                                    * over such a NodePool: without s-operators the spread engine declines as before.
+                                    * s-operators: the same NodePools on the spread engine (csrc/topo_engine.h, "Complement templates on the
+                                    * spread engine": a NodeClaim that still holds its NodePool's own NotIn / Exists / Gt / Lt is counted by
+                                    * no spread or affinity group until a pod's domain choice has narrowed it), with existing nodes and limit
+                                    * stages — instead of reason 3, or of never reaching the spread engine (Gt / Lt: reason 0). Pods with such
+                                    * operators (4), pod-side bounds and minValues (1) still go to the general engine.
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -10,8 +10,9 @@ enum Decline : int {
   DECLINE_NONE = 0,                    // the fast engine solved the problem
   // FastCold::setup(), for both engines
   DECLINE_NOT_PLAIN = 1,               // outside the view's plain / plain_topo / plain_nodes (/ plain_ops under engines 15 / 16), relaxation rows, more than 4 resources, 32 templates or kMaxItWords
-                                       // words of types; the host raises it for a batch that Gt / Lt NodePools alone keep from the cursor engine (ksolve_impl.h, plain_ops)
-  DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, Exists, DoesNotExist; Gt, Lt on the spread engine) — not the cursor engine under engines 15 / 16
+                                       // words of types; the host raises it for a batch that Gt / Lt NodePools alone keep from the cursor engine (ksolve_impl.h, plain_ops),
+                                       // and under engines 18 / 19 for a topology batch outside plain_topo (pod-side bounds, minValues, ...)
+  DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, Exists, DoesNotExist; Gt, Lt on the spread engine) — not the cursor engine under engines 15 / 16, not the spread engine under 18 / 19
   DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply)
   DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
   DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits

@@ -140,7 +140,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   FastLimits* lim;        // [1] engines 11-14: the engine goes on when a NodePool limit binds (Workspace::t_its has 32 rows then); null otherwise
   FastPlan plan;
   int enabled;
-  int ops;                // engines 15 / 16: setup() accepts NodePool requirements that are not In sets (NotIn, Exists, DoesNotExist, Gt, Lt) — "Complement templates" below
+  int ops;                // engines 15 / 16 (a cursor handle), 18 / 19 (a spread handle): setup() accepts NodePool requirements that are not In sets (NotIn, Exists, DoesNotExist, Gt, Lt) — "Complement templates" below
 };
 
 // whole-record moves between LDS and registers (a struct behind an address-space-3 pointer has no implicit copy)
@@ -655,13 +655,13 @@ struct FastCold {
       if (W::leader()) { lim->n_ids = (uint32_t)T; lim->first_claim = 0xFFFFFFFFu; }
       W::sync();
     }
-    const bool ops = F.ops && !topo;   // engines 15 / 16, the cursor engine only: complement templates (below)
+    const bool ops = F.ops != 0;   // complement templates (below): engines 15 / 16 on the cursor engine, 18 / 19 on the spread engine — the host sets the switch per engine
     if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes) || (ops && P.plain_ops))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
     // Instance types may use any operator. Pods are positive, so a claim's set on a key is either concrete — against it the NotIn /
     // DoesNotExist escape of requirements.go:260-265 never applies — or still the template's own requirement, and that one meets the
     // instance types once, below, where the escape does apply (a DoesNotExist type passes a NotIn pool and fails an Exists or Gt
     // pool). Either way a claim's types only shrink: compatible() stays monotone.
-    // templates: only In sets, but for engines 15 / 16
+    // templates: only In sets, but for engines 15 / 16 (18 / 19 for the spread engine)
     if (!ops && W::reduce_or(T, [&](int t) {
       const ReqRef tr = Pv.tmpl_reqs.at(d, t);
       uint64_t neg = (uint64_t)(tr.complement | tr.has_gte | tr.has_lte);

@@ -85,6 +85,7 @@ struct ksolve_handle {
   ks::TopoWork tw{};            // spread engine (topo_engine.h): workspace + LDS plan; tw.enabled while the problem may qualify (it borrows fw's buffers)
   ks::TopoArgs* d_topo_args = nullptr;
   bool daemon_groups = false;   // the problem carries DaemonSets (ksolve_problem_desc.tmpl_daemon_first)
+  bool spread_complement = false;   // a spread handle of engines 18 / 19 whose NodePools carry a requirement that is not a non-empty In set
   // probes of a resident cluster (ksolve_probe_create): a probe handle shares the base's device tables
   ksolve_handle* base = nullptr;         // non-null: this handle is a probe of `base`
   bool prepared = false;                 // base: phases 1-3 have run and h_rank is valid
@@ -905,10 +906,13 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     const bool node_only = P.pv_on || d->pod_node;   // CSI volume limits, a resident cluster: they concern existing nodes alone
     const bool common = !min_values && !P.reserved_on && !d->n_override_groups && !P.hp_on && !P.vol_on;   // no minValues, reservations, override groups, host ports, volumes: every predicate asks this
     const bool no_bounds = !pod_bounds && !tmpl_bounds;
+    // the spread engine's share of the bounds: under the spread_operators switch (engines 18 / 19) the templates' Gt / Lt are its
+    // business (complement templates), the pods' never
+    const bool no_topo_bounds = h->eng.spread_operators ? !pod_bounds : no_bounds;
     // with existing nodes: the stage's own reasons (30-33) behind the one for everything else
     auto nodes_decline = [&](bool rest) { return rest && !node_only ? node_stage_declines(d, P.dict, req_words) : (uint32_t)ks::DECLINE_NODES_NOT_PLAIN; };
     P.plain = (common && no_bounds && !topology && !nodes) ? 1 : 0;
-    P.plain_topo = (common && no_bounds && !nodes) ? 1 : 0;
+    P.plain_topo = (common && no_topo_bounds && !nodes) ? 1 : 0;
     P.lite = (P.plain && !d->tmpl_daemon_first && req_words <= 64 && it_words <= 8 && d->n_res <= 4) ? 1 : 0;
     // plain_nodes: plain but for existing nodes the cursor engine's node stage can place pods on (node_stage.h); otherwise the reason (30-34)
     P.plain_nodes = 0;
@@ -928,13 +932,16 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
         P.plain_ops = h->fast_reason ? 0 : 1;
       } else if (rest && tmpl_bounds && !nodes) h->fast_reason = ks::DECLINE_NOT_PLAIN;
     }
+    // ... and the spread_operators switch names what keeps a topology batch outside plain_topo (pod-side bounds, minValues, ...) the
+    // same way; every other setting leaves such a batch without a reason, as before
+    if (h->eng.spread_operators && topology && !nodes && !P.plain_topo) h->fast_reason = ks::DECLINE_NOT_PLAIN;
     // plain_topo with nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
     // engine's node path rests on (topo_nodes.h): every node carries ONE value of every dictionary key a group uses (35), among the
     // sixteen a group's counters hold (36), and no group honours nodeTaintsPolicy while a node is tainted (43, extended to nodes:
     // TopologyNodeFilter.Matches must be true for every node as it is for every claim). The view's plain_topo says it: a handle
     // with nodes runs ksolve_pack_topo_nodes.
     if (h->eng.spread_nodes && nodes && topology) {
-      uint32_t why = nodes_decline(common && no_bounds);
+      uint32_t why = nodes_decline(common && no_topo_bounds);
       std::vector<uint8_t> dom((size_t)d->n_keys * d->n_nodes, 0xFF);
       bool any_taint = false;
       for (uint32_t e = 0; e < d->n_nodes; ++e) any_taint = any_taint || d->node_taints[e] != 0;
@@ -1003,6 +1010,19 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       fw.o_key = nullptr; fw.o_ord = nullptr; fw.o_snap = nullptr;
       tw.rec = dz<ks::TopoRec>(h, mc);
       if (h->eng.spread_limits) fw.lim = dz<ks::FastLimits>(h, 1);
+      fw.ops = h->eng.spread_operators ? 1 : 0;   // engines 18 / 19; a spread handle of 15 / 16 declines complement templates as before
+      if (fw.ops) {
+        // ... and whether this problem has one: what FastCold::setup() declines with reason 3 without the switch (the batch path asks)
+        bool complement = any_nonzero(d->tmpl_reqs.complement, d->n_templates) || any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
+        for (uint32_t t = 0; t < d->n_templates && !complement; ++t)
+          for (uint32_t k = 0; k < d->n_keys && !complement; ++k) {
+            if (!((d->tmpl_reqs.defined[t] >> k) & 1u)) continue;
+            bool empty = true;   // In [] == DoesNotExist
+            for (uint32_t x = P.dict.key_word_off[k]; x < P.dict.key_word_off[k + 1]; ++x) empty = empty && !d->tmpl_reqs.mask[(size_t)t * req_words + x];
+            complement = empty;
+          }
+        h->spread_complement = complement;
+      }
       auto align = [](int x) { return (x + 15) & ~15; };
       ks::FastPlan& fp = fw.plan;
       fp.rows = 1; fp.helper = 0; fp.global_state = 2; fp.cap = 0;
@@ -2466,7 +2486,8 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
   if (h->base) { ksolve_status st = KSOLVE_OK; solve_probes(&h, 1, out, &st, fresh_context); return st; }
   ksolve_status st = solve_prepare(h, fresh_context);
   if (st != KSOLVE_OK) return st;
-  if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes)) return outside_shape(h, EnginePolicy::Spread);
+  if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes))
+    return h->eng.spread_operators && h->fast_reason ? declined(h, "spread") : outside_shape(h, EnginePolicy::Spread);
   if (h->eng.cursor_only() && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
     return h->eng.operators && h->fast_reason ? declined(h, "cursor") : outside_shape(h, EnginePolicy::Cursor);
   if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
@@ -2586,8 +2607,8 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i] != KSOLVE_OK || !hs[i]->n_pods) continue;
     ksolve_handle* h = hs[i];
-    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom) && h->n_classes) {
-      // a DaemonSet problem of the spread engine's shape, or one with existing nodes (engine 9 / 10): alone through solve(), so that the batch runs the engine ksolve_solve would
+    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom || h->spread_complement) && h->n_classes) {
+      // a DaemonSet problem of the spread engine's shape, one with existing nodes (engine 9 / 10) or one over complement templates (18 / 19): alone through solve(), so that the batch runs the engine ksolve_solve would
       be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1;
     }
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {

@@ -32,6 +32,19 @@
 // groups on one pod, maxSkew beyond a counter's range, an unschedulable pod, NodePool limits that exclude a type — unless the handle
 // asked for limit stages, engines 13 / 14, fast_engine.h FastLimits — ...) makes it stop
 // with status 3 before it has written a result; the host runs the general engine on the same problem. There is no CPU path.
+//
+// Complement templates on the spread engine (engines 18 / 19, FastWork::ops on a spread handle; fast_engine.h "Complement templates").
+// A NodePool's NotIn / Exists / Gt / Lt fills the template's field of the key with the values E it admits and sets the guard bit above
+// it: "the claim still holds the pool's own requirement". Every consumer of the packed set here already reads it that way:
+//   * the domain choice (apply_choice) ANDs the candidates with the field — nodeDomains.Has(domain) for a complement set
+//     (topologygroup.go:274-291, :355-359, :432-436) — and writes a concrete set with the guard bit clear (zc.clear covers it);
+//   * Record (record_zonal) skips a claim whose guard bit is set: domains.Len() == 1 is false for a complement set however few
+//     values E has (topology.go:207). Anti-affinity never meets such a claim: a pod that a group of type 2 counts is also tested
+//     against it or its inverse group (the two share selector and key, topology.go:52-56), and that test has narrowed the key;
+//   * a limit stage copies the template's packed set, guard bits included (fast_engine.h limit_stage_id), and the requirement-set
+//     cache and the records read the stage's template through FastLimits::real (create_entry, ksolve_fast_records);
+//   * the existing-node path (topo_nodes.h) reads no template.
+// Pods stay positive (reason 4), and so does everything else the shape check asks.
 #pragma once
 #include "fast_engine.h"
 #include "run_order.h"
@@ -295,7 +308,7 @@ struct TopoEngine {
       KS_LDS TopoZg* const Z = &st->zg[ctz64(zs)];
       const uint32_t ow = (uint32_t)fast_uniform((int)(*(const KS_LDS uint32_t*)&Z->type));   // type | var << 8 | off << 16 | width << 24
       const int off = (int)((ow >> 16) & 0xFF), width = (int)(ow >> 24);
-      if ((m2 >> (off + width)) & 1) continue;   // the claim does not define the key: Exists, no values
+      if ((m2 >> (off + width)) & 1) continue;   // the claim does not define the key (Exists, no values) or still holds its NodePool's own NotIn / Exists / Gt / Lt (engines 18 / 19): not one domain, whatever the field holds
       const uint32_t f = (uint32_t)(m2 >> off) & ((1u << width) - 1);
       if ((ow & 0xFF) == 2) {
         // anti-affinity (and its inverse groups) blocks every domain the pod could land in (topology.go:203-206, :213-219)

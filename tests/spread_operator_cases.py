@@ -1,0 +1,313 @@
+"""Topology batches over NodePools whose requirements are not In sets — NotIn, Exists, DoesNotExist, Gt, Lt — for the spread engine's
+complement templates (csrc/topo_engine.h "Complement templates on the spread engine", csrc/fast_engine.h FastCold::setup; engines
+"auto-operators-spread" / "spread-operators"; tests/test_spread_engine_operators.py on the emulation,
+tests/test_gpu_spread_operators.py on the device): known shapes, the seeded fuzz generator and the comparison helpers.
+
+What the reference does with such a pool under topology: the NodeClaim starts with the pool's requirement as it stands; a pod's
+domain choice reads it through nodeDomains.Has (topologygroup.go:274-291, :355-359, :432-436) and leaves a concrete In set; Record
+(topology.go:197-220) counts a claim for a spread or affinity group only once its set on the key is ONE concrete value — a
+complement set has Len() = MaxInt64 - len(values), however few dictionary values it still admits.
+
+Every problem here has an open NodePool of the lowest weight, so that the oracle leaves no pod unschedulable (reason 27 is the
+general engine's business)."""
+import copy
+import random
+
+import daemonset_cases as dc
+import operator_cases as oc
+import parity
+import spread_limit_cases as sl
+import spread_node_cases as sn
+import test_spread_engine as tse
+from karpenter_amd import fixtures as fx
+from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported
+
+solve, same, ZONES = tse.solve, sn.same, oc.ZONES
+claims_of, req_of = oc.claims_of, oc.req_of
+AUTO, ONLY = "auto-operators-spread", "spread-operators"
+WEB = {"app": "web"}
+
+
+def refusal(prob, engine, lib):
+    try:
+        solve(prob, engine, lib)
+    except Unsupported as e:
+        return str(e)
+    raise AssertionError(f"{engine} solved a problem it must refuse")
+
+
+def check_engine(oracle, lib, prob, reason, base="auto"):
+    """One problem five ways. The oracle's result, computed once, without pod errors. `base` ("auto"; "auto-nodes-spread" with
+    existing nodes) hands the problem to the general engine with `reason` — 3 for NotIn / Exists / DoesNotExist pools, 0 for Gt / Lt
+    pools (the host never offers them to the spread engine), 34 with existing nodes — and equals the oracle; "spread-limits" refuses:
+    what engines 0-17 do. "spread-operators" solves it on the spread engine — no fallback, reason 0 — and equals the oracle in
+    claims, instance-type lists, claim requirements (operator, values, bounds: parity.canon_req), pod assignment and the
+    reference-equivalent evaluation count; "auto-operators-spread" gives the same digest on the same engine."""
+    want = oracle.solve(prob)
+    assert not want["podErrors"], want["podErrors"]
+    plain = solve(prob, base, lib)
+    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", reason), plain["counters"]
+    same(plain, want, prob)
+    text = refusal(prob, "spread-limits", lib)
+    assert (f"spread engine declined the problem (reason {reason})" in text) if reason == 3 else ("spread engine requested for a problem outside its shape" in text), text
+    got = solve(prob, ONLY, lib)
+    assert got["counters"]["engine"] == "spread" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
+    digest = parity.results_digest(got)[0]   # (before same(): under DaemonSets it puts the instance-type lists into a canonical order)
+    same(got, want, prob)
+    auto = solve(prob, AUTO, lib)
+    assert auto["counters"]["engine"] == "spread" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
+    assert parity.results_digest(auto)[0] == digest
+    same(auto, want, prob)
+    return got, want
+
+
+def check_declined(oracle, lib, prob, reason):
+    """A problem the spread engine still hands back under engines 18 / 19: "spread-operators" refuses and names `reason`,
+    "auto-operators-spread" equals the oracle on the general engine with that reason."""
+    text = refusal(prob, ONLY, lib)
+    assert f"spread engine declined the problem (reason {reason})" in text, text
+    auto = solve(prob, AUTO, lib)
+    assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
+    same(auto, oracle.solve(prob), prob)
+    return auto
+
+
+def zone_of(claim):
+    """(operator, values) of the claim's zone requirement."""
+    op, vals = req_of(claim, fx.ZONE)
+    return op, tuple(vals)
+
+
+def pods_by_zone(res, uids):
+    """How many of the pods `uids` sit on claims narrowed to each single zone."""
+    out = {}
+    for c in res["newNodeClaims"]:
+        op, vals = zone_of(c)
+        n = len(uids & set(c["pods"]))
+        if n:
+            assert op == "In" and len(vals) == 1, (c["nodePool"], op, vals)
+            out[vals[0]] = out.get(vals[0], 0) + n
+    return out
+
+
+def spread_pods(n, cpu="1", labels=WEB, **kw):
+    return [fx.pod(requests={"cpu": cpu}, labels=labels, topology_spread=[fx.spread(fx.ZONE, labels, **kw)]) for _ in range(n)]
+
+
+# ---- 1: NotIn on the spread key: operator_cases.spread_problem() ------------------------------------------------------------------
+
+# ---- 2: counted but not narrowed, |E| = 1 -----------------------------------------------------------------------------------------
+
+def counted_problem(operator="NotIn"):
+    """Pool `only-3` (weight 10) admits test-zone-3 alone: written zone NotIn [test-zone-1, test-zone-2], or — `operator` "In" — zone
+    In [test-zone-3]. Three 7-cpu pods labelled app=web without constraints take a claim of it each (queue order is by size), then
+    six 1-cpu pods app=web spread over the zones (maxSkew 1) with app=web as their selector. Under NotIn the three claims hold a
+    complement set — one admitted value, but not a concrete one — and count for nothing: the six land 2 / 2 / 2. Under In the three
+    count in test-zone-3, and the six land 3 / 3 on zones 1 and 2."""
+    only = fx.req(fx.ZONE, "NotIn", "test-zone-1", "test-zone-2") if operator == "NotIn" else fx.req(fx.ZONE, "In", "test-zone-3")
+    pools = [fx.node_pool("only-3", weight=10, requirements=[only]), fx.node_pool("open")]
+    pods = [fx.pod(requests={"cpu": "7"}, labels=WEB) for _ in range(3)] + spread_pods(6)
+    return fx.problem(fx.fake_instance_types(8), pools, pods)
+
+
+def spread_uids(prob):
+    return {p["uid"] for p in prob["pods"] if p.get("topologySpreadConstraints")}
+
+
+# ---- 3: bounds ----------------------------------------------------------------------------------------------------------------------
+
+def bounds_problem():
+    """Pool `above` (weight 10): integer Gt 2 (the 1..8-cpu catalogue labels a type `integer` = its cpus), plus `open`; twelve 1-cpu
+    pods with a zonal spread, four 2-cpu pods without constraints."""
+    pools = [fx.node_pool("above", weight=10, requirements=[fx.req(fx.FAKE_INTEGER_LABEL, "Gt", 2)]), fx.node_pool("open")]
+    return fx.problem(fx.fake_instance_types(8), pools, spread_pods(12) + [fx.pod(requests={"cpu": "2"}) for _ in range(4)])
+
+
+def integer_req(claim):
+    return next((r for r in claim["requirements"] if r["key"] == fx.FAKE_INTEGER_LABEL), None)
+
+
+# ---- 4: two dictionary-key groups ---------------------------------------------------------------------------------------------------
+
+def two_keys_problem():
+    """Pool `both` (weight 10): capacity-type Exists and zone NotIn [test-zone-3], plus `open`; thirty pods with a zone spread
+    (maxSkew 3) and a capacity-type spread (maxSkew 4) — kind 12 of test_spread_engine.mix: loose enough to be satisfiable together —
+    and six pods without constraints."""
+    pools = [fx.node_pool("both", weight=10, requirements=[fx.req(fx.CAPACITY_TYPE, "Exists"), fx.req(fx.ZONE, "NotIn", "test-zone-3")]), fx.node_pool("open")]
+    pods = [fx.pod(requests={"cpu": "500m"}, labels=WEB, topology_spread=[fx.spread(fx.ZONE, WEB, max_skew=3), fx.spread(fx.CAPACITY_TYPE, WEB, max_skew=4)]) for _ in range(30)]
+    return fx.problem(fx.fake_instance_types(12), pools, pods + [fx.pod(requests={"cpu": "1"}) for _ in range(6)])
+
+
+# ---- 5: zonal anti-affinity with its inverse group, zonal affinity ----------------------------------------------------------------
+
+def affinity_problem():
+    """Kinds 2 and 10 of test_spread_engine.mix over oc.notin_zone_pool(): two pods with anti-affinity on the zone, labelled with its
+    selector and pinned to test-zone-2 / test-zone-3 (each blocks the zone for the other, through the group and its inverse group),
+    a pod the selector matches that owns nothing (the inverse group keeps it out of both: test-zone-1, the open pool), pods with
+    zonal self-affinity per label, and pods without constraints."""
+    lonely = {"zone-lonely": "x"}
+    pods = [fx.pod(requests={"cpu": "2"}, labels=dict(lonely, **{"my-label": "a"}), pod_anti_requirements=[fx.affinity_term(fx.ZONE, lonely)],
+                   node_selector={fx.ZONE: z}) for z in ZONES[1:]]
+    pods.append(fx.pod(requests={"cpu": "300m"}, labels=lonely))
+    for lab in ({"my-label": "a"}, {"my-label": "b"}):
+        pods += [fx.pod(requests={"cpu": "1500m"}, labels=lab, pod_requirements=[fx.affinity_term(fx.ZONE, lab)]) for _ in range(7)]
+    pods += [fx.pod(requests={"cpu": "700m"}, labels={"my-label": "c"}) for _ in range(5)]
+    return fx.problem(fx.fake_instance_types(8), [oc.notin_zone_pool(), fx.node_pool("open")], pods)
+
+
+# ---- 6: DoesNotExist on the spread key ----------------------------------------------------------------------------------------------
+
+def does_not_exist_problem():
+    """Pool `nowhere` (weight 10): zone DoesNotExist — every type of the catalogue carries a zone, so the pool has no type and no
+    claim —, plus `open`; a zonal spread and pods without constraints."""
+    pools = [fx.node_pool("nowhere", weight=10, requirements=[fx.req(fx.ZONE, "DoesNotExist")]), fx.node_pool("open")]
+    return fx.problem(fx.fake_instance_types(8), pools, spread_pods(9) + [fx.pod(requests={"cpu": "2"}) for _ in range(3)])
+
+
+# ---- 7: limit stages ------------------------------------------------------------------------------------------------------------------
+
+ADDED = [fx.req(fx.ZONE, "NotIn", "test-zone-9"), fx.req(fx.FAKE_INTEGER_LABEL, "Gt", 0)]
+
+
+def with_complements(prob):
+    """A copy of `prob` with zone NotIn [test-zone-9] and integer Gt 0 added to every NodePool: requirements that exclude nothing the
+    problem has, so the packing is the unmodified problem's, on complement templates."""
+    p = copy.deepcopy(prob)
+    for pool in p["nodePools"]:
+        pool["requirements"] = list(pool["requirements"]) + copy.deepcopy(ADDED)
+    return p
+
+
+def limit_mix_problem():
+    return with_complements(sl.mix_problem(*sl.MIX[0][:2]))
+
+
+def limit_chain_problem():
+    return with_complements(sl.zonal_chain_problem())
+
+
+def limit_notin_problem():
+    """oc.limit_problem() under topology: oc.notin_zone_pool() with limits.cpu = 36 — every claim of ten 3-cpu pods without
+    constraints lists the 8-cpu type, so the fifth claim opens under the list narrowed to at most 4 cpu, a limit stage —, then
+    twelve 1-cpu pods with a zonal spread. A stage claim that no spread pod joined still prints NotIn [test-zone-1]."""
+    pods = [fx.pod(requests={"cpu": "3"}) for _ in range(10)] + spread_pods(12)
+    return fx.problem(fx.fake_instance_types(8), [oc.notin_zone_pool(limits={"cpu": "36"}), fx.node_pool("open")], pods)
+
+
+def complement_kinds(claim):
+    """The claim's requirements that are still complement sets: {(key, operator, gte, lte)}."""
+    return {(r["key"], r["operator"], r["gte"], r["lte"]) for r in claim["requirements"] if r["complement"]}
+
+
+# ---- 8: existing nodes --------------------------------------------------------------------------------------------------------------
+
+def nodes_mix_problem():
+    return with_complements(sn.mix_problem(sn.MIX[0][0], sn.MIX[0][1]))
+
+
+def nodes_limit_problem():
+    return with_complements(sl.mix_nodes_problem())
+
+
+# ---- 9: DaemonSet overhead ----------------------------------------------------------------------------------------------------------
+
+def daemonset_problem():
+    prob = oc.spread_problem()
+    prob["daemonSetPods"] = dc.random_daemonsets(random.Random(32000), ZONES)
+    return prob
+
+
+# ---- 10: still outside the shape ----------------------------------------------------------------------------------------------------
+
+def pod_notin_problem():
+    prob = oc.spread_problem()
+    prob["pods"].append(fx.pod(requests={"cpu": "1"}, node_requirements=[fx.req(fx.FAKE_EXOTIC_LABEL, "NotIn", "optional")]))
+    return prob
+
+
+def pod_gt_problem():
+    prob = oc.spread_problem()
+    prob["pods"].append(fx.pod(requests={"cpu": "1"}, node_requirements=[fx.req(fx.FAKE_INTEGER_LABEL, "Gt", 4)]))
+    return prob
+
+
+def min_values_problem():
+    prob = oc.spread_problem()
+    prob["nodePools"][0]["requirements"].append(fx.req(fx.INSTANCE_TYPE, "Exists", min_values=2))
+    return prob
+
+
+def node_filter_problem():
+    prob = oc.spread_problem()
+    prob["pods"].append(fx.pod(requests={"cpu": "1"}, labels=WEB, node_selector={fx.CAPACITY_TYPE: "on-demand"}, topology_spread=[fx.spread(fx.ZONE, WEB)]))
+    return prob
+
+
+# ---- 12, 13: repeated solves, batches -----------------------------------------------------------------------------------------------
+
+def batch_cells(lib, probs, engine):
+    """(engine, reason, digest) of every problem as a member of ONE SolveBatch under `engine`."""
+    scheds = [NewScheduler(dict(p, options=dict(p.get("options", {}), engine=engine)), solver_lib=lib) for p in probs]
+    try:
+        return [(r["counters"]["engine"], r["counters"]["engineFallbackReason"], parity.results_digest(r)[0]) for r in SolveBatch(scheds)]
+    finally:
+        for s in scheds:
+            s.close()
+
+
+def lone_cell(lib, prob, engine):
+    r = solve(prob, engine, lib)
+    return r["counters"]["engine"], r["counters"]["engineFallbackReason"], parity.results_digest(r)[0]
+
+
+# ---- 15: seeded fuzz ----------------------------------------------------------------------------------------------------------------
+
+FUZZ_KINDS = (0, 0, 1, 1, 2, 3, 4, 5, 6, 7, 9, 10, 12, 12)
+
+
+def fuzz_problem(seed):
+    """One to three weighted NodePools `pool-i` (weight 50 - 10 i, no taints), each with one or two draws of
+    operator_cases._pool_requirement (a repeated key is dropped), then `open`; 30 to 119 pods of test_spread_engine.mix in the kinds
+    that rarely leave a pod unschedulable; the 1..12-cpu catalogue."""
+    rng = random.Random(88000 + seed)
+    pools = []
+    for i in range(rng.randint(1, 3)):
+        reqs, seen = [], set()
+        for _ in range(rng.randint(1, 2)):
+            r = oc._pool_requirement(rng)
+            if r["key"] not in seen:
+                seen.add(r["key"]); reqs.append(r)
+        pools.append(fx.node_pool(f"pool-{i}", weight=50 - 10 * i, requirements=reqs))
+    pools.append(fx.node_pool("open"))
+    pods = tse.mix(rng, rng.randrange(30, 120), kinds=FUZZ_KINDS)
+    return fx.problem(fx.fake_instance_types(12), pools, pods)
+
+
+def has_non_in_pool(prob):
+    return any(r["operator"] != "In" for p in prob["nodePools"] for r in p["requirements"])
+
+
+FUZZ_SEEDS = list(range(120))
+GPU_FUZZ_SEEDS = list(range(0, 120, 4))
+
+
+def run_fuzz(oracle, lib, seeds):
+    """Every seed equals the oracle under "auto-operators-spread"; a seed the spread engine did not solve reports reason 27 (a pod the
+    first pass cannot place: the general engine's business) and nothing else. Returns (seeds that ended on the spread engine with
+    reason 0, how many of those have a NodePool with a requirement that is not an In set, the seeds of the rest)."""
+    on_spread, non_in, rest = 0, 0, []
+    for seed in seeds:
+        prob = fuzz_problem(seed)
+        got = solve(prob, AUTO, lib)
+        same(got, oracle.solve(prob), prob)
+        c = got["counters"]
+        if c["engine"] == "spread":
+            assert c["engineFallbackReason"] == 0, (seed, c)
+            on_spread += 1
+            non_in += has_non_in_pool(prob)
+        else:
+            assert (c["engine"], c["engineFallbackReason"]) == ("general", 27), (seed, c)
+            rest.append(seed)
+    print(f"auto-operators-spread kept {on_spread} of {len(seeds)} seeds on the spread engine, {non_in} of them over a NodePool with a requirement "
+          f"that is not an In set; reason 27 for seeds {rest}")
+    return on_spread, non_in, rest
