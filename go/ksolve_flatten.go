@@ -976,6 +976,10 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // KsolveEngineAutoOperatorsSpread = "auto-operators-spread" (18): KsolveEngineAutoOperators, and the spread engine takes such
 // NodePools too — topology batches over them no longer go to the general engine. KsolveEngineSpreadOperators (19) is the spread
 // engine alone with that acceptance and refuses instead of falling back (tests). 17 has no name.
+// KsolveEngineAutoUnschedulable = "auto-unschedulable" (20): KsolveEngineAutoOperatorsSpread, and the cursor engine keeps a pod
+// that nothing takes — Results.PodErrors, ordinary input — instead of handing the whole batch to the general engine (reason 27):
+// the setting for batches that may run into their NodePools' limits. KsolveEngineCursorUnschedulable (21) is the cursor engine
+// alone with that switch and refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -991,6 +995,9 @@ const (
 
 	KsolveEngineAutoOperatorsSpread uint32 = 18
 	KsolveEngineSpreadOperators     uint32 = 19
+
+	KsolveEngineAutoUnschedulable   uint32 = 20
+	KsolveEngineCursorUnschedulable uint32 = 21
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

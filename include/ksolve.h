@@ -275,7 +275,8 @@ typedef struct {
                                     * engine declined the problem (reason N)" or "... requested for a problem outside its shape".
                                     * Switches: nodes / s-nodes = the cursor / spread engine may take a problem with existing nodes;
                                     * limits / s-limits = the cursor / spread engine goes on when a NodePool limit binds; operators = the
-                                    * cursor engine takes NodePools whose requirements are not In sets; s-operators = the spread engine does.
+                                    * cursor engine takes NodePools whose requirements are not In sets; s-operators = the spread engine does;
+                                    * unschedulable = the cursor engine keeps pods that can go nowhere and reports their errors.
                                     *
                                     *    value  name                 engines that may run       a decline     switches
                                     *      0    auto                 cursor, spread, general    falls back    -
@@ -298,7 +299,9 @@ typedef struct {
                                     *     17    (no name)            cursor                     refuses       - (as 2, except that the library does not choose the first memory plan by the problem's size)
                                     *     18    auto-operators-spread cursor, spread, general   falls back    nodes, s-nodes, limits, s-limits, operators, s-operators
                                     *     19    spread-operators     spread                     refuses       s-nodes, s-limits, s-operators
-                                    *   above 19: no name; as 17.
+                                    *     20    auto-unschedulable   cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable
+                                    *     21    cursor-unschedulable cursor                     refuses       nodes, limits, operators, unschedulable
+                                    *   above 21: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
@@ -336,6 +339,13 @@ typedef struct {
                                     * no spread or affinity group until a pod's domain choice has narrowed it), with existing nodes and limit
                                     * stages — instead of reason 3, or of never reaching the spread engine (Gt / Lt: reason 0). Pods with such
                                     * operators (4), pod-side bounds and minValues (1) still go to the general engine.
+                                    * unschedulable: a pod that no existing node, no NodeClaim and no NodePool takes no longer makes the cursor
+                                    * engine hand the batch back (reason 27): the pod is set aside with the error the reference reports for it —
+                                    * the first NodePool's, in NodePool order, with the instance-type filter's flags in pod_error_diag —, the
+                                    * reference's second round over such pods is replayed behind the last queue entry (queue pops, evaluation
+                                    * count, the error of a pod whose NodePools have meanwhile run into a limit), and the Results carry
+                                    * pod_assignment -1, pod_error and pod_error_diag (csrc/fast_engine.h, "Unschedulable pods"). The spread
+                                    * engine still declines with 27, and so does a batch with preferences (relaxation rows).
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -28,7 +28,7 @@
 // The hot loop touches LDS and registers only (claim state, order, requirement-set cache, class slots); HBM sees the
 // queue (64 pods per fetch) and the two result stores per pod.
 //
-// Everything this engine does not handle (an unschedulable pod, NodePool limits that actually exclude a type — unless the handle
+// Everything this engine does not handle (an unschedulable pod — unless the handle asked to keep them, "Unschedulable pods" below —, NodePool limits that actually exclude a type — unless the handle
 // asked for limit stages, FastLimits below —, more claims
 // than the LDS plan holds, non-positive operators — on pods; on NodePools unless the handle asked for complement templates, setup()
 // below —, ...) makes it stop with status 3 before it has written a result;
@@ -141,6 +141,17 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   FastPlan plan;
   int enabled;
   int ops;                // engines 15 / 16 (a cursor handle), 18 / 19 (a spread handle): setup() accepts NodePool requirements that are not In sets (NotIn, Exists, DoesNotExist, Gt, Lt) — "Complement templates" below
+  // Engines 20 / 21 (a cursor handle only): a pod no claim and no template takes is SET ASIDE with its error instead of stopping the
+  // engine — "Unschedulable pods" below. The arrays are allocated for such handles only, [n_pods] each, indexed by the order in which
+  // the pods were set aside (the order of the reference's pushes, queue.go:63-66); us_n is reset by setup().
+  int unsched;
+  uint32_t* us_n;         // [1] pods set aside
+  uint32_t* us_entry;     // the pod's entry in the queue the loop reads
+  uint32_t* us_last;      // lastLen (queue.go:63-66): the reference's queue length right after it pushed the pod back
+  uint8_t* us_err;        // the error of the pod's last attempt (engine.h E_*) and its diagnostic bits (filter_instance_types)
+  uint8_t* us_diag;
+  uint64_t* us_cls;       // [n_pods >= n_classes] by class: the verdict of the class's last failed template walk (FastCold::new_claim), reset by setup()
+  uint32_t* pod_qpos;     // [n_pods], behind the existing-node stage only: a pod's position in the FULL queue (ksolve_fast_requeue)
 };
 
 // whole-record moves between LDS and registers (a struct behind an address-space-3 pointer has no implicit copy)
@@ -490,8 +501,18 @@ struct FastHot {
   uint32_t bcls[64], oclaim[64], ocnt[64], nxt_cls[64];
 };
 
-template <class W, int GS, int R>
-struct FastCold {
+// US: the engine keeps unschedulable pods (engines 20 / 21, "Unschedulable pods" below) — a COMPILE-TIME switch on the device, so
+// that the kernels of every other setting are compiled without a line of it (their driver, FastEngine::solve, is inlined into the
+// kernel function: one more call there cost the headline 1 %); the kernels of 20 / 21 are instantiations of their own
+// (ksolve_pack_fast_unsched.hip). The host emulation builds it into its one engine per plan and FastWork::unsched decides at run time.
+constexpr bool kFastKeepBuiltIn = !KS_DEVICE;
+struct FastKeepState {
+  int us_err_ = 0, us_diag_ = 0;   // error and flags of the template walk that just failed (new_claim's result 2)
+  uint32_t us_epoch = 1;           // bumped whenever a pool's remaining resources change (0: no verdict)
+};
+struct FastNoKeepState {};
+template <class W, int GS, int R, bool US = kFastKeepBuiltIn>
+struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
   const ProblemView* Pk;
   const Workspace* Sk;
   const FastWork* Fk;
@@ -529,6 +550,46 @@ struct FastCold {
     aslot = (KS_LDS FastSlot*)(lds + pl.off_slot);
   }
 
+  // compatible(it, reqs) (nodeclaim.go:620-622) of requirement set vm for the keys pods select on, word w of the type list `tits` of
+  // vm's template or limit stage (the template's other keys are in t_its already)
+  KS_DEV uint64_t compat_word(uint64_t vm, const uint64_t* tits, int w) const {
+    const ProblemView& Pv = *Pk;
+    KS_LDS FastMisc& Mm = *Mp;
+    const int iw = Pv.it_words;
+    uint64_t acc = tits[w];
+    for (int j = 0; j < nv; ++j) {
+      const int k = Mm.vkey[j];
+      if (!((Pv.it_keys >> k) & 1u)) continue;
+      if ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1) continue;   // guard bit set: the requirement set does not define the key, or holds the template's own complement set — in t_its already
+      uint64_t field = (vm >> Mm.voff[j]) & (Mm.fmask[j] >> Mm.voff[j]);
+      uint64_t r = Pv.key_undef[(size_t)k * iw + w];
+      if (!field) r |= Pv.key_neg[(size_t)k * iw + w];   // an empty set is the template's DoesNotExist (a pod's In never leaves one): the escape of requirements.go:260-265
+      const size_t base = (size_t)Mm.vword[j] * 64;
+      while (field) { const int b = ctz64(field); field &= field - 1; r |= Pv.kv_has[(base + b) * iw + w]; }
+      acc &= r;
+    }
+    return acc;
+  }
+  // the zone x capacity-type cells a compatible available offering may sit in (nodeclaim.go:624-638, types.go:553-570) for requirement
+  // set vm of id t (template tr)
+  KS_DEV uint64_t offering_cells(uint64_t vm, int t, int tr) const {
+    const ProblemView& P = *Pk;
+    const Dict& d = P.dict;
+    uint32_t zones = (1u << P.n_zones) - 1, cts = (1u << P.n_cts) - 1;
+    const ReqRef tq = P.tmpl_reqs.at(d, tr);   // (the values the template's requirement Has(): a NotIn zone is not a zone set)
+    const uint32_t tdef = Mp->tdef[t];
+    if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)req_values_word(d, tq, d.key_zone, d.key_word_off[d.key_zone]);
+    if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)req_values_word(d, tq, d.key_ct, d.key_word_off[d.key_ct]);
+    for (int j = 0; j < nv; ++j) {
+      const uint32_t field = (uint32_t)((vm >> Mp->voff[j]) & (Mp->fmask[j] >> Mp->voff[j]));
+      if (Mp->vkey[j] == d.key_zone) zones &= field;
+      if (Mp->vkey[j] == d.key_ct) cts &= field;
+    }
+    uint64_t cells = 0;
+    for (uint32_t z = zones; z; z &= z - 1) cells |= (uint64_t)cts << (__builtin_ctz(z) * 4);
+    return cells;
+  }
+
   // F(requirement set vm) and its Pareto-maximal allocatable vectors -> a new cache entry
   KS_COLD int create_entry(uint64_t vm) {
     vm = W::uniform(vm);
@@ -536,43 +597,11 @@ struct FastCold {
     const int t = (int)(vm >> 56);
     const int tr = F.lim ? (int)F.lim->real[t] : t;   // t may be a limit stage (FastLimits): its row of t_its, the template's requirements and overhead
     const int iw = P.it_words, n_its = P.n_its, nr = P.n_res;
-    const Dict& d = P.dict;
     const ProblemView& Pv = P;
-    KS_LDS FastMisc& Mm = *Mp;
     const uint64_t* tits = S.t_its + (size_t)t * iw;
     KS_LDS uint64_t* its = Mp->its;
-    const int nvv = nv;
-    // compatible(it, reqs) (nodeclaim.go:620-622) for the keys pods select on; the template's other keys are in t_its already
-    W::for_n(iw, [&](int w) {
-      uint64_t acc = tits[w];
-      for (int j = 0; j < nvv; ++j) {
-        const int k = Mm.vkey[j];
-        if (!((Pv.it_keys >> k) & 1u)) continue;
-        if ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1) continue;   // guard bit set: the requirement set does not define the key, or holds the template's own complement set — in t_its already
-        uint64_t field = (vm >> Mm.voff[j]) & (Mm.fmask[j] >> Mm.voff[j]);
-        uint64_t r = Pv.key_undef[(size_t)k * iw + w];
-        if (!field) r |= Pv.key_neg[(size_t)k * iw + w];   // an empty set is the template's DoesNotExist (a pod's In never leaves one): the escape of requirements.go:260-265
-        const size_t base = (size_t)Mm.vword[j] * 64;
-        while (field) { const int b = ctz64(field); field &= field - 1; r |= Pv.kv_has[(base + b) * iw + w]; }
-        acc &= r;
-      }
-      its[w] = acc;
-    });
-    // a compatible available offering (nodeclaim.go:624-638, types.go:553-570)
-    uint32_t zones = (1u << P.n_zones) - 1, cts = (1u << P.n_cts) - 1;
-    {
-      const ReqRef tq = P.tmpl_reqs.at(d, tr);   // (the values the template's requirement Has(): a NotIn zone is not a zone set)
-      const uint32_t tdef = Mp->tdef[t];
-      if (d.key_zone >= 0 && ((tdef >> d.key_zone) & 1u)) zones &= (uint32_t)req_values_word(d, tq, d.key_zone, d.key_word_off[d.key_zone]);
-      if (d.key_ct >= 0 && ((tdef >> d.key_ct) & 1u)) cts &= (uint32_t)req_values_word(d, tq, d.key_ct, d.key_word_off[d.key_ct]);
-      for (int j = 0; j < nv; ++j) {
-        const uint32_t field = (uint32_t)((vm >> Mp->voff[j]) & (Mp->fmask[j] >> Mp->voff[j]));
-        if (Mp->vkey[j] == d.key_zone) zones &= field;
-        if (Mp->vkey[j] == d.key_ct) cts &= field;
-      }
-    }
-    uint64_t cells = 0;
-    for (uint32_t z = zones; z; z &= z - 1) cells |= (uint64_t)cts << (__builtin_ctz(z) * 4);
+    W::for_n(iw, [&](int w) { its[w] = compat_word(vm, tits, w); });
+    const uint64_t cells = offering_cells(vm, t, tr);
     for (int j = 0; j < iw; ++j) {
       const uint64_t in = its[j];
       const uint64_t okm = in ? W::ballot([&](int l) { const int it = j * 64 + l; return it < n_its && ((in >> l) & 1) && (Pv.it_off_avail[it] & cells) != 0; }) : 0ull;
@@ -654,6 +683,11 @@ struct FastCold {
       W::for_n(32, [&](int i) { lim->real[i] = (uint8_t)i; lim->cur[i] = (uint8_t)i; });
       if (W::leader()) { lim->n_ids = (uint32_t)T; lim->first_claim = 0xFFFFFFFFu; }
       W::sync();
+    }
+    if constexpr (US) if (F.unsched) {   // no pod set aside yet, no verdict cached ("Unschedulable pods" below)
+      uint64_t* const uc = F.us_cls;
+      W::for_n(nc, [&](int c) { uc[c] = 0; });
+      W::store(F.us_n, 0u); W::sync();
     }
     const bool ops = F.ops != 0;   // complement templates (below): engines 15 / 16 on the cursor engine, 18 / 19 on the spread engine — the host sets the switch per engine
     if (!(topo ? P.plain_topo : (P.plain || (F.nodes && P.plain_nodes) || (ops && P.plain_ops))) || P.n_rows != P.n_pods || nr > 4 || T > 32 || iw > kMaxItWords) return DECLINE_NOT_PLAIN;
@@ -1081,14 +1115,89 @@ struct FastCold {
     return s;
   }
 
-  // addToNewNodeClaim (scheduler.go:695-790) for a pod no in-flight claim accepted: 1 = claim n created (appended to the
-  // order with one pod; its acceptance words computed), 0 = the engine must stop (bail_code; DECLINE_KERNEL_CAPACITY = capacity).
-  KS_COLD int new_claim(int slot, int bi, int n) {
-    slot = (int)W::uniform((uint64_t)(uint32_t)slot); bi = (int)W::uniform((uint64_t)(uint32_t)bi); n = (int)W::uniform((uint64_t)(uint32_t)n);
+  // Unschedulable pods (engines 20 / 21, FastWork::unsched). A pod that no existing node, no in-flight claim and no template takes
+  // is ordinary input: the reference records its error, pushes it to the back of the queue with lastLen = the queue's length after
+  // the push (queue.go:63-66), pops it again behind everything that was in front of it, and stops at the first pop whose lastLen
+  // equals the queue's length (queue.go:52-56). For this engine's shape a pod that failed stays failed: CanAdd failures are
+  // permanent (fact 1 above), the nodes' and the NodePools' remaining resources only shrink, and a claim opened later from template t
+  // under a type list L' accepts a class only if t under a list L that contains L' would have accepted the class alone — which the
+  // failed attempt tested. So the pod leaves the loop for good: it is SET ASIDE (set_aside below) with the error of its attempt, its
+  // queue entry keeps "not placed", and the loop goes on with the next pod. What the reference's second round still changes — a
+  // queue pop and n_nodes + n_claims + (templates attempted) evaluations per retried pod, a hostname number per template attempted,
+  // the sort of a failing attempt, and the error of a pod whose templates have meanwhile run into a limit — is replayed after the
+  // last queue entry by retry_unschedulable, pop by pop, over the pods in the order they were set aside. A retry evaluates the
+  // templates again — by a walk when a pool's remaining resources have changed since the class's last failed walk, by that walk's
+  // kept verdict otherwise (below) — and a walk that finds a template which WOULD take the pod stops the engine with
+  // DECLINE_UNSCHEDULABLE_POD as before this switch, and the general engine answers. So the net stands wherever the limits moved,
+  // the one way a verdict can change; under unchanged limits the verdict is the same walk's, not the permanence argument's.
+  //
+  // The error (engine.h add_to_new_claim) is that of the FIRST template in template order: E_LIMITS for one skipped before NewNodeClaim,
+  // else CanAdd's first failing check — taints, Requirements.Compatible, the instance-type filter with InstanceTypeFilterError's flags;
+  // E_NO_TEMPLATES when no template survived NewScheduler's prefilter.
+  //
+  // The walk's verdict is a function of the pod's class and of the NodePools' remaining resources alone (the claims do not enter), and
+  // those change only when a claim of a limited pool is created (subtract_max). So the verdict of a failed walk is kept per class
+  // (FastWork::us_cls: error | flags << 8 | templates attempted << 16 | us_epoch << 32) and stands while us_epoch does: the next pod
+  // of the class — thousands once the pools are used up — and the retries cost a load instead of a walk over the type lists. A
+  // verdict never outlives a change of the limits, so an error that turns into Limits later is seen.
+  // (us_err_ / us_diag_ / us_epoch: FastKeepState above, a base of this class under US only.)
+
+  // InstanceTypeFilterError's flags (nodeclaim.go:585-592; engine.h filter_instance_types with want_diag) of a NEW claim with requirement
+  // set vm — a template or limit-stage id and the fields — and requests `size`: requirementsMet 1, fits 2, hasOffering 4, and the pairs
+  // requirements + offering without fit 16, fit + offering without requirements 32. One pass over the id's type list.
+  KS_COLD int filter_diag(uint64_t vm, const int32_t* size) {
+    vm = W::uniform(vm);
     const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
-    const FastSlot cs = lds_get(&aslot[slot]);
+    const int t = (int)(vm >> 56);
+    const int tr = F.lim ? (int)F.lim->real[t] : t;
+    const int iw = P.it_words, n_its = P.n_its, nr = P.n_res;
+    const ProblemView& Pv = P;
+    const uint64_t* tits = S.t_its + (size_t)t * iw;
+    const uint64_t cells = offering_cells(vm, t, tr);
+    const int64_t* eff = eff_alloc(P, tr);   // allocatable less the template's daemon overhead, as in create_entry
+    const int32_t z0 = size[0], z1 = size[1], z2 = size[2], z3 = size[3];
+    bool d_req = false, d_fit = false, d_off = false, d_ro = false, d_fo = false;
+    for (int w = 0; w < iw; ++w) {
+      const uint64_t in = tits[w];
+      if (!in) continue;
+      const uint64_t cm = compat_word(vm, tits, w);
+      const uint64_t off = in & W::ballot([&](int l) { const int it = w * 64 + l; return it < n_its && (Pv.it_off_avail[it] & cells) != 0; });
+      const uint64_t itfits = off & W::ballot([&](int l) {
+        const int it = w * 64 + l;
+        if (it >= n_its) return false;
+        bool f = (int64_t)z0 <= eff[it];
+        if (nr > 1) f = f && (int64_t)z1 <= eff[(size_t)n_its + it];
+        if (nr > 2) f = f && (int64_t)z2 <= eff[(size_t)2 * n_its + it];
+        if (nr > 3) f = f && (int64_t)z3 <= eff[(size_t)3 * n_its + it];
+        return f;
+      });   // (fits() reports itFits only with a compatible offering, nodeclaim.go:624-638)
+      d_req |= cm != 0; d_fit |= itfits != 0; d_off |= off != 0; d_ro |= (cm & off & ~itfits) != 0; d_fo |= (itfits & ~cm) != 0;
+    }
+    return (d_req ? 1 : 0) | (d_fit ? 2 : 0) | (d_off ? 4 : 0) | (d_ro ? 16 : 0) | (d_fo ? 32 : 0);
+  }
+
+  // addToNewNodeClaim (scheduler.go:695-790) for a pod of class k (record cs) that no in-flight claim accepted, n claims in flight:
+  // 1 = claim n created (appended to the order with one pod; its acceptance words computed), 0 = the engine must stop (bail_code;
+  // DECLINE_KERNEL_CAPACITY = capacity), 2 (FastWork::unsched only) = no template takes the pod: us_err_ / us_diag_.
+  // retry: the pod was set aside before and no template may take it (retry_unschedulable).
+  KS_DEV int new_claim(const FastSlot& cs, int k, int n, bool retry) {   // (inlined into its two callers: without US the event below is the one function it was)
+    k = (int)W::uniform((uint64_t)(uint32_t)k); n = (int)W::uniform((uint64_t)(uint32_t)n);
+    const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
     const int T = P.n_templates, cap = F.plan.cap;
+    const bool keep = US && F.unsched != 0;
+    if constexpr (US) if (keep && !active_templates) { this->us_err_ = E_NO_TEMPLATES; this->us_diag_ = 0; return 2; }   // scheduler.go:604-606: no template walk
+    int first_err = 0, first_diag = 0;
     n_ref_extra += (unsigned long long)n;
+    if constexpr (US) if (keep) {
+      const uint64_t v = W::uniform(F.us_cls[k]);
+      if ((uint32_t)(v >> 32) == this->us_epoch) {   // the class's last walk failed under these very limits: its verdict, and what the walk would count
+        const uint32_t tried = (uint32_t)(v >> 16) & 0xFFFFu;
+        host_seq += tried; n_ref_extra += (unsigned long long)tried;
+        this->us_err_ = (int)(v & 0xFFu); this->us_diag_ = (int)((v >> 8) & 0xFFu);
+        return 2;
+      }
+    }
+    const uint32_t seq0 = host_seq;
     for (int t = 0; t < T; ++t) {
       if (!((active_templates >> t) & 1u)) continue;
       const uint32_t lm = P.tmpl_limit_mask[t];
@@ -1096,20 +1205,27 @@ struct FastCold {
       if (lm) {
         if (F.lim) {
           ts = (int)W::uniform((uint64_t)(uint32_t)limit_stage(t, lm));
-          if (ts == -1) continue;   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
+          if (ts == -1) { if (!first_err) first_err = E_LIMITS; continue; }   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
           if (ts < 0) { bail_code = DECLINE_LIMIT_STAGES; return 0; }
         } else { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail_code = why; return 0; } }
       }
       host_seq++;
       n_ref_extra++;
-      if (!((cs.tmplok >> t) & 1u)) continue;
+      if (!((cs.tmplok >> t) & 1u)) {   // Taints.ToleratesPod comes first (nodeclaim.go:126), then Compatible
+        if (keep && !first_err) first_err = (P.tmpl_taints[t] & ~P.cls_tolerates[k]) ? E_TAINTS : E_INCOMPATIBLE;
+        continue;
+      }
       const uint64_t m = Mp->tvmask[ts] & cs.cvmask;
-      if (!fast_fields_ok(m, cs.dmask)) continue;
+      if (!fast_fields_ok(m, cs.dmask)) { if (!first_err) first_err = E_INCOMPATIBLE; continue; }
       FastEnt e;
       int eh = fast_lookup(ent, m, e);
       if (eh < 0) { eh = create_entry(m); if (eh < 0) { bail_code = DECLINE_CACHE_FULL_NEW_CLAIM; return 0; } e = lds_get(&ent[eh]); }
       const int32_t zero[4] = {0, 0, 0, 0};
-      if (!fast_fits(pool, e, zero, cs.size)) continue;
+      if (!fast_fits(pool, e, zero, cs.size)) {
+        if constexpr (US) if (keep && !first_err) { first_err = E_INSTANCE_TYPES; first_diag = (int)W::uniform((uint64_t)(uint32_t)filter_diag(m, cs.size)); }
+        continue;
+      }
+      if (retry) { bail_code = DECLINE_UNSCHEDULABLE_POD; return 0; }   // the safety net: a pod that failed would be placed now
       if (n_claims >= S.max_claims) { bail_code = DECLINE_KERNEL_CAPACITY; return 0; }   // capacity: reported as such
       if (n_claims >= cap) { bail_code = DECLINE_CLAIM_SLOTS; return 0; }
       const int c = n_claims++;
@@ -1129,9 +1245,93 @@ struct FastCold {
       }
       W::sync();
       if (lm) subtract_max<W>(P, S, F, t, lm, eh, cs.size);
+      if constexpr (US) if (lm) this->us_epoch++;   // (the limits moved: no cached verdict stands)
       return 1;
     }
-    bail_code = DECLINE_UNSCHEDULABLE_POD;   // error codes and diagnostics come from the general engine
+    if (!keep) { bail_code = DECLINE_UNSCHEDULABLE_POD; return 0; }   // error codes and diagnostics come from the general engine
+    if constexpr (US) {
+      this->us_err_ = first_err ? first_err : E_NO_TEMPLATES; this->us_diag_ = first_diag;
+      if (W::leader()) F.us_cls[k] = (uint64_t)(uint32_t)this->us_err_ | ((uint64_t)(uint32_t)this->us_diag_ << 8) | ((uint64_t)(host_seq - seq0) << 16) | ((uint64_t)this->us_epoch << 32);
+      W::sync();
+    }
+    return 2;
+  }
+
+  // The pod of queue entry e goes to the back of the reference's queue (queue.go:63-66) with the error of the attempt that just
+  // failed. lastLen = the entries of the FULL queue still in front of it — behind the existing-node stage the loop's queue is the
+  // compacted one, and the pod's position in the full one comes from ksolve_fast_requeue — plus the pods set aside so far, this one
+  // included.
+  // false: the list is full — every pod is set aside once at most, so it never is —: the engine stops as it did before the switch.
+  KS_COLD bool set_aside(int e) {
+    e = (int)W::uniform((uint64_t)(uint32_t)e);
+    const ProblemView& P = *Pk; const FastWork& F = *Fk;
+    const uint32_t i = (uint32_t)W::uniform((uint64_t)*F.us_n);
+    if (i >= (uint32_t)P.n_pods) { bail_code = DECLINE_UNSCHEDULABLE_POD; return false; }
+    const uint32_t pos = F.nodes ? F.pod_qpos[F.nd_pod[e]] : (uint32_t)e;
+    if (W::leader()) {
+      F.us_entry[i] = (uint32_t)e; F.us_last[i] = (uint32_t)P.n_pods - pos - 1u + i + 1u;
+      F.us_err[i] = (uint8_t)this->us_err_; F.us_diag[i] = (uint8_t)this->us_diag_;
+      *F.us_n = i + 1u;
+    }
+    W::sync();
+    return true;
+  }
+
+  // The driver's FEV_NEWCLAIM event for the pod of entry bi of the loop's block, its class in `slot`: new_claim's result; with 2 the
+  // pod is set aside and the block's entry reads "not placed" — the driver goes on behind it as it does behind a created claim
+  // (the step is counted; no claim waits for its place in the order).
+  KS_COLD int new_claim(int slot, int bi, int n) {
+    slot = (int)W::uniform((uint64_t)(uint32_t)slot); bi = (int)W::uniform((uint64_t)(uint32_t)bi);
+    KS_LDS FastHot* const h = hs;
+    const FastSlot cs = lds_get(&aslot[slot]);
+    const int made = new_claim(cs, (int)(h->bcls[bi] & ~kFastLastBit), n, false);
+    if constexpr (!US) return made;
+    else {
+    if (made != 2) return made;
+    if (!set_aside((int)W::uniform((uint64_t)(uint32_t)h->base) + bi)) return 0;
+    if (W::leader()) { h->oclaim[bi] = 0xFFFFFFFFu; h->ocnt[bi] = 0; h->bi = bi + 1; }
+    W::sync();
+    return 2;
+    }
+  }
+
+  // The reference's pops behind the last queue entry: the pods set aside, in push order. None can be placed (above), so the queue
+  // keeps its length — the number of pods set aside — from here on, and the loop ends at the first pod whose lastLen equals it: the
+  // first of the run of failed pods at the queue's tail, or, when every pod was retried, the first pod again. A retried pod is a step
+  // like any other (step limit, cancel flag); its attempt evaluates every existing node and every in-flight claim, sorts (scheduler.go:598
+  // — the defect the last commit left), walks the templates under the limits as they stand NOW and keeps that error.
+  // Returns 3 when the engine must stop (bail_code), 0 otherwise; a step limit or a cancellation met here goes to the loop's status.
+  KS_COLD int retry_unschedulable() {
+    const ProblemView& P = *Pk; const Workspace& S = *Sk; const FastWork& F = *Fk;
+    KS_LDS FastHot* const h = hs;
+    if (!F.unsched || fast_uniform(h->status) != 0 || (F.nodes && F.nodes->limit_hit)) return 0;
+    const uint32_t nu = (uint32_t)W::uniform((uint64_t)*F.us_n);
+    const int n = (int)W::uniform((uint64_t)(uint32_t)h->n);
+    const long long ms = S.max_steps;
+    const long long before = F.nodes ? (long long)F.nodes->n_placed : 0;   // pops of the existing-node stage
+    int steps = (int)W::uniform((uint64_t)(uint32_t)h->steps), status = 0;
+    for (uint32_t i = 0; i < nu; ++i) {
+      if ((uint32_t)W::uniform((uint64_t)F.us_last[i]) == nu) break;                                   // queue.go:52-56
+      if (ms >= 0 && before + steps >= ms) { status = 2; break; }
+      if ((i & 63u) == 0 && S.cancel_flag) {
+        const int cv = fast_uniform((int)W::poll_flag(S.cancel_flag));
+        if (cv > 0 || (cv < 0 && before + steps >= -(long long)cv)) { status = 2; break; }
+      }
+      steps++;
+      n_ref_extra += (unsigned long long)(F.nodes ? P.n_nodes : 0);
+      if (active_templates && fast_uniform(h->pend_a) >= 0) {
+        if (fast_uniform(h->pend_new)) place_new_claim(n); else slow_sort(n, fast_uniform(h->pend_a), 0);
+        if (W::leader()) { h->pend_a = -1; h->pend_new = 0; }
+        W::sync();
+      }
+      const uint32_t e = (uint32_t)W::uniform((uint64_t)F.us_entry[i]);
+      const int k = (int)(W::uniform((uint64_t)F.q_class[e]) & ~kFastLastBit);
+      const FastSlot cs = F.cls[k];
+      if (new_claim(cs, k, n, true) != 2) return 3;
+      if (W::leader()) { F.us_err[i] = (uint8_t)this->us_err_; F.us_diag[i] = (uint8_t)this->us_diag_; F.us_last[i] = nu; }
+    }
+    if (W::leader()) { h->steps = steps; if (status) h->status = status; }
+    W::sync();
     return 0;
   }
 
@@ -2133,9 +2333,9 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
 }
 
 // The driver: runs the loop, handles its events through FastCold.
-template <class W, int GS = 0, int R = 1, bool HP = false>
+template <class W, int GS = 0, int R = 1, bool HP = false, bool US = kFastKeepBuiltIn>
 struct FastEngine {
-  FastCold<W, GS, R> cold;
+  FastCold<W, GS, R, US> cold;
   KS_LDS FastHot* hs;
   KS_DEV FastEngine(const ProblemView* p, const Workspace* s, const FastWork* f, char* lds) { cold.init(p, s, f, lds); hs = cold.hs; }
 
@@ -2218,13 +2418,15 @@ struct FastEngine {
         W::sync();
       } else if (ev == FEV_NEWCLAIM) {
         const int n = fast_uniform(h->n), bi = fast_uniform(h->bi);
-        const int made = fast_uniform(cold.new_claim(fast_uniform(h->ev_arg), bi, n));
+        const int made = fast_uniform(cold.new_claim(fast_uniform(h->ev_arg), bi, n));   // (2, engines 20 / 21: the pod was set aside and the loop's state stands behind it)
         if (!made) { cold.finish(fast_uniform(cold.bail_code) == DECLINE_KERNEL_CAPACITY ? 1 : 3, 0, (unsigned long long)fast_uniform(h->steps), 0, 0, 0, nullptr); return; }
-        if (W::leader()) { h->oclaim[bi] = (uint32_t)n; h->ocnt[bi] = 0; h->n = n + 1; h->pend_new = 1; h->pend_a = 0x7FFFFFFF; h->bi = bi + 1; }   // (pend_a: the loop tests one flag)   // claim ids are handed out in creation order
+        if ((!US || made == 1) && W::leader()) { h->oclaim[bi] = (uint32_t)n; h->ocnt[bi] = 0; h->n = n + 1; h->pend_new = 1; h->pend_a = 0x7FFFFFFF; h->bi = bi + 1; }   // (pend_a: the loop tests one flag)   // claim ids are handed out in creation order
         W::sync();
       } else { cold.bail_code = DECLINE_UNKNOWN_EVENT; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }
       if (ev >= 1 && ev <= 5) { tev[ev] += W::clock() - te0; nev[ev]++; }
     }
+    // the pods set aside come back behind the last queue entry ("Unschedulable pods"; nothing to do without the switch)
+    if constexpr (US) if (fast_uniform(cold.retry_unschedulable()) == 3) { cold.finish(3, 0, (unsigned long long)fast_uniform(h->steps), 0, 0, 0, nullptr); return; }
     // profiling builds (-DKSOLVE_PHASE_TIMERS): cycles inside the loop function, per event kind, in total; event counts
     unsigned long long tc[16] = {h->hot_cycles, tev[1], tev[2], tev[3], tev[4], tev[5], W::clock() - t_begin, nev[3] + (nev[4] << 20) + (nev[1] << 40),
                                  t_fast, n_fast, t_slow, n_slow, nev[1], nev[2], nev[3] + (nev[4] << 32), nev[5]};
@@ -2268,6 +2470,15 @@ KS_FN void fast_scatter_body(int i, const FastQueueArgs& a) {
   if (c == 0xFFFFFFFFu) return;
   const uint32_t p = a.sorted[i];
   a.assign[p] = (int32_t)c; a.slot[p] = a.q_cnt[i];
+}
+
+// ksolve_fast_unsched — one thread per pod set aside (engines 20 / 21), after the loop: its error and diagnostic bits under its pod
+//                       index (Results.pod_error / pod_error_diag); `sorted` = the pods of the queue the loop read
+struct FastUnschedArgs { const uint32_t* sorted; const uint32_t* us_n; const uint32_t* us_entry; const uint8_t* us_err; const uint8_t* us_diag; uint8_t* err; uint8_t* diag; };
+KS_FN void fast_unsched_body(int i, const FastUnschedArgs& a) {
+  if ((uint32_t)i >= *a.us_n) return;
+  const uint32_t p = a.sorted[a.us_entry[i]];
+  a.err[p] = a.us_err[i]; a.diag[p] = a.us_diag[i];
 }
 
 // ksolve_fast_records — one wavefront per claim: materialises the hot claim record the finalize kernel and the result

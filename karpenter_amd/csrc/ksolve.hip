@@ -559,6 +559,10 @@ __global__ void ksolve_fast_scatter(int n, ks::FastQueueArgs a) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ks::fast_scatter_body(i, a);
 }
+__global__ void ksolve_fast_unsched(int n, ks::FastUnschedArgs a) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ks::fast_unsched_body(i, a);
+}
 // One wavefront per claim: hot claim records (requirement masks, InstanceTypeOptions) from the cursor engine's compact state.
 __global__ void __launch_bounds__(64) ksolve_fast_records(ks::FastRecordArgs a) {
   ks::fast_record_body<ks::Wave>((int)blockIdx.x, a);
@@ -701,14 +705,18 @@ static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, 
   if (hipEventElapsedTime(&ms, b->ev0[ksi::T_PACK], b->ev1[ksi::T_PACK]) == hipSuccess) h->timers.ms[ksi::T_PACK] = ms;
 }
 typedef void (*ksolve_pack_fast_fn)(const ks::FastArgs*);
-static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows) {
+static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows, bool unsched) {
+  if (unsched) {   // engines 20 / 21: the kernels with the set-aside list compiled in
+    if (rows == 1) return plan == 2 ? ksolve_pack_fast_u_g2r1 : plan == 1 ? ksolve_pack_fast_u_g1r1 : ksolve_pack_fast_u_g0r1;
+    return plan == 2 ? ksolve_pack_fast_u_g2r4 : plan == 1 ? ksolve_pack_fast_u_g1r4 : ksolve_pack_fast_u_g0r4;
+  }
   if (rows == 1) return plan == 2 ? ksolve_pack_fast_g2r1 : plan == 1 ? ksolve_pack_fast_g1r1 : ksolve_pack_fast_g0r1;
   return plan == 2 ? ksolve_pack_fast_g2r4 : plan == 1 ? ksolve_pack_fast_g1r4 : ksolve_pack_fast_g0r4;
 }
 static void be_launch_pack_fast(ksolve_handle* h) {
   const int lds_bytes = h->fw.plan.total_bytes;
   const bool two = h->fw.plan.helper != 0;   // (plan 0, one row of class slots: placer + refresher)
-  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : pack_fast_kernel(h->fw.plan.global_state, h->fw.plan.rows);
+  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : pack_fast_kernel(h->fw.plan.global_state, h->fw.plan.rows, h->fw.unsched != 0);
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));
@@ -765,6 +773,11 @@ static void be_launch_fast_records(ksolve_handle* h, int n_claims) {
   const int n = (int)h->n_pods;
   hipLaunchKernelGGL(ksolve_fast_scatter, grid_for(n), dim3(256), 0, HB(h)->stream, n, fast_queue_args(h));
   hip_check(h, hipGetLastError(), "ksolve_fast_scatter launch");
+}
+static void be_launch_fast_unsched(ksolve_handle* h) {
+  const int n = (int)h->n_pods;
+  hipLaunchKernelGGL(ksolve_fast_unsched, grid_for(n), dim3(256), 0, HB(h)->stream, n, ksi::fast_unsched_args(h));
+  hip_check(h, hipGetLastError(), "ksolve_fast_unsched launch");
 }
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
   const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;

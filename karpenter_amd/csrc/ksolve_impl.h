@@ -294,6 +294,7 @@ static int be_device_of(const ksolve_handle* h);     // the device ordinal the h
 static void be_free(ksolve_handle* h, void* p);   // releases one be_alloc'ed block before the handle goes
 static void be_launch_node_dead0(ksolve_handle* h, int n_blocks, const ks::NodeDeadArgs& a);   // one wavefront per 64 nodes
 static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: TopoEngine<W, true>::solve (existing nodes: topo_nodes.h)
+static void be_launch_fast_unsched(ksolve_handle* h);               // engines 20 / 21, one thread per pod set aside: fast_unsched_body (errors under the pod indices)
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
@@ -998,6 +999,12 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       if (P.plain_nodes || (P.plain_ops && d->n_nodes > 0)) { fw.nodes = dz<ks::FastNodes>(h, 1); fw.nd_pod = dz<uint32_t>(h, d->n_pods); }
       if (h->eng.limits) fw.lim = dz<ks::FastLimits>(h, 1);
       fw.ops = h->eng.operators ? 1 : 0;
+      fw.unsched = h->eng.unschedulable && !h->eng.pair ? 1 : 0;   // engines 20 / 21: the set-aside list (fast_engine.h, "Unschedulable pods")
+      if (fw.unsched) {
+        fw.us_n = dz<uint32_t>(h, 1); fw.us_entry = dz<uint32_t>(h, d->n_pods); fw.us_last = dz<uint32_t>(h, d->n_pods);
+        fw.us_err = dz<uint8_t>(h, d->n_pods); fw.us_diag = dz<uint8_t>(h, d->n_pods); fw.us_cls = dz<uint64_t>(h, d->n_pods);   // (a class per pod at most)
+        if (fw.nodes) fw.pod_qpos = dz<uint32_t>(h, d->n_pods);
+      }
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the
@@ -2419,7 +2426,12 @@ static void fast_plan_set(ksolve_handle* h, int plan, int rows) {
 // ksolve_fast_requeue / ksolve_fast_remark behind ksolve_pack_nodes: the compacted queue's tables, the full queue's pods
 static ks::FastRequeueArgs fast_requeue_args(ksolve_handle* h) {
   return ks::FastRequeueArgs{ks::FastQueueArgs{h->fw.nd_pod, h->pv.row_class, h->fw.q_class, h->fw.q_claim, h->fw.q_cnt, h->ws.assign, h->ws.slot, h->fw.cls_first, h->fw.cls_last, h->fw.max_active},
-                             h->pv.sorted_pods, h->fw.nodes};
+                             h->pv.sorted_pods, h->fw.nodes, h->fw.pod_qpos};
+}
+
+// ksolve_fast_unsched behind the loop of engines 20 / 21 (the view's queue is the one the loop read: the compacted one behind the node stage)
+static ks::FastUnschedArgs fast_unsched_args(ksolve_handle* h) {
+  return ks::FastUnschedArgs{h->pv.sorted_pods, h->fw.us_n, h->fw.us_entry, h->fw.us_err, h->fw.us_diag, h->ws.err, h->ws.diag};
 }
 
 // The static (class, node) rows of the fast engines' node paths (node_stage.h, topo_nodes.h). They are a function of the problem, but
@@ -2536,6 +2548,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
         h->engine_used = 2;
         h->fast_reason = 0;   // (a first attempt that ran out of LDS claim slots is not a fallback to the general engine)
         if (o.n_claims) be_launch_fast_records(h, o.n_claims);
+        if (h->fw.unsched) be_launch_fast_unsched(h);   // the errors of the pods it set aside (none: nothing is written)
         return solve_finish(h, out);
       }
       h->fast_reason = o.reason;   // (DECLINE_CAPACITY, 100 = more claims than max_claims: the general engine reports it, or moves to BIG)
@@ -2546,6 +2559,8 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
         int next = h->fw.plan.global_state + 1;
         if (next == 1) {
           fast_plan_set(h, 1, h->fw.plan.rows);
+          // (under engines 20 / 21 the pops include the pods set aside, which took no claim: the rate is then an underestimate and the
+          // choice leans to plan 1; harmless — a plan 1 that runs out as well ends with 26 again and moves to plan 2)
           const double placed = (double)(o.pops > 0 ? o.pops : 1);
           const bool holds_all = h->fw.plan.cap >= (int)((h->fast_mc + 63) & ~63u);   // plan 1 has a slot for every claim the problem may open
           if (!holds_all && (double)had * (double)h->n_pods / placed * 1.25 > (double)h->fw.plan.cap) next = 2;
@@ -2614,7 +2629,7 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan; a handle whose claims live in HBM (an earlier Solve() moved it there, or engine =
       // cursor-wide / cursor-hbm) runs alone on the kernel of its plan
-      if (h->fw.plan.global_state == 0 && !h->fw.nodes && !h->fw.lim) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop; so does one of engines 11 / 12)
+      if (h->fw.plan.global_state == 0 && !h->fw.nodes && !h->fw.lim && !h->fw.unsched) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop; so does one of engines 11 / 12, and one of 20 / 21: a kernel follows its loop)
       else { be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1; }
     }
     else if (h->eng.refuses()) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");   // (the batch path's short form; a spread-only handle gets the cursor wording too: a known wart)
@@ -2728,6 +2743,10 @@ static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
   const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
   for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_requeue_body(i, q);
   for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_remark_body(i, q);
+}
+static void be_launch_fast_unsched(ksolve_handle* h) {
+  const ks::FastUnschedArgs a = ksi::fast_unsched_args(h);
+  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_unsched_body(i, a);
 }
 static void be_launch_pack_topo_nodes(ksolve_handle* h) {
   std::vector<char> lds((size_t)h->tw.plan.total_bytes + 64, (char)0xA5);

@@ -200,8 +200,11 @@ KS_DEV void pack_nodes_body(const FastArgs* a, char* lds) {
 // (Results.pod_assignment = -2 - node, pod_slot), then entry i of the COMPACTED queue as ksolve_fast_queue builds it (class, "not
 // placed", the class's first / last entry; a.q.sorted = FastWork::nd_pod). Entries past the compacted queue read "not placed".
 // ksolve_fast_remark — kFastLastBit over the compacted queue.
-struct FastRequeueArgs { FastQueueArgs q; const uint32_t* full_sorted; const FastNodes* nodes; };
+// pod_qpos (engines 20 / 21, FastWork::pod_qpos; null otherwise): every pod's position in the full queue, which the loop needs for
+// the reference's queue lengths when it sets a pod aside.
+struct FastRequeueArgs { FastQueueArgs q; const uint32_t* full_sorted; const FastNodes* nodes; uint32_t* pod_qpos; };
 KS_DEV void fast_requeue_body(int i, const FastRequeueArgs& a) {
+  if (a.pod_qpos) a.pod_qpos[a.full_sorted[i]] = (uint32_t)i;
   const uint32_t e = a.q.q_claim[i];
   if (e != 0xFFFFFFFFu) { const uint32_t p = a.full_sorted[i]; a.q.assign[p] = -2 - (int32_t)e; a.q.slot[p] = a.q.q_cnt[i]; }
   if ((uint32_t)i < a.nodes->n_left) fast_queue_body(i, a.q);

@@ -23,6 +23,13 @@ __global__ void ksolve_pack_fast_g2r1(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_g0r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_g1r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_g2r4(const ks::FastArgs* a);
+// ... and the same six with the set-aside list of engines 20 / 21 compiled in (ksolve_pack_fast_unsched.hip)
+__global__ void ksolve_pack_fast_u_g0r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_u_g1r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_u_g2r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_u_g0r4(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_u_g1r4(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_u_g2r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast2(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_batch(const ks::FastArgs* const* items);
 __global__ void ksolve_pack_topo(const ks::TopoArgs* a);
