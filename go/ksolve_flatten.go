@@ -980,6 +980,10 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // that nothing takes — Results.PodErrors, ordinary input — instead of handing the whole batch to the general engine (reason 27):
 // the setting for batches that may run into their NodePools' limits. KsolveEngineCursorUnschedulable (21) is the cursor engine
 // alone with that switch and refuses instead of falling back (tests).
+// KsolveEngineAutoUnschedulableSpread = "auto-unschedulable-spread" (22): KsolveEngineAutoUnschedulable, and the spread engine keeps
+// such pods too and retries them as the reference's second round does — a pod whose affinity target sits later in the batch is
+// placed there — instead of handing a topology batch to the general engine (reason 27). KsolveEngineSpreadUnschedulable (23) is
+// the spread engine alone with that switch and refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -998,6 +1002,9 @@ const (
 
 	KsolveEngineAutoUnschedulable   uint32 = 20
 	KsolveEngineCursorUnschedulable uint32 = 21
+
+	KsolveEngineAutoUnschedulableSpread uint32 = 22
+	KsolveEngineSpreadUnschedulable     uint32 = 23
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

@@ -276,7 +276,8 @@ typedef struct {
                                     * Switches: nodes / s-nodes = the cursor / spread engine may take a problem with existing nodes;
                                     * limits / s-limits = the cursor / spread engine goes on when a NodePool limit binds; operators = the
                                     * cursor engine takes NodePools whose requirements are not In sets; s-operators = the spread engine does;
-                                    * unschedulable = the cursor engine keeps pods that can go nowhere and reports their errors.
+                                    * unschedulable = the cursor engine keeps pods that can go nowhere and reports their errors;
+                                    * s-unschedulable = the spread engine does, and retries them for real.
                                     *
                                     *    value  name                 engines that may run       a decline     switches
                                     *      0    auto                 cursor, spread, general    falls back    -
@@ -301,7 +302,9 @@ typedef struct {
                                     *     19    spread-operators     spread                     refuses       s-nodes, s-limits, s-operators
                                     *     20    auto-unschedulable   cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable
                                     *     21    cursor-unschedulable cursor                     refuses       nodes, limits, operators, unschedulable
-                                    *   above 21: no name; as 17.
+                                    *     22    auto-unschedulable-spread cursor, spread, general falls back nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable, s-unschedulable
+                                    *     23    spread-unschedulable spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable
+                                    *   above 23: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
@@ -345,7 +348,15 @@ typedef struct {
                                     * reference's second round over such pods is replayed behind the last queue entry (queue pops, evaluation
                                     * count, the error of a pod whose NodePools have meanwhile run into a limit), and the Results carry
                                     * pod_assignment -1, pod_error and pod_error_diag (csrc/fast_engine.h, "Unschedulable pods"). The spread
-                                    * engine still declines with 27, and so does a batch with preferences (relaxation rows).
+                                    * engine still declines with 27 under 20 / 21, and so does a batch with preferences (relaxation rows).
+                                    * s-unschedulable: the spread engine sets such a pod aside too — its error may be Topology (3): the pod's
+                                    * domain choice leaves the NodePool's requirement set no domain — and gives every pod on the list the
+                                    * reference's second round as a FULL attempt: with topology a retry can succeed (an affinity target placed
+                                    * later in the batch, domain counts that moved), the pod is then assigned and carries no error, and the pods
+                                    * behind it get further pops. pod_error / pod_error_diag are those of a pod's LAST attempt
+                                    * (csrc/topo_engine.h, "The spread engine's unschedulable pods"). A batch with a preference pod is not
+                                    * offered to a fast engine at all (reason 0); a nodeSelector next to a spread (43), pod-side NotIn (4),
+                                    * Gt / Lt and minValues (1) still go to the general engine.
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -26,7 +26,7 @@ enum Decline : int {
   DECLINE_LIMIT_EXCLUDES_TYPE = 24,    // a NodePool limit excludes an instance type of the template (scheduler.go:1069-1085); both engines, as 23
   DECLINE_CACHE_FULL_NEW_CLAIM = 25,   // no room for the cache entry of a new claim's requirement set (addToNewNodeClaim, scheduler.go:695-790); both engines
   DECLINE_CLAIM_SLOTS = 26,            // more in-flight claims than the cursor engine's memory plan holds: the host moves to the next plan
-  DECLINE_UNSCHEDULABLE_POD = 27,      // a pod no claim and no template takes: error codes and diagnostics are the general engine's; both engines — the cursor engine not under engines 20 / 21, which set the pod aside with its error (there only the retry's safety net names 27)
+  DECLINE_UNSCHEDULABLE_POD = 27,      // a pod no claim and no template takes: error codes and diagnostics are the general engine's; both engines — the cursor engine not under engines 20 / 21, which set the pod aside with its error (there only the retry's safety net names 27), the spread engine not under 22 / 23, which set it aside and retry it for real
   DECLINE_REFRESHER_DEAD = 28,         // two-wavefront kernel: the refresher wavefront does not answer
   DECLINE_LIMIT_STAGES = 29,           // engines 11-14, both engines: NodePool limits narrowed the templates' type lists more often than there are free template ids (limit stages)
   // existing nodes, decided by create() (cursor: engines 7 / 8, spread: engines 9 / 10)

@@ -1018,6 +1018,12 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       tw.rec = dz<ks::TopoRec>(h, mc);
       if (h->eng.spread_limits) fw.lim = dz<ks::FastLimits>(h, 1);
       fw.ops = h->eng.spread_operators ? 1 : 0;   // engines 18 / 19; a spread handle of 15 / 16 declines complement templates as before
+      fw.unsched = h->eng.spread_unschedulable ? 1 : 0;   // engines 22 / 23: the set-aside list and the second round (topo_engine.h, "The spread engine's unschedulable pods")
+      if (fw.unsched) {
+        // (the list is a FIFO that moves on while the second round pushes pods back: twice the pods, topo_engine.h retry_unschedulable)
+        fw.us_n = dz<uint32_t>(h, 1); fw.us_entry = dz<uint32_t>(h, 2 * (size_t)d->n_pods); fw.us_last = dz<uint32_t>(h, 2 * (size_t)d->n_pods);
+        fw.us_err = dz<uint8_t>(h, 2 * (size_t)d->n_pods); fw.us_diag = dz<uint8_t>(h, 2 * (size_t)d->n_pods); fw.us_cls = dz<uint64_t>(h, d->n_pods);   // (a class per pod at most)
+      }
       if (fw.ops) {
         // ... and whether this problem has one: what FastCold::setup() declines with reason 3 without the switch (the batch path asks)
         bool complement = any_nonzero(d->tmpl_reqs.complement, d->n_templates) || any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
@@ -2525,6 +2531,7 @@ static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_con
       h->engine_used = 3;
       h->fast_reason = 0; h->fast_attempts = 1;
       if (o.n_claims || h->tw.nd.dom) be_launch_fast_records(h, o.n_claims);   // (pods on existing nodes are scattered with the queue's results even when no claim was opened)
+      if (h->fw.unsched) be_launch_fast_unsched(h);   // engines 22 / 23: the errors of the pods that ended on the set-aside list (none: nothing is written)
       return solve_finish(h, out);
     }
     h->fast_reason = o.reason;
@@ -2622,8 +2629,8 @@ static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_re
   for (uint32_t i = 0; i < n; ++i) {
     if (st[i] != KSOLVE_OK || !hs[i]->n_pods) continue;
     ksolve_handle* h = hs[i];
-    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom || h->spread_complement) && h->n_classes) {
-      // a DaemonSet problem of the spread engine's shape, one with existing nodes (engine 9 / 10) or one over complement templates (18 / 19): alone through solve(), so that the batch runs the engine ksolve_solve would
+    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom || h->spread_complement || h->fw.unsched) && h->n_classes) {
+      // a DaemonSet problem of the spread engine's shape, one with existing nodes (engine 9 / 10), one over complement templates (18 / 19) or any spread handle that keeps unschedulable pods (22 / 23): alone through solve(), so that the batch runs the engine ksolve_solve would
       be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1;
     }
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {

@@ -55,8 +55,45 @@ namespace ks {
 
 // NODES: the problem has existing nodes, and every pod is offered to them first (topo_nodes.h; kernel ksolve_pack_topo_nodes). The
 // code of the plain instantiation is what it was: every line of the node path stands behind `if constexpr (NODES)`.
-template <class W, bool NODES = false>
-struct TopoEngine {
+//
+// The spread engine's unschedulable pods (engines 22 / 23, FastWork::unsched on a spread handle; US below). A pod that no node, no
+// claim and no template takes is ordinary input: the reference records its error, pushes it to the back of the queue with lastLen =
+// the queue's length after the push (queue.go:63-66), pops it again behind everything that stood in front of it and stops at the
+// first pop whose lastLen equals the queue's length (queue.go:52-56). Unlike the cursor engine's pods (fast_engine.h, "Unschedulable
+// pods") such a pod does NOT stay failed: domain counts move, an affinity target is placed later in the batch (scheduler.go:442-446),
+// so the second round is a real one.
+//   * A failing first attempt is finished as the reference's add() finishes it (scheduler.go:594-612, :695-790): every node and every
+//     claim counts as evaluated, the pending sort has happened, and new_claim walks the templates in order — a template skipped by its
+//     limit draws no hostname number and is no evaluation, every other one draws a number and is one evaluation, limit stages are
+//     created as on a successful attempt. The error is the FIRST active template's in CanAdd's own order (nodeclaim.go:124-240):
+//     Limits (7) for a skipped template, Taints (1), Incompatible (2), Topology (3) when the domain choice leaves the template's set
+//     no domain, InstanceTypes (4) with the filter's flags on the set that CanAdd reached (FastCold::filter_diag), NoTemplates (6).
+//     All four places that named DECLINE_UNSCHEDULABLE_POD end in new_claim's walk: a pod without a possible domain fails every
+//     template's CanAdd at Topology at the latest (its candidate mask is empty, so lane_test says no by itself).
+//   * The pod is set aside (FastWork::us_entry / us_last / us_err / us_diag, push order; the loop index IS the queue position: the
+//     engine walks the full queue, nodes inline), its queue entry keeps "not placed", and the loop goes on as behind a created claim.
+//   * Behind the last block retry_unschedulable replays queue.go:46-60 on that list: pop the head, stop at the first pop whose lastLen
+//     equals the list's length, honour max_steps and the cancel flag, count a pop. The pod gets a FULL attempt (attempt(): the node
+//     step, the pending sort, the domain choice, the scan of the list or of the whole order, the commit or new_claim). A success
+//     writes the pod's queue entry and leaves the list shorter, so the pods behind it get further pops; a failure is pushed back
+//     with a new lastLen and THAT attempt's error. topology.Update on the push-back (scheduler.go:482) changes nothing for a pod
+//     without preferences, and pods with preferences never get here (DECLINE_TOPO_PREFERENCES).
+//   * An attempt is a function of the pod's class and the engine's state. us_epoch counts the commits — a pod on a node, a pod on a
+//     claim, a new claim (with its limit subtraction) — and the verdict of a failed attempt is kept per class with the epoch it was
+//     reached under (FastWork::us_cls: error | flags << 8 | templates evaluated << 16 | epoch << 32). A pod whose class failed under
+//     the current epoch replays the verdict: n_nodes + n + evaluated templates evaluations, as many hostname numbers, the same error.
+//     Without it the round that ends the loop costs (unschedulable pods) x (claims) lane tests.
+// On the device US is a compile-time switch with kernels of its own (ksolve_pack_topo_unsched.hip): every line of it stands behind
+// `if constexpr (US)`, and the kernels of every other setting are compiled from what they were compiled from. The host emulation
+// builds it in and FastWork::unsched decides at run time.
+struct TopoKeepState {
+  int us_err_ = 0, us_diag_ = 0;   // error and flags of the attempt that just failed (new_claim's result -2, attempt's 0)
+  int us_status = 0;               // retry_unschedulable: the status the solve ends with (2: step limit / cancel, 1: capacity, 3: bail)
+  uint32_t us_epoch = 1;           // commits so far + 1 (0: no verdict)
+};
+struct TopoNoKeepState {};
+template <class W, bool NODES = false, bool US = kFastKeepBuiltIn>
+struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
   FastCold<W, 2, 1> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
   RunOrder<W> order;        // Go's sort.Slice permutation as one ring per pod count
   const ProblemView* Pk; const Workspace* Sk; const FastWork* Fk; const TopoWork* Tk;
@@ -384,7 +421,12 @@ struct TopoEngine {
     bool possible = true, possible2 = true;
     const ZChoice zc = choose_domains(tc.zg[0], (tc.zself & 1u) != 0, cs.cvmask, zkv, possible);
     const ZChoice zd = choose_domains(tc.zg[1], (tc.zself & 2u) != 0, cs.cvmask, zkw, possible2);
-    if (!possible || !possible2) { bail = DECLINE_UNSCHEDULABLE_POD; return -1; }
+    if (!possible || !possible2) {
+      if constexpr (US) { if (!keeps()) { bail = DECLINE_UNSCHEDULABLE_POD; return -1; } }   // (kept: the walk below — every CanAdd ends at Topology at the latest)
+      else { bail = DECLINE_UNSCHEDULABLE_POD; return -1; }
+    }
+    [[maybe_unused]] int first_err = 0, first_diag = 0;
+    [[maybe_unused]] const uint32_t seq0 = cold.host_seq;
     KClass kc; kc.hlim = tc.hlim; kc.cvmask = cs.cvmask; kc.dmask = cs.dmask; kc.s0 = cs.size[0]; kc.s1 = cs.size[1]; kc.s2 = cs.size[2]; kc.s3 = cs.size[3]; kc.tmplok = cs.tmplok;
     for (int t = 0; t < T; ++t) {
       if (!((cold.active_templates >> t) & 1u)) continue;
@@ -393,7 +435,7 @@ struct TopoEngine {
       if (lm) {
         if (F.lim) {
           ts = (int)W::uniform((uint64_t)(uint32_t)limit_stage(t, lm));
-          if (ts == -1) continue;   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
+          if (ts == -1) { if constexpr (US) { if (!first_err) first_err = E_LIMITS; } continue; }   // the reference returns before NewNodeClaim: no hostname number, no CanAdd
           if (ts < 0) { bail = DECLINE_LIMIT_STAGES; return -1; }
           kc.tmplok |= ((kc.tmplok >> t) & 1u) << ts;   // (this pod's copy of the class came from the loop's registers)
         } else { const int why = limits_exclude<W>(P, S, t, lm); if (why) { bail = why; return -1; } }
@@ -405,12 +447,19 @@ struct TopoEngine {
       int v = lane_test(Mp->tvmask[ts], 0, 0, 0, 0, 0ull, kc, zc, zkv, zd, zkw, cold.ent, m2);   // (every lane computes the same verdict: the state is wave-uniform)
       v = fast_uniform(v);
       m2 = W::uniform(m2);
-      if (v == 0) continue;
+      if (v == 0) {
+        // (US: a refusal by the first probe's cached vectors alone — walk_error 0 — goes on to the long way, which names InstanceTypes)
+        if constexpr (US) { const int we = keeps() ? walk_error(t, ts, tc.pad, kc.tmplok, kc.cvmask, kc.dmask, zc, zkv, zd, zkw) : -1; if (we) { if (we > 0 && !first_err) first_err = we; continue; } }
+        else continue;
+      }
       FastEnt e;
       int eh = fast_lookup(cold.ent, m2, e);
       if (eh < 0) { eh = cold.create_entry(m2); if (eh < 0) { bail = DECLINE_CACHE_FULL_NEW_CLAIM; return -1; } e = lds_get(&cold.ent[eh]); }
       const int32_t zero[4] = {0, 0, 0, 0};
-      if (!fast_fits(cold.pool, e, zero, cs.size)) continue;
+      if (!fast_fits(cold.pool, e, zero, cs.size)) {
+        if constexpr (US) { if (!first_err && keeps()) { first_err = E_INSTANCE_TYPES; first_diag = (int)W::uniform((uint64_t)(uint32_t)cold.filter_diag(m2, cs.size)); } }
+        continue;
+      }
       if (cold.n_claims >= S.max_claims) { bail = DECLINE_KERNEL_CAPACITY; return -1; }
       const int c = cold.n_claims++;
       TopoRec nrq;
@@ -428,10 +477,207 @@ struct TopoEngine {
       if (track_fields) lists_add(nrq.hcnt, (uint32_t)c);
       W::sync();
       if (lm) subtract_max<W>(P, S, F, t, lm, eh, cs.size);
+      if constexpr (US) this->us_epoch++;   // a new claim (and its limit subtraction): no kept verdict stands
       return c;
+    }
+    if constexpr (US) if (keeps()) {
+      // no template takes the pod: the error of the first one, and the verdict for the class's next pods while nothing is committed
+      this->us_err_ = first_err ? first_err : E_NO_TEMPLATES; this->us_diag_ = first_diag;
+      if (W::leader()) F.us_cls[tc.pad] = (uint64_t)(uint32_t)this->us_err_ | ((uint64_t)(uint32_t)this->us_diag_ << 8) | ((uint64_t)(cold.host_seq - seq0) << 16) | ((uint64_t)this->us_epoch << 32);
+      W::sync();
+      last_kind = 0;   // the failing attempt's sort (scheduler.go:598) has made the last step's move: finish() takes nothing back
+      return -2;
     }
     bail = DECLINE_UNSCHEDULABLE_POD;   // error codes, diagnostics and the relaxation ladder are the general engine's
     return -1;
+  }
+  // ---- unschedulable pods (US; "The spread engine's unschedulable pods" above) ----
+  KS_DEV bool keeps() const { if constexpr (US) return Fk->unsched != 0; else return false; }
+  // CanAdd's first failing check (nodeclaim.go:124-240) on a FRESH claim of template t (requirement-set id ts) that lane_test refused:
+  // Taints.ToleratesPod, then Requirements.Compatible, then the topology's domain choice (the hostname counters of a fresh claim are
+  // zero); 0: none of these — the instance-type filter
+  KS_COLD int walk_error(int t, int ts, uint32_t k, uint32_t tmplok, uint64_t cvmask, uint64_t dmask, ZChoice zc, LaneVar<uint64_t> zkv, ZChoice zd, LaneVar<uint64_t> zkw) const {
+    const ProblemView& P = *Pk;
+    if (!((tmplok >> t) & 1u)) return (P.tmpl_taints[t] & ~P.cls_tolerates[k]) ? E_TAINTS : E_INCOMPATIBLE;
+    const uint64_t m = W::uniform(Mp->tvmask[ts]) & cvmask;
+    if (!fast_fields_ok(m, dmask)) return E_INCOMPATIBLE;
+    uint64_t m2 = m;
+    bool ok = true;
+    if (zc.on) ok = apply_choice<true>(m, m2, zc, zkv) && ok;
+    if (zd.on) ok = apply_choice<false>(m, m2, zd, zkw) && ok;
+    return ok ? 0 : E_TOPOLOGY;
+  }
+  // the pod of queue position q goes to the back of the reference's queue with the error of the attempt that just failed (first
+  // round: the list's head is entry 0). lastLen = the pods still in front of the queue's end + the pods set aside, this one included.
+  KS_COLD void set_aside(int q) {
+    if constexpr (US) {
+      q = (int)W::uniform((uint64_t)(uint32_t)q);
+      const FastWork& F = *Fk;
+      const uint32_t i = (uint32_t)W::uniform((uint64_t)*F.us_n);
+      if (W::leader()) {
+        F.us_entry[i] = (uint32_t)q; F.us_last[i] = (uint32_t)Pk->n_pods - (uint32_t)q - 1u + i + 1u;
+        F.us_err[i] = (uint8_t)this->us_err_; F.us_diag[i] = (uint8_t)this->us_diag_;
+        *F.us_n = i + 1u;
+      }
+      W::sync();
+    }
+  }
+  // new_claim for the loop's pod at queue position q; -2: no template takes it, and it is set aside
+  KS_COLD int claim_or_aside(TopoClass tc, FastSlot cs, int q) {
+    const int c = fast_uniform(new_claim(tc, cs));
+    if (c == -2) set_aside(q);
+    return c;
+  }
+  // the kept verdict v of the pod's class stands (its epoch is the current one): what the attempt would count, and its error
+  KS_COLD void replay(uint64_t v) {
+    if constexpr (US) {
+      v = W::uniform(v);
+      const uint32_t tried = (uint32_t)(v >> 16) & 0xFFFFu;
+      n_ref += (unsigned long long)(NODES ? Pk->n_nodes : 0) + (unsigned long long)order.n + (unsigned long long)tried;
+      cold.host_seq += tried;
+      this->us_err_ = (int)(v & 0xFFu); this->us_diag_ = (int)((v >> 8) & 0xFFu);
+      last_kind = 0;
+    }
+  }
+  KS_COLD void replay_aside(int q, uint64_t v) { replay(v); set_aside(q); }
+  // the kept verdicts of the classes of the block's pods, one per lane (read again behind every failed attempt)
+  KS_COLD LaneVar<uint64_t> reload_us(int base, int bn) {
+    LaneVar<uint64_t> us;
+    const uint32_t* qc = Fk->q_class; const uint64_t* uc = Fk->us_cls;
+    W::each([&](int l) { us.at(l) = uc[qc[base + (l < bn ? l : bn - 1)] & ~kFastLastBit]; });
+    return us;
+  }
+  // One pod of the second round, queue position q: a full attempt from the out-of-line parts of the loop's step.
+  // 1: placed (its queue entry written), 0: failed (us_err_ / us_diag_), -1: the solve ends (us_status; bail).
+  KS_COLD int attempt(uint32_t q) {
+    if constexpr (!US) return -1;
+    else {
+    const ProblemView& P = *Pk; const FastWork& F = *Fk;
+    q = (uint32_t)W::uniform((uint64_t)q);
+    const uint32_t k = (uint32_t)W::uniform((uint64_t)F.q_class[q]) & ~kFastLastBit;
+    const uint64_t uv = W::uniform(F.us_cls[k]);
+    if ((uint32_t)(uv >> 32) == this->us_epoch) { replay(uv); return 0; }
+    TopoClass tc = Tk->cls[k];
+    tc.pad = k;
+    const FastSlot cs = F.cls[k];
+    if constexpr (NODES) {
+      if ((uint32_t)W::uniform((uint64_t)Tk->nd.cursor[k]) < (uint32_t)P.node_words) {
+        const TopoNodePick pk = node_step(k, cs.cvmask, tc.hlim, tc.hinc, tc.zsel, (int)tc.zg[0], (int)tc.zg[1], tc.zself);
+        const int node = fast_uniform(pk.node);
+        if (node >= 0) {
+          n_ref += (unsigned long long)node + 1;
+          if (W::leader()) { F.q_claim[q] = (uint32_t)(-2 - node); F.q_cnt[q] = pk.slot; }
+          W::sync();
+          this->us_epoch++;   // a pod on a node
+          return 1;
+        }
+      }
+      n_ref += (unsigned long long)P.n_nodes;
+    }
+    if (order.defect_claim >= 0) {   // scheduler.go:598
+      sort_cold();
+      if (fast_uniform((int)order.overflow)) { this->us_status = 1; return -1; }
+    }
+    KClass kc; kc.hlim = tc.hlim; kc.cvmask = cs.cvmask; kc.dmask = cs.dmask; kc.s0 = cs.size[0]; kc.s1 = cs.size[1]; kc.s2 = cs.size[2]; kc.s3 = cs.size[3]; kc.tmplok = cs.tmplok;
+    LaneVar<uint64_t> zkv;
+    bool possible = true;
+    const ZChoice zc = choose_domains((int)tc.zg[0], (tc.zself & 1u) != 0, cs.cvmask, zkv, possible);
+    Accept A; A.found = 0; A.x = 0; A.pos = 0; A.cnt = 0; A.m2 = 0; A.hcnt = 0; A.q0 = A.q1 = A.q2 = A.q3 = 0;
+    if (possible) {
+      const bool two = tc.zg[1] >= 0;
+      const uint32_t excl = tc.excl;
+      const bool listed = excl != 0xFFu && fast_uniform((int)st->track_field[excl & (kTopoTrack - 1)]) != 0xFF;
+      ZChoice zn; zn.vm = 0; zn.off = 0; zn.width = 0; zn.multi = false; zn.on = false; zn.clear = 0;
+      if (listed) {
+        if (fast_uniform((int)st->n_free[excl & (kTopoTrack - 1)]) > 0) A = two ? scan_two((int)excl, kc, zc, zkv, (int)tc.zg[1], (tc.zself & 2u) != 0) : scan_list((int)excl, kc, zc, zkv, zn, zkv);
+      } else if (two) A = scan_two(-1, kc, zc, zkv, (int)tc.zg[1], (tc.zself & 2u) != 0);
+      else if (order.n > 0) A = scan_order(kc, zc, zkv, zn, zkv);
+      if (fast_uniform(bail)) { this->us_status = 3; return -1; }
+    }
+    if (fast_uniform(A.found)) {
+      // NodeClaim.Add (nodeclaim.go:247-263), as the loop commits it
+      const uint32_t x = (uint32_t)fast_uniform((int)A.x), pos = (uint32_t)fast_uniform((int)A.pos), cnt = (uint32_t)fast_uniform((int)A.cnt);
+      const uint64_t m2 = W::uniform(A.m2), kh = W::uniform(A.hcnt);
+      n_ref += (unsigned long long)pos + 1;
+      TopoRec nrq;
+      nrq.vmask = m2;
+      nrq.req[0] = fast_uniform(A.q0) + cs.size[0]; nrq.req[1] = fast_uniform(A.q1) + cs.size[1]; nrq.req[2] = fast_uniform(A.q2) + cs.size[2]; nrq.req[3] = fast_uniform(A.q3) + cs.size[3];
+      nrq.hcnt = host_add(kh, tc.hinc);
+      if (W::leader()) { Tk->rec[x] = nrq; F.q_claim[q] = x; F.q_cnt[q] = cnt; }
+      W::sync();
+      record_zonal(tc.zsel, m2);
+      const uint64_t zero_before = ~(kh | (kh >> 1) | (kh >> 2)) & kTopoOnes;
+      const uint64_t leaving = tc.hinc & zero_before & track_fields;
+      if (leaving) lists_remove(leaving, x);
+      move_cold((int)x, (int)cnt, pos);
+      if (fast_uniform((int)order.overflow)) { this->us_status = 1; return -1; }
+      this->us_epoch++;   // a pod on a claim
+      return 1;
+    }
+    const int c = fast_uniform(new_claim(tc, cs));
+    if (c >= 0) {
+      if (W::leader()) { F.q_claim[q] = (uint32_t)c; F.q_cnt[q] = 0u; }
+      W::sync();
+      return 1;
+    }
+    if (c == -2) return 0;
+    this->us_status = fast_uniform(bail) == DECLINE_KERNEL_CAPACITY ? 1 : 3;
+    return -1;
+    }
+  }
+  // entries [head, tail) of the set-aside list move to its front (the destination lies in front of the source: 64 at a time, read before written)
+  KS_COLD void us_compact(uint32_t head, uint32_t tail) {
+    const FastWork& F = *Fk;
+    const uint32_t len = tail - head;
+    if (!head) return;
+    for (uint32_t o = 0; o < len; o += 64) {
+      LaneVar<uint32_t> e, ll, ed;
+      W::each([&](int l) { const uint32_t i = head + o + (uint32_t)l; if (o + (uint32_t)l < len) { e.at(l) = F.us_entry[i]; ll.at(l) = F.us_last[i]; ed.at(l) = (uint32_t)F.us_err[i] | ((uint32_t)F.us_diag[i] << 8); } });
+      W::sync();
+      W::each([&](int l) { const uint32_t i = o + (uint32_t)l; if (i < len) { F.us_entry[i] = e.at(l); F.us_last[i] = ll.at(l); F.us_err[i] = (uint8_t)ed.at(l); F.us_diag[i] = (uint8_t)(ed.at(l) >> 8); } });
+      W::sync();
+    }
+  }
+  // The reference's pops behind the last queue entry (queue.go:46-60) over the pods set aside, a FIFO in FastWork::us_* (2 n_pods
+  // entries: the list never holds more than n_pods, and it is moved to the front when its tail reaches the end). Returns the steps
+  // counted; us_status: how the solve ends.
+  KS_COLD uint32_t retry_unschedulable(uint32_t steps) {
+    if constexpr (US) {
+      const Workspace& S = *Sk; const FastWork& F = *Fk;
+      steps = (uint32_t)W::uniform((uint64_t)steps);
+      uint32_t head = 0, tail = (uint32_t)W::uniform((uint64_t)*F.us_n);
+      const uint32_t cap = 2u * (uint32_t)Pk->n_pods;
+      const long long ms = S.max_steps;
+      uint32_t round = 0;
+      // A pass over the list without a success ends the loop and every success shortens the list, so U (U + 1) pops bound it for U
+      // pods set aside. The bound is never met; should the bookkeeping ever be wrong, the engine declines (27) instead of spinning.
+      unsigned long long pops_left = (unsigned long long)tail * ((unsigned long long)tail + 1ull);
+      while (head < tail) {
+        const uint32_t len = tail - head;
+        if ((uint32_t)W::uniform((uint64_t)F.us_last[head]) == len) break;   // queue.go:52-56: nothing was placed since this pod was pushed
+        if (pops_left-- == 0) { bail = DECLINE_UNSCHEDULABLE_POD; this->us_status = 3; break; }
+        if (ms >= 0 && (long long)steps >= ms) { this->us_status = 2; break; }
+        if ((round++ & 63u) == 0 && S.cancel_flag) {
+          const int cv = fast_uniform((int)W::poll_flag(S.cancel_flag));
+          if (cv > 0 || (cv < 0 && (long long)steps >= -(long long)cv)) { this->us_status = 2; break; }
+        }
+        steps++;
+        const uint32_t q = (uint32_t)W::uniform((uint64_t)F.us_entry[head]);
+        head++;
+        const int r = fast_uniform(attempt(q));
+        if (r < 0) break;
+        if (r == 0) {
+          if (tail == cap) { us_compact(head, tail); tail -= head; head = 0; }
+          if (W::leader()) { F.us_entry[tail] = q; F.us_last[tail] = tail + 1u - head; F.us_err[tail] = (uint8_t)this->us_err_; F.us_diag[tail] = (uint8_t)this->us_diag_; }
+          W::sync();
+          tail++;
+        }
+      }
+      us_compact(head, tail);
+      W::store(F.us_n, tail - head);
+      W::sync();
+    }
+    return steps;
   }
   // a claim gained a pod and pdqsort's repair is not the single stable move (or its run lies beyond the LDS tables): through RunOrder
   KS_COLD void move_cold(int x, int k, uint32_t a_pos) {
@@ -591,7 +837,7 @@ struct TopoEngine {
     LaneVar<uint64_t> zkw;
     bool p2 = true;
     const ZChoice zd = choose_domains(zg1, self1, kc.cvmask, zkw, p2);
-    if (!p2) { bail = DECLINE_UNSCHEDULABLE_POD; Accept A; A.found = 0; A.x = 0; A.pos = 0; A.cnt = 0; A.m2 = 0; A.hcnt = 0; A.q0 = A.q1 = A.q2 = A.q3 = 0; return A; }
+    if (!p2) { if (!keeps()) bail = DECLINE_UNSCHEDULABLE_POD; Accept A; A.found = 0; A.x = 0; A.pos = 0; A.cnt = 0; A.m2 = 0; A.hcnt = 0; A.q0 = A.q1 = A.q2 = A.q3 = 0; return A; }
     return list_t >= 0 ? scan_list(list_t, kc, zc, zkv, zd, zkw) : scan_order(kc, zc, zkv, zd, zkw);
   }
   KS_COLD void sort_cold() { order.sort(); }
@@ -672,6 +918,16 @@ struct TopoEngine {
       if (why2) { bail = why2; finish(3, 0); return; }
     }
     if constexpr (NODES) topo_nodes_init<W>(Pk, Sk, Tk);
+    [[maybe_unused]] bool keep = false;
+    if constexpr (US) {
+      keep = fast_uniform(Fk->unsched) != 0;
+      if (keep) {   // no pod set aside yet, no verdict kept: repeated solves start clean
+        uint64_t* const uc = Fk->us_cls;
+        W::for_n(Pk->n_classes, [&](int c) { uc[c] = 0; });
+        W::store(Fk->us_n, 0u);
+        W::sync();
+      }
+    }
     const int np = fast_uniform(Pk->n_pods);
     const int max_claims = fast_uniform(Sk->max_claims);
     KS_GLOBAL TopoRec* const rec = (KS_GLOBAL TopoRec*)fast_uniform(Tk->rec);
@@ -705,12 +961,14 @@ struct TopoEngine {
     uint32_t windows = 0, steps = 0;
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0, t7 = 0, t8 = 0;
     int status = 0;
-    auto push = [&]() { order.n = n; order.max_cnt = max_cnt; cold.n_claims = n_claims; cold.host_seq = host_seq; track_fields = trk; last_kind = S_->last[0]; last_x = S_->last[1]; last_p = S_->last[2]; n_ref = ref; };
+    [[maybe_unused]] uint32_t epoch = 1;             // us_epoch (US)
+    auto push = [&]() { if constexpr (US) this->us_epoch = epoch; order.n = n; order.max_cnt = max_cnt; cold.n_claims = n_claims; cold.host_seq = host_seq; track_fields = trk; last_kind = S_->last[0]; last_x = S_->last[1]; last_p = S_->last[2]; n_ref = ref; };
     auto set_last = [&](int kind, int x, int pos) { if (W::leader()) { S_->last[0] = kind; S_->last[1] = x; S_->last[2] = pos; } };
     auto pull = [&]() {
       n = fast_uniform(order.n); max_cnt = fast_uniform(order.max_cnt); n_claims = fast_uniform(cold.n_claims); host_seq = (uint32_t)fast_uniform((int)cold.host_seq);
       trk = W::uniform(track_fields); set_last(last_kind, last_x, last_p); ref = W::uniform(n_ref);
       pending = fast_uniform(order.defect_claim) >= 0;
+      if constexpr (US) epoch = (uint32_t)fast_uniform((int)this->us_epoch);
     };
     // ---- the front of the order, in registers: the claims at positions 0 .. wn-1 with their records (lane = position) ----
     // Pods go to the emptiest claims (scheduler.go:598 sorts by pod count), so the first acceptor is almost always among the first
@@ -775,6 +1033,13 @@ struct TopoEngine {
           c_node.at(l) = k | (gcur[k] >= nwn ? 0x80000000u : 0u);
         });
       }
+      // US: the kept verdict of each pod's class (a copy that is behind can only miss: its epoch is an older one)
+      [[maybe_unused]] LaneVar<uint64_t> c_us;
+      [[maybe_unused]] LaneVar<uint32_t> c_k;
+      if constexpr (US) {
+        if (keep) { fence(); c_us = reload_us(base, bn); }
+        W::each([&](int l) { c_k.at(l) = gqcls[base + (l < bn ? l : bn - 1)] & ~kFastLastBit; });
+      }
       if (cancel) {
         // > 0: ksolve_cancel / the deadline; < 0 (tests only, KSOLVE_TEST_CANCEL_AT): as if the cancel landed once -flag pods were placed
         const int cv = fast_uniform((int)W::poll_flag(cancel));
@@ -786,6 +1051,11 @@ struct TopoEngine {
         steps++;
         unsigned long long tq = W::clock();
 #define KS_TSEC(acc) { const unsigned long long tn_ = W::clock(); acc += tn_ - tq; tq = tn_; }
+        if constexpr (US) if (keep) {
+          // the class's last attempt failed and nothing was committed since: the same verdict, the same counts — the pod is set aside
+          const uint64_t uv = c_us.bcast(bi);
+          if ((uint32_t)(uv >> 32) == epoch) { fence(); push(); replay_aside(base + bi, uv); pull(); continue; }
+        }
         if constexpr (NODES) {
           // ---- addToExistingNode (scheduler.go:594, :614-656): the nodes first. A pod that lands on one never reaches sort.Slice
           // (scheduler.go:598): a move that is pending in `order` stays pending, and the last move stays the last ----
@@ -798,6 +1068,7 @@ struct TopoEngine {
             if (node >= 0) {
               ref += (unsigned long long)node + 1;
               oclaim.set(bi, (uint32_t)(-2 - node)); ocntv.set(bi, (uint32_t)fast_uniform((int)pk.slot));   // Results.pod_assignment = -2 - node
+              if constexpr (US) epoch++;   // a pod on a node
               continue;
             }
           }
@@ -821,7 +1092,11 @@ struct TopoEngine {
         LaneVar<uint64_t> zkv;
         bool possible = true;
         const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, kc.cvmask, zkv, possible);
-        if (!possible) { bail = DECLINE_UNSCHEDULABLE_POD; status = 3; break; }
+        bool skip_scan = false;   // US: no domain can take the pod — straight to new_claim's walk, which names the error (every claim counts as evaluated there)
+        if (!possible) {
+          if constexpr (US) { if (keep) skip_scan = true; else { bail = DECLINE_UNSCHEDULABLE_POD; status = 3; break; } }
+          else { bail = DECLINE_UNSCHEDULABLE_POD; status = 3; break; }
+        }
         const bool two = zg1 >= 0;   // a second group on a dictionary key (rare): its pods take the out-of-line paths all the way
         KS_TSEC(t2)
         // ---- addToInflightNode (scheduler.go:658-692): the first claim of the order that accepts ----
@@ -830,7 +1105,8 @@ struct TopoEngine {
         uint32_t kx = 0, a_pos = 0, kcn = 0; uint64_t km = 0, kh = 0; int32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
         bool from_window = false;   // the acceptor is lane a_pos of the window registers
         const bool listed = excl != 0xFFu && fast_uniform((int)S_->track_field[excl & (kTopoTrack - 1)]) != 0xFF;
-        if (listed) {
+        if (skip_scan) {
+        } else if (listed) {
           // (usually nobody is on the list: every claim holds a member already — straight to addToNewNodeClaim)
           if (fast_uniform((int)S_->n_free[excl & (kTopoTrack - 1)]) > 0) {
             fence(); push();
@@ -911,6 +1187,7 @@ struct TopoEngine {
             if (v == 1) {
               ref += (unsigned long long)n + 1;
               host_seq++;
+              if constexpr (US) epoch++;   // a new claim
               const int c = n_claims++;
               TopoRec nrq;
               nrq.vmask = m2; nrq.req[0] = kc.s0; nrq.req[1] = kc.s1; nrq.req[2] = kc.s2; nrq.req[3] = kc.s3; nrq.hcnt = host_add(0, hinc);
@@ -950,10 +1227,19 @@ struct TopoEngine {
           if (!made) {
             push();
             TopoClass tcc; tcc.hlim = kc.hlim; tcc.hinc = hinc; tcc.zsel = zsel; tcc.zg[0] = (int16_t)zg0; tcc.zg[1] = (int16_t)zg1; tcc.zself = zselfw; tcc.excl = excl; tcc.pad = 0;
+            if constexpr (US) tcc.pad = c_k.bcast(bi);   // the class id, for the error of a failing walk and its kept verdict
             FastSlot csc; csc.cvmask = kc.cvmask; csc.dmask = kc.dmask; csc.size[0] = kc.s0; csc.size[1] = kc.s1; csc.size[2] = kc.s2; csc.size[3] = kc.s3; csc.tmplok = kc.tmplok; csc.kdef = 0;
             fence();
-            const int c = fast_uniform(new_claim(tcc, csc));
+            int c;
+            if constexpr (US) c = fast_uniform(claim_or_aside(tcc, csc, base + bi)); else c = fast_uniform(new_claim(tcc, csc));
             pull(); wvalid = false;
+            if constexpr (US) if (c == -2) {
+              // set aside: the entry keeps "not placed", the loop goes on as behind a created claim
+              if (fast_uniform(tok_stale)) c_tok = reload_tok(base, bn);
+              c_us = reload_us(base, bn);
+              KS_TSEC(t6)
+              continue;
+            }
             if (c < 0) { status = fast_uniform(bail) == DECLINE_KERNEL_CAPACITY ? 1 : 3; break; }
             if (fast_uniform(tok_stale)) c_tok = reload_tok(base, bn);   // a limit stage was created: the classes accept one more template id
             oclaim.set(bi, (uint32_t)c); ocntv.set(bi, 0u);
@@ -969,6 +1255,7 @@ struct TopoEngine {
         nrq.hcnt = host_add(kh, hinc);
         if (W::leader()) store_rec(rec + kx, nrq);
         dirty = true;
+        if constexpr (US) epoch++;   // a pod on a claim
         oclaim.set(bi, kx); ocntv.set(bi, kcn);
         record_zonal(zsel, km);
         // the anti-affinity lists: the claim leaves those whose counter this pod takes from zero
@@ -1043,6 +1330,10 @@ struct TopoEngine {
     n_tests = (unsigned long long)windows * 64; n_windows = windows; n_listed = 0;
     tc0 = t0; tc1 = t1; tc2 = t2; tc3 = t3; tc4 = t4; tc5 = t5; tc6 = t6; tc7 = t7; tc8 = t8;
     W::sync();
+    if constexpr (US) if (keep && !status) {   // the reference's second round over the pods set aside
+      steps = (uint32_t)fast_uniform((int)retry_unschedulable(steps));
+      status = fast_uniform(this->us_status);
+    }
     finish(status, steps);
   }
 };

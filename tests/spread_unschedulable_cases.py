@@ -1,0 +1,292 @@
+"""Topology batches that leave pods UNSCHEDULABLE — or that place them only in the reference's SECOND round —, for the spread
+engine's set-aside list (csrc/topo_engine.h, "The spread engine's unschedulable pods"; engines "auto-unschedulable-spread" /
+"spread-unschedulable"; tests/test_spread_engine_unschedulable.py on the emulation, tests/test_gpu_spread_unschedulable.py on the
+device): known shapes, the comparison helpers and the fuzz runners.
+
+What the reference does with a pod nothing takes stands in tests/unschedulable_cases.py. With topology two things are new. The
+error can be Topology (3): the pod's domain choice leaves a template's requirement set no domain (nodeclaim.go:164-242). And the
+second round PLACES pods (scheduler.go:442-446): a pod with required affinity to a pod later in the queue fails at its first pop
+and succeeds at a later one, so `pops` exceeds pods + failed pods, the queue gets shorter between retries, and the pods behind a
+success get further pops."""
+import daemonset_cases as dc
+import operator_cases as oc
+import parity
+import spread_limit_cases as slc
+import spread_node_cases as sn
+import spread_operator_cases as soc
+import test_spread_engine as tse
+import unschedulable_cases as uc
+from karpenter_amd import fixtures as fx
+from karpenter_amd.scheduling import NewScheduler
+
+solve, same = dc.solve, dc.same
+AUTO, ONLY = "auto-unschedulable-spread", "spread-unschedulable"   # 22, 23
+BASE, BASE_ONLY = "auto-unschedulable", "spread-operators"         # 20, 19: every switch but the one under test
+WEB = {"app": "web"}
+errors_of, n_pods = uc.errors_of, uc.n_pods
+
+
+def where(res):
+    return res["counters"]["engine"], res["counters"]["engineFallbackReason"]
+
+
+def check_engine(oracle, lib, prob, want=None):
+    """One problem five ways. The oracle's answer (`want`: computed before). "auto-unschedulable" (20) ends on the general engine
+    with reason 27 and equals it; "spread-operators" (19) refuses and names 27: what every setting up to 21 does.
+    "spread-unschedulable" and "auto-unschedulable-spread" end on the spread engine — no fallback, reason 0 — and equal the oracle in
+    claims and their order, hostnames, pod errors with their flags, the reference-equivalent evaluation count (dc.same) and queue
+    pops; the two give one digest."""
+    want = want or oracle.solve(prob)
+    plain = solve(prob, BASE, lib)
+    assert where(plain) == ("general", 27), plain["counters"]
+    same(plain, want)
+    text = soc.refusal(prob, BASE_ONLY, lib)
+    assert "spread engine declined the problem (reason 27)" in text, text
+    out = []
+    for engine in (ONLY, AUTO):
+        got = solve(prob, engine, lib)
+        assert where(got) == ("spread", 0), (engine, got["counters"])
+        digest = parity.results_digest(got)[0]   # (before same(): under DaemonSets it puts the instance-type lists into a canonical order)
+        same(got, want)
+        assert got["counters"]["pops"] == want["counters"]["pops"], (engine, got["counters"]["pops"], want["counters"]["pops"])
+        out.append((got, digest))
+    assert out[0][1] == out[1][1]
+    return out[0][0], want
+
+
+def check_declined(oracle, lib, prob, reason):
+    """A problem the spread engine still hands back under 22 / 23: "spread-unschedulable" refuses and names `reason` (0: the batch is
+    not offered to a fast engine at all, "outside its shape"), "auto-unschedulable-spread" equals the oracle on the general engine
+    with it."""
+    text = soc.refusal(prob, ONLY, lib)
+    assert ("outside its shape" if reason == 0 else f"spread engine declined the problem (reason {reason})") in text, text
+    auto = solve(prob, AUTO, lib)
+    assert where(auto) == ("general", reason), auto["counters"]
+    same(auto, oracle.solve(prob))
+    return auto
+
+
+# ---- the building blocks ---------------------------------------------------------------------------------------------------------------
+
+def web(n, cpu, labels=WEB):
+    """n pods labelled app=web with a zonal spread on that label."""
+    return [fx.pod(requests={"cpu": cpu}, labels=labels, topology_spread=[fx.spread(fx.ZONE, labels)]) for _ in range(n)]
+
+
+def aff(x, key=fx.ZONE):
+    """required pod affinity on `key` to app=x"""
+    return [fx.affinity_term(key, {"app": x})]
+
+
+def chain_pods(pinned=True):
+    """2 x a (3 cpu, affinity to b), 2 x b (2 cpu, affinity to c), 2 x c (1 cpu; pinned: nodeSelector test-zone-2). Queue order is a,
+    b, c: a and b fail at their first pop (nobody to be affine to, and they do not match their own selector); c opens a claim; the
+    second round places b, the third places a — when c's claim is down to ONE zone (topology.go:207)."""
+    sel = {fx.ZONE: "test-zone-2"} if pinned else None
+    return ([fx.pod(requests={"cpu": "3"}, labels={"app": "a"}, pod_requirements=aff("b")) for _ in range(2)] +
+            [fx.pod(requests={"cpu": "2"}, labels={"app": "b"}, pod_requirements=aff("c")) for _ in range(2)] +
+            [fx.pod(requests={"cpu": "1"}, labels={"app": "c"}, node_selector=sel) for _ in range(2)])
+
+
+def problem(pods, **pool):
+    return fx.problem(fx.fake_instance_types(8), [fx.node_pool(**pool)], pods)
+
+
+def chain_web_problem():
+    return problem(chain_pods() + web(6, "500m"))
+
+
+def chain_unpinned_problem():
+    return problem(chain_pods(pinned=False) + web(6, "500m"))
+
+
+def chain_nodes_problem():
+    return fx.with_existing_nodes(chain_unpinned_problem(), 4, seed=1)
+
+
+def chain_limits_problem():
+    return problem(chain_pods() + web(6, "500m"), limits={"cpu": "8"})
+
+
+def limits_problem():
+    """One 100-cpu pod, twelve 3-cpu spread pods, limits cpu 16: the big pod fails with InstanceTypes first and with Limits at its retry."""
+    return problem([fx.pod(requests={"cpu": "100"})] + web(12, "3"), limits={"cpu": "16"})
+
+
+def interleaved_problem():
+    """Four pods in queue order: z (3 cpu, pinned to test-zone-2) opens a claim; x1 (2 cpu, affinity to app=y) fails — nobody to be
+    affine to; y (2 cpu, app=y, pinned to test-zone-2) joins z's claim; x2, of x1's CLASS, is placed beside it. The verdict x1 left
+    for its class must not outlive y's commit. The second round places x1."""
+    pin = {fx.ZONE: "test-zone-2"}
+    pods = [fx.pod(requests={"cpu": "3"}, labels={"app": "z"}, node_selector=pin),
+            fx.pod(requests={"cpu": "2"}, labels={"app": "x"}, pod_requirements=aff("y")),
+            fx.pod(requests={"cpu": "2"}, labels={"app": "y"}, node_selector=pin),
+            fx.pod(requests={"cpu": "2"}, labels={"app": "x"}, pod_requirements=aff("y"))]
+    return problem(pods)
+
+
+def interleaved_nodes_problem():
+    """interleaved with existing nodes that have room, and without z: x1 (200m, affinity to app=y) fails; y (200m, app=y) lands on a
+    NODE; x2, of x1's class, follows y to that node's zone. The verdict x1 left for its class must not outlive a node placement
+    inside the loop."""
+    pods = [fx.pod(requests={"cpu": "200m"}, labels={"app": "x"}, pod_requirements=aff("y")),
+            fx.pod(requests={"cpu": "200m"}, labels={"app": "y"}),
+            fx.pod(requests={"cpu": "200m"}, labels={"app": "x"}, pod_requirements=aff("y"))]
+    return fx.with_existing_nodes(problem(pods), 3, seed=2, fill=(0.0, 0.1))
+
+
+def chain_on_nodes_problem():
+    """A chain small enough for the existing nodes: 2 x a (300m, affinity to b), 2 x b (200m, affinity to c), 2 x c (100m). c lands on
+    a node; the second round puts b ON A NODE, and a, whose class failed earlier in that round, must get a real attempt behind it:
+    a verdict must not outlive a node placement in the second round."""
+    pods = ([fx.pod(requests={"cpu": "300m"}, labels={"app": "a"}, pod_requirements=aff("b")) for _ in range(2)] +
+            [fx.pod(requests={"cpu": "200m"}, labels={"app": "b"}, pod_requirements=aff("c")) for _ in range(2)] +
+            [fx.pod(requests={"cpu": "100m"}, labels={"app": "c"}) for _ in range(2)])
+    return fx.with_existing_nodes(problem(pods), 3, seed=2, fill=(0.0, 0.1))
+
+
+def hand_problems():
+    """(name, problem, (pops, claims, errors) of the oracle): the issue's table, facts about the reference."""
+    tail40 = [fx.pod(requests={"cpu": "1m"}, labels={"app": "tail"}, pod_requirements=aff("nobody")) for _ in range(40)]
+    anti = {"app": "anti"}
+    zonal_anti = [fx.pod(requests={"cpu": "1"}, labels=anti, pod_anti_requirements=[fx.affinity_term(fx.ZONE, anti)]) for _ in range(5)]
+    host = {"app": "host"}
+    host_anti = [fx.pod(requests={"cpu": "1"}, labels=host, pod_anti_requirements=[fx.affinity_term(fx.HOSTNAME, host)]) for _ in range(6)]
+    own = {"app": "own"}
+    two = [fx.pod(requests={"cpu": "1"}, labels=own, topology_spread=[fx.spread(fx.ZONE, own)], pod_requirements=aff("nobody", fx.CAPACITY_TYPE)) for _ in range(3)]
+    return [("spread+big", uc.spread_problem(), (14, 3, {(4, 21): 1})),
+            ("chain", problem(chain_pods()), (12, 2, {})),
+            ("chain+web", chain_web_problem(), (18, 4, {})),
+            ("chain+web+big", problem(chain_pods() + web(6, "500m") + [fx.pod(requests={"cpu": "100"})]), (22, 4, {(4, 21): 1})),
+            ("chain+limits", chain_limits_problem(), (23, 1, {(7, 0): 7})),
+            ("chain+tail40", problem(chain_pods() + web(6, "500m") + tail40), (138, 4, {(3, 0): 40})),
+            ("chain-unpinned", chain_unpinned_problem(), (16, 3, {(3, 0): 4})),
+            ("chain-nodes", chain_nodes_problem(), (18, 3, {})),
+            ("absent-affinity", problem(web(6, "1") + [fx.pod(requests={"cpu": "1500m"}, labels={"app": "x"}, pod_requirements=aff("nobody")) for _ in range(3)]), (12, 3, {(3, 0): 3})),
+            ("zonal-anti", problem(zonal_anti + web(6, "500m")), (15, 3, {(3, 0): 4})),
+            ("limits", limits_problem(), (14, 2, {(7, 0): 11})),
+            ("host-anti-limits", problem(host_anti, limits={"cpu": "6"}), (6, 1, {(7, 0): 5})),
+            ("two-groups", problem(web(6, "1") + two), (12, 3, {(3, 0): 3})),
+            # (not of the issue's table: a kept verdict against a commit on a claim inside the loop, on a node inside the loop, on a node in the second round)
+            ("interleaved", interleaved_problem(), (5, 2, {})),
+            ("interleaved-nodes", interleaved_nodes_problem(), (4, 0, {})),
+            ("chain-on-nodes", chain_on_nodes_problem(), (12, 0, {}))]
+
+
+def check_expectation(prob, want, expect):
+    pops, claims, errors = expect
+    assert (want["counters"]["pops"], len(want["newNodeClaims"]), errors_of(want)) == (pops, claims, errors), \
+        (want["counters"]["pops"], len(want["newNodeClaims"]), errors_of(want))
+
+
+# ---- further cases from the existing modules: the oracle leaves pod errors, no table figures -------------------------------------------
+
+def daemonset_problem():
+    """uc.daemonset_problem()'s pods with a zonal spread: the DaemonSet's overhead alone makes the 7800m pods unschedulable."""
+    prob = uc.daemonset_problem()
+    lab = {"app": "ds"}
+    pods = [dict(p, labels=lab, topologySpreadConstraints=[fx.spread(fx.ZONE, lab)]) for p in prob["pods"]]
+    return dict(prob, pods=pods)
+
+
+def complement_problem():
+    """A pool zone NotIn [test-zone-1] alone under six spread pods, and two pods pinned to test-zone-1 — out of the pool: Incompatible
+    (2) on a complement template. (The pinned pods carry no spread of their own: a nodeSelector next to a spread is reason 43.)"""
+    pool = fx.node_pool("not-1", requirements=[fx.req(fx.ZONE, "NotIn", "test-zone-1")])
+    pods = web(6, "1") + [fx.pod(requests={"cpu": "500m"}, node_selector={fx.ZONE: "test-zone-1"}) for _ in range(2)]
+    return fx.problem(fx.fake_instance_types(8), [pool], pods)
+
+
+def stage_chain_alone():
+    """slc.stage_chain_problem(3) without its catch-all pool: limit stages are created during failing walks too."""
+    prob = slc.stage_chain_problem(3)
+    return dict(prob, nodePools=[p for p in prob["nodePools"] if p["name"] != "catch-all"])
+
+
+def tainted_first_problem():
+    """A heavier tainted pool in front of an open one: spread pods (placed by the open pool), a 100-cpu pod and an affinity pod
+    without a target — the FIRST template's error is Taints (1) for both, whatever the second template says (4 and 3)."""
+    pools = [fx.node_pool("tainted", weight=10, taints=oc.taint("tainted")), fx.node_pool("open")]
+    pods = web(6, "1") + [fx.pod(requests={"cpu": "100"}), fx.pod(requests={"cpu": "500m"}, labels={"app": "x"}, pod_requirements=aff("nobody"))]
+    return fx.problem(fx.fake_instance_types(8), pools, pods)
+
+
+def no_template_problem():
+    """uc.no_template_problem()'s pool with spread pods: NoTemplates (6), and the first pop of the second round ends the loop."""
+    pools = [fx.node_pool("nowhere", requirements=[fx.req(fx.ZONE, "In", uc.ABSENT)])]
+    return fx.problem(fx.fake_instance_types(8), pools, web(9, "1"))
+
+
+def further_problems():
+    return [("daemonset", daemonset_problem()), ("complement", complement_problem()), ("stage-chain", stage_chain_alone()),
+            ("tainted-first", tainted_first_problem()), ("no-template", no_template_problem())]
+
+
+# ---- still declined ----------------------------------------------------------------------------------------------------------------------
+
+def declined_problems():
+    """(name, problem, reason): a failing pod with a node-affinity preference (0: its relaxation rows keep the batch away from every
+    fast engine — the host decides before the kernel's own guard, DECLINE_TOPO_PREFERENCES 41, is asked), a pod with a nodeSelector
+    AND a spread (43), pod-side NotIn (4), pod-side Gt / Lt and a NodePool with minValues (1), and more limit stages than template
+    ids (29) — each on top of a batch that leaves a pod unschedulable."""
+    base = uc.spread_problem()
+    more = lambda *pods: dict(base, pods=base["pods"] + list(pods))
+    pref = fx.pod(requests={"cpu": "100"}, node_preferences=[fx.req(fx.ZONE, "In", "test-zone-1")])
+    sel = fx.pod(requests={"cpu": "1"}, labels=WEB, node_selector={fx.ZONE: "test-zone-1"}, topology_spread=[fx.spread(fx.ZONE, WEB)])
+    notin = fx.pod(requests={"cpu": "1"}, node_requirements=[fx.req(fx.ZONE, "NotIn", "test-zone-3")])
+    gt = fx.pod(requests={"cpu": "1"}, node_requirements=[fx.req(fx.FAKE_INTEGER_LABEL, "Gt", 4)])
+    lt = fx.pod(requests={"cpu": "1"}, node_requirements=[fx.req(fx.FAKE_INTEGER_LABEL, "Lt", 3)])
+    minv = dict(base, nodePools=[fx.node_pool(requirements=[fx.req(fx.INSTANCE_TYPE, "Exists", min_values=2)])])
+    stages = slc.stage_chain_problem(4)
+    stages = dict(stages, pods=stages["pods"] + [fx.pod(requests={"cpu": "10000"})])
+    return [("preference", more(pref), 0), ("selector+spread", more(sel), 43), ("pod-notin", more(notin), 4), ("pod-gt", more(gt), 1),
+            ("pod-lt", more(lt), 1), ("min-values", minv, 1), ("limit-stages", stages, 29)]
+
+
+# ---- repeated solves ---------------------------------------------------------------------------------------------------------------------
+
+def digests_of_repeated_solves(lib, prob, engine, n):
+    """limit_cases.digests_of_repeated_solves for a spread handle."""
+    s = NewScheduler(dict(prob, options=dict(prob.get("options", {}), engine=engine)), solver_lib=lib)
+    try:
+        out = set()
+        for _ in range(n):
+            r = s.Solve()
+            assert where(r) == ("spread", 0), r["counters"]
+            out.add(parity.results_digest(r)[0])
+        return out, r
+    finally:
+        s.close()
+
+
+# ---- fuzz ----------------------------------------------------------------------------------------------------------------------------------
+
+SHAPE_REASONS = set(range(1, 9)) | {20, 21, 25, 26, 29} | set(range(30, 37)) | set(range(40, 52)) | {60, 61, 62, 100}   # decline.h without 27
+
+
+def run_fuzz(oracle, lib, family, seeds):
+    """family(seed) under "auto-unschedulable-spread": every seed equals the oracle, pops included; a seed that leaves the spread
+    engine does so with a shape reason, never 27, and is printed with it. Returns (seeds with pod errors in the oracle, seeds on the
+    spread engine, {seed: reason} of the rest)."""
+    with_errors, on_spread, rest = 0, 0, {}
+    for seed in seeds:
+        prob = family(seed)
+        want = oracle.solve(prob)
+        with_errors += bool(want["podErrors"])
+        got = solve(prob, AUTO, lib)
+        sn.same(got, want, prob)
+        assert got["counters"]["pops"] == want["counters"]["pops"], (seed, got["counters"]["pops"], want["counters"]["pops"])
+        engine, reason = where(got)
+        assert reason != 27, (seed, got["counters"])
+        if engine == "spread":
+            assert reason == 0, (seed, got["counters"])
+            on_spread += 1
+        else:
+            assert engine in ("general", "cursor") and (engine == "cursor" or reason in SHAPE_REASONS), (seed, got["counters"])
+            if engine == "general":
+                rest[seed] = reason
+    print(f"{AUTO}: {on_spread} of {len(seeds)} seeds of {family.__module__}.{family.__name__} on the spread engine ({with_errors} with pod errors in the oracle); reasons of the rest {rest}")
+    return with_errors, on_spread, rest
+
+
+FAMILIES = {"operators": (soc.fuzz_problem, list(range(120))), "limits": (tse.fuzz_problem, slc.FUZZ_SEEDS), "nodes": (sn.fuzz_problem, list(range(48)))}
