@@ -949,6 +949,16 @@ ksolve_status ksolve_test_reqalg(const ksolve_test_reqalg_in* in, ksolve_test_re
 ksolve_status ksolve_test_it_index(const ksolve_test_it_index_in* in, ksolve_test_it_index_out* out) {
   return test_on_bare_handle("ksolve_test_it_index", [&](ksolve_handle* h) { return ksi::test_it_index(h, in, out); });
 }
+// the queue order, the queue marking and the static node rows alone (ksolve_impl.h test_sort_pods, test_fast_queue, test_node_dead0; test builds only)
+ksolve_status ksolve_test_sort_pods(const ksolve_test_sort_pods_in* in, ksolve_test_sort_pods_out* out) {
+  return test_on_bare_handle("ksolve_test_sort_pods", [&](ksolve_handle* h) { return ksi::test_sort_pods(h, in, out); });
+}
+ksolve_status ksolve_test_fast_queue(const ksolve_test_fast_queue_in* in, ksolve_test_fast_queue_out* out) {
+  return test_on_bare_handle("ksolve_test_fast_queue", [&](ksolve_handle* h) { return ksi::test_fast_queue(h, in, out); });
+}
+ksolve_status ksolve_test_node_dead0(const ksolve_test_node_dead0_in* in, ksolve_test_node_dead0_out* out) {
+  return test_on_bare_handle("ksolve_test_node_dead0", [&](ksolve_handle* h) { return ksi::test_node_dead0(h, in, out); });
+}
 #endif
 ksolve_status ksolve_probe_create(ksolve_handle* base, const ksolve_probe* probe, ksolve_handle** out) {
   if (!out) return KSOLVE_ERR_INVALID;

@@ -202,6 +202,58 @@ typedef struct {
   uint32_t error, it_words;
 } ksolve_test_it_index_out;
 
+// ksolve_test_sort_pods — TEST BUILDS ONLY: the queue order (be_sort_pods: ksolve_iota, five passes of ksolve_sort_key and a stable
+// radix sort) alone on raw host tables, uploaded and sized as create() does. tests/queue_cases.py holds the definition.
+typedef struct {
+  uint32_t n_pods, n_rows;                         // n_rows >= n_pods: the stride of `requests`
+  const int64_t* requests;                         // [2][n_rows]: cpu, memory
+  const int64_t* creation;                         // [n_pods]
+  const uint64_t *uid_hi, *uid_lo;                 // [n_pods]
+} ksolve_test_sort_pods_in;
+typedef struct {
+  uint32_t* sorted;                                // [n_pods] the caller's
+} ksolve_test_sort_pods_out;
+
+// ksolve_test_fast_queue — TEST BUILDS ONLY: the queue marking (be_launch_fast_queue: ksolve_fast_queue, ksolve_fast_overlap,
+// ksolve_fast_mark) alone on a given queue: the three fills of solve_prepare(), one launch with fw.enabled set, everything it wrote
+// downloaded. Every sorted[i] < n_rows and every row_class[r] < n_classes (checked).
+typedef struct {
+  uint32_t n_pods, n_rows, n_classes;
+  const uint32_t* sorted;                          // [n_pods]
+  const uint32_t* row_class;                       // [n_rows]
+  uint32_t count_live;
+} ksolve_test_fast_queue_in;
+typedef struct {
+  uint32_t *q_class, *q_claim;                     // [n_pods] the caller's
+  uint32_t *cls_first, *cls_last;                  // [n_classes] the caller's
+  uint32_t max_active;
+} ksolve_test_fast_queue_out;
+
+// ksolve_test_node_dead0 — TEST BUILDS ONLY: the static (class, node) rows (kernels.h node_dead0_body over nodecheck.h) alone. The
+// class records are laid out by be_launch_class_gather with class_rep[k] = k from the class-side tables, the node side is uploaded as
+// it comes (the SoA layout of NodeTabs, stride n_nodes), then one be_launch_node_dead0 without node bounds, as both of its callers
+// have it. node_words = ceil(n_nodes / 64). tests/node_row_cases.py holds the definition.
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;
+  const int64_t* value_int;
+  const uint64_t *value_is_int, *value_valid;
+  uint32_t n_classes, n_res;
+  const ksolve_reqsets* cls_reqs;                  // n_classes rows
+  const int64_t* requests;                         // [n_res][n_classes]
+  const uint64_t* tolerates;                       // [n_classes]
+  const uint64_t* host_ports;                      // [n_classes][2] (ports | conflicting triples) or null
+  uint32_t n_nodes, hp_on;
+  const uint64_t* node_mask;                       // [req_words][n_nodes]
+  const uint32_t *node_defined, *node_complement;  // [n_nodes]
+  const int64_t* node_remaining;                   // [n_res][n_nodes]
+  const uint64_t* node_taints;                     // [n_nodes]
+  const uint64_t* node_hp;                         // [n_nodes] or null
+} ksolve_test_node_dead0_in;
+typedef struct {
+  uint64_t* dead0;                                 // [n_classes][node_words] the caller's
+  uint32_t node_words;
+} ksolve_test_node_dead0_out;
+
 namespace ks {
 struct ReqalgTestArgs {
   Dict dict;
@@ -1304,6 +1356,111 @@ static ksolve_status test_it_index(ksolve_handle* h, const ksolve_test_it_index_
   be_d2h(h, out->key_neg, key_neg, (size_t)nk * it_words * 8);
   be_d2h(h, out->it_alloc_ok, alloc_ok, (size_t)it_words * 8);
   be_d2h(h, &out->error, A.error, 4);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The queue order alone (see ksolve_test_sort_pods_in): create()'s uploads and buffers, solve_prepare()'s phase 3.
+static ksolve_status test_sort_pods(ksolve_handle* h, const ksolve_test_sort_pods_in* in, ksolve_test_sort_pods_out* out) {
+  if (!in || !out || !in->requests || !in->creation || !in->uid_hi || !in->uid_lo || !out->sorted) return fail(h, KSOLVE_ERR_INVALID, "test_sort_pods: missing table");
+  const uint32_t n = in->n_pods, n_rows = in->n_rows;
+  if (n < 1 || n_rows < n || n > 0x7FFFFFFFu) return fail(h, KSOLVE_ERR_INVALID, "test_sort_pods: sizes out of range");
+  h->n_pods = n; h->n_rows = n_rows;
+  ks::SortKeyArgs& S = h->sort_args;
+  S.n_pods = (int)n; S.n_rows = (int)n_rows; S.requests = up(h, in->requests, (size_t)2 * n_rows);
+  S.creation = up(h, in->creation, n);
+  S.uid_hi = up(h, in->uid_hi, n); S.uid_lo = up(h, in->uid_lo, n);
+  h->d_idx_a = dz<uint32_t>(h, n); h->d_idx_b = dz<uint32_t>(h, n);
+  h->d_key_a = dz<uint64_t>(h, n); h->d_key_b = dz<uint64_t>(h, n);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_sort_pods(h);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_d2h(h, out->sorted, h->pv.sorted_pods, (size_t)n * 4);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The queue marking alone (see ksolve_test_fast_queue_in): the buffers of fast_shared_alloc() and solve_prepare(), its three fills, one
+// be_launch_fast_queue.
+static ksolve_status test_fast_queue(ksolve_handle* h, const ksolve_test_fast_queue_in* in, ksolve_test_fast_queue_out* out) {
+  if (!in || !out || !in->sorted || !in->row_class || !out->q_class || !out->q_claim || !out->cls_first || !out->cls_last) return fail(h, KSOLVE_ERR_INVALID, "test_fast_queue: missing table");
+  const uint32_t n = in->n_pods, n_rows = in->n_rows, nc = in->n_classes;
+  if (n < 1 || n_rows < 1 || nc < 1 || n > 0x7FFFFFFFu || nc > 0x7FFFFFFFu) return fail(h, KSOLVE_ERR_INVALID, "test_fast_queue: sizes out of range");
+  for (uint32_t i = 0; i < n; ++i) if (in->sorted[i] >= n_rows) return fail(h, KSOLVE_ERR_INVALID, "test_fast_queue: a queue entry outside the rows");
+  for (uint32_t r = 0; r < n_rows; ++r) if (in->row_class[r] >= nc) return fail(h, KSOLVE_ERR_INVALID, "test_fast_queue: a row class outside the classes");
+  h->n_pods = n; h->n_rows = n_rows; h->n_classes = nc;
+  h->pv.sorted_pods = up(h, in->sorted, n);
+  h->pv.row_class = up(h, in->row_class, n_rows);
+  fast_shared_alloc(h, 1, 0);
+  h->fw.cls_first = dz<uint32_t>(h, nc); h->fw.cls_last = dz<uint32_t>(h, nc);
+  h->fw.enabled = 1;   // (the overlap launch is the cursor engine's)
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_fill(h, h->fw.cls_first, 0xFF, (size_t)nc * 4); be_fill(h, h->fw.cls_last, 0, (size_t)nc * 4); be_fill(h, h->fw.max_active, 0, 4);
+  be_launch_fast_queue(h, in->count_live != 0);
+  be_d2h(h, out->q_class, h->fw.q_class, (size_t)n * 4);
+  be_d2h(h, out->q_claim, h->fw.q_claim, (size_t)n * 4);
+  be_d2h(h, out->cls_first, h->fw.cls_first, (size_t)nc * 4);
+  be_d2h(h, out->cls_last, h->fw.cls_last, (size_t)nc * 4);
+  be_d2h(h, &out->max_active, h->fw.max_active, 4);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The static node rows alone (see ksolve_test_node_dead0_in): the class tables as create() and solve_prepare() make them (every class
+// its own representative row), the node tables as create() uploads them, the launch of sweep_prepare() / node_static_rows().
+static ksolve_status test_node_dead0(ksolve_handle* h, const ksolve_test_node_dead0_in* in, ksolve_test_node_dead0_out* out) {
+  if (!in || !out || !in->cls_reqs || !in->cls_reqs->mask || !in->cls_reqs->defined || !in->cls_reqs->complement || !in->requests || !in->tolerates || !in->node_mask ||
+      !in->node_defined || !in->node_complement || !in->node_remaining || !in->node_taints || !out->dead0) return fail(h, KSOLVE_ERR_INVALID, "test_node_dead0: missing table");
+  const uint32_t nk = in->n_keys, nc = in->n_classes, nr = in->n_res, ne = in->n_nodes;
+  if (nc < 1 || ne < 1 || nr < 1 || nr > (uint32_t)kMaxRes || nc > 0x7FFFFFu || ne > 0x7FFFFFFFu) return fail(h, KSOLVE_ERR_INVALID, "test_node_dead0: sizes out of range");
+  if ((!in->cls_reqs->gte && any_nonzero(in->cls_reqs->has_gte, nc)) || (!in->cls_reqs->lte && any_nonzero(in->cls_reqs->has_lte, nc))) return fail(h, KSOLVE_ERR_INVALID, "test_node_dead0: a has_gte / has_lte bit without the bounds column");
+  ks::RowArgs& R = h->row_args;
+  ks::Dict dict{};
+  if (ksolve_status st = test_dict(h, "test_node_dead0", nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, dict)) return st;
+  const uint32_t rw = (uint32_t)dict.req_words, nw = (ne + 63) / 64;
+  h->n_keys = nk; h->req_words = rw; h->n_res = nr; h->n_rows = nc; h->n_classes = nc; h->n_nodes = ne;
+  // ---- the class side: rows as create() uploads them, class tables as solve_prepare() sizes and gathers them ----
+  R.dict = dict; R.n_rows = (int)nc; R.n_res = (int)nr;
+  R.requests = up(h, in->requests, (size_t)nr * nc);
+  bool rows_nil = true;
+  if (in->cls_reqs->min_values) for (size_t i = 0; i < (size_t)nc * nk; ++i) if (in->cls_reqs->min_values[i] >= 0) rows_nil = false;
+  R.reqs = upload_reqs(h, *in->cls_reqs, nc, rw, nk, !rows_nil);
+  R.strict = R.reqs;
+  R.tolerates = up(h, in->tolerates, nc);
+  R.vol = nullptr; R.cls_vol = nullptr; R.topo_words = 0; R.topo_owned = nullptr; R.topo_selected = nullptr; R.cls_topo = nullptr;
+  R.host_ports = in->host_ports ? up(h, in->host_ports, (size_t)nc * 2) : nullptr;
+  const ks::RecLayout lay{(int)rw, 1, (int)nr, (int)nk};
+  std::vector<uint32_t> rep(nc);
+  for (uint32_t k = 0; k < nc; ++k) rep[k] = k;
+  R.class_rep = up(h, rep.data(), nc);
+  R.cls_requests = dz<int64_t>(h, (size_t)nc * nr);
+  h->d_cls_reqs = alloc_reqs(h, nc, rw, nk);
+  h->d_cls_strict = alloc_reqs(h, nc, rw, nk);
+  R.cls_reqs = h->d_cls_reqs; R.cls_strict = h->d_cls_strict;
+  R.cls_tolerates = dz<uint64_t>(h, nc);
+  R.cls_host_ports = R.host_ports ? dz<uint64_t>(h, (size_t)nc * 2) : nullptr;
+  R.cls_hot = dz<uint64_t>(h, (size_t)nc * lay.k_hot_words());
+  R.cls_cold = dz<uint64_t>(h, (size_t)nc * lay.cold_words());
+  R.lay = lay;
+  R.min_request = dz<int64_t>(h, nr);
+  // ---- the node side ----
+  const uint64_t* n_mask0 = up(h, in->node_mask, (size_t)rw * ne);
+  const uint32_t* n_defined0 = up(h, in->node_defined, ne);
+  const uint32_t* n_complement0 = up(h, in->node_complement, ne);
+  const int64_t* n_remaining0 = up(h, in->node_remaining, (size_t)nr * ne);
+  const uint64_t* node_taints = up(h, in->node_taints, ne);
+  const uint64_t* node_hp0 = in->node_hp ? up(h, in->node_hp, ne) : nullptr;
+  uint64_t* dead0 = dz<uint64_t>(h, (size_t)nc * nw);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_fill(h, R.min_request, 0x7F, (size_t)nr * 8);
+  be_launch_class_gather(h, (int)nc, R);
+  ks::NodeDeadArgs a{};
+  a.dict = dict; a.lay = lay; a.n_nodes = (int)ne; a.node_words = (int)nw; a.n_classes = (int)nc; a.hp_on = in->hp_on ? 1 : 0;
+  a.cls_hot = R.cls_hot; a.cls_cold = R.cls_cold; a.cls_hp = R.cls_host_ports; a.node_taints = node_taints;
+  a.pristine.mask = n_mask0; a.pristine.defined = n_defined0; a.pristine.complement = n_complement0;
+  a.pristine.hg = nullptr; a.pristine.hl = nullptr; a.pristine.gte = nullptr; a.pristine.lte = nullptr;
+  a.pristine.remaining = n_remaining0; a.pristine.hp = node_hp0; a.pristine.stride = ne;
+  a.dead0 = dead0;
+  be_launch_node_dead0(h, (int)nw, a);
+  out->node_words = nw;
+  be_d2h(h, out->dead0, dead0, (size_t)nc * nw * 8);
   be_sync(h);
   return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
 }

@@ -224,6 +224,17 @@ static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, 
   be_toc(h, ksi::T_PACK);
 }
 
+// a test-only entry point's run on a bare handle, as the device build's test_on_bare_handle has it
+template <class F>
+static ksolve_status test_on_bare_handle(const char* who, F run) {
+  ksolve_handle* h = new ksolve_handle();
+  h->backend = new EmuBackend();
+  const ksolve_status st = run(h);
+  if (st != KSOLVE_OK) fprintf(stderr, "%s: %s\n", who, h->error.c_str());
+  ksolve_destroy(h);
+  return st;
+}
+
 extern "C" {
 ksolve_status ksolve_create(const ksolve_problem_desc* desc, const ksolve_options* opts, ksolve_handle** out) {
   ksolve_handle* h = new ksolve_handle();
@@ -292,6 +303,16 @@ ksolve_status ksolve_test_it_index(const ksolve_test_it_index_in* in, ksolve_tes
   if (st != KSOLVE_OK) fprintf(stderr, "ksolve_test_it_index: %s\n", h->error.c_str());
   ksolve_destroy(h);
   return st;
+}
+// the queue order, the queue marking and the static node rows alone (ksolve_impl.h test_sort_pods, test_fast_queue, test_node_dead0)
+ksolve_status ksolve_test_sort_pods(const ksolve_test_sort_pods_in* in, ksolve_test_sort_pods_out* out) {
+  return test_on_bare_handle("ksolve_test_sort_pods", [&](ksolve_handle* h) { return ksi::test_sort_pods(h, in, out); });
+}
+ksolve_status ksolve_test_fast_queue(const ksolve_test_fast_queue_in* in, ksolve_test_fast_queue_out* out) {
+  return test_on_bare_handle("ksolve_test_fast_queue", [&](ksolve_handle* h) { return ksi::test_fast_queue(h, in, out); });
+}
+ksolve_status ksolve_test_node_dead0(const ksolve_test_node_dead0_in* in, ksolve_test_node_dead0_out* out) {
+  return test_on_bare_handle("ksolve_test_node_dead0", [&](ksolve_handle* h) { return ksi::test_node_dead0(h, in, out); });
 }
 // The product's Go-sort (csrc/go_sort.h, used by the finalize kernel for OrderByPrice) on an array of integer keys:
 // out_perm receives the original indices in sorted order, ties as Go's sort.Slice leaves them.
