@@ -984,6 +984,10 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // such pods too and retries them as the reference's second round does — a pod whose affinity target sits later in the batch is
 // placed there — instead of handing a topology batch to the general engine (reason 27). KsolveEngineSpreadUnschedulable (23) is
 // the spread engine alone with that switch and refuses instead of falling back (tests).
+// KsolveEngineAutoFiltersSpread = "auto-filters-spread" (24): KsolveEngineAutoUnschedulableSpread, and the spread engine evaluates
+// topology node filters that can say no — a Deployment with a spread constraint AND a nodeSelector, required node affinity or
+// nodeTaintsPolicy Honor no longer sends its batch to the general engine (reason 43). KsolveEngineSpreadFilters (25) is the spread
+// engine alone with that switch and refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -1005,6 +1009,9 @@ const (
 
 	KsolveEngineAutoUnschedulableSpread uint32 = 22
 	KsolveEngineSpreadUnschedulable     uint32 = 23
+
+	KsolveEngineAutoFiltersSpread uint32 = 24
+	KsolveEngineSpreadFilters     uint32 = 25
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

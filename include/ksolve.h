@@ -277,7 +277,9 @@ typedef struct {
                                     * limits / s-limits = the cursor / spread engine goes on when a NodePool limit binds; operators = the
                                     * cursor engine takes NodePools whose requirements are not In sets; s-operators = the spread engine does;
                                     * unschedulable = the cursor engine keeps pods that can go nowhere and reports their errors;
-                                    * s-unschedulable = the spread engine does, and retries them for real.
+                                    * s-unschedulable = the spread engine does, and retries them for real; s-filters = the spread engine
+                                    * counts pods through topology node filters that can say no (a spread constraint beside a nodeSelector,
+                                    * required node affinity, or nodeTaintsPolicy Honor over tainted NodePools or nodes).
                                     *
                                     *    value  name                 engines that may run       a decline     switches
                                     *      0    auto                 cursor, spread, general    falls back    -
@@ -304,7 +306,9 @@ typedef struct {
                                     *     21    cursor-unschedulable cursor                     refuses       nodes, limits, operators, unschedulable
                                     *     22    auto-unschedulable-spread cursor, spread, general falls back nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable, s-unschedulable
                                     *     23    spread-unschedulable spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable
-                                    *   above 23: no name; as 17.
+                                    *     24    auto-filters-spread  cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable, s-unschedulable, s-filters
+                                    *     25    spread-filters       spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable, s-filters
+                                    *   above 25: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is

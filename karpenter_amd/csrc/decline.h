@@ -41,7 +41,9 @@ enum Decline : int {
   DECLINE_TOPO_GROUPS = 40,            // no topology group, more than kTopoMaxGroups, or aliased groups
   DECLINE_TOPO_PREFERENCES = 41,       // a pod with preferences: podDomains = StrictRequirements differs from its requirements (topology.go:230)
   DECLINE_TOPO_RELAXATION_GROUP = 42,  // a group created by a relaxing pod (topology.go:162-194)
-  DECLINE_TOPO_NODE_FILTER = 43,       // a group's TopologyNodeFilter can reject a claim or node (topologynodefilter.go:68-96); create() raises it for tainted nodes
+  DECLINE_TOPO_NODE_FILTER = 43,       // a group's TopologyNodeFilter can reject a claim or node (topologynodefilter.go:68-96); create() raises it for tainted nodes.
+                                       // Engines 24 / 25 evaluate such filters themselves and keep 43 for what their slots do not hold: a term that is not positive In sets on
+                                       // packed variable keys, more than kTopoFiltTerms terms, more than kTopoFiltSlots filters decided per claim, a filter on a group that is no spread group
   DECLINE_TOPO_SKEW_RANGE = 44,        // dictionary-key spread: maxSkew outside 1..30000, or minDomains above 30000
   DECLINE_TOPO_HOST_AFFINITY = 45,     // pod affinity on the hostname
   DECLINE_TOPO_HOST_GROUPS = 46,       // more hostname groups than kTopoMaxHost

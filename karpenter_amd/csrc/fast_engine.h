@@ -145,6 +145,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   // engine — "Unschedulable pods" below. The arrays are allocated for such handles only, [n_pods] each, indexed by the order in which
   // the pods were set aside (the order of the reference's pushes, queue.go:63-66); us_n is reset by setup().
   int unsched;
+  int filt;               // engines 24 / 25 (a spread handle only): topology node filters that can say no are evaluated by the engine (topo_engine.h, "Topology node filters")
   uint32_t* us_n;         // [1] pods set aside
   uint32_t* us_entry;     // the pod's entry in the queue the loop reads
   uint32_t* us_last;      // lastLen (queue.go:63-66): the reference's queue length right after it pushed the pod back
@@ -153,6 +154,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   uint64_t* us_cls;       // [n_pods >= n_classes] by class: the verdict of the class's last failed template walk (FastCold::new_claim), reset by setup()
   uint32_t* pod_qpos;     // [n_pods], behind the existing-node stage only: a pod's position in the FULL queue (ksolve_fast_requeue)
 };
+static_assert(offsetof(FastWork, us_n) == offsetof(FastWork, unsched) + 8, "FastWork::filt fills the gap behind unsched: the layout every kernel reads stays what it was");
 
 // whole-record moves between LDS and registers (a struct behind an address-space-3 pointer has no implicit copy)
 typedef uint64_t __attribute__((may_alias)) u64_alias;   // the records are moved as 8-byte words whatever their field types

@@ -731,13 +731,15 @@ static void launch_pack_topo(ksolve_handle* h, void (*fn)(const ks::TopoArgs*), 
   hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::TopoArgs*)h->d_topo_args);
   hip_check(h, hipGetLastError(), what);
 }
-// (engines 22 / 23: the kernels with the set-aside list compiled in)
+// (engines 22 / 23: the kernels with the set-aside list compiled in; 24 / 25: those with the topology node filters as well)
 static void be_launch_pack_topo(ksolve_handle* h) {
-  if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_u, "ksolve_pack_topo_u launch");
+  if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_f, "ksolve_pack_topo_f launch");
+  else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_u, "ksolve_pack_topo_u launch");
   else launch_pack_topo(h, ksolve_pack_topo, "ksolve_pack_topo launch");
 }
 static void be_launch_pack_topo_nodes(ksolve_handle* h) {
-  if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_nodes_u, "ksolve_pack_topo_nodes_u launch");
+  if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_nodes_f, "ksolve_pack_topo_nodes_f launch");
+  else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_nodes_u, "ksolve_pack_topo_nodes_u launch");
   else launch_pack_topo(h, ksolve_pack_topo_nodes, "ksolve_pack_topo_nodes launch");
 }
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {

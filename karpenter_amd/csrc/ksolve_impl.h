@@ -991,15 +991,16 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     // plain_topo with nodes: plain_topo without its "no nodes" term, plus the node stage's own conditions (30-33) and what the spread
     // engine's node path rests on (topo_nodes.h): every node carries ONE value of every dictionary key a group uses (35), among the
     // sixteen a group's counters hold (36), and no group honours nodeTaintsPolicy while a node is tainted (43, extended to nodes:
-    // TopologyNodeFilter.Matches must be true for every node as it is for every claim). The view's plain_topo says it: a handle
-    // with nodes runs ksolve_pack_topo_nodes.
+    // TopologyNodeFilter.Matches must be true for every node as it is for every claim — unless the handle evaluates the filters
+    // itself, engines 24 / 25: such a group then gets a filter slot, topo_engine.h "Topology node filters"). The view's plain_topo
+    // says it: a handle with nodes runs ksolve_pack_topo_nodes.
     if (h->eng.spread_nodes && nodes && topology) {
       uint32_t why = nodes_decline(common && no_topo_bounds);
       std::vector<uint8_t> dom((size_t)d->n_keys * d->n_nodes, 0xFF);
       bool any_taint = false;
       for (uint32_t e = 0; e < d->n_nodes; ++e) any_taint = any_taint || d->node_taints[e] != 0;
       for (uint32_t g = 0; g < d->topo.n && !why; ++g) {
-        if (d->topo.filter_taint_honor[g] && any_taint) { why = ks::DECLINE_TOPO_NODE_FILTER; break; }
+        if (d->topo.filter_taint_honor[g] && any_taint && !h->eng.spread_filters) { why = ks::DECLINE_TOPO_NODE_FILTER; break; }
         const int32_t k = d->topo.key[g];
         if (k < 0 || dom[(size_t)k * d->n_nodes] != 0xFF) continue;   // the hostname, or a key an earlier group filled in
         for (uint32_t e = 0; e < d->n_nodes && !why; ++e) {
@@ -1064,6 +1065,9 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
     ks::TopoWork& tw = h->tw;
     tw.enabled = (!fw.enabled && P.plain_topo && d->topo.n > 0 && d->topo.n <= (uint32_t)ks::kTopoMaxGroups && d->n_res <= 4 && h->eng.may_spread() &&
                   d->n_pod_rows == d->n_pods && d->n_pods > 0 && !d->pod_node) ? 1 : 0;
+    // ... and engines 24 / 25 name what keeps a topology batch of pods with preferences from the spread engine as its own guard would
+    // (their relaxation rows: the host decides before the kernel is asked); every other setting leaves such a batch without a reason
+    if (!tw.enabled && h->eng.spread_filters && P.plain_topo && d->topo.n > 0 && d->n_pod_rows != d->n_pods && !h->fast_reason) h->fast_reason = ks::DECLINE_TOPO_PREFERENCES;
     if (tw.enabled) {
       fast_shared_alloc(h, mc, 0);
       fw.o_key = nullptr; fw.o_ord = nullptr; fw.o_snap = nullptr;
@@ -1076,6 +1080,8 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
         fw.us_n = dz<uint32_t>(h, 1); fw.us_entry = dz<uint32_t>(h, 2 * (size_t)d->n_pods); fw.us_last = dz<uint32_t>(h, 2 * (size_t)d->n_pods);
         fw.us_err = dz<uint8_t>(h, 2 * (size_t)d->n_pods); fw.us_diag = dz<uint8_t>(h, 2 * (size_t)d->n_pods); fw.us_cls = dz<uint64_t>(h, d->n_pods);   // (a class per pod at most)
       }
+      fw.filt = h->eng.spread_filters ? 1 : 0;   // engines 24 / 25: topology node filters that can say no (topo_engine.h, "Topology node filters")
+      if (fw.filt) tw.filt = dz<ks::TopoFilt>(h, 1);
       if (fw.ops) {
         // ... and whether this problem has one: what FastCold::setup() declines with reason 3 without the switch (the batch path asks)
         bool complement = any_nonzero(d->tmpl_reqs.complement, d->n_templates) || any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);

@@ -1,6 +1,6 @@
 // pack_kernels.h — the pack kernels (one wavefront per scheduling problem) live in translation units of their own, so that build()
 // compiles them side by side (the general engine's instantiations alone are minutes of one hipcc): ksolve_pack_general.hip,
-// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip. ksolve.hip (the HIP backend of the C
+// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip, ksolve_pack_topo_filter.hip. ksolve.hip (the HIP backend of the C
 // ABI) launches them through these declarations; no device function crosses a translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +37,9 @@ __global__ void ksolve_pack_topo_nodes(const ks::TopoArgs* a);   // ... with exi
 // ... and the two with the set-aside list and the second round of engines 22 / 23 compiled in (ksolve_pack_topo_unsched.hip)
 __global__ void ksolve_pack_topo_u(const ks::TopoArgs* a);
 __global__ void ksolve_pack_topo_nodes_u(const ks::TopoArgs* a);
+// ... and those two with the topology node filters of engines 24 / 25 compiled in as well (ksolve_pack_topo_filter.hip)
+__global__ void ksolve_pack_topo_f(const ks::TopoArgs* a);
+__global__ void ksolve_pack_topo_nodes_f(const ks::TopoArgs* a);
 // the cursor engine's existing-node stage (node_stage.h), `remaining` in LDS / in the HBM workspace
 __global__ void ksolve_pack_nodes_lds(const ks::FastArgs* a);
 __global__ void ksolve_pack_nodes_hbm(const ks::FastArgs* a);

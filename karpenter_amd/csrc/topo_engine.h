@@ -86,14 +86,43 @@ namespace ks {
 // On the device US is a compile-time switch with kernels of its own (ksolve_pack_topo_unsched.hip): every line of it stands behind
 // `if constexpr (US)`, and the kernels of every other setting are compiled from what they were compiled from. The host emulation
 // builds it in and FastWork::unsched decides at run time.
+//
+// Topology node filters (engines 24 / 25, FastWork::filt on a spread handle; FS below). A spread group's TopologyNodeFilter
+// (topologynodefilter.go:38-97: one requirement set per required node-affinity term of the owning pod, each merged with its
+// nodeSelector, and its tolerations under nodeTaintsPolicy Honor) is asked in ONE place, Record (topology.go:197-220 with
+// topologygroup.go:152-154): a pod the group selects is counted on a claim or node only if some term is strictly Compatible with
+// the bin's requirements as the commit leaves them (topologynodefilter.go:71 forwards no option: a key the bin does not define fails
+// an In term, well known or not) and the owner tolerates the bin's taints. CanAdd and the domain choice never ask it, and the
+// host builder has applied it to the domains and counts the groups start with. So all that changes is which of a class's hinc
+// fields and zsel bits count on THIS bin:
+//   * setup_filters packs every term like a pod class (positive In sets on packed variable keys, at most kTopoFiltTerms of them;
+//     anything else keeps DECLINE_TOPO_NODE_FILTER) and resolves the filter per (class, group that counts the class). With cf the
+//     class's field of a term key and tf the term's: the term NEVER matches when the class selects on the key and cf & tf = 0 (the
+//     bin's field stays inside cf); it ALWAYS matches when the class selects on every key of the term with cf inside tf (the bin's
+//     field is a non-empty subset of cf, and the key is defined). The filter is ALWAYS if some term is, NEVER if all are; the
+//     taint part likewise over the active templates the class tolerates. NEVER clears the group's bit in the class's hinc / zsel,
+//     ALWAYS leaves it — the owner of a group is always ALWAYS on the requirement part —, anything else is DYNAMIC: the group gets
+//     one of kTopoFiltSlots slots (TopoFilt, in HBM: the LDS plan is full) and the class its bit in TopoClass::pad.
+//   * At the five Record sites — new_claim, the loop's own new claim, the loop's NodeClaim.Add, attempt()'s, the node commit of
+//     topo_nodes_place — a class with slots asks claim_cut / topo_node_filter_cut about the bin's packed word AFTER the commit. A
+//     guard bit there means "the template does not define the key" (FastMisc::tdef of the claim's real template, through
+//     FastLimits::real for a limit stage: the term fails) or "still the NodePool's own NotIn / Exists / Gt / Lt" (defined; the field
+//     holds the values it admits, and the term passes iff it shares one). A class without slots pays a wave-uniform test of a word
+//     the loop has loaded anyway. Anti-affinity counters and lists are never filtered.
+//   * Existing nodes: the requirement part's static verdicts carry over (a node that passed the class's strict Compatible row
+//     defines the class's keys inside cf); the taint part does not, so a group that honours taints over a problem with nodes is
+//     DYNAMIC unless it is ALWAYS for claims and no node is tainted.
+// On the device FS is a compile-time switch like US, with kernels of its own (ksolve_pack_topo_filter.hip, US on as well): every
+// line stands behind `if constexpr (FS)`. The host emulation builds it in and FastWork::filt decides at run time.
 struct TopoKeepState {
   int us_err_ = 0, us_diag_ = 0;   // error and flags of the attempt that just failed (new_claim's result -2, attempt's 0)
   int us_status = 0;               // retry_unschedulable: the status the solve ends with (2: step limit / cancel, 1: capacity, 3: bail)
   uint32_t us_epoch = 1;           // commits so far + 1 (0: no verdict)
 };
 struct TopoNoKeepState {};
-template <class W, bool NODES = false, bool US = kFastKeepBuiltIn>
+template <class W, bool NODES = false, bool US = kFastKeepBuiltIn, bool FS = kFastKeepBuiltIn>
 struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
+  static_assert(!FS || US, "the engines that evaluate node filters keep unschedulable pods too (24 = 22 + filters, 25 = 23 + filters)");
   FastCold<W, 2, 1> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
   RunOrder<W> order;        // Go's sort.Slice permutation as one ring per pod count
   const ProblemView* Pk; const Workspace* Sk; const FastWork* Fk; const TopoWork* Tk;
@@ -129,7 +158,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
     for (int g = 0; g < G; ++g) {
       const bool inv = (T.inverse_mask[g >> 6] >> (g & 63)) & 1;
       if (!((T.initially_active[g >> 6] >> (g & 63)) & 1)) return DECLINE_TOPO_RELAXATION_GROUP;             // created by a relaxing pod (topology.go:162-194)
-      {
+      if (!filters()) {   // (engines 24 / 25: setup_filters below)
         // TopologyNodeFilter.Matches (topologynodefilter.go:68-96) must be true for every claim: no taint policy to honor (or no
         // tainted template), and no node-affinity terms — or one that requires nothing (a pod without nodeSelector / node affinity)
         if (T.f_taint[g] && any_taint) return DECLINE_TOPO_NODE_FILTER;
@@ -214,7 +243,123 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       return b;
     });
     if (bad) return DECLINE_TOPO_CLASS;
+    if constexpr (FS) { if (filters()) { W::sync(); return setup_filters(); } }
     return DECLINE_NONE;
+  }
+  // ---- topology node filters (FS; "Topology node filters" above) ----
+  KS_DEV bool filters() const { if constexpr (FS) return Fk->filt != 0; else return false; }
+  // the shape check of the filters that can say no, their static verdict per class, and the slots of the rest
+  KS_COLD int setup_filters() {
+    if constexpr (!FS) return DECLINE_NONE;
+    else {
+    const ProblemView& P = *Pk; const TopoView& T = P.topo; const Dict& d = P.dict;
+    KS_LDS TopoState& S_ = *st;
+    const int G = T.n_groups, nc = P.n_classes, words = T.words, nvv = cold.nv, Tn = P.n_templates;
+    TopoClass* tc = Tk->cls; const FastSlot* fc = Fk->cls; TopoFilt* ft = Tk->filt;
+    [[maybe_unused]] bool node_taint = false;
+    if constexpr (NODES) node_taint = W::reduce_or(P.n_nodes, [&](int e) { return P.node_taints[e]; }) != 0;
+    const uint32_t active = cold.active_templates;
+    int ns = 0;
+    for (int g = 0; g < G; ++g) {
+      const bool ftaint = T.f_taint[g] != 0;
+      const uint32_t a = T.f_first[g], b = T.f_first[g + 1];
+      bool open = !T.f_affinity[g] || a == b;
+      for (uint32_t i = a; i < b; ++i) if (T.f_reqs.defined[i] == 0) open = true;   // a term that requires nothing
+      if (open && !ftaint) continue;   // Matches is true for every bin
+      if (((T.inverse_mask[g >> 6] >> (g & 63)) & 1) || T.type[g] != 0) return DECLINE_TOPO_NODE_FILTER;   // only spread groups carry a filter (topologygroup.go:88-99)
+      TopoFiltSlot s;
+      for (int i = 0; i < kTopoFiltTerms; ++i) { s.fvm[i] = 0; s.fdm[i] = 0; }
+      s.hbit = 0; s.zbit = 0; s.tmask = ~0u; s.group = (uint16_t)g; s.n_terms = 0; s.taint = ftaint ? 1 : 0;
+      if (!open) {
+        if (b - a > (uint32_t)kTopoFiltTerms) return DECLINE_TOPO_NODE_FILTER;
+        for (uint32_t i = a; i < b; ++i) {
+          const ReqRef r = T.f_reqs.at(d, (int)i);
+          if (r.complement | r.has_gte | r.has_lte) return DECLINE_TOPO_NODE_FILTER;   // positive In sets without bounds only
+          uint32_t left = r.defined;
+          uint64_t fvm = 0, fdm = 0;
+          for (int j = 0; j < nvv; ++j) {
+            const int k = Mp->vkey[j];
+            if (!((left >> k) & 1u)) continue;
+            left &= ~(1u << k);
+            const uint64_t f = (r.mask[Mp->vword[j]] << Mp->voff[j]) & Mp->fmask[j];
+            if (!f) return DECLINE_TOPO_NODE_FILTER;   // In [] == DoesNotExist
+            fvm |= f; fdm |= Mp->fmask[j];
+          }
+          if (left) return DECLINE_TOPO_NODE_FILTER;   // a key that is not a packed variable key
+          s.fvm[s.n_terms] = fvm; s.fdm[s.n_terms] = fdm; s.n_terms++;
+        }
+      }
+      if (ftaint) {
+        const uint64_t tol = T.f_tolerates[g];
+        uint32_t tm = 0;
+        for (int t = 0; t < Tn; ++t) if (!(P.tmpl_taints[t] & ~tol)) tm |= 1u << t;
+        s.tmask = tm;
+      }
+      const int gm = S_.gmap[g];
+      if (gm < 0x100) s.hbit = 1ull << (4 * gm); else s.zbit = 1ull << (gm - 0x100);
+      // 0: the filter ALWAYS matches where a pod of class c lands (or the group does not count the class), 1: NEVER, 2: DYNAMIC
+      auto resolve = [&](int c) -> int {
+        if (!((T.cls_topo[(size_t)c * 2 * words + words + (g >> 6)] >> (g & 63)) & 1)) return 0;
+        const FastSlot k = fc[c];
+        int rq = 0;
+        if (s.n_terms) {
+          bool any_always = false, all_never = true;
+          for (int i = 0; i < (int)s.n_terms; ++i) {
+            bool never = false, always = true;
+            for (int j = 0; j < nvv; ++j) {
+              const uint64_t fm = Mp->fmask[j];
+              if (!(s.fdm[i] & fm)) continue;
+              const bool sel = (k.dmask & fm) != 0;
+              const uint64_t cf = k.cvmask & fm, tf = s.fvm[i] & fm;
+              if (sel && !(cf & tf)) never = true;
+              if (!(sel && !(cf & ~tf))) always = false;
+            }
+            if (!never) { all_never = false; if (always) any_always = true; }
+          }
+          rq = any_always ? 0 : all_never ? 1 : 2;
+        }
+        int tq = 0;
+        if (s.taint) {
+          const uint32_t ok = k.tmplok & active;
+          tq = !(ok & ~s.tmask) ? 0 : !(ok & s.tmask) ? 1 : 2;
+          if constexpr (NODES) { if (P.n_nodes > 0 && (node_taint || tq == 1)) tq = 2; }   // a node's taints are its own
+        }
+        return (rq == 1 || tq == 1) ? 1 : (rq == 0 && tq == 0) ? 0 : 2;
+      };
+      const bool dyn = W::reduce_or(nc, [&](int c) { return (uint64_t)(resolve(c) == 2 ? 1 : 0); }) != 0;
+      if (dyn) {
+        if (ns >= kTopoFiltSlots) return DECLINE_TOPO_NODE_FILTER;
+        if (W::leader()) ft->slot[ns] = s;
+      }
+      const uint32_t sbit = dyn ? 1u << ns : 0u;
+      W::for_n(nc, [&](int c) {
+        const int r = resolve(c);
+        if (r == 1) { tc[c].hinc &= ~s.hbit; tc[c].zsel &= ~s.zbit; }
+        else if (r == 2) tc[c].pad |= sbit;
+      });
+      if (dyn) ns++;
+      W::sync();
+    }
+    return DECLINE_NONE;
+    }
+  }
+  // the slots `fs` of a class against the claim whose requirement set the commit leaves at m
+  KS_COLD TopoFiltCut claim_cut(uint32_t fs, uint64_t m) const {
+    TopoFiltCut none; none.h = 0; none.z = 0;
+    if constexpr (!FS) return none;
+    else {
+      m = W::uniform(m);
+      const int t = (int)(m >> 56) & 31;
+      const int real = Fk->lim ? (int)Fk->lim->real[t] : t;   // a limit stage stands for its template
+      const uint32_t tdef = Mp->tdef[real];
+      const int nvv = cold.nv;
+      uint64_t undef = 0;
+      for (int j = 0; j < nvv; ++j) {
+        const uint64_t guard = 1ull << (Mp->voff[j] + Mp->vwidth[j]);
+        if ((m & guard) && !((tdef >> Mp->vkey[j]) & 1u)) undef |= guard;   // (a guard bit over a key the template defines: its own NotIn / Exists / Gt / Lt)
+      }
+      return topo_filter_cut(Tk->filt, Mp, nvv, fs, m, undef, [&](const TopoFiltSlot& s) { return ((s.tmask >> real) & 1u) != 0; });
+    }
   }
 
   // ---- the pod's domain choice on the dictionary-key group it owns, before any claim is looked at ----
@@ -465,7 +610,12 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       TopoRec nrq;
       nrq.vmask = m2;
       for (int q = 0; q < 4; ++q) nrq.req[q] = cs.size[q];
-      nrq.hcnt = host_add(0, tc.hinc);
+      uint64_t hinc_n = tc.hinc, zsel_n = tc.zsel;   // what Record counts on this claim
+      if constexpr (FS) if (filters()) {
+        const uint32_t fsw = (uint32_t)W::uniform((uint64_t)Tk->cls[tc.pad].pad);
+        if (fsw) { const TopoFiltCut cut = claim_cut(fsw, m2); hinc_n &= ~W::uniform(cut.h); zsel_n &= ~W::uniform(cut.z); }
+      }
+      nrq.hcnt = host_add(0, hinc_n);
       if (W::leader()) { Tk->rec[c] = nrq; F.c_hostseq[c] = cold.host_seq; }
       order.append(c);
       if (order.single_move(order.defect)) {   // (its place behind the claims with one pod: now, like every single stable move)
@@ -473,7 +623,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
         order.defect = -1; order.defect_claim = -1; order.defect_append = false;
         last_kind = 2; last_x = c; last_p = 0;
       } else last_kind = 0;
-      record_zonal(tc.zsel, m2);
+      record_zonal(zsel_n, m2);
       if (track_fields) lists_add(nrq.hcnt, (uint32_t)c);
       W::sync();
       if (lm) subtract_max<W>(P, S, F, t, lm, eh, cs.size);
@@ -558,6 +708,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
     const uint64_t uv = W::uniform(F.us_cls[k]);
     if ((uint32_t)(uv >> 32) == this->us_epoch) { replay(uv); return 0; }
     TopoClass tc = Tk->cls[k];
+    [[maybe_unused]] const uint32_t fsw = (uint32_t)W::uniform((uint64_t)tc.pad);   // FS: the class's filter slots
     tc.pad = k;
     const FastSlot cs = F.cls[k];
     if constexpr (NODES) {
@@ -602,12 +753,14 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       TopoRec nrq;
       nrq.vmask = m2;
       nrq.req[0] = fast_uniform(A.q0) + cs.size[0]; nrq.req[1] = fast_uniform(A.q1) + cs.size[1]; nrq.req[2] = fast_uniform(A.q2) + cs.size[2]; nrq.req[3] = fast_uniform(A.q3) + cs.size[3];
-      nrq.hcnt = host_add(kh, tc.hinc);
+      uint64_t hinc_n = tc.hinc, zsel_n = tc.zsel;
+      if constexpr (FS) if (fsw && filters()) { const TopoFiltCut cut = claim_cut(fsw, m2); hinc_n &= ~W::uniform(cut.h); zsel_n &= ~W::uniform(cut.z); }
+      nrq.hcnt = host_add(kh, hinc_n);
       if (W::leader()) { Tk->rec[x] = nrq; F.q_claim[q] = x; F.q_cnt[q] = cnt; }
       W::sync();
-      record_zonal(tc.zsel, m2);
+      record_zonal(zsel_n, m2);
       const uint64_t zero_before = ~(kh | (kh >> 1) | (kh >> 2)) & kTopoOnes;
-      const uint64_t leaving = tc.hinc & zero_before & track_fields;
+      const uint64_t leaving = hinc_n & zero_before & track_fields;
       if (leaving) lists_remove(leaving, x);
       move_cold((int)x, (int)cnt, pos);
       if (fast_uniform((int)order.overflow)) { this->us_status = 1; return -1; }
@@ -849,7 +1002,10 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
     const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, cvmask, zkv, p0);
     const ZChoice zd = choose_domains(zg1, (zselfw & 2u) != 0, cvmask, zkv, p1);
     if (!p0 || !p1) { TopoNodePick none; none.node = -1; none.slot = 0; return none; }   // (no domain anywhere: the claim path stops with DECLINE_UNSCHEDULABLE_POD)
-    return topo_nodes_place<W>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm);
+    if constexpr (FS) {
+      TopoNodeFilt nf; nf.fs = filters() ? (uint32_t)W::uniform((uint64_t)Tk->cls[k].pad) : 0u; nf.nv = cold.nv; nf.ft = Tk->filt;
+      return topo_nodes_place<W, TopoNodeFilt>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm, nf);
+    } else return topo_nodes_place<W>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm);
   }
 
   KS_COLD void finish(int status, unsigned long long steps) {
@@ -1006,6 +1162,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       LaneVar<uint64_t> c_hlim, c_hinc, c_zsel, c_cvm, c_dm;
       LaneVar<int32_t> c_zg, c_s0, c_s1, c_s2, c_s3;
       LaneVar<uint32_t> c_zself, c_excl, c_tok, oclaim, ocntv;
+      [[maybe_unused]] LaneVar<uint32_t> c_fs;   // FS: the filter slots of each pod's class (TopoClass::pad)
       const KS_GLOBAL uint32_t* const gqcls = (const KS_GLOBAL uint32_t*)fast_uniform(S_->q_class);
       const KS_GLOBAL TopoClass* const gtc = (const KS_GLOBAL TopoClass*)fast_uniform(S_->tcls);
       const KS_GLOBAL FastSlot* const gcs = (const KS_GLOBAL FastSlot*)fast_uniform(S_->fcls);
@@ -1016,6 +1173,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
         const uint64_t w3 = tp[3], w4 = tp[4];
         c_hlim.at(l) = tp[0]; c_hinc.at(l) = tp[1]; c_zsel.at(l) = tp[2];
         c_zg.at(l) = (int32_t)(uint32_t)w3; c_zself.at(l) = (uint32_t)(w3 >> 32); c_excl.at(l) = (uint32_t)w4;   // (zg: two int16 in one word)
+        if constexpr (FS) c_fs.at(l) = (uint32_t)(w4 >> 32);
         const KS_GLOBAL u64_alias* sp = (const KS_GLOBAL u64_alias*)(gcs + k);
         const uint64_t v2 = sp[2], v3 = sp[3], v4 = sp[4];
         c_cvm.at(l) = sp[0]; c_dm.at(l) = sp[1];
@@ -1189,8 +1347,10 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
               host_seq++;
               if constexpr (US) epoch++;   // a new claim
               const int c = n_claims++;
+              uint64_t hinc_n = hinc, zsel_n = zsel;   // what Record counts on this claim
+              if constexpr (FS) { const uint32_t fsw = c_fs.bcast(bi); if (fsw) { const TopoFiltCut cut = claim_cut(fsw, m2); hinc_n &= ~W::uniform(cut.h); zsel_n &= ~W::uniform(cut.z); } }
               TopoRec nrq;
-              nrq.vmask = m2; nrq.req[0] = kc.s0; nrq.req[1] = kc.s1; nrq.req[2] = kc.s2; nrq.req[3] = kc.s3; nrq.hcnt = host_add(0, hinc);
+              nrq.vmask = m2; nrq.req[0] = kc.s0; nrq.req[1] = kc.s1; nrq.req[2] = kc.s2; nrq.req[3] = kc.s3; nrq.hcnt = host_add(0, hinc_n);
               // the new claim: behind the last claim with one pod — the end of run 1; every later run starts one position further right
               const RunEnt e1 = lds_get16(&RT->e[1]);
               const uint32_t m1 = (1u << RT->log2cap[1]) - 1u;
@@ -1204,7 +1364,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
               const int top = max_cnt + 1;
               W::each([&](int l) { for (int kk = 2 + l; kk <= top; kk += 64) RT->e[kk].prefix += 1; });
               n++;
-              record_zonal(zsel, m2);
+              record_zonal(zsel_n, m2);
               if (trk) {
                 // the lists of claims without a member of an anti-affinity group: the new claim joins those whose counter it leaves at zero
                 const uint64_t zero_now = ~(nrq.hcnt | (nrq.hcnt >> 1) | (nrq.hcnt >> 2)) & kTopoOnes & trk;
@@ -1252,16 +1412,18 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
         TopoRec nrq;
         nrq.vmask = km;
         nrq.req[0] = k0 + kc.s0; nrq.req[1] = k1 + kc.s1; nrq.req[2] = k2 + kc.s2; nrq.req[3] = k3 + kc.s3;
-        nrq.hcnt = host_add(kh, hinc);
+        uint64_t hinc_n = hinc, zsel_n = zsel;   // what Record counts on this claim
+        if constexpr (FS) { const uint32_t fsw = c_fs.bcast(bi); if (fsw) { const TopoFiltCut cut = claim_cut(fsw, km); hinc_n &= ~W::uniform(cut.h); zsel_n &= ~W::uniform(cut.z); } }
+        nrq.hcnt = host_add(kh, hinc_n);
         if (W::leader()) store_rec(rec + kx, nrq);
         dirty = true;
         if constexpr (US) epoch++;   // a pod on a claim
         oclaim.set(bi, kx); ocntv.set(bi, kcn);
-        record_zonal(zsel, km);
+        record_zonal(zsel_n, km);
         // the anti-affinity lists: the claim leaves those whose counter this pod takes from zero
         {
           const uint64_t zero_before = ~(kh | (kh >> 1) | (kh >> 2)) & kTopoOnes;
-          const uint64_t leaving = hinc & zero_before & trk;
+          const uint64_t leaving = hinc_n & zero_before & trk;
           if (leaving) { push(); lists_remove(leaving, kx); pull(); }   // (LDS only)
         }
         KS_TSEC(t7)

@@ -35,6 +35,53 @@ namespace ks {
 
 struct TopoNodePick { int node; uint32_t slot; };   // node < 0: no node takes the pod
 
+// ---- Topology node filters (engines 24 / 25; topo_engine.h, "Topology node filters") ----
+// TopologyNodeFilter.Matches (topologynodefilter.go:68-96) of slot s for a bin whose packed requirement word is m. `undef`: the guard
+// bits of the keys the bin does not define — the strict Compatible of :71 fails an In term on such a key, well known or not, while a
+// guard bit that stands for a NodePool's own NotIn / Exists / Gt / Lt is a defined key whose field holds the values it admits.
+KS_FN bool topo_filter_matches(const TopoFiltSlot& s, const KS_LDS FastMisc* Mp, int nv, uint64_t m, uint64_t undef, bool taints_ok) {
+  if (!taints_ok) return false;
+  if (!s.n_terms) return true;
+  for (int i = 0; i < (int)s.n_terms; ++i) {   // any term (topologynodefilter.go:89-95)
+    bool ok = true;
+    for (int j = 0; j < nv; ++j) {
+      const uint64_t fm = Mp->fmask[j];
+      if (!(s.fdm[i] & fm)) continue;
+      if (!(m & s.fvm[i] & fm) || ((undef >> (Mp->voff[j] + Mp->vwidth[j])) & 1)) ok = false;
+    }
+    if (ok) return true;
+  }
+  return false;
+}
+// the slots `fs` of a class against one bin: the bits of its hinc / zsel that Record (topology.go:197-220) does not count there
+template <class TOK>
+KS_FN TopoFiltCut topo_filter_cut(const TopoFilt* ft, const KS_LDS FastMisc* Mp, int nv, uint32_t fs, uint64_t m, uint64_t undef, TOK taints_ok) {
+  TopoFiltCut c; c.h = 0; c.z = 0;
+  for (uint32_t b = fs & ((1u << kTopoFiltSlots) - 1u); b; b &= b - 1) {
+    const TopoFiltSlot s = ft->slot[ctz64(b)];
+    if (!topo_filter_matches(s, Mp, nv, m, undef, taints_ok(s))) { c.h |= s.hbit; c.z |= s.zbit; }
+  }
+  return c;
+}
+struct TopoNoFilt { static constexpr bool on = false; };   // every other setting: the node commit counts what the class says
+struct TopoNodeFilt { static constexpr bool on = true; uint32_t fs; int nv; const TopoFilt* ft; };   // fs: the class's slots (0: none)
+// ... against an existing node: its packed word from its label row (a node defines a key with ONE value, ksolve_impl.h
+// node_stage_declines) and its own taints against the owner's tolerations
+template <class W>
+KS_COLD TopoFiltCut topo_node_filter_cut(const ProblemView* Pk, const Workspace* Sk, const KS_LDS FastMisc* Mp, TopoNodeFilt ctx, int node) {
+  const int nn = Pk->n_nodes;
+  const uint32_t ndef = Sk->n_defined0[node];
+  uint64_t m = 0, undef = 0;
+  for (int j = 0; j < ctx.nv; ++j) {
+    const uint64_t guard = 1ull << (Mp->voff[j] + Mp->vwidth[j]);
+    if ((ndef >> Mp->vkey[j]) & 1u) m |= (Sk->n_mask0[(size_t)Mp->vword[j] * nn + node] << Mp->voff[j]) & Mp->fmask[j];
+    else { m |= Mp->fmask[j] | guard; undef |= guard; }
+  }
+  const uint64_t taints = Pk->node_taints[node];
+  const uint64_t* tol = Pk->topo.f_tolerates;
+  return topo_filter_cut(ctx.ft, Mp, ctx.nv, ctx.fs, m, undef, [&](const TopoFiltSlot& s) { return !(s.taint && (taints & ~tol[s.group])); });
+}
+
 // the per-solve state, from the pristine tables (the kernel's own set-up has accepted the problem: at most sixteen hostname groups)
 template <class W>
 KS_COLD void topo_nodes_init(const ProblemView* Pk, const Workspace* Sk, const TopoWork* Tk) {
@@ -55,9 +102,10 @@ KS_COLD void topo_nodes_init(const ProblemView* Pk, const Workspace* Sk, const T
 
 // One pod of class k: the node that takes it, committed. hlim / hinc / zsel: the class's TopoClass; (zg0, vm0), (zg1, vm1): the
 // dictionary-key groups it is tested against (-1: none) with their candidate-domain masks of this step.
-template <class W>
+// FILT: engines 24 / 25 — the filters of the groups that count the class are asked about the node that takes the pod.
+template <class W, class FILT = TopoNoFilt>
 KS_COLD TopoNodePick topo_nodes_place(const ProblemView* Pk, const Workspace* Sk, const TopoWork* Tk, KS_LDS TopoState* st, const KS_LDS FastMisc* Mp,
-                                      uint32_t k, uint64_t hlim, uint64_t hinc, uint64_t zsel, int zg0, uint32_t vm0, int zg1, uint32_t vm1) {
+                                      uint32_t k, uint64_t hlim, uint64_t hinc, uint64_t zsel, int zg0, uint32_t vm0, int zg1, uint32_t vm1, FILT filt = FILT()) {
   TopoNodePick pick; pick.node = -1; pick.slot = 0;
   const TopoNodes N = Tk->nd;
   const int nn = fast_uniform(Pk->n_nodes), nw = fast_uniform(Pk->node_words), nr = fast_uniform(Pk->n_res);
@@ -102,6 +150,8 @@ KS_COLD TopoNodePick topo_nodes_place(const ProblemView* Pk, const Workspace* Sk
       if (cand) {
         const int wl = ctz64(cand), node = nb + wl;
         pick.node = node; pick.slot = cv.bcast(wl);
+        uint64_t hinc_n = hinc, zsel_n = zsel;   // what Record counts on THIS node
+        if constexpr (FILT::on) if (filt.fs) { const TopoFiltCut cut = topo_node_filter_cut<W>(Pk, Sk, Mp, filt, node); hinc_n &= ~cut.h; zsel_n &= ~cut.z; }
         // ExistingNode.Add (existingnode.go:172-185), by the node's own lane from the values it has just read
         W::each([&](int l) {
           if (l == wl) {
@@ -110,12 +160,12 @@ KS_COLD TopoNodePick topo_nodes_place(const ProblemView* Pk, const Workspace* Sk
             if (nr > 2) rem[(size_t)2 * nn + node] = v2.at(l) - r2;
             if (nr > 3) rem[(size_t)3 * nn + node] = v3.at(l) - r3;
             cnt[node] = cv.at(l) + 1;
-            N.hword[node] = topo_host_add(hwv.at(l), hinc);
+            N.hword[node] = topo_host_add(hwv.at(l), hinc_n);
           }
         });
         // Record (topology.go:197-220) on every dictionary-key group that counts the pod: the node's one domain
         const uint32_t zw0 = z0v.bcast(wl), zw1 = z1v.bcast(wl);
-        for (uint64_t zs = zsel; zs; zs &= zs - 1) {
+        for (uint64_t zs = zsel_n; zs; zs &= zs - 1) {
           KS_LDS TopoZg* const Z = &st->zg[ctz64(zs)];
           const int key = (int)Mp->vkey[fast_uniform((int)Z->var)];
           const uint32_t z = key == key0 ? zw0 : key == key1 ? zw1 : (uint32_t)fast_uniform((int)N.dom[(size_t)key * nn + node]);

@@ -12,6 +12,8 @@ constexpr int kTopoMaxZg = 64;        // ... and on dictionary keys
 constexpr int kTopoMaxDom = 16;       // domains of such a key
 constexpr int kTopoTrack = 4;         // anti-affinity counters with a list of the claims that hold no member
 constexpr int kTopoFreeCap = 1024;    // entries of such a list (more: the list is dropped, its classes scan the order)
+constexpr int kTopoFiltSlots = 16;    // topology node filters of a problem that are decided per claim / node (engines 24 / 25); more: DECLINE_TOPO_NODE_FILTER
+constexpr int kTopoFiltTerms = 4;     // node-affinity terms of such a filter
 constexpr uint64_t kTopoGuard = 0x8888888888888888ull, kTopoOnes = 0x1111111111111111ull;
 
 KS_FN uint64_t topo_host_add(uint64_t hcnt, uint64_t hinc) {   // per-field +1, saturating at 7
@@ -21,7 +23,7 @@ KS_FN uint64_t topo_host_add(uint64_t hcnt, uint64_t hinc) {   // per-field +1, 
 struct TopoRec { uint64_t vmask; int32_t req[4]; uint64_t hcnt; };   // 32 B: an in-flight claim (requirement set, requests, hostname-group counters)
 // a pod class's topology: limits on the hostname counters it is tested against (field = 8 | limit; 8 | 7 where it has none),
 // the counters and dictionary-key groups a pod of the class is counted by, the dictionary-key group it owns
-struct TopoClass { uint64_t hlim, hinc, zsel; int16_t zg[2]; uint32_t zself; uint32_t excl; uint32_t pad; };   // 48 B; zg: up to two dictionary-key groups it is tested against (-1: none), zself bit i: it is selected by zg[i] itself
+struct TopoClass { uint64_t hlim, hinc, zsel; int16_t zg[2]; uint32_t zself; uint32_t excl; uint32_t pad; };   // 48 B; pad: engines 24 / 25, the filter slots (TopoFilt) of the groups that count the class; zg: up to two dictionary-key groups it is tested against (-1: none), zself bit i: it is selected by zg[i] itself
 struct TopoZg {   // a group on a dictionary key (LDS): sixteen counters and name ranks, then one 16-byte header
   int32_t cnt[kTopoMaxDom];
   uint16_t rank[kTopoMaxDom];
@@ -52,7 +54,20 @@ struct TopoNodes {
   const uint8_t* dom;     // [n_keys][n_nodes] the node's domain on a dictionary key some group uses: the value's bit inside the key's words
   const uint64_t* dead0;  // [n_classes][node_words] the static (class, node) verdicts (ksolve_node_dead0) for this solve's class ids
 };
-struct TopoWork { TopoClass* cls; TopoRec* rec; TopoPlan plan; int enabled; TopoNodes nd; };
+// Engines 24 / 25 (topo_engine.h, "Topology node filters"): a spread group whose TopologyNodeFilter cannot be decided per class at
+// set-up. Each node-affinity term is packed like a pod class: fvm = the values it admits per field of the packed requirement word,
+// fdm = the fields it selects on. In HBM, written by setup_topo, read on the commits of the classes that carry the slot only.
+struct TopoFiltSlot {
+  uint64_t fvm[kTopoFiltTerms], fdm[kTopoFiltTerms];
+  uint64_t hbit, zbit;    // the group's bit in TopoClass::hinc / zsel (one of them)
+  uint32_t tmask;         // templates whose taints the group's owner tolerates (every bit set: nodeTaintsPolicy Ignore)
+  uint16_t group;         // the group, for f_tolerates against a node's taints
+  uint8_t n_terms;        // 0: nodeAffinityPolicy Ignore, or nothing required
+  uint8_t taint;          // nodeTaintsPolicy Honor
+};
+struct TopoFilt { TopoFiltSlot slot[kTopoFiltSlots]; };
+struct TopoFiltCut { uint64_t h, z; };   // the bits of hinc / zsel whose filters say no to one claim or node
+struct TopoWork { TopoClass* cls; TopoRec* rec; TopoPlan plan; int enabled; TopoNodes nd; TopoFilt* filt; };   // filt: engines 24 / 25 only, null otherwise
 struct TopoArgs { ProblemView pv; Workspace ws; FastWork fw; TopoWork tw; };
 
 }  // namespace ks

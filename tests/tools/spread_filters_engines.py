@@ -1,0 +1,83 @@
+"""Timing tool of the spread engine's topology node filters (TEST TOOL; csrc/topo_engine.h "Topology node filters"), on the device.
+
+fixtures.config3(n_types=--types) — the BASELINE configs[2] topology mix — at each of --pods, two ways:
+  * selectors: every Deployment that owns a spread constraint also carries nodeSelector karpenter.sh/capacity-type = spot, as a
+    Deployment on spot capacity would. Its groups' filters can say no to the claims the other pods open (the pool does not define the
+    key), so "auto-unschedulable-spread" (22: the parent's behaviour) hands the batch to the general engine with reason 43, and
+    "auto-filters-spread" (24) solves it on the spread engine with one filter slot per group.
+  * plain: the mix as it is, under 22 and 24: the new kernels (ksolve_pack_topo_f) against ksolve_pack_topo_u on a batch without a slot.
+Every solve is a FRESH handle, the time is the host clock around Solve() without result download: --repeats solves per leg after one
+warm-up, then one more with Results for the digest. Prints ONE JSON line; exit status 1 when a pair of digests differs.
+usage: python tests/tools/spread_filters_engines.py [--pods 20000,100000] [--types N] [--repeats N] [--variants selectors,plain]"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+ENGINES = ("auto-unschedulable-spread", "auto-filters-spread")
+
+
+def variants(fx, pods, types, which):
+    out = []
+    base = fx.config3(pods=pods, n_types=types)
+    if "selectors" in which:
+        prob = copy.deepcopy(base)
+        for g in prob["podGroups"]:
+            if g["template"].get("topologySpreadConstraints"):
+                g["template"]["nodeSelector"] = {fx.CAPACITY_TYPE: "spot"}
+        out.append((f"selectors-{pods}", prob))
+    if "plain" in which:
+        out.append((f"plain-{pods}", base))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pods", default="20000,100000")
+    ap.add_argument("--types", type=int, default=500)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--variants", default="selectors,plain")
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import parity
+    from karpenter_amd import fixtures as fx
+    from karpenter_amd.scheduling import NewScheduler
+
+    def solve_fresh(prob, engine, want_results):
+        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
+        try:
+            t = time.perf_counter()
+            r = s.Solve(want_results=want_results)
+            return r, time.perf_counter() - t
+        finally:
+            s.close()
+
+    out = {"tool": "spread_filters_engines", "types": args.types, "repeats": args.repeats, "cases": {}}
+    for pods in [int(x) for x in args.pods.split(",")]:
+        for name, prob in variants(fx, pods, args.types, args.variants.split(",")):
+            case = {"pods": pods, "engines": {}}
+            for engine in ENGINES:
+                solve_fresh(prob, engine, False)   # warm-up
+                times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
+                r, _ = solve_fresh(prob, engine, True)
+                c = r["counters"]
+                case["engines"][engine] = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "pops": c["pops"],
+                                           "podErrors": len(r["podErrors"]), "solve_s": [round(x, 4) for x in times], "median_s": round(statistics.median(times), 4),
+                                           "results_digest": parity.results_digest(r)[0]}
+            legs = case["engines"]
+            case["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
+            case["base_over_filters"] = round(legs[ENGINES[0]]["median_s"] / legs[ENGINES[1]]["median_s"], 2)
+            out["cases"][name] = case
+            print(json.dumps({name: case}), file=sys.stderr, flush=True)
+    print(json.dumps(out), flush=True)
+    return 0 if all(c["digests_agree"] for c in out["cases"].values()) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
