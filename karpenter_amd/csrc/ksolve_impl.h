@@ -254,6 +254,102 @@ typedef struct {
   uint32_t node_words;
 } ksolve_test_node_dead0_out;
 
+// ksolve_test_finalize — TEST BUILDS ONLY: the finalize kernel (kernels.h finalize_body over go_sort.h) alone, and with `slot_of` the
+// sweep's claim gather (claim_gather_body) behind it. The claims come as plain columns, one row per SLOT of the claim arrays; the hook
+// packs them into hot and cold records through RecLayout's accessors, as the engines leave them: a slot with `slot_used` clear, the
+// fields finalize does not read (totals, heads, pod count, hostname sequence), a bound slot without its flag bit and the whole cold
+// record of a slot without bounds and without `c_minv_flag` hold `poison`. Without slot_of claim c is slot c (n_slots == n_claims), as
+// solve_finish() launches it; with it the launch is sweep_run()'s. The outputs start as bytes of 0xA5 and come back whole.
+// it_words = ceil(n_its / 64). tests/result_cases.py holds the definition.
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;
+  const int64_t* value_int;
+  const uint64_t *value_is_int, *value_valid;
+  int32_t key_zone, key_ct, key_it;                // -1: the problem has no such key
+  uint32_t n_its, n_zones, n_cts, n_res, n_templates;
+  const uint64_t* it_off_avail;                    // [n_its] bit zone * 4 + capacity type
+  const double* it_off_price;                      // [n_its][64]
+  const ksolve_reqsets* it_reqs;                   // n_its rows
+  const int32_t* dg_first;                         // [n_templates + 1]
+  const int64_t* dg_ov;                            // [n_dg][n_res]
+  const uint64_t* dg_its;                          // [n_dg][it_words]
+  uint64_t dg_nonempty;
+  const uint64_t* t_its;                           // [n_templates][it_words]
+  const uint32_t* it_resv_first;                   // [n_its + 1] or null: no reservation tables (c_reserved is not handed to the kernel)
+  const uint8_t *resv_zone, *resv_id;
+  const double* resv_price;
+  uint32_t truncate_n, best_effort;
+  uint32_t n_claims, n_slots;
+  const uint32_t* slot_of;                         // [n_claims] or null
+  const uint8_t* slot_used;                        // [n_slots]
+  const ksolve_reqsets* c_reqs;                    // n_slots rows; min_values null: none
+  const uint8_t* c_minv_flag;                      // [n_slots] the claim's has-minValues flag (meta2 flags bit 1)
+  const uint64_t* c_its;                           // [n_slots][it_words]
+  const uint32_t* c_template;                      // [n_slots]
+  const uint64_t* c_reserved;                      // [n_slots] held reservation ids, or null: zeros
+  uint64_t poison;
+} ksolve_test_finalize_in;
+// every table is the caller's
+typedef struct {
+  double* cheapest;                                // [n_claims]
+  int64_t* daemon_requests;                        // [n_claims][n_res]
+  int32_t* sort_idx; double* sort_price;           // [n_claims][n_its]   (untouched when truncate_n == 0)
+  uint32_t* ordered_count; uint8_t* trunc_failed;  // [n_claims]
+  uint32_t hot_words, cold_words;
+  uint64_t *rec_hot, *rec_cold;                    // [n_slots][hot_words], [n_slots][cold_words]: the records as the hook packed them
+  uint64_t *g_hot, *g_cold, *g_reserved;           // [n_claims]...: what the gather wrote (slot_of only)
+} ksolve_test_finalize_out;
+
+// ksolve_test_eff_alloc — TEST BUILDS ONLY: the fast engines' effective allocatable (kernels.h eff_alloc_body) alone on raw tables,
+// one be_launch_eff_alloc. it_eff is uploaded as the caller filled it and downloaded whole. tests/result_cases.py holds the definition.
+typedef struct {
+  uint32_t n_templates, n_its, n_res, tmpl_ov;
+  const int64_t* it_alloc;                         // [n_res][n_its]
+  const int32_t* dg_first;                         // [n_templates + 1]
+  const int64_t* dg_ov;                            // [n_dg][n_res]
+  const uint64_t* dg_its;                          // [n_dg][it_words]
+  int64_t* it_eff;                                 // [n_templates][n_res][n_its] in and out
+} ksolve_test_eff_alloc_io;
+
+// ksolve_test_fast_records — TEST BUILDS ONLY: the cursor engine's claim records (fast_engine.h fast_record_body) and the scatter of the
+// queue's results (fast_scatter_body) alone: the least of ProblemView, Workspace and FastWork the two kernels read, built from raw tables,
+// c_hot / c_cold / assign / slot filled with `poison`, one be_launch_fast_records. The records come back as raw words and unpacked to
+// columns through RecLayout's accessors the way decode_claim reads them (without its reservation step). A claim's compact state is
+// FastClaim: vmask (fields of the variable keys, a guard bit above each, the template or limit stage in the top byte) and requests.
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;
+  const int64_t* value_int;
+  const uint64_t *value_is_int, *value_valid;
+  uint32_t n_its, n_res, n_templates;
+  const ksolve_reqsets* tmpl_reqs;                 // n_templates rows
+  const int64_t* it_alloc;                         // [n_res][n_its]
+  const int64_t* it_eff;                           // [n_templates][n_res][n_its] or null
+  uint32_t tmpl_ov;
+  uint32_t nv;                                     // variable keys: FastVar
+  const uint8_t *vkey, *voff, *vwidth;             // [nv]
+  const uint16_t* vword;                           // [nv]
+  const uint8_t* lim_real;                         // [32] FastLimits::real, or null: no FastLimits
+  uint32_t n_claims, n_ent;
+  const uint64_t* c_vmask;                         // [n_claims]
+  const int32_t* c_req;                            // [n_claims][4]
+  const uint16_t* c_ent;                           // [n_claims] < n_ent
+  const uint64_t* ent_its;                         // [n_ent][it_words]
+  const uint32_t *c_npods, *c_hostseq;             // [n_claims]
+  uint32_t n_pods;
+  const uint32_t *sorted, *q_claim, *q_cnt;        // [n_pods]
+  uint64_t poison;
+} ksolve_test_fast_records_in;
+// every table is the caller's
+typedef struct {
+  uint32_t hot_words, cold_words;
+  uint64_t *c_hot, *c_cold;                        // [n_claims][hot_words], [n_claims][cold_words] raw
+  uint64_t *mask, *its;                            // [n_claims][req_words], [n_claims][it_words]
+  int64_t *total, *head;                           // [n_claims][n_res]
+  uint32_t *defined, *complement, *has_gte, *has_lte, *tmpl, *npods, *host_seq, *flags;   // [n_claims]
+  int64_t *gte, *lte; int32_t* minv;               // [n_claims][n_keys]: the cold record's three parts as they lie there, written or not
+  int32_t* assign; uint32_t* slot;                 // [n_pods]
+} ksolve_test_fast_records_out;
+
 namespace ks {
 struct ReqalgTestArgs {
   Dict dict;
@@ -1469,6 +1565,249 @@ static ksolve_status test_node_dead0(ksolve_handle* h, const ksolve_test_node_de
   be_d2h(h, out->dead0, dead0, (size_t)nc * nw * 8);
   be_sync(h);
   return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// the daemon-overhead groups of the two hooks below, checked: every index the kernels form from them stays inside the tables
+static ksolve_status test_groups(ksolve_handle* h, const char* who, uint32_t nt, const int32_t* dg_first, uint32_t& n_dg) {
+  const std::string w(who);
+  if (nt < 1 || nt > 32) return fail(h, KSOLVE_ERR_INVALID, w + ": n_templates out of range");
+  if (dg_first[0] != 0) return fail(h, KSOLVE_ERR_INVALID, w + ": dg_first[0] is not 0");
+  for (uint32_t t = 0; t < nt; ++t) if (dg_first[t + 1] < dg_first[t]) return fail(h, KSOLVE_ERR_INVALID, w + ": dg_first decreases");
+  if (dg_first[nt] > 64) return fail(h, KSOLVE_ERR_INVALID, w + ": more than 64 groups");
+  n_dg = (uint32_t)dg_first[nt];
+  return KSOLVE_OK;
+}
+// The finalize kernel alone (see ksolve_test_finalize_in): the tables as create() uploads them, the outputs sized as solve_finish() and
+// sweep_run() size them, their launches.
+static ksolve_status test_finalize(ksolve_handle* h, const ksolve_test_finalize_in* in, ksolve_test_finalize_out* out) {
+  if (!in || !out || !in->it_off_avail || !in->it_off_price || !in->it_reqs || !in->it_reqs->mask || !in->it_reqs->defined || !in->it_reqs->complement || !in->dg_first ||
+      !in->dg_ov || !in->dg_its || !in->t_its || !in->slot_used || !in->c_reqs || !in->c_reqs->mask || !in->c_reqs->defined || !in->c_reqs->complement || !in->c_reqs->has_gte ||
+      !in->c_reqs->has_lte || !in->c_reqs->gte || !in->c_reqs->lte || !in->c_minv_flag || !in->c_its || !in->c_template || !out->cheapest || !out->daemon_requests || !out->rec_hot || !out->rec_cold)
+    return fail(h, KSOLVE_ERR_INVALID, "test_finalize: missing table");
+  const uint32_t nk = in->n_keys, n_its = in->n_its, nr = in->n_res, nt = in->n_templates, C = in->n_claims, S = in->n_slots;
+  if (n_its < 1 || nr < 1 || nr > (uint32_t)kMaxRes || C < 1 || S < 1 || C > 0xFFFFFu || S > 0xFFFFFu || in->n_zones < 1 || in->n_zones > 16 || in->n_cts < 1 || in->n_cts > 4)
+    return fail(h, KSOLVE_ERR_INVALID, "test_finalize: sizes out of range");
+  const uint32_t iw = (n_its + 63) / 64;
+  if (iw > (uint32_t)kMaxItWords) return fail(h, KSOLVE_ERR_UNSUPPORTED, "test_finalize: more than 2048 instance types");
+  if (!in->slot_of && S != C) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: n_slots differs from n_claims without slot_of");
+  if (in->slot_of && (!out->g_hot || !out->g_cold || !out->g_reserved)) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: missing table");
+  const bool trunc = in->truncate_n != 0;
+  if (trunc && (!out->sort_idx || !out->sort_price || !out->ordered_count || !out->trunc_failed)) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: missing table");
+  const bool resv = in->it_resv_first != nullptr;
+  if (resv && (!in->resv_zone || !in->resv_id || !in->resv_price)) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: missing table");
+  if (!resv && in->c_reserved) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: held reservations without the reservation tables");
+  uint32_t n_dg = 0;
+  if (ksolve_status st = test_groups(h, "test_finalize", nt, in->dg_first, n_dg)) return st;
+  uint32_t n_off = 0;
+  if (resv) {
+    if (in->it_resv_first[0] != 0) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: it_resv_first[0] is not 0");
+    for (uint32_t i = 0; i < n_its; ++i) if (in->it_resv_first[i + 1] < in->it_resv_first[i]) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: it_resv_first decreases");
+    n_off = in->it_resv_first[n_its];
+    for (uint32_t o = 0; o < n_off; ++o) if (in->resv_zone[o] >= in->n_zones || in->resv_id[o] >= 64) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: a reservation offering out of range");
+  }
+  const uint64_t tail = (n_its & 63) ? ~0ull << (n_its & 63) : 0ull;
+  for (uint32_t s = 0; s < S; ++s) if (in->slot_used[s]) {
+    if (in->c_template[s] >= nt) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: a claim's template outside the templates");
+    if (in->c_its[(size_t)s * iw + iw - 1] & tail) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: a claim holds a type past n_its");
+  }
+  if (in->slot_of) for (uint32_t c = 0; c < C; ++c) if (in->slot_of[c] >= S || !in->slot_used[in->slot_of[c]]) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: slot_of names no claim");
+  if (!in->slot_of) for (uint32_t s = 0; s < S; ++s) if (!in->slot_used[s]) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: an unused slot without slot_of");
+  ks::Dict dict{};
+  if (ksolve_status st = test_dict(h, "test_finalize", nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, dict)) return st;
+  for (int32_t k : {in->key_zone, in->key_ct, in->key_it}) if (k < -1 || k >= (int32_t)nk) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: a key index outside the keys");
+  if (in->key_zone >= 0 && dict.key_word_off[in->key_zone + 1] == dict.key_word_off[in->key_zone]) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: the zone key has no word");
+  if (in->key_ct >= 0 && dict.key_word_off[in->key_ct + 1] == dict.key_word_off[in->key_ct]) return fail(h, KSOLVE_ERR_INVALID, "test_finalize: the capacity-type key has no word");
+  dict.key_zone = in->key_zone; dict.key_ct = in->key_ct; dict.key_it = in->key_it;
+  const uint32_t rw = (uint32_t)dict.req_words;
+  const ks::RecLayout lay{(int)rw, (int)iw, (int)nr, (int)nk};
+  const size_t hw = (size_t)lay.c_hot_words(), cw = (size_t)lay.cold_words();
+  // ---- the claim records, packed through the layout's accessors ----
+  std::vector<uint64_t> hot(S * hw, in->poison), cold(S * cw, in->poison), held(S, in->poison);
+  const ksolve_reqsets& q = *in->c_reqs;
+  for (uint32_t s = 0; s < S; ++s) if (in->slot_used[s]) {
+    uint64_t* r = hot.data() + s * hw;
+    for (uint32_t w = 0; w < rw; ++w) r[lay.c_mask() + w] = q.mask[(size_t)s * rw + w];
+    for (uint32_t w = 0; w < iw; ++w) r[lay.c_its() + w] = in->c_its[(size_t)s * iw + w];
+    r[lay.c_f0()] = (uint64_t)q.defined[s] | ((uint64_t)q.complement[s] << 32);
+    r[lay.c_f1()] = (uint64_t)q.has_gte[s] | ((uint64_t)q.has_lte[s] << 32);
+    r[lay.c_meta()] = (uint64_t)in->c_template[s] | (in->poison & 0xFFFFFFFF00000000ull);
+    r[lay.c_meta2()] = (in->poison & 0xFFFFFFFFull) | ((uint64_t)(in->c_minv_flag[s] ? 2u : 0u) << 32);
+    held[s] = in->c_reserved ? in->c_reserved[s] : 0;
+    if (q.has_gte[s] | q.has_lte[s] | (in->c_minv_flag[s] ? 1u : 0u)) {
+      uint64_t* cd = cold.data() + s * cw;
+      int64_t* cg = (int64_t*)cd; int64_t* cl = cg + nk; int32_t* cv = (int32_t*)(cd + 2 * nk);
+      for (uint32_t k = 0; k < nk; ++k) {
+        if ((q.has_gte[s] >> k) & 1u) cg[k] = q.gte[(size_t)s * nk + k];
+        if ((q.has_lte[s] >> k) & 1u) cl[k] = q.lte[(size_t)s * nk + k];
+        cv[k] = q.min_values ? q.min_values[(size_t)s * nk + k] : -1;
+      }
+    }
+  }
+  const uint64_t* d_hot = up(h, hot.data(), hot.size());
+  const uint64_t* d_cold = up(h, cold.data(), cold.size());
+  const uint64_t* d_held = up(h, held.data(), held.size());
+  // ---- the problem's tables ----
+  const uint64_t* avail = up(h, in->it_off_avail, n_its);
+  const double* price = up(h, in->it_off_price, (size_t)n_its * 64);
+  const ReqTable it_reqs = upload_reqs(h, *in->it_reqs, n_its, rw, nk);
+  const int* dg_first = up(h, (const int*)in->dg_first, nt + 1);
+  const int64_t* dg_ov = up(h, in->dg_ov, (size_t)n_dg * nr);
+  const uint64_t* dg_its = up(h, in->dg_its, (size_t)n_dg * iw);
+  const uint64_t* t_its = up(h, in->t_its, (size_t)nt * iw);
+  const uint32_t* rf = resv ? up(h, in->it_resv_first, n_its + 1) : nullptr;
+  const uint8_t* rz = resv ? up(h, in->resv_zone, n_off) : nullptr;
+  const uint8_t* ri = resv ? up(h, in->resv_id, n_off) : nullptr;
+  const double* rp = resv ? up(h, in->resv_price, n_off) : nullptr;
+  const uint32_t* slot_of = in->slot_of ? up(h, in->slot_of, C) : nullptr;
+  // ---- the outputs ----
+  double* cheapest = dz<double>(h, C);
+  int64_t* dreq = dz<int64_t>(h, (size_t)C * nr);
+  int32_t* s_idx = trunc ? dz<int32_t>(h, (size_t)C * n_its) : nullptr;
+  double* s_price = trunc ? dz<double>(h, (size_t)C * n_its) : nullptr;
+  uint32_t* s_cnt = trunc ? dz<uint32_t>(h, C) : nullptr;
+  uint8_t* s_fail = trunc ? dz<uint8_t>(h, C) : nullptr;
+  uint64_t* g_hot = slot_of ? dz<uint64_t>(h, C * hw) : nullptr;
+  uint64_t* g_cold = slot_of ? dz<uint64_t>(h, C * cw) : nullptr;
+  uint64_t* g_resv = slot_of ? dz<uint64_t>(h, C) : nullptr;
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_fill(h, cheapest, 0xA5, (size_t)C * 8); be_fill(h, dreq, 0xA5, (size_t)C * nr * 8);
+  if (trunc) { be_fill(h, s_idx, 0xA5, (size_t)C * n_its * 4); be_fill(h, s_price, 0xA5, (size_t)C * n_its * 8); be_fill(h, s_cnt, 0xA5, (size_t)C * 4); be_fill(h, s_fail, 0xA5, C); }
+  if (slot_of) { be_fill(h, g_hot, 0xA5, C * hw * 8); be_fill(h, g_cold, 0xA5, C * cw * 8); be_fill(h, g_resv, 0xA5, (size_t)C * 8); }
+  ks::FinalizeArgs F{dict, (int)n_its, (int)iw, (int)in->n_zones, (int)in->n_cts, avail, price, d_hot, d_cold, lay, cheapest,
+                     dg_first, dg_ov, dg_its, in->dg_nonempty, t_its, dreq,
+                     resv ? d_held : nullptr, rf, rz, ri, rp,
+                     0, 0, it_reqs, nullptr, nullptr, nullptr, nullptr, slot_of};
+  if (trunc) {
+    F.truncate_n = (int)in->truncate_n; F.best_effort = in->best_effort ? 1 : 0;
+    F.sort_idx = s_idx; F.sort_price = s_price; F.ordered_count = s_cnt; F.trunc_failed = s_fail;
+  }
+  be_launch_finalize(h, (int)C, F);
+  if (slot_of) {
+    ks::ClaimGatherArgs G{lay, slot_of, d_hot, d_cold, d_held, g_hot, g_cold, g_resv};
+    be_launch_claim_gather(h, (int)C, G);
+  }
+  out->hot_words = (uint32_t)hw; out->cold_words = (uint32_t)cw;
+  memcpy(out->rec_hot, hot.data(), hot.size() * 8); memcpy(out->rec_cold, cold.data(), cold.size() * 8);
+  be_d2h(h, out->cheapest, cheapest, (size_t)C * 8);
+  be_d2h(h, out->daemon_requests, dreq, (size_t)C * nr * 8);
+  if (trunc) {
+    be_d2h(h, out->sort_idx, s_idx, (size_t)C * n_its * 4); be_d2h(h, out->sort_price, s_price, (size_t)C * n_its * 8);
+    be_d2h(h, out->ordered_count, s_cnt, (size_t)C * 4); be_d2h(h, out->trunc_failed, s_fail, C);
+  }
+  if (slot_of) { be_d2h(h, out->g_hot, g_hot, C * hw * 8); be_d2h(h, out->g_cold, g_cold, C * cw * 8); be_d2h(h, out->g_reserved, g_resv, (size_t)C * 8); }
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The effective allocatable alone (see ksolve_test_eff_alloc_io): create()'s launch on the caller's tables.
+static ksolve_status test_eff_alloc(ksolve_handle* h, ksolve_test_eff_alloc_io* io) {
+  if (!io || !io->it_alloc || !io->dg_first || !io->dg_ov || !io->dg_its || !io->it_eff) return fail(h, KSOLVE_ERR_INVALID, "test_eff_alloc: missing table");
+  const uint32_t nt = io->n_templates, n_its = io->n_its, nr = io->n_res;
+  if (n_its < 1 || nr < 1 || nr > (uint32_t)kMaxRes) return fail(h, KSOLVE_ERR_INVALID, "test_eff_alloc: sizes out of range");
+  const uint32_t iw = (n_its + 63) / 64;
+  if (iw > (uint32_t)kMaxItWords) return fail(h, KSOLVE_ERR_UNSUPPORTED, "test_eff_alloc: more than 2048 instance types");
+  uint32_t n_dg = 0;
+  if (ksolve_status st = test_groups(h, "test_eff_alloc", nt, io->dg_first, n_dg)) return st;
+  if (nt < 32 && (io->tmpl_ov >> nt)) return fail(h, KSOLVE_ERR_INVALID, "test_eff_alloc: tmpl_ov names a template that is not there");
+  for (uint32_t t = 0; t < nt; ++t) if (((io->tmpl_ov >> t) & 1u) && io->dg_first[t + 1] == io->dg_first[t]) return fail(h, KSOLVE_ERR_INVALID, "test_eff_alloc: a template of tmpl_ov without a group");
+  const size_t n_eff = (size_t)nt * nr * n_its;
+  int64_t* eff = up(h, io->it_eff, n_eff);
+  const ks::EffAllocArgs A{(int)nt, (int)n_its, (int)iw, (int)nr, io->tmpl_ov, up(h, io->it_alloc, (size_t)nr * n_its), up(h, (const int*)io->dg_first, nt + 1),
+                           up(h, io->dg_ov, (size_t)n_dg * nr), up(h, io->dg_its, (size_t)n_dg * iw), eff};
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_launch_eff_alloc(h, A);
+  be_d2h(h, io->it_eff, eff, n_eff * 8);
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
+}
+// The cursor engine's claim records and the scatter alone (see ksolve_test_fast_records_in): the tables as create() uploads them, the
+// workspace as fast_shared_alloc() and create() size it, the launch of solve().
+static ksolve_status test_fast_records(ksolve_handle* h, const ksolve_test_fast_records_in* in, ksolve_test_fast_records_out* out) {
+  if (!in || !out || !in->tmpl_reqs || !in->tmpl_reqs->mask || !in->tmpl_reqs->defined || !in->tmpl_reqs->complement || !in->it_alloc || !in->c_vmask || !in->c_req || !in->c_ent ||
+      !in->ent_its || !in->c_npods || !in->c_hostseq || !in->sorted || !in->q_claim || !in->q_cnt || !out->c_hot || !out->c_cold || !out->mask || !out->its || !out->total || !out->head ||
+      !out->defined || !out->complement || !out->has_gte || !out->has_lte || !out->tmpl || !out->npods || !out->host_seq || !out->flags || !out->gte || !out->lte || !out->minv ||
+      !out->assign || !out->slot || (in->nv && (!in->vkey || !in->voff || !in->vwidth || !in->vword)))
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: missing table");
+  const uint32_t nk = in->n_keys, n_its = in->n_its, nr = in->n_res, nt = in->n_templates, C = in->n_claims, n_pods = in->n_pods, n_ent = in->n_ent;
+  if (n_its < 1 || nr < 1 || nr > 4 || nt < 1 || nt > 32 || C < 1 || C > 0xFFFFu || n_pods < 1 || n_pods > 0xFFFFFFu || n_ent < 1 || n_ent > (uint32_t)ks::kFastEnt || in->nv > (uint32_t)ks::kFastMaxVar)
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: sizes out of range");
+  const uint32_t iw = (n_its + 63) / 64;
+  if (iw > (uint32_t)kMaxItWords) return fail(h, KSOLVE_ERR_UNSUPPORTED, "test_fast_records: more than 2048 instance types");
+  if (in->tmpl_ov && !in->it_eff) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: tmpl_ov without it_eff");
+  if (nt < 32 && (in->tmpl_ov >> nt)) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: tmpl_ov names a template that is not there");
+  const ksolve_reqsets& tr = *in->tmpl_reqs;
+  if ((!tr.gte && any_nonzero(tr.has_gte, nt)) || (!tr.lte && any_nonzero(tr.has_lte, nt))) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: a has_gte / has_lte bit without the bounds column");
+  ks::Dict dict{};
+  if (ksolve_status st = test_dict(h, "test_fast_records", nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, dict)) return st;
+  const uint32_t rw = (uint32_t)dict.req_words;
+  ks::FastVar fv{};
+  fv.nv = (int)in->nv;
+  for (uint32_t j = 0; j < in->nv; ++j) {
+    if (in->vkey[j] >= nk || in->vword[j] >= rw || in->vwidth[j] < 1 || (uint32_t)in->voff[j] + in->vwidth[j] >= (uint32_t)ks::kFastVarBits)
+      return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: a variable key outside the keys, the words or the 56 bits");
+    fv.vkey[j] = in->vkey[j]; fv.voff[j] = in->voff[j]; fv.vwidth[j] = in->vwidth[j]; fv.vword[j] = in->vword[j];
+  }
+  for (uint32_t c = 0; c < C; ++c) {
+    const uint32_t ts = (uint32_t)(in->c_vmask[c] >> 56);
+    if (ts >= 32 || (in->lim_real ? in->lim_real[ts] : ts) >= nt) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: a claim's template outside the templates");
+    if (in->c_ent[c] >= n_ent) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: a claim's cache entry outside the entries");
+  }
+  for (uint32_t i = 0; i < n_pods; ++i) if (in->sorted[i] >= n_pods) return fail(h, KSOLVE_ERR_INVALID, "test_fast_records: a queue entry outside the pods");
+  const ks::RecLayout lay{(int)rw, (int)iw, (int)nr, (int)nk};
+  const size_t hw = (size_t)lay.c_hot_words(), cw = (size_t)lay.cold_words();
+  h->n_keys = nk; h->req_words = rw; h->n_res = nr; h->n_its = n_its; h->it_words = iw; h->n_pods = n_pods;
+  ks::ProblemView& P = h->pv;
+  ks::Workspace& W = h->ws;
+  ks::FastWork& fw = h->fw;
+  P.dict = dict; P.lay = lay; P.n_res = (int)nr; P.n_its = (int)n_its; P.it_words = (int)iw; P.n_templates = (int)nt;
+  P.tmpl_reqs = upload_reqs(h, tr, nt, rw, nk);
+  P.it_alloc = up(h, in->it_alloc, (size_t)nr * n_its);
+  P.it_eff = in->it_eff ? up(h, in->it_eff, (size_t)nt * nr * n_its) : nullptr;
+  P.tmpl_ov = in->tmpl_ov;
+  P.sorted_pods = up(h, in->sorted, n_pods);
+  fast_shared_alloc(h, C, 0);
+  std::vector<ks::FastClaim> state(C);
+  for (uint32_t c = 0; c < C; ++c) { state[c].vmask = in->c_vmask[c]; for (int r = 0; r < 4; ++r) state[c].req[r] = in->c_req[(size_t)c * 4 + r]; }
+  std::vector<uint64_t> ents((size_t)ks::kFastEnt * iw, in->poison);   // (the entries no claim names hold poison)
+  memcpy(ents.data(), in->ent_its, (size_t)n_ent * iw * 8);
+  ks::FastLimits lim{};
+  if (in->lim_real) { memcpy(lim.real, in->lim_real, 32); fw.lim = up(h, &lim, 1); }
+  W.max_claims = (int)C; W.claim_words = (int)((C + 63) / 64);
+  W.c_hot = dz<uint64_t>(h, C * hw); W.c_cold = dz<uint64_t>(h, C * cw);
+  W.assign = dz<int32_t>(h, n_pods); W.slot = dz<uint32_t>(h, n_pods);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_h2d(h, fw.var, &fv, sizeof(fv));
+  be_h2d(h, fw.c_state, state.data(), (size_t)C * sizeof(ks::FastClaim));
+  be_h2d(h, fw.c_ent, in->c_ent, (size_t)C * 2);
+  be_h2d(h, fw.c_npods, in->c_npods, (size_t)C * 4);
+  be_h2d(h, fw.c_hostseq, in->c_hostseq, (size_t)C * 4);
+  be_h2d(h, fw.ent_its, ents.data(), ents.size() * 8);
+  be_h2d(h, fw.q_claim, in->q_claim, (size_t)n_pods * 4);
+  be_h2d(h, fw.q_cnt, in->q_cnt, (size_t)n_pods * 4);
+  std::vector<uint64_t> hot(C * hw, in->poison), cold(C * cw, in->poison);
+  std::vector<uint32_t> pods(n_pods, (uint32_t)in->poison);
+  be_h2d(h, W.c_hot, hot.data(), hot.size() * 8); be_h2d(h, W.c_cold, cold.data(), cold.size() * 8);
+  be_h2d(h, W.assign, pods.data(), (size_t)n_pods * 4); be_h2d(h, W.slot, pods.data(), (size_t)n_pods * 4);
+  be_launch_fast_records(h, (int)C);
+  be_d2h(h, hot.data(), W.c_hot, hot.size() * 8); be_d2h(h, cold.data(), W.c_cold, cold.size() * 8);
+  be_d2h(h, out->assign, W.assign, (size_t)n_pods * 4); be_d2h(h, out->slot, W.slot, (size_t)n_pods * 4);
+  be_sync(h);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  out->hot_words = (uint32_t)hw; out->cold_words = (uint32_t)cw;
+  memcpy(out->c_hot, hot.data(), hot.size() * 8); memcpy(out->c_cold, cold.data(), cold.size() * 8);
+  for (uint32_t c = 0; c < C; ++c) {   // as decode_claim reads a record
+    const uint64_t* hr = hot.data() + c * hw; const uint64_t* cr = cold.data() + c * cw;
+    for (uint32_t x = 0; x < rw; ++x) out->mask[(size_t)c * rw + x] = hr[lay.c_mask() + x];
+    for (uint32_t x = 0; x < iw; ++x) out->its[(size_t)c * iw + x] = hr[lay.c_its() + x];
+    for (uint32_t r = 0; r < nr; ++r) { out->total[(size_t)c * nr + r] = (int64_t)hr[lay.c_total() + r]; out->head[(size_t)c * nr + r] = (int64_t)hr[lay.c_head() + r]; }
+    out->defined[c] = (uint32_t)hr[lay.c_f0()]; out->complement[c] = (uint32_t)(hr[lay.c_f0()] >> 32);
+    out->has_gte[c] = (uint32_t)hr[lay.c_f1()]; out->has_lte[c] = (uint32_t)(hr[lay.c_f1()] >> 32);
+    out->tmpl[c] = (uint32_t)hr[lay.c_meta()]; out->npods[c] = (uint32_t)(hr[lay.c_meta()] >> 32);
+    out->host_seq[c] = (uint32_t)hr[lay.c_meta2()]; out->flags[c] = (uint32_t)(hr[lay.c_meta2()] >> 32);
+    for (uint32_t k = 0; k < nk; ++k) {
+      out->gte[(size_t)c * nk + k] = ((const int64_t*)cr)[k]; out->lte[(size_t)c * nk + k] = ((const int64_t*)cr)[nk + k];
+      out->minv[(size_t)c * nk + k] = ((const int32_t*)(cr + 2 * nk))[k];
+    }
+  }
+  return KSOLVE_OK;
 }
 #endif
 

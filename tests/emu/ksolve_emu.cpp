@@ -314,6 +314,17 @@ ksolve_status ksolve_test_fast_queue(const ksolve_test_fast_queue_in* in, ksolve
 ksolve_status ksolve_test_node_dead0(const ksolve_test_node_dead0_in* in, ksolve_test_node_dead0_out* out) {
   return test_on_bare_handle("ksolve_test_node_dead0", [&](ksolve_handle* h) { return ksi::test_node_dead0(h, in, out); });
 }
+// the finalize kernel (with the sweep's claim gather) and the effective allocatable alone (ksolve_impl.h test_finalize, test_eff_alloc)
+ksolve_status ksolve_test_finalize(const ksolve_test_finalize_in* in, ksolve_test_finalize_out* out) {
+  return test_on_bare_handle("ksolve_test_finalize", [&](ksolve_handle* h) { return ksi::test_finalize(h, in, out); });
+}
+ksolve_status ksolve_test_eff_alloc(ksolve_test_eff_alloc_io* io) {
+  return test_on_bare_handle("ksolve_test_eff_alloc", [&](ksolve_handle* h) { return ksi::test_eff_alloc(h, io); });
+}
+// the cursor engine's claim records and the scatter of the queue's results alone (ksolve_impl.h test_fast_records)
+ksolve_status ksolve_test_fast_records(const ksolve_test_fast_records_in* in, ksolve_test_fast_records_out* out) {
+  return test_on_bare_handle("ksolve_test_fast_records", [&](ksolve_handle* h) { return ksi::test_fast_records(h, in, out); });
+}
 // The product's Go-sort (csrc/go_sort.h, used by the finalize kernel for OrderByPrice) on an array of integer keys:
 // out_perm receives the original indices in sorted order, ties as Go's sort.Slice leaves them.
 void ksolve_emu_go_sort(const long long* keys, int n, int* out_perm) {
