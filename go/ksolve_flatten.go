@@ -988,6 +988,9 @@ func flatten(ctx context.Context, s *Scheduler, pods []*corev1.Pod, maxSteps int
 // topology node filters that can say no — a Deployment with a spread constraint AND a nodeSelector, required node affinity or
 // nodeTaintsPolicy Honor no longer sends its batch to the general engine (reason 43). KsolveEngineSpreadFilters (25) is the spread
 // engine alone with that switch and refuses instead of falling back (tests).
+// KsolveEngineAutoPodOperators = "auto-pod-operators" (26): KsolveEngineAutoFiltersSpread, and the cursor engine takes pods whose
+// nodeAffinity uses NotIn, Exists or DoesNotExist — one such pod no longer sends its batch to the general engine (reasons 4 / 8).
+// KsolveEngineCursorPodOperators (27) is the cursor engine alone with that switch and refuses instead of falling back (tests).
 var KsolveEngine uint32 = KsolveEngineAuto
 
 const (
@@ -1012,6 +1015,9 @@ const (
 
 	KsolveEngineAutoFiltersSpread uint32 = 24
 	KsolveEngineSpreadFilters     uint32 = 25
+
+	KsolveEngineAutoPodOperators   uint32 = 26
+	KsolveEngineCursorPodOperators uint32 = 27
 )
 
 // uidWords: the pod UID as two big-endian words, so that (hi, lo) compares like the UID strings do (queue.go:107).

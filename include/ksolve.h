@@ -308,7 +308,9 @@ typedef struct {
                                     *     23    spread-unschedulable spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable
                                     *     24    auto-filters-spread  cursor, spread, general    falls back    nodes, s-nodes, limits, s-limits, operators, s-operators, unschedulable, s-unschedulable, s-filters
                                     *     25    spread-filters       spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable, s-filters
-                                    *   above 25: no name; as 17.
+                                    *     26    auto-pod-operators   cursor, spread, general    falls back    as 24, + pod-operators = the cursor engine takes pods with NotIn, Exists and DoesNotExist requirements
+                                    *     27    cursor-pod-operators cursor                     refuses       nodes, limits, operators, unschedulable, pod-operators
+                                    *   above 27: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is

@@ -13,11 +13,18 @@ enum Decline : int {
                                        // words of types; the host raises it for a batch that Gt / Lt NodePools alone keep from the cursor engine (ksolve_impl.h, plain_ops),
                                        // and under engines 18 / 19 for a topology batch outside plain_topo (pod-side bounds, minValues, ...)
   DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, Exists, DoesNotExist; Gt, Lt on the spread engine) — not the cursor engine under engines 15 / 16, not the spread engine under 18 / 19
-  DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply)
+  DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply) — not the cursor engine under engines 26 / 27, which take NotIn, Exists and
+                                       // DoesNotExist on pods (fast_engine.h, "The cursor engine's pod operators"); the existing-node stage and the spread engine raise it under every setting
   DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
   DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits
   DECLINE_QUANTITY_RANGE = 7,          // an allocatable, effective allocatable or request outside 31 bits
-  DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive)
+  DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive) — as 4: not the cursor engine under engines 26 / 27
+  // engines 26 / 27 only: what the pod operators leave to the general engine (fast_engine.h, "The cursor engine's pod operators")
+  DECLINE_CLASS_KEY_DEFINEDNESS = 9,   // a custom key some NodePool leaves undefined, with a NotIn / DoesNotExist class and an In / Exists class on it: whether the second kind is
+                                       // admissible depends on whether a pod of the first kind joined the claim before (requirements.go:185-193)
+  DECLINE_CLASS_DNE_MIXED = 10,        // a key with a DoesNotExist class and a NotIn class or a NotIn NodePool: the packed set "no dictionary value left" would stand for both
+  DECLINE_CLASS_NOTIN_BOUNDS = 11,     // a pod's NotIn on a key where a NodePool carries Gt / Lt: the claim would print the pod's values outside the bounds
+  DECLINE_CLASS_EXISTS_UNDEFINED = 12, // a pod's Exists on a well-known key some NodePool leaves undefined: the claim would print Exists
   // the cursor engine's loop
   DECLINE_CACHE_FULL = 20,             // no room for a requirement set's cache entry or Pareto vectors (a claim's acceptance words, a new class slot)
   DECLINE_REFRESH_FAILED = 21,         // the same while the driver recomputed a claim's acceptance words

@@ -28,6 +28,7 @@ struct EnginePolicy {
   bool unschedulable;   // the cursor engine keeps a pod that can go nowhere and reports its error (fast_engine.h, "Unschedulable pods")
   bool spread_unschedulable; // the spread engine does, and retries such pods for real (topo_engine.h, "The spread engine's unschedulable pods")
   bool spread_filters;  // the spread engine counts pods through topology node filters that can say no (topo_engine.h, "Topology node filters")
+  bool pod_operators;   // the cursor engine takes pod classes with NotIn, Exists and DoesNotExist requirements (fast_engine.h, "The cursor engine's pod operators")
   const char* name;     // options.engine of the host library's problem document; nullptr = no name
 
   constexpr bool general_only() const { return run == General; }
@@ -37,38 +38,40 @@ struct EnginePolicy {
   constexpr bool may_spread() const { return run == Auto || run == Spread; }   // (a cursor-only handle never tries the spread engine)
 };
 
-//                                              run                    plan pick   pair   nodes  s-nodes limits s-lim  ops    s-ops  unsched s-uns  s-filt name
+//                                              run                    plan pick   pair   nodes  s-nodes limits s-lim  ops    s-ops  unsched s-uns  s-filt p-ops  name
 inline constexpr EnginePolicy kEngineSettings[] = {
-  /*  0 */ {EnginePolicy::Auto,    0, true,  false, false, false, false, false, false, false, false, false, false, "auto"},
-  /*  1 */ {EnginePolicy::General, 0, false, false, false, false, false, false, false, false, false, false, false, "general"},
-  /*  2 */ {EnginePolicy::Cursor,  0, true,  false, false, false, false, false, false, false, false, false, false, "cursor"},
-  /*  3 */ {EnginePolicy::Cursor,  1, false, false, false, false, false, false, false, false, false, false, false, "cursor-wide"},
-  /*  4 */ {EnginePolicy::Cursor,  2, false, false, false, false, false, false, false, false, false, false, false, "cursor-hbm"},
-  /*  5 */ {EnginePolicy::Cursor,  0, false, true,  false, false, false, false, false, false, false, false, false, "cursor-pair"},
-  /*  6 */ {EnginePolicy::Spread,  0, false, false, false, false, false, false, false, false, false, false, false, "spread"},
-  /*  7 */ {EnginePolicy::Auto,    0, true,  false, true,  false, false, false, false, false, false, false, false, "auto-nodes"},
-  /*  8 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, false, false, false, false, false, false, false, "cursor-nodes"},
-  /*  9 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  false, false, false, false, false, false, false, "auto-nodes-spread"},
-  /* 10 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, false, false, false, false, false, false, "spread-nodes"},
-  /* 11 */ {EnginePolicy::Auto,    0, true,  false, true,  false, true,  false, false, false, false, false, false, "auto-limits"},
-  /* 12 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, false, false, false, false, false, "cursor-limits"},
-  /* 13 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  false, false, false, false, false, "auto-limits-spread"},
-  /* 14 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, false, false, false, false, "spread-limits"},
-  /* 15 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  false, false, false, false, "auto-operators"},
-  /* 16 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, false, false, false, "cursor-operators"},
-  /* 17 */ {EnginePolicy::Cursor,  0, false, false, false, false, false, false, false, false, false, false, false, nullptr},   // no name: what a value past the table stands for (below), kept as it was
-  /* 18 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  false, false, false, "auto-operators-spread"},
-  /* 19 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, false, false, "spread-operators"},
-  /* 20 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  false, false, "auto-unschedulable"},
-  /* 21 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, true,  false, false, "cursor-unschedulable"},
-  /* 22 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  false, "auto-unschedulable-spread"},
-  /* 23 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  false, "spread-unschedulable"},
-  /* 24 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  "auto-filters-spread"},
-  /* 25 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  true,  "spread-filters"},
+  /*  0 */ {EnginePolicy::Auto,    0, true,  false, false, false, false, false, false, false, false, false, false, false, "auto"},
+  /*  1 */ {EnginePolicy::General, 0, false, false, false, false, false, false, false, false, false, false, false, false, "general"},
+  /*  2 */ {EnginePolicy::Cursor,  0, true,  false, false, false, false, false, false, false, false, false, false, false, "cursor"},
+  /*  3 */ {EnginePolicy::Cursor,  1, false, false, false, false, false, false, false, false, false, false, false, false, "cursor-wide"},
+  /*  4 */ {EnginePolicy::Cursor,  2, false, false, false, false, false, false, false, false, false, false, false, false, "cursor-hbm"},
+  /*  5 */ {EnginePolicy::Cursor,  0, false, true,  false, false, false, false, false, false, false, false, false, false, "cursor-pair"},
+  /*  6 */ {EnginePolicy::Spread,  0, false, false, false, false, false, false, false, false, false, false, false, false, "spread"},
+  /*  7 */ {EnginePolicy::Auto,    0, true,  false, true,  false, false, false, false, false, false, false, false, false, "auto-nodes"},
+  /*  8 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, false, false, false, false, false, false, false, false, "cursor-nodes"},
+  /*  9 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  false, false, false, false, false, false, false, false, "auto-nodes-spread"},
+  /* 10 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, false, false, false, false, false, false, false, "spread-nodes"},
+  /* 11 */ {EnginePolicy::Auto,    0, true,  false, true,  false, true,  false, false, false, false, false, false, false, "auto-limits"},
+  /* 12 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, false, false, false, false, false, false, "cursor-limits"},
+  /* 13 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  false, false, false, false, false, false, "auto-limits-spread"},
+  /* 14 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, false, false, false, false, false, "spread-limits"},
+  /* 15 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  false, false, false, false, false, "auto-operators"},
+  /* 16 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, false, false, false, false, "cursor-operators"},
+  /* 17 */ {EnginePolicy::Cursor,  0, false, false, false, false, false, false, false, false, false, false, false, false, nullptr},   // no name: what a value past the table stands for (below), kept as it was
+  /* 18 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  false, false, false, false, "auto-operators-spread"},
+  /* 19 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, false, false, false, "spread-operators"},
+  /* 20 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  false, false, false, "auto-unschedulable"},
+  /* 21 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, true,  false, false, false, "cursor-unschedulable"},
+  /* 22 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  false, false, "auto-unschedulable-spread"},
+  /* 23 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  false, false, "spread-unschedulable"},
+  /* 24 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  false, "auto-filters-spread"},
+  /* 25 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  true,  false, "spread-filters"},
+  /* 26 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  true,  "auto-pod-operators"},
+  /* 27 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, true,  false, false, true,  "cursor-pod-operators"},
 };
 inline constexpr uint32_t kEngineSettingCount = (uint32_t)(sizeof(kEngineSettings) / sizeof(kEngineSettings[0]));
 // A value past the table is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch.
-inline constexpr EnginePolicy kEngineSettingPastTable = {EnginePolicy::Cursor, 0, false, false, false, false, false, false, false, false, false, false, false, nullptr};
+inline constexpr EnginePolicy kEngineSettingPastTable = {EnginePolicy::Cursor, 0, false, false, false, false, false, false, false, false, false, false, false, false, nullptr};
 
 inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineSettingCount ? kEngineSettings[value] : kEngineSettingPastTable; }
 

@@ -30,8 +30,8 @@
 //
 // Everything this engine does not handle (an unschedulable pod — unless the handle asked to keep them, "Unschedulable pods" below —, NodePool limits that actually exclude a type — unless the handle
 // asked for limit stages, FastLimits below —, more claims
-// than the LDS plan holds, non-positive operators — on pods; on NodePools unless the handle asked for complement templates, setup()
-// below —, ...) makes it stop with status 3 before it has written a result;
+// than the LDS plan holds, non-positive operators — on pods unless the handle asked for pod operators, "The cursor engine's pod operators"
+// below; on NodePools unless the handle asked for complement templates, setup() below —, ...) makes it stop with status 3 before it has written a result;
 // the host then runs the general engine (engine.h) on the same problem. There is no CPU path.
 #pragma once
 #include <type_traits>
@@ -87,6 +87,9 @@ struct FastMisc {   // small LDS tables
 };
 
 struct FastVar { int nv; uint8_t vkey[kFastMaxVar], voff[kFastMaxVar], vwidth[kFastMaxVar]; uint16_t vword[kFastMaxVar]; };   // the keys pods select on
+// engines 26 / 27 ("The cursor engine's pod operators" below), one record in HBM written by setup() and read by ksolve_fast_records:
+// on = every field's top bit is the phantom value, dne = the variable keys (bit j) some pod class requires DoesNotExist on
+struct FastPodOps { uint32_t on, dne; };
 
 // What the existing-node stage leaves for the loop and for the counters (one record in HBM, written by ksolve_pack_nodes)
 struct FastNodes {
@@ -153,6 +156,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   uint8_t* us_diag;
   uint64_t* us_cls;       // [n_pods >= n_classes] by class: the verdict of the class's last failed template walk (FastCold::new_claim), reset by setup()
   uint32_t* pod_qpos;     // [n_pods], behind the existing-node stage only: a pod's position in the FULL queue (ksolve_fast_requeue)
+  FastPodOps* podops;     // [1] engines 26 / 27 (a cursor handle only), null otherwise: setup() accepts pod classes with NotIn, Exists and DoesNotExist requirements — "The cursor engine's pod operators" below. The last field: every other kernel reads the layout it always read
 };
 static_assert(offsetof(FastWork, us_n) == offsetof(FastWork, unsched) + 8, "FastWork::filt fills the gap behind unsched: the layout every kernel reads stays what it was");
 
@@ -513,8 +517,49 @@ struct FastKeepState {
   uint32_t us_epoch = 1;           // bumped whenever a pool's remaining resources change (0: no verdict)
 };
 struct FastNoKeepState {};
-template <class W, int GS, int R, bool US = kFastKeepBuiltIn>
-struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
+
+// The cursor engine's pod operators (engines 26 / 27, FastWork::podops). PO is a compile-time switch like US: the kernels of 26 / 27
+// are instantiations of their own (ksolve_pack_fast_podops.hip, US on as well), every other kernel is compiled without a line of
+// it, and the host emulation builds it into its one engine and FastWork::podops decides at run time.
+//
+// A pod class may carry NotIn, Exists and DoesNotExist requirements (Gt / Lt stay outside: reason 1, on the host). The packed word
+// keeps its form and the loops keep their code — a claim accepts a class when every field the class selects on keeps a bit — because
+// every field gets one more bit on top, the PHANTOM value: "some value outside the dictionary". A complement set (NotIn, Exists, a
+// key nobody defined) holds it, a concrete In set does not, so
+//   NotIn S     class field = the dictionary's values outside S | phantom, guard bit set (the AND keeps the claim's)
+//   Exists      class field = all ones, guard bit set: the claim's set stays what it is, and an In [] / DoesNotExist claim fails
+//   DoesNotExist class field = the phantom bit alone, guard bit set
+//   In Q        as ever: Q, guard bit clear
+// and Requirements.Compatible + Add (requirements.go:254-274, requirement.go:181-254) come out of the same AND:
+//   In F ∩ NotIn S = F \ S, concrete, empty = not compatible;  complement ∩ NotIn S keeps the phantom bit: always compatible, even
+//   when no dictionary value is left;  In F ∩ DoesNotExist = nothing: not compatible;  undefined / NotIn / DoesNotExist ∩ DoesNotExist =
+//   the phantom bit alone: the escape of requirements.go:260-265, and that IS the DoesNotExist state (an In pod finds nothing in it,
+//   a NotIn or DoesNotExist pod finds the phantom bit).
+// A template's DoesNotExist is the phantom bit alone as well, guard bit set (it stays the template's own requirement).
+// What the word cannot tell is decided per (class, template) in tmplok, where it is static, and declined where it is not:
+//   Exists class x DoesNotExist template, DoesNotExist class x Exists / Gt / Lt template: tmplok off (the word would say yes);
+//   a negative class may name a custom key the template does not define, In / Exists may not (requirements.go:185-193) — and
+//     once a negative pod joined, the claim Has() the key: a batch with both kinds of class on such a key is DECLINE_CLASS_KEY_DEFINEDNESS;
+//   "phantom bit alone" is DoesNotExist or a NotIn set that covers the dictionary: a key with a DoesNotExist class and a NotIn class or
+//     a NotIn template is DECLINE_CLASS_DNE_MIXED (this covers the Exists template that a NotIn pod turns into NotIn);
+//   a pod's NotIn value outside a template's Gt / Lt bounds would have to print: DECLINE_CLASS_NOTIN_BOUNDS;
+//   a pod's Exists on a well-known key a template leaves undefined would have to print Exists: DECLINE_CLASS_EXISTS_UNDEFINED.
+// A claim whose guard bit is set and whose field is narrower than its template's has met pods: it meets the instance types again
+// (compat_word) and prints as NotIn (the dictionary's values outside the field) or DoesNotExist (fast_record_body).
+struct FastPodOpsState { uint32_t dne_vars = 0; int po_on = 0; };   // variable keys (bit j) with a DoesNotExist class; the switch is on
+struct FastNoPodOpsState {};
+// the field (without offset) and the guard bit of template requirement tr on key k, dictionary word x, in a field of `width` bits
+// whose top bit is the phantom value
+KS_FN uint64_t fast_po_tmpl_field(const Dict& d, const ReqRef& tr, int k, uint32_t x, int width, bool& guard) {
+  const uint64_t ph = 1ull << (width - 1);
+  const uint64_t v = req_values_word(d, tr, k, x);
+  if (bit(tr.complement, k)) { guard = true; return v | ph; }
+  guard = v == 0;           // In [] == DoesNotExist
+  return v ? v : ph;
+}
+template <class W, int GS, int R, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn>
+struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, std::conditional<PO, FastPodOpsState, FastNoPodOpsState>::type {
+  KS_DEV bool po() const { if constexpr (PO) return this->po_on != 0; else return false; }
   const ProblemView* Pk;
   const Workspace* Sk;
   const FastWork* Fk;
@@ -562,6 +607,23 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
     for (int j = 0; j < nv; ++j) {
       const int k = Mm.vkey[j];
       if (!((Pv.it_keys >> k) & 1u)) continue;
+      if constexpr (PO) if (po() && ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1)) {
+        // pod operators: a guard bit over a field narrower than the template's (or than all ones on a key the template leaves
+        // undefined) is a NotIn set pods have grown, or DoesNotExist. Concrete types by kv_has over the dictionary values left, types
+        // without the key and — against a set that is still a complement — complement types always, NotIn / DoesNotExist types by the
+        // escape; an Exists type fails DoesNotExist. The template's own requirement skips as ever.
+        const uint64_t fm = Mm.fmask[j] >> Mm.voff[j];
+        const uint64_t f = (vm >> Mm.voff[j]) & fm;
+        if (f == ((Mm.tvmask[vm >> 56] >> Mm.voff[j]) & fm)) continue;
+        uint64_t r = Pv.key_undef[(size_t)k * iw + w] | Pv.key_neg[(size_t)k * iw + w];
+        if (!((this->dne_vars >> j) & 1u)) {
+          r |= Pv.key_compl[(size_t)k * iw + w];
+          const size_t base = (size_t)Mm.vword[j] * 64;
+          for (uint64_t dv = f & (fm >> 1); dv; dv &= dv - 1) r |= Pv.kv_has[(base + ctz64(dv)) * iw + w];
+        }
+        acc &= r;
+        continue;
+      }
       if ((vm >> (Mm.voff[j] + Mm.vwidth[j])) & 1) continue;   // guard bit set: the requirement set does not define the key, or holds the template's own complement set — in t_its already
       uint64_t field = (vm >> Mm.voff[j]) & (Mm.fmask[j] >> Mm.voff[j]);
       uint64_t r = Pv.key_undef[(size_t)k * iw + w];
@@ -704,8 +766,33 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
       for (uint32_t ks_ = tr.defined & ~tr.complement; ks_; ks_ &= ks_ - 1) if (!key_nonempty(d, tr.mask, __builtin_ctz(ks_))) neg |= 1;   // In [] == DoesNotExist
       return neg; })) return DECLINE_TEMPLATE_NOT_POSITIVE;
     // classes: only In sets; the keys they define are the variable keys
-    if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return DECLINE_CLASS_NOT_POSITIVE;
+    // ... but for engines 26 / 27 (pod operators, above), on the cursor engine alone
+    bool pod_ops = false;
+    if constexpr (PO) { pod_ops = !topo && F.podops != nullptr; this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0; }
+    if (!pod_ops && W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return DECLINE_CLASS_NOT_POSITIVE;
     uint32_t vk = (uint32_t)W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.defined[c]; });
+    uint32_t k_dne = 0;   // pod operators: keys some class requires DoesNotExist on
+    if constexpr (PO) if (pod_ops) {
+      // keys by the operator the classes use on them (reqalg.h OP_*: In, NotIn, Exists, DoesNotExist), one reduction per operator
+      uint32_t kop[4];
+      for (int op = 0; op < 4; ++op) kop[op] = (uint32_t)W::reduce_or(nc, [&](int c) {
+        const ReqRef cr = Pv.cls_reqs.at(d, c);
+        uint64_t m = 0;
+        for (uint32_t ks_ = cr.defined; ks_; ks_ &= ks_ - 1) { const int k = __builtin_ctz(ks_); if (req_op(d, cr, k) == op) m |= 1ull << k; }
+        return m; });
+      uint32_t t_undef = 0, t_notin = 0, t_bounds = 0;   // keys some template leaves undefined, requires NotIn on, bounds
+      for (int t = 0; t < T; ++t) {
+        const ReqRef tr = Pv.tmpl_reqs.at(d, t);
+        t_undef |= ~tr.defined; t_bounds |= tr.has_gte | tr.has_lte;
+        for (uint32_t ks_ = tr.defined & tr.complement; ks_; ks_ &= ks_ - 1) { const int k = __builtin_ctz(ks_); if (req_op(d, tr, k) == OP_NOTIN) t_notin |= 1u << k; }
+      }
+      const uint32_t wkm = d.well_known_mask;
+      if ((kop[OP_NOTIN] | kop[OP_DNE]) & (kop[OP_IN] | kop[OP_EXISTS]) & t_undef & ~wkm) return DECLINE_CLASS_KEY_DEFINEDNESS;
+      if (kop[OP_DNE] & (kop[OP_NOTIN] | t_notin)) return DECLINE_CLASS_DNE_MIXED;
+      if (kop[OP_NOTIN] & t_bounds) return DECLINE_CLASS_NOTIN_BOUNDS;
+      if (kop[OP_EXISTS] & t_undef & wkm) return DECLINE_CLASS_EXISTS_UNDEFINED;
+      k_dne = kop[OP_DNE];
+    }
     if (topo) vk |= (uint32_t)W::reduce_or(P.topo.n_groups, [&](int g) { return Pv.topo.key[g] >= 0 ? (uint64_t)1 << Pv.topo.key[g] : (uint64_t)0; });
     if (d.key_hostname >= 0 && ((vk >> d.key_hostname) & 1u)) return DECLINE_SELECTS_HOST_OR_TYPE;
     if (d.key_it >= 0 && ((vk >> d.key_it) & 1u)) return DECLINE_SELECTS_HOST_OR_TYPE;
@@ -715,8 +802,9 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
       if (!((vk >> k) & 1u)) continue;
       if (d.key_word_off[k + 1] - d.key_word_off[k] != 1 || nv >= kFastMaxVar) return DECLINE_KEYS_DO_NOT_PACK;
       const uint64_t valid = d.value_valid[d.key_word_off[k]];
-      const int width = valid ? 64 - __builtin_clzll(valid) : 1;
+      const int width = (valid ? 64 - __builtin_clzll(valid) : 1) + (pod_ops ? 1 : 0);   // (pod operators: + the phantom bit)
       if (bits + width + 1 > kFastVarBits) return DECLINE_KEYS_DO_NOT_PACK;
+      if constexpr (PO) if ((k_dne >> k) & 1u) this->dne_vars |= 1u << nv;
       if (W::leader()) {
         Mp->vkey[nv] = (uint8_t)k; Mp->voff[nv] = (uint8_t)bits; Mp->vwidth[nv] = (uint8_t)width; Mp->vword[nv] = (uint16_t)d.key_word_off[k];
         Mp->fmask[nv] = ((1ull << width) - 1) << bits;
@@ -728,6 +816,7 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
     if (W::leader()) {
       FastVar fv;
       fv.nv = nv;
+      if constexpr (PO) if (F.podops) { F.podops->on = pod_ops ? 1u : 0u; F.podops->dne = this->dne_vars; }
       for (int j = 0; j < kFastMaxVar; ++j) { fv.vkey[j] = Mp->vkey[j]; fv.voff[j] = Mp->voff[j]; fv.vwidth[j] = Mp->vwidth[j]; fv.vword[j] = Mp->vword[j]; }
       *F.var = fv;
     }
@@ -758,6 +847,11 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
       for (int j = 0; j < nvv; ++j) {
         const int k = Mm.vkey[j];
         const uint64_t guard = 1ull << (Mm.voff[j] + Mm.vwidth[j]);
+        if (pod_ops && ((tdef >> k) & 1u)) {   // pod operators: complement sets hold the phantom bit, DoesNotExist is that bit alone and keeps the guard bit
+          bool g = false;
+          const uint64_t f = fast_po_tmpl_field(d, tr, k, Mm.vword[j], Mm.vwidth[j], g);
+          vm |= ((f << Mm.voff[j]) & Mm.fmask[j]) | (g ? guard : 0ull);
+        } else
         if ((tdef >> k) & 1u) vm |= ((req_values_word(d, tr, k, Mm.vword[j]) << Mm.voff[j]) & Mm.fmask[j]) | (bit(tr.complement, k) ? guard : 0ull);
         else vm |= Mm.fmask[j] | guard;   // undefined: every value, and the guard bit says so
       }
@@ -819,7 +913,21 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
       const uint64_t* cm = Pv.cls_reqs.mask + (size_t)c * d.req_words;
       const uint32_t kdef = Pv.cls_reqs.defined[c];
       uint64_t vm = 0xFFull << 56, dm = 0, badc = 0;
+      uint32_t kpos = kdef, kexists = 0, kdne = 0;   // pod operators: keys the class requires In or Exists on, Exists, DoesNotExist
       for (int j = 0; j < nvv; ++j) {
+        if (pod_ops && ((kdef >> Mm.vkey[j]) & 1u) && (((Pv.cls_reqs.complement[c] >> Mm.vkey[j]) & 1u) || !cm[Mm.vword[j]])) {
+          // NotIn S: the dictionary's values outside S and the phantom bit; Exists: all ones; DoesNotExist (== In []): the phantom bit
+          // alone. The guard bit stays set: the AND keeps the claim's.
+          const int k = Mm.vkey[j];
+          const uint64_t ph = 1ull << (Mm.voff[j] + Mm.vwidth[j] - 1), guard = ph << 1;
+          const bool comp = ((Pv.cls_reqs.complement[c] >> k) & 1u) != 0;
+          const uint64_t s_ = cm[Mm.vword[j]];
+          uint64_t f;
+          if (!comp) { f = ph; kdne |= 1u << k; kpos &= ~(1u << k); }
+          else if (!s_) { f = Mm.fmask[j]; kexists |= 1u << k; }
+          else { f = (((~s_ & d.value_valid[Mm.vword[j]]) << Mm.voff[j]) & Mm.fmask[j]) | ph; kpos &= ~(1u << k); }
+          vm |= f | guard; dm |= Mm.fmask[j];
+        } else
         if ((kdef >> Mm.vkey[j]) & 1u) {
           const uint64_t f = (cm[Mm.vword[j]] << Mm.voff[j]) & Mm.fmask[j];
           if (!f) badc = 1;   // In [] == DoesNotExist: not positive
@@ -831,7 +939,19 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type {
       for (int r = 0; r < 4; ++r) s.size[r] = r < nr ? (int32_t)Pv.cls_requests[(size_t)c * nr + r] : 0;
       uint32_t ok = 0;
       const uint64_t tol = Pv.cls_tolerates[c];
-      for (int t = 0; t < T; ++t) if (!(Pv.tmpl_taints[t] & ~tol) && !(kdef & ~Mm.tdef[t] & ~wk)) ok |= 1u << t;
+      if (!pod_ops) { for (int t = 0; t < T; ++t) if (!(Pv.tmpl_taints[t] & ~tol) && !(kdef & ~Mm.tdef[t] & ~wk)) ok |= 1u << t; }
+      else for (int t = 0; t < T; ++t) {
+        // pod operators: a negative requirement may name a key the template does not define (requirements.go:185-193), and what the
+        // packed word cannot tell: Exists against the template's DoesNotExist, DoesNotExist against its Exists / Gt / Lt
+        if ((Pv.tmpl_taints[t] & ~tol) || (kpos & ~Mm.tdef[t] & ~wk)) continue;
+        const ReqRef tr = Pv.tmpl_reqs.at(d, t);
+        bool v = true;
+        for (uint32_t ks_ = (kexists | kdne) & tr.defined; ks_; ks_ &= ks_ - 1) {
+          const int k = __builtin_ctz(ks_), top = req_op(d, tr, k);
+          if (((kexists >> k) & 1u) ? top == OP_DNE : !op_negative(top)) v = false;
+        }
+        if (v) ok |= 1u << t;
+      }
       s.tmplok = ok; s.kdef = kdef;
       fc[c] = s;
       return badc;
@@ -2335,9 +2455,9 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
 }
 
 // The driver: runs the loop, handles its events through FastCold.
-template <class W, int GS = 0, int R = 1, bool HP = false, bool US = kFastKeepBuiltIn>
+template <class W, int GS = 0, int R = 1, bool HP = false, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn>
 struct FastEngine {
-  FastCold<W, GS, R, US> cold;
+  FastCold<W, GS, R, US, PO> cold;
   KS_LDS FastHot* hs;
   KS_DEV FastEngine(const ProblemView* p, const Workspace* s, const FastWork* f, char* lds) { cold.init(p, s, f, lds); hs = cold.hs; }
 
@@ -2505,10 +2625,25 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   // complement template, engines 15 / 16) says the claim still holds the template's own requirement: its raw mask words, its
   // complement flag and its bounds, as the general engine's claims carry them (engine.h, the template records).
   const ReqRef tr = P.tmpl_reqs.at(d, t);
-  uint32_t vdef = tr.defined, vcompl = tr.complement, vhg = tr.has_gte, vhl = tr.has_lte, concrete = 0;
+  // Pod operators (engines 26 / 27, FastWork::podops): a set guard bit over a field narrower than the template's — than all ones on a
+  // key the template leaves undefined — is a set pods have changed: NotIn (the template's values and the pods': the dictionary's
+  // values outside the field; no bounds, DECLINE_CLASS_NOTIN_BOUNDS), or DoesNotExist on a key with a DoesNotExist class.
+  const bool pod_ops = a.fw.podops && a.fw.podops->on;
+  const uint32_t dne_vars = pod_ops ? a.fw.podops->dne : 0u;
+  uint32_t vdef = tr.defined, vcompl = tr.complement, vhg = tr.has_gte, vhl = tr.has_lte, concrete = 0, grown = 0, gone = 0;
   for (int j = 0; j < fv.nv; ++j) {
     const uint32_t kb = 1u << fv.vkey[j];
-    if ((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) { if (!(tr.defined & kb)) vdef &= ~kb; }
+    if ((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) {
+      bool own = true;
+      if (pod_ops) {
+        const uint64_t fm = (1ull << fv.vwidth[j]) - 1;
+        bool g = false;
+        own = ((st.vmask >> fv.voff[j]) & fm) == ((tr.defined & kb) ? fast_po_tmpl_field(d, tr, fv.vkey[j], fv.vword[j], fv.vwidth[j], g) & fm : fm);
+      }
+      if (own) { if (!(tr.defined & kb)) vdef &= ~kb; }
+      else if ((dne_vars >> j) & 1u) { vdef |= kb; gone |= kb; vcompl &= ~kb; vhg &= ~kb; vhl &= ~kb; }
+      else { vdef |= kb; grown |= kb; vcompl |= kb; vhg &= ~kb; vhl &= ~kb; }
+    }
     else { vdef |= kb; concrete |= kb; vcompl &= ~kb; vhg &= ~kb; vhl &= ~kb; }
   }
   uint64_t* rec = a.ws.c_hot + (size_t)c * ly.c_hot_words();
@@ -2516,6 +2651,8 @@ KS_DEV void fast_record_body(int c, const FastRecordArgs& a) {
   W::for_n(ly.rw, [&](int w) {
     uint64_t v = tm[w];
     for (int j = 0; j < fv.nv; ++j) if (fv.vword[j] == w && ((concrete >> fv.vkey[j]) & 1u)) v = (st.vmask >> fv.voff[j]) & ((1ull << fv.vwidth[j]) - 1);
+    for (int j = 0; j < fv.nv; ++j) if (fv.vword[j] == w && (((grown | gone) >> fv.vkey[j]) & 1u))
+      v = ((gone >> fv.vkey[j]) & 1u) ? 0ull : d.value_valid[w] & ~((st.vmask >> fv.voff[j]) & ((1ull << (fv.vwidth[j] - 1)) - 1));
     rec[ly.c_mask() + w] = v;
   });
   if (vhg | vhl) {   // the cold record is read only then (decode_claim, finalize_body)

@@ -705,7 +705,11 @@ static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, 
   if (hipEventElapsedTime(&ms, b->ev0[ksi::T_PACK], b->ev1[ksi::T_PACK]) == hipSuccess) h->timers.ms[ksi::T_PACK] = ms;
 }
 typedef void (*ksolve_pack_fast_fn)(const ks::FastArgs*);
-static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows, bool unsched) {
+static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows, bool unsched, bool podops) {
+  if (podops) {   // engines 26 / 27: the kernels with the set-aside list and the pod operators compiled in
+    if (rows == 1) return plan == 2 ? ksolve_pack_fast_p_g2r1 : plan == 1 ? ksolve_pack_fast_p_g1r1 : ksolve_pack_fast_p_g0r1;
+    return plan == 2 ? ksolve_pack_fast_p_g2r4 : plan == 1 ? ksolve_pack_fast_p_g1r4 : ksolve_pack_fast_p_g0r4;
+  }
   if (unsched) {   // engines 20 / 21: the kernels with the set-aside list compiled in
     if (rows == 1) return plan == 2 ? ksolve_pack_fast_u_g2r1 : plan == 1 ? ksolve_pack_fast_u_g1r1 : ksolve_pack_fast_u_g0r1;
     return plan == 2 ? ksolve_pack_fast_u_g2r4 : plan == 1 ? ksolve_pack_fast_u_g1r4 : ksolve_pack_fast_u_g0r4;
@@ -716,7 +720,7 @@ static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows, bool unsched) {
 static void be_launch_pack_fast(ksolve_handle* h) {
   const int lds_bytes = h->fw.plan.total_bytes;
   const bool two = h->fw.plan.helper != 0;   // (plan 0, one row of class slots: placer + refresher)
-  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : pack_fast_kernel(h->fw.plan.global_state, h->fw.plan.rows, h->fw.unsched != 0);
+  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : pack_fast_kernel(h->fw.plan.global_state, h->fw.plan.rows, h->fw.unsched != 0, h->fw.podops != nullptr);
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));

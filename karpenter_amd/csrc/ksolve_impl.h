@@ -1154,6 +1154,10 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
         fw.us_err = dz<uint8_t>(h, d->n_pods); fw.us_diag = dz<uint8_t>(h, d->n_pods); fw.us_cls = dz<uint64_t>(h, d->n_pods);   // (a class per pod at most)
         if (fw.nodes) fw.pod_qpos = dz<uint32_t>(h, d->n_pods);
       }
+      // engines 26 / 27: pod classes with NotIn, Exists and DoesNotExist (fast_engine.h, "The cursor engine's pod operators"); the kernels are
+      // those of the set-aside list with the switch compiled in, so the two go together. Pod-side Gt / Lt and minValues stay outside
+      // `plain` (reason 1 above), whatever the setting.
+      fw.podops = h->eng.pod_operators && fw.unsched ? dz<ks::FastPodOps>(h, 1) : nullptr;
     }
     // spread engine (topo_engine.h): candidate when the problem is plain but for its topology groups and has no relaxation rows; the
     // kernel checks the rest (which kinds of groups, positive operators, ...) and hands the problem back otherwise. It runs on the

@@ -1,6 +1,6 @@
 // pack_kernels.h — the pack kernels (one wavefront per scheduling problem) live in translation units of their own, so that build()
 // compiles them side by side (the general engine's instantiations alone are minutes of one hipcc): ksolve_pack_general.hip,
-// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip, ksolve_pack_topo_filter.hip. ksolve.hip (the HIP backend of the C
+// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_fast_unsched.hip, ksolve_pack_fast_podops.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip, ksolve_pack_topo_filter.hip. ksolve.hip (the HIP backend of the C
 // ABI) launches them through these declarations; no device function crosses a translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +30,13 @@ __global__ void ksolve_pack_fast_u_g2r1(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_u_g0r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_u_g1r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_u_g2r4(const ks::FastArgs* a);
+// ... and the same six with the pod operators of engines 26 / 27 compiled in as well (ksolve_pack_fast_podops.hip)
+__global__ void ksolve_pack_fast_p_g0r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_p_g1r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_p_g2r1(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_p_g0r4(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_p_g1r4(const ks::FastArgs* a);
+__global__ void ksolve_pack_fast_p_g2r4(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast2(const ks::FastArgs* a);
 __global__ void ksolve_pack_fast_batch(const ks::FastArgs* const* items);
 __global__ void ksolve_pack_topo(const ks::TopoArgs* a);
