@@ -2,51 +2,16 @@
 tests/test_gpu_daemonsets.py on the device): the known answers, seeded fuzz generators and the comparison helper."""
 import random
 
-import parity
+import engine_checks as ec
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler
-
-
-def sorted_its(res):
-    """Daemon-overhead groups are visited in Go map order by the reference (scheduler.go:1001), so the order of
-    InstanceTypeOptions across groups is not defined: compare them as sets."""
-    for c in res["newNodeClaims"]:
-        c["instanceTypes"] = sorted(c["instanceTypes"])
-    return res
-
-
-def solve(prob, engine, lib):
-    s = NewScheduler(dict(prob, options=dict(prob.get("options", {}), engine=engine)), solver_lib=lib)
-    try:
-        return s.Solve()
-    finally:
-        s.close()
-
-
-def same(got, want):
-    parity.assert_same_results(sorted_its(got), sorted_its(want))
-    assert got["counters"]["referenceBinEvaluations"] == want["counters"]["binEvaluations"]   # V (SURVEY.md §8d)
-    assert abs(got["packingCost"] - want["packingCost"]) < 1e-9 * max(1.0, want["packingCost"])
+from mix_cases import fuzz_problem, lite_problem
 
 
 def check_engine(oracle, lib, prob, engine, plans=()):
     """engine (cursor / spread) must solve it — no fallback, reason 0 — and equal the oracle; so must auto (which has to pick the
-    same engine) and the general engine; `plans`: further cursor settings that must agree."""
-    want = oracle.solve(prob)
-    got = solve(prob, engine, lib)
-    assert got["counters"]["engine"] == engine and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want)
-    auto = solve(prob, "auto", lib)
-    assert auto["counters"]["engine"] == engine and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want)
-    general = solve(prob, "general", lib)
-    assert general["counters"]["engine"] == "general"
-    same(general, want)
-    for other in plans:
-        r = solve(prob, other, lib)
-        assert r["counters"]["engine"] == "cursor" and r["counters"]["engineFallbackReason"] == 0
-        same(r, want)
-    return got, want
+    same engine) and the general engine; `plans`: further cursor settings that must agree. Instance-type lists as sets: daemon-overhead
+    groups are visited in Go map order by the reference (scheduler.go:1001), so their order across groups is not defined."""
+    return ec.three_ways(oracle, lib, prob, engine, plans=plans)
 
 
 def four_resource_default_types():
@@ -99,7 +64,6 @@ def _zones(prob):
 
 
 def cursor_fuzz_problem(seed):
-    from test_cursor_engine import lite_problem
     rng = random.Random(31000 + seed)
     prob = lite_problem(rng, rng.choice([30, 200, 900]))
     prob["daemonSetPods"] = random_daemonsets(rng, _zones(prob))
@@ -107,7 +71,6 @@ def cursor_fuzz_problem(seed):
 
 
 def spread_fuzz_problem(seed):
-    from test_spread_engine import fuzz_problem
     prob = fuzz_problem(seed)
     rng = random.Random(32000 + seed)
     prob["daemonSetPods"] = random_daemonsets(rng, _zones(prob))
@@ -117,16 +80,11 @@ def spread_fuzz_problem(seed):
 def run_fuzz(oracle, lib, make, seeds, engine):
     """Whatever `auto` runs equals the oracle; returns (problems that ran on `engine`, histogram of fallback reasons)."""
     ran, reasons = 0, {}
-    for seed in seeds:
-        prob = make(seed)
-        got = solve(prob, "auto", lib)
-        same(got, oracle.solve(prob))
-        c = got["counters"]
-        if c["engine"] == engine:
-            assert c["engineFallbackReason"] == 0
+    for _, _, _, _, on, reason in ec.fuzz_cases(oracle, lib, ((seed, make(seed)) for seed in seeds), "auto", pops=False):
+        if on == engine:
             ran += 1
         else:
-            assert c["engine"] == "general"
-            reasons[c["engineFallbackReason"]] = reasons.get(c["engineFallbackReason"], 0) + 1
+            assert on == "general"
+            reasons[reason] = reasons.get(reason, 0) + 1
     print(f"{engine}: {ran} of {len(seeds)} on the fast engine; general engine by reason {dict(sorted(reasons.items()))}")
     return ran, reasons

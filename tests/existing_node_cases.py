@@ -3,27 +3,18 @@ emulation, tests/test_gpu_cursor_nodes.py on the device): known shapes, the seed
 import random
 
 import daemonset_cases as dc
+import engine_checks as ec
 from karpenter_amd import fixtures as fx
-
-same, solve = dc.same, dc.solve
+from mix_cases import lite_problem
 
 
 def check_engine(oracle, lib, prob, variant=None):
     """"cursor-nodes" must solve it on the cursor engine — no fallback, reason 0 — and equal the oracle claim by claim, node by node
     and in the reference-equivalent evaluation count; so must "auto-nodes" (which has to pick the same engine) and the general
     engine. `variant`: where the stage must have kept the nodes' remaining resources (1 LDS, 2 HBM; phaseCycles[19])."""
-    want = oracle.solve(prob)
-    got = solve(prob, "cursor-nodes", lib)
-    assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want)
+    got, want = ec.three_ways(oracle, lib, prob, "cursor-nodes", auto="auto-nodes", kind="cursor")
     if variant is not None:
         assert got["counters"]["phaseCycles"][19] == variant
-    auto = solve(prob, "auto-nodes", lib)
-    assert auto["counters"]["engine"] == "cursor" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want)
-    general = solve(prob, "general", lib)
-    assert general["counters"]["engine"] == "general"
-    same(general, want)
     return got, want
 
 
@@ -84,8 +75,7 @@ def _zones(prob):
 
 
 def fuzz_problem(seed):
-    """test_cursor_engine.lite_problem plus random nodes (fixtures.with_existing_nodes) and, two times in three, random DaemonSets."""
-    from test_cursor_engine import lite_problem
+    """mix_cases.lite_problem plus random nodes (fixtures.with_existing_nodes) and, two times in three, random DaemonSets."""
     rng = random.Random(33000 + seed)
     prob = lite_problem(rng, rng.choice([30, 200, 900]))
     prob = fx.with_existing_nodes(prob, rng.choice([1, 5, 40, 64, 130]), seed=seed, fill=(0.3, 1.0))
@@ -97,17 +87,12 @@ def fuzz_problem(seed):
 def run_fuzz(oracle, lib, seeds):
     """Whatever "auto-nodes" runs equals the oracle; returns (problems the cursor engine solved, pods it put on nodes, reasons)."""
     ran, placed, reasons = 0, 0, {}
-    for seed in seeds:
-        prob = fuzz_problem(seed)
-        got = solve(prob, "auto-nodes", lib)
-        same(got, oracle.solve(prob))
-        c = got["counters"]
-        if c["engine"] == "cursor":
-            assert c["engineFallbackReason"] == 0
+    for _, _, _, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), "auto-nodes", pops=False):
+        if on == "cursor":
             ran += 1
             placed += on_nodes(got)
         else:
-            assert c["engine"] == "general"
-            reasons[c["engineFallbackReason"]] = reasons.get(c["engineFallbackReason"], 0) + 1
+            assert on == "general"
+            reasons[reason] = reasons.get(reason, 0) + 1
     print(f"cursor + node stage: {ran} of {len(seeds)}, {placed} pods on existing nodes; general engine by reason {dict(sorted(reasons.items()))}")
     return ran, placed, reasons

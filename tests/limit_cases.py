@@ -1,6 +1,6 @@
 """Problems whose NodePool limits BIND for the cursor engine's limit stages (csrc/fast_engine.h FastLimits, engines "auto-limits" /
 "cursor-limits"; tests/test_cursor_engine_limits.py on the emulation, tests/test_gpu_cursor_limits.py on the device): known shapes,
-the seeded fuzz generator and the comparison helper.
+the seeded fuzz generator and its Switch (tests/engine_checks.py).
 
 What the reference does when a limit binds (scheduler.go:706-727): a template whose pool has no node left, or whose type list
 filtered by the remaining resources is empty, is skipped for the pod; a list that shrank opens the NodeClaim with the shorter list;
@@ -8,11 +8,15 @@ subtractMax (scheduler.go:1049-1066) then takes the largest capacity among the c
 import random
 
 import daemonset_cases as dc
-import parity
+import engine_checks as ec
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, Unsupported
+from mix_cases import lite_problem
 
-same, solve = dc.same, dc.solve
+# 11, 12 over "auto" ("auto-nodes" for a problem with existing nodes, which "auto" does not try): what engines 0-10 do is to decline
+# with reason 23 / 24. No engine-only leg below the switch. declined(): plain "auto" stops earlier, at the limit.
+SWITCH = ec.Switch("cursor", only="cursor-limits", auto="auto-limits", base="auto", reasons=(23, 24), base_first=True)
+check_declined = SWITCH.declined
+
 
 def _limit_word(res):
     """phaseCycles[23] of a cursor solve under engines 11 / 12 (csrc/fast_engine.h FastCold::finish; zero under every other setting):
@@ -33,39 +37,8 @@ def rows(res):
 
 
 def check_engine(oracle, lib, prob, base="auto"):
-    """The limit binds in this problem: under `base` ("auto"; "auto-nodes" for a problem with existing nodes, which "auto" does not
-    try) the cursor engine declines with reason 23 / 24 and the general engine's result equals the oracle — what engines 0-10 do.
-    "cursor-limits" solves it on the cursor engine — no fallback, reason 0 — and equals the oracle in claims, instance-type lists,
-    pod assignment and the reference-equivalent evaluation count; "auto-limits" gives the same result on the same engine."""
-    want = oracle.solve(prob)
-    plain = solve(prob, base, lib)
-    assert plain["counters"]["engine"] == "general" and plain["counters"]["engineFallbackReason"] in (23, 24), plain["counters"]
-    same(plain, want)
-    got = solve(prob, "cursor-limits", lib)
-    assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want)
-    auto = solve(prob, "auto-limits", lib)
-    assert auto["counters"]["engine"] == "cursor" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want)
-    assert parity.results_digest(auto)[0] == parity.results_digest(got)[0]
-    return got, want
-
-
-def check_declined(oracle, lib, prob, reason, base_reasons=(23, 24)):
-    """A problem the cursor engine still hands back under engines 11 / 12: "cursor-limits" refuses and names `reason`, "auto-limits"
-    equals the oracle on the general engine with that reason; plain "auto" stops earlier, at the limit."""
-    plain = solve(prob, "auto", lib)
-    assert plain["counters"]["engine"] == "general" and plain["counters"]["engineFallbackReason"] in base_reasons, plain["counters"]
-    try:
-        solve(prob, "cursor-limits", lib)
-    except Unsupported as e:
-        assert f"cursor engine declined the problem (reason {reason})" in str(e), str(e)
-    else:
-        raise AssertionError("cursor-limits solved a problem it must refuse")
-    auto = solve(prob, "auto-limits", lib)
-    assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == reason, auto["counters"]
-    same(auto, oracle.solve(prob))
-    return auto
+    """The limit binds in this problem: SWITCH.check under `base`."""
+    return SWITCH.check(oracle, lib, prob, base=base)
 
 
 def pool_of(res):
@@ -217,11 +190,10 @@ def _zones(prob):
 
 
 def fuzz_problem(seed, open_catch_all=False):
-    """test_cursor_engine.lite_problem with a cpu limit on EVERY NodePool, drawn between 5% and 60% of the batch's total cpu request;
+    """mix_cases.lite_problem with a cpu limit on EVERY NodePool, drawn between 5% and 60% of the batch's total cpu request;
     DaemonSets two times in three and existing nodes one time in two, as existing_node_cases.fuzz_problem adds them.
     open_catch_all: the lightest pool (lite_problem's "catch-all") keeps no limit, so that pods the limited pools turn away have
     somewhere to go."""
-    from test_cursor_engine import lite_problem
     rng = random.Random(35000 + seed)
     prob = lite_problem(rng, rng.choice([30, 200, 900]))
     total = sum(fx.quantity_float(p["requests"]["cpu"]) for p in prob["pods"])
@@ -259,36 +231,12 @@ def run_fuzz(oracle, lib, seeds, open_catch_all=False):
     "auto-nodes", which is "auto" for a problem without existing nodes and differs from "auto-limits" in the limits alone —, how
     many of those "auto-limits" solved on the cursor engine, histogram of the reasons "auto-limits" ended with)."""
     binds, on_cursor, reasons = 0, 0, {}
-    for seed in seeds:
-        prob = fuzz_problem(seed, open_catch_all)
-        want = oracle.solve(prob)
-        got = solve(prob, "auto-limits", lib)
-        same(got, want)
-        c = got["counters"]
-        plain = solve(prob, "auto-nodes", lib)["counters"]
-        bound = plain["engine"] == "general" and plain["engineFallbackReason"] in (23, 24)
+    problems = ((seed, fuzz_problem(seed, open_catch_all)) for seed in seeds)
+    for seed, prob, want, got, on, r in ec.fuzz_cases(oracle, lib, problems, SWITCH.auto, pops=False, mode=SWITCH.mode):
+        bound = ec.where(ec.solve(prob, "auto-nodes", lib)) in (("general", 23), ("general", 24))
         binds += bound
-        if c["engine"] == "cursor":
-            assert c["engineFallbackReason"] == 0
-            on_cursor += bound
-            reasons[0] = reasons.get(0, 0) + 1
-        else:
-            assert c["engine"] == "general"
-            r = c["engineFallbackReason"]
-            assert (r == 27 and want["podErrors"]) or r == 29 or r in SHAPE_REASONS, (seed, c)
-            reasons[r] = reasons.get(r, 0) + 1
+        on_cursor += bound and on == "cursor"
+        assert on == "cursor" or (r == 27 and want["podErrors"]) or r == 29 or r in SHAPE_REASONS, (seed, got["counters"])
+        reasons[r] = reasons.get(r, 0) + 1
     print(f"limits bind in {binds} of {len(seeds)} seeds; auto-limits kept {on_cursor} of those on the cursor engine; reasons {dict(sorted(reasons.items()))}")
     return binds, on_cursor, reasons
-
-
-def digests_of_repeated_solves(lib, prob, engine, n):
-    s = NewScheduler(dict(prob, options=dict(prob.get("options", {}), engine=engine)), solver_lib=lib)
-    try:
-        out = set()
-        for _ in range(n):
-            r = s.Solve()
-            assert r["counters"]["engine"] == "cursor" and r["counters"]["engineFallbackReason"] == 0, r["counters"]
-            out.add(parity.results_digest(r)[0])
-        return out, r
-    finally:
-        s.close()

@@ -1,7 +1,7 @@
 """Problems whose NodePools carry requirements that are not In sets — NotIn, Exists, DoesNotExist, Gt, Lt — for the cursor engine's
 complement templates (csrc/fast_engine.h FastCold::setup, "Complement templates"; engines "auto-operators" / "cursor-operators";
 tests/test_cursor_engine_operators.py on the emulation, tests/test_gpu_cursor_operators.py on the device): known shapes, the seeded
-fuzz generator and the comparison helper.
+fuzz generator and its Switch (tests/engine_checks.py).
 
 What the reference does with such a pool: the NodeClaim starts with the pool's requirement as it stands (requirement.go:60-112: a
 complement set, bounds for Gt / Lt); a pod's In Q meets it by Intersection (requirement.go:181-214) and leaves the concrete set of
@@ -12,57 +12,22 @@ Every problem here has an open NodePool of the lowest weight, so that the oracle
 these cases are about)."""
 import random
 
-import daemonset_cases as dc
-import limit_cases as lc
-import parity
+import engine_checks as ec
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import Unsupported
 
-same, solve = dc.same, dc.solve
 K = "example.com/k"
 ZONES = ["test-zone-1", "test-zone-2", "test-zone-3"]
-
-
-def refuses(prob, engine, lib, reason):
-    try:
-        solve(prob, engine, lib)
-    except Unsupported as e:
-        assert f"(reason {reason})" in str(e), str(e)
-    else:
-        raise AssertionError(f"{engine} solved a problem it must refuse")
+# 15, 16 over "auto" / "cursor" ("auto-nodes" / "cursor-nodes" for a problem with existing nodes, which "auto" does not try): what
+# engines 0-14 do is to decline with the reason given per call — 3 for NotIn / Exists / DoesNotExist pools, 1 for Gt / Lt pools (34
+# with existing nodes). The engine-only setting declines with 3 alone; the host finds 1 and 34 when it creates the handle ("outside its
+# shape ... (reason N)"). The oracle's result has no pod errors.
+SWITCH = ec.Switch("cursor", only="cursor-operators", auto="auto-operators", base="auto", base_only="cursor", base_only_declines=(3,), errors=False)
+check_declined = SWITCH.declined
 
 
 def check_engine(oracle, lib, prob, reason, base="auto", base_cursor="cursor"):
-    """One problem five ways. The oracle's result, computed once, without pod errors. `base` ("auto"; "auto-nodes" for a problem with
-    existing nodes, which "auto" does not try) hands the problem to the general engine with `reason` — 3 for NotIn / Exists /
-    DoesNotExist pools, 1 for Gt / Lt pools (34 with existing nodes) — and equals the oracle; `base_cursor` refuses with that reason:
-    what engines 0-14 do. "cursor-operators" solves it on the cursor engine — no fallback, reason 0 — and equals the oracle in claims,
-    instance-type lists, claim requirements (operator, values, bounds: parity.canon_req), pod assignment and the reference-equivalent
-    evaluation count; "auto-operators" gives the same result on the same engine."""
-    want = oracle.solve(prob)
-    assert not want["podErrors"], want["podErrors"]
-    plain = solve(prob, base, lib)
-    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", reason), plain["counters"]
-    same(plain, want)
-    refuses(prob, base_cursor, lib, reason)
-    got = solve(prob, "cursor-operators", lib)
-    assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want)
-    auto = solve(prob, "auto-operators", lib)
-    assert auto["counters"]["engine"] == "cursor" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want)
-    assert parity.results_digest(auto)[0] == parity.results_digest(got)[0]
-    return got, want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the cursor engine still hands back under engines 15 / 16: "cursor-operators" refuses and names `reason`,
-    "auto-operators" equals the oracle on the general engine with that reason."""
-    refuses(prob, "cursor-operators", lib, reason)
-    auto = solve(prob, "auto-operators", lib)
-    assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
-    same(auto, oracle.solve(prob))
-    return auto
+    """One problem five ways (SWITCH.check): the claims' requirements are compared by operator, values and bounds (parity.canon_req)."""
+    return SWITCH.check(oracle, lib, prob, reason=reason, base=base, base_only=base_cursor)
 
 
 def claims_of(res, pool):
@@ -282,18 +247,11 @@ def run_fuzz(oracle, lib, seeds):
     """Every seed equals the oracle under "auto-operators", and the oracle reports no pod error for any. Returns (seeds that ended on
     the cursor engine with reason 0, {seed: reason} of the rest)."""
     on_cursor, rest = 0, {}
-    for seed in seeds:
-        prob = fuzz_problem(seed)
-        want = oracle.solve(prob)
+    for seed, _, want, _, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), SWITCH.auto, pops=False, mode=SWITCH.mode):
         assert not want["podErrors"], (seed, want["podErrors"])
-        got = solve(prob, "auto-operators", lib)
-        same(got, want)
-        c = got["counters"]
-        if c["engine"] == "cursor":
-            assert c["engineFallbackReason"] == 0, (seed, c)
+        if on == "cursor":
             on_cursor += 1
         else:
-            assert c["engine"] == "general", (seed, c)
-            rest[seed] = c["engineFallbackReason"]
+            rest[seed] = reason
     print(f"auto-operators kept {on_cursor} of {len(seeds)} seeds on the cursor engine; reasons of the rest {rest}")
     return on_cursor, rest

@@ -9,69 +9,31 @@ complement set (NotIn, Exists, Gt, Lt) a NotIn always intersects and grows the e
 DoesNotExist pass without an intersection (:260-265), and what is left is DoesNotExist when one of them is."""
 import random
 
-import daemonset_cases as dc
-import limit_cases as lc
+import engine_checks as ec
 import operator_cases as oc
-import parity
 from karpenter_amd import fixtures as fx
 
-same, solve, refuses = dc.same, dc.solve, oc.refuses
 claims_of, req_of = oc.claims_of, oc.req_of
 ZONES = oc.ZONES
 K = "example.com/k"
-BASE, BASE_CURSOR = "auto-filters-spread", "cursor-unschedulable"   # 24 and 21: every switch but the one under test
-ENGINE, AUTO = "cursor-pod-operators", "auto-pod-operators"         # 27 and 26
+# 26, 27 over 24 / 21 (every switch but the one under test): what every setting up to 25 does is to decline with the reason given per
+# call — 4 for NotIn / Exists pods, 8 for DoesNotExist. The oracle's result has no pod errors.
+SWITCH = ec.Switch("cursor", only="cursor-pod-operators", auto="auto-pod-operators", base="auto-filters-spread", base_only="cursor-unschedulable", errors=False)
+ENGINE, AUTO, BASE, BASE_CURSOR = SWITCH.only, SWITCH.auto, SWITCH.base, SWITCH.base_only
+# ... and for a problem that leaves pods unschedulable: pod errors required, queue pops compared, no engine-only leg below the switch
+UNSCHEDULABLE = SWITCH._replace(errors=True, pops=True, base_only=None)
+check_declined = SWITCH.declined
 
 
 def check_engine(oracle, lib, prob, reason=4):
-    """One problem four ways. The oracle's result, computed once, without pod errors. "auto-filters-spread" (24) hands the problem to the
-    general engine with `reason` — 4 for NotIn / Exists pods, 8 for DoesNotExist — and equals the oracle; "cursor-unschedulable" (21)
-    refuses with that reason: what every setting up to 25 does. "cursor-pod-operators" solves it on the cursor engine — no fallback,
-    reason 0 — and equals the oracle in claims, instance-type lists, claim requirements (operator, values, bounds: parity.canon_req),
-    pod assignment and the reference-equivalent evaluation count; "auto-pod-operators" gives the same digest on the same engine."""
-    want = oracle.solve(prob)
-    assert not want["podErrors"], want["podErrors"]
-    plain = solve(prob, BASE, lib)
-    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", reason), plain["counters"]
-    same(plain, want)
-    refuses(prob, BASE_CURSOR, lib, reason)
-    got = solve(prob, ENGINE, lib)
-    assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want)
-    auto = solve(prob, AUTO, lib)
-    assert auto["counters"]["engine"] == "cursor" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want)
-    assert parity.results_digest(auto)[0] == parity.results_digest(got)[0]
-    return got, want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the cursor engine still hands back under engines 26 / 27: "cursor-pod-operators" refuses and names `reason`,
-    "auto-pod-operators" equals the oracle on the general engine with that reason."""
-    refuses(prob, ENGINE, lib, reason)
-    auto = solve(prob, AUTO, lib)
-    assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
-    same(auto, oracle.solve(prob))
-    return auto
+    """One problem five ways (SWITCH.check): the claims' requirements are compared by operator, values and bounds (parity.canon_req)."""
+    return SWITCH.check(oracle, lib, prob, reason=reason)
 
 
 def check_unschedulable(oracle, lib, prob, reason=4):
     """A problem that leaves pods unschedulable: 24 falls back with `reason`, 26 / 27 end on the cursor engine and equal the oracle in
     claims, pod errors with their flags, evaluation count and queue pops."""
-    want = oracle.solve(prob)
-    assert want["podErrors"], "the oracle schedules every pod of this problem"
-    plain = solve(prob, BASE, lib)
-    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", reason), plain["counters"]
-    same(plain, want)
-    out = []
-    for engine in (ENGINE, AUTO):
-        got = solve(prob, engine, lib)
-        assert (got["counters"]["engine"], got["counters"]["engineFallbackReason"]) == ("cursor", 0), (engine, got["counters"])
-        same(got, want)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (engine, got["counters"]["pops"], want["counters"]["pops"])
-        out.append(got)
-    assert parity.results_digest(out[0])[0] == parity.results_digest(out[1])[0]
-    return out[0], want
+    return UNSCHEDULABLE.check(oracle, lib, prob, reason=reason)
 
 
 def kinds(res, key, pool=None):
@@ -322,19 +284,13 @@ def run_fuzz(oracle, lib, seeds):
     """Every seed equals the oracle under "auto-pod-operators", and the oracle reports no pod error for any. Returns (seeds that ended
     on the cursor engine with reason 0, {seed: reason} of the rest, seeds with a pod requirement that is not an In set)."""
     on_cursor, rest, turned = 0, {}, 0
-    for seed in seeds:
-        prob = fuzz_problem(seed)
+    for seed, prob, want, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), AUTO, pops=False, mode=SWITCH.mode):
         turned += any(r["operator"] != "In" for p in prob["pods"] for r in pod_reqs(p))
-        want = oracle.solve(prob)
         assert not want["podErrors"], (seed, want["podErrors"])
-        got = solve(prob, AUTO, lib)
-        same(got, want)
-        c = got["counters"]
-        if c["engine"] == "cursor":
-            assert c["engineFallbackReason"] == 0, (seed, c)
+        if on == "cursor":
             on_cursor += 1
         else:
-            assert c["engine"] == "general" and c["engineFallbackReason"] in FUZZ_REASONS, (seed, c)
-            rest[seed] = c["engineFallbackReason"]
+            assert reason in FUZZ_REASONS, (seed, got["counters"])
+            rest[seed] = reason
     print(f"auto-pod-operators kept {on_cursor} of {len(seeds)} seeds on the cursor engine; reasons of the rest {rest}; {turned} seeds carry pod operators")
     return on_cursor, rest, turned

@@ -15,17 +15,20 @@ the three count, the owners land 0 / 3 / 3 over the zones; where they do not, 2 
 import copy
 import random
 
-import daemonset_cases as dc
+import engine_checks as ec
 import operator_cases as oc
 import parity
 import spread_limit_cases as sl
 import spread_operator_cases as so
 from karpenter_amd import fixtures as fx
 
-solve, same = dc.solve, dc.same     # (dc.same compares pod errors and their flags too)
-refusal, lone_cell, batch_cells = so.refusal, so.lone_cell, so.batch_cells
-AUTO, ONLY = "auto-filters-spread", "spread-filters"               # 24, 25
-BASE, BASE_ONLY = "auto-unschedulable-spread", "spread-unschedulable"   # 22, 23: every switch but the one under test
+lone_cell, batch_cells = so.lone_cell, so.batch_cells
+# 24, 25 over 22 / 23 (every switch but the one under test): what every setting up to 23 does is to decline with reason 43. Pod
+# errors and their flags are compared (parity), and queue pops.
+SWITCH = ec.Switch("spread", only="spread-filters", auto="auto-filters-spread", base="auto-unschedulable-spread", base_only="spread-unschedulable",
+                   reasons=(43,), pops=True)
+AUTO, ONLY, BASE, BASE_ONLY = SWITCH.auto, SWITCH.only, SWITCH.base, SWITCH.base_only
+check_declined = SWITCH.declined
 WEB = {"app": "web"}
 ZONES = oc.ZONES
 SPOT, ON_DEMAND = "spot", "on-demand"
@@ -33,54 +36,21 @@ TEAM = "example.com/team"           # a custom label key: not well known
 COUNTED, NOT_COUNTED = {ZONES[1]: 3, ZONES[2]: 3}, {ZONES[0]: 2, ZONES[1]: 2, ZONES[2]: 2}
 
 
-def where(res):
-    return res["counters"]["engine"], res["counters"]["engineFallbackReason"]
-
-
 def check_engine(oracle, lib, prob, want=None):
-    """One problem four ways; the oracle's result is computed once (`want`: computed before). "auto-unschedulable-spread" (22) hands
-    it to the general engine with reason 43 and equals the oracle; "spread-unschedulable" (23) refuses and names 43: what every
-    setting up to 23 does. "spread-filters" solves it on the spread engine — no fallback, reason 0 — and equals the oracle in
-    claims, instance-type lists, claim requirements, pod assignment, pod errors, the reference-equivalent evaluation count
-    (daemonset_cases.same) and queue pops; "auto-filters-spread" gives the same digest on the same engine."""
-    want = want or oracle.solve(prob)
-    plain = solve(prob, BASE, lib)
-    assert where(plain) == ("general", 43), plain["counters"]
-    same(plain, want)
-    text = refusal(prob, BASE_ONLY, lib)
-    assert "spread engine declined the problem (reason 43)" in text, text
-    got = solve(prob, ONLY, lib)
-    assert where(got) == ("spread", 0), got["counters"]
-    digest = parity.results_digest(got)[0]
-    same(got, want)
-    assert got["counters"]["pops"] == want["counters"]["pops"], (got["counters"]["pops"], want["counters"]["pops"])
-    auto = solve(prob, AUTO, lib)
-    assert where(auto) == ("spread", 0), auto["counters"]
-    assert parity.results_digest(auto)[0] == digest
-    same(auto, want)
-    return got, want
+    """One problem five ways (SWITCH.check; `want`: the oracle's result, computed before)."""
+    return SWITCH.check(oracle, lib, prob, want=want)
 
 
 def check_open(oracle, lib, prob):
     """The other one of a pair when it has NO filter that can say no (policy Ignore): the spread engine solves it under 25 as it
     does under 23, and equals the oracle."""
     want = oracle.solve(prob)
-    got = solve(prob, ONLY, lib)
-    assert where(got) == ("spread", 0), got["counters"]
-    same(got, want)
-    assert parity.results_digest(solve(prob, BASE_ONLY, lib))[0] == parity.results_digest(got)[0]
+    got = ec.solve(prob, ONLY, lib)
+    assert ec.where(got) == ("spread", 0), got["counters"]
+    digest = parity.results_digest(got)[0]
+    SWITCH.same(got, want, prob)
+    assert parity.results_digest(ec.solve(prob, BASE_ONLY, lib))[0] == digest
     return got, want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the spread engine still hands back under 24 / 25: "spread-filters" refuses and names `reason`,
-    "auto-filters-spread" equals the oracle on the general engine with it."""
-    text = refusal(prob, ONLY, lib)
-    assert f"spread engine declined the problem (reason {reason})" in text, text
-    auto = solve(prob, AUTO, lib)
-    assert where(auto) == ("general", reason), auto["counters"]
-    same(auto, oracle.solve(prob))
-    return auto
 
 
 def owner_uids(prob):
@@ -382,19 +352,12 @@ def run_fuzz(oracle, lib, seeds):
     """Every seed equals the oracle under "auto-filters-spread", pops included. Returns (seeds on the spread engine with reason 0,
     how many of those are discriminating, {seed: reason} of the rest — reasons of FUZZ_REASONS only)."""
     on_spread, disc, rest = 0, 0, {}
-    for seed in seeds:
-        prob = fuzz_problem(seed)
-        want = oracle.solve(prob)
-        got = solve(prob, AUTO, lib)
-        same(got, want)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (seed, got["counters"]["pops"], want["counters"]["pops"])
-        engine, reason = where(got)
-        if engine == "spread":
-            assert reason == 0, (seed, got["counters"])
+    for seed, prob, want, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), AUTO, pops=True, mode=SWITCH.mode):
+        if on == "spread":
             on_spread += 1
             disc += discriminating(oracle, prob, want)
         else:
-            assert engine == "general" and reason in FUZZ_REASONS, (seed, got["counters"])
+            assert reason in FUZZ_REASONS, (seed, got["counters"])
             rest[seed] = reason
     print(f"{AUTO}: {on_spread} of {len(seeds)} seeds on the spread engine, {disc} of them discriminating; reasons of the rest {rest}")
     return on_spread, disc, rest

@@ -7,51 +7,23 @@ What the reference does when a limit binds (scheduler.go:706-727) stands in test
 engine's; the ones here carry at least one topology constraint, so engines 0-12 end on the general engine with reason 23 / 24."""
 import copy
 
+import engine_checks as ec
 import limit_cases as lc
+import mix_cases
 import parity
-import spread_node_cases as sn
-import test_spread_engine as tse
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, Unsupported
+from karpenter_amd.scheduling import NewScheduler
 
-solve, same, stages, pool_of = tse.solve, sn.same, lc.stages, lc.pool_of
+stages, pool_of = lc.stages, lc.pool_of
+# 13, 14 over "auto" ("auto-nodes-spread" with existing nodes): what engines 0-12 do is to stop with reason 23 / 24. No engine-only
+# leg below the switch. declined(): plain "auto" stops earlier, at the limit.
+SWITCH = ec.Switch("spread", only="spread-limits", auto="auto-limits-spread", base="auto", reasons=(23, 24), base_first=True)
+check_declined = SWITCH.declined
 
 
 def check_engine(oracle, lib, prob, base="auto"):
-    """The common check. Under `base` ("auto"; "auto-nodes-spread" with existing nodes) the spread engine stops with reason 23 / 24
-    and the general engine's result equals the oracle: the limit binds. "spread-limits" solves the problem on the spread engine —
-    no fallback, reason 0 — and equals the oracle in claims, nodes, referenceBinEvaluations and cost (sets under DaemonSets);
-    "auto-limits-spread" gives the same digest on the same engine."""
-    want = oracle.solve(prob)
-    plain = solve(prob, base, lib)
-    assert plain["counters"]["engine"] == "general" and plain["counters"]["engineFallbackReason"] in (23, 24), plain["counters"]
-    same(plain, want, prob)
-    got = solve(prob, "spread-limits", lib)
-    assert got["counters"]["engine"] == "spread" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    digest = parity.results_digest(got)[0]   # (before same(): under DaemonSets it puts the instance-type lists into a canonical order)
-    same(got, want, prob)
-    auto = solve(prob, "auto-limits-spread", lib)
-    assert auto["counters"]["engine"] == "spread" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    assert parity.results_digest(auto)[0] == digest
-    same(auto, want, prob)
-    return got, want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the spread engine still hands back under engines 13 / 14: "spread-limits" refuses and names `reason`,
-    "auto-limits-spread" equals the oracle on the general engine with that reason; plain "auto" stops earlier, at the limit."""
-    plain = solve(prob, "auto", lib)
-    assert plain["counters"]["engine"] == "general" and plain["counters"]["engineFallbackReason"] in (23, 24), plain["counters"]
-    try:
-        solve(prob, "spread-limits", lib)
-    except Unsupported as e:
-        assert f"spread engine declined the problem (reason {reason})" in str(e), str(e)
-    else:
-        raise AssertionError("spread-limits solved a problem it must refuse")
-    auto = solve(prob, "auto-limits-spread", lib)
-    assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == reason, auto["counters"]
-    same(auto, oracle.solve(prob), prob)
-    return auto
+    """The limit binds in this problem: SWITCH.check under `base`."""
+    return SWITCH.check(oracle, lib, prob, base=base)
 
 
 # ---- 1, 2, 6: the benchmark mix over two pools --------------------------------------------------------------------------------------
@@ -149,7 +121,7 @@ def repeated_solves(lib, prob, engine, n):
 
 # ---- 8: seeded fuzz -----------------------------------------------------------------------------------------------------------------
 
-FUZZ_SEEDS = [s for s in range(96) if s % 5 == 2]     # test_spread_engine.fuzz_problem: pools "few" (cpu 20, weight 5) + "rest"
+FUZZ_SEEDS = [s for s in range(96) if s % 5 == 2]     # mix_cases.fuzz_problem: pools "few" (cpu 20, weight 5) + "rest"
 FUZZ_ON_SPREAD = [2, 12, 17, 22, 32, 37, 42, 52, 57, 62, 67, 72, 77, 82, 92]   # no pod errors in the oracle; engines 0-12 stop with 24
 FUZZ_UNSCHEDULABLE = [27]                              # the oracle leaves one pod unschedulable: reason 27 under every setting
 FUZZ_NODE_FILTER = [7, 47, 87]                         # a pod with a nodeSelector AND a spread constraint: reason 43, as before
@@ -161,19 +133,13 @@ def run_fuzz(oracle, lib, seeds):
     stops with 24 under "auto"), seed 27 ends with reason 27 and has pod errors in the oracle, seeds 7 / 47 / 87 end with 43.
     Returns the limit stages created, summed over the seeds."""
     made = 0
-    for seed in seeds:
-        prob = tse.fuzz_problem(seed)
-        want = oracle.solve(prob)
-        got = solve(prob, "auto-limits-spread", lib)
-        same(got, want, prob)
-        c = got["counters"]
-        where = (c["engine"], c["engineFallbackReason"])
+    for seed, prob, want, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, mix_cases.fuzz_problem(seed)) for seed in seeds), SWITCH.auto, pops=False):
         if seed in FUZZ_ON_SPREAD:
-            assert not want["podErrors"] and where == ("spread", 0), (seed, c)
-            assert solve(prob, "auto", lib)["counters"]["engineFallbackReason"] == 24, seed
+            assert not want["podErrors"] and (on, reason) == ("spread", 0), (seed, got["counters"])
+            assert ec.solve(prob, "auto", lib)["counters"]["engineFallbackReason"] == 24, seed
             made += stages(got)[0]
         elif seed in FUZZ_UNSCHEDULABLE:
-            assert len(want["podErrors"]) == 1 and where == ("general", 27), (seed, c)
+            assert len(want["podErrors"]) == 1 and (on, reason) == ("general", 27), (seed, got["counters"])
         else:
-            assert seed in FUZZ_NODE_FILTER and where == ("general", 43), (seed, c)
+            assert seed in FUZZ_NODE_FILTER and (on, reason) == ("general", 43), (seed, got["counters"])
     return made

@@ -4,35 +4,17 @@ device): the benchmark mix with nodes, block edges, the node that refuses and la
 and the comparison helper."""
 import random
 
-import daemonset_cases as dc
-import test_spread_engine as tse
+import engine_checks as ec
+import mix_cases
 from karpenter_amd import fixtures as fx
-
-solve = tse.solve
-
-
-def same(got, want, prob=None):
-    """test_spread_engine.same: claims, nodes, referenceBinEvaluations and cost. With DaemonSets the reference visits the
-    daemon-overhead groups in Go map order (scheduler.go:1001), so the order of InstanceTypeOptions ACROSS groups is not defined:
-    such problems compare them as sets (daemonset_cases.same), everything else alike."""
-    (dc.same if prob is not None and prob.get("daemonSetPods") else tse.same)(got, want)
 
 
 def check_engine(oracle, lib, prob):
     """"spread-nodes" must solve it on the spread engine — no fallback, reason 0 — and equal the oracle: claims, nodes, the
-    reference-equivalent evaluation count and the cost; so must "auto-nodes-spread" (which has to pick the same engine) and the
+    reference-equivalent evaluation count and the cost (instance-type lists as sets under DaemonSets, whose overhead groups the
+    reference visits in Go map order, scheduler.go:1001); so must "auto-nodes-spread" (which has to pick the same engine) and the
     general engine."""
-    want = oracle.solve(prob)
-    got = solve(prob, "spread-nodes", lib)
-    assert got["counters"]["engine"] == "spread" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    same(got, want, prob)
-    auto = solve(prob, "auto-nodes-spread", lib)
-    assert auto["counters"]["engine"] == "spread" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    same(auto, want, prob)
-    general = solve(prob, "general", lib)
-    assert general["counters"]["engine"] == "general"
-    same(general, want, prob)
-    return got, want
+    return ec.three_ways(oracle, lib, prob, "spread-nodes", auto="auto-nodes-spread", kind="spread")
 
 
 def on_nodes(res):
@@ -94,7 +76,7 @@ def node_then_claim_then_node(want, prob):
 
 def fuzz_problem(seed):
     rng = random.Random(51000 + seed)
-    return fx.with_existing_nodes(tse.fuzz_problem(seed), rng.choice([1, 5, 40, 64, 130]), seed=seed, fill=(0.3, 1.0))
+    return fx.with_existing_nodes(mix_cases.fuzz_problem(seed), rng.choice([1, 5, 40, 64, 130]), seed=seed, fill=(0.3, 1.0))
 
 
 def run_fuzz(oracle, lib, seeds):
@@ -102,22 +84,16 @@ def run_fuzz(oracle, lib, seeds):
     the spread engine under "auto" and the oracle solves it WITH nodes without pod errors; returns (candidates, candidates the
     spread engine solved with reason 0, pods it put on nodes, histogram of the other candidates' reasons)."""
     cands, ran, placed, reasons = 0, 0, 0, {}
-    for seed in seeds:
-        prob = fuzz_problem(seed)
-        want = oracle.solve(prob)
-        got = solve(prob, "auto-nodes-spread", lib)
-        same(got, want, prob)
-        c = got["counters"]
-        bare = solve(dict(prob, stateNodes=[]), "auto", lib)["counters"]["engine"]
+    for _, prob, want, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), "auto-nodes-spread", pops=False):
+        bare = ec.solve(dict(prob, stateNodes=[]), "auto", lib)["counters"]["engine"]
         if bare != "spread" or want["podErrors"]:
             continue
         cands += 1
-        if c["engine"] == "spread":
-            assert c["engineFallbackReason"] == 0
+        if on == "spread":
             ran += 1
             placed += on_nodes(got)
         else:
-            reasons[c["engineFallbackReason"]] = reasons.get(c["engineFallbackReason"], 0) + 1
+            reasons[reason] = reasons.get(reason, 0) + 1
     print(f"spread engine with nodes: {ran} of {cands} candidates ({len(seeds)} seeds), {placed} pods on existing nodes; "
           f"general engine by reason {dict(sorted(reasons.items()))}")
     return cands, ran, placed, reasons

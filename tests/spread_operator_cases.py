@@ -14,62 +14,29 @@ import copy
 import random
 
 import daemonset_cases as dc
+import engine_checks as ec
+import mix_cases
 import operator_cases as oc
 import parity
 import spread_limit_cases as sl
 import spread_node_cases as sn
-import test_spread_engine as tse
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported
+from karpenter_amd.scheduling import NewScheduler, SolveBatch
 
-solve, same, ZONES = tse.solve, sn.same, oc.ZONES
-claims_of, req_of = oc.claims_of, oc.req_of
-AUTO, ONLY = "auto-operators-spread", "spread-operators"
+ZONES, claims_of, req_of = oc.ZONES, oc.claims_of, oc.req_of
+# 18, 19 over "auto" ("auto-nodes-spread" with existing nodes) / "spread-limits": what engines 0-17 do is to decline with the reason
+# given per call — 3 for NotIn / Exists / DoesNotExist pools, 34 with existing nodes, 0 for Gt / Lt pools (the host never offers them
+# to the spread engine). "spread-limits" declines with 3 alone; the host finds the others when it creates the handle ("outside its
+# shape"). The oracle's result has no pod errors.
+SWITCH = ec.Switch("spread", only="spread-operators", auto="auto-operators-spread", base="auto", base_only="spread-limits", base_only_declines=(3,), errors=False)
+AUTO, ONLY = SWITCH.auto, SWITCH.only
 WEB = {"app": "web"}
-
-
-def refusal(prob, engine, lib):
-    try:
-        solve(prob, engine, lib)
-    except Unsupported as e:
-        return str(e)
-    raise AssertionError(f"{engine} solved a problem it must refuse")
+check_declined = SWITCH.declined
 
 
 def check_engine(oracle, lib, prob, reason, base="auto"):
-    """One problem five ways. The oracle's result, computed once, without pod errors. `base` ("auto"; "auto-nodes-spread" with
-    existing nodes) hands the problem to the general engine with `reason` — 3 for NotIn / Exists / DoesNotExist pools, 0 for Gt / Lt
-    pools (the host never offers them to the spread engine), 34 with existing nodes — and equals the oracle; "spread-limits" refuses:
-    what engines 0-17 do. "spread-operators" solves it on the spread engine — no fallback, reason 0 — and equals the oracle in
-    claims, instance-type lists, claim requirements (operator, values, bounds: parity.canon_req), pod assignment and the
-    reference-equivalent evaluation count; "auto-operators-spread" gives the same digest on the same engine."""
-    want = oracle.solve(prob)
-    assert not want["podErrors"], want["podErrors"]
-    plain = solve(prob, base, lib)
-    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", reason), plain["counters"]
-    same(plain, want, prob)
-    text = refusal(prob, "spread-limits", lib)
-    assert (f"spread engine declined the problem (reason {reason})" in text) if reason == 3 else ("spread engine requested for a problem outside its shape" in text), text
-    got = solve(prob, ONLY, lib)
-    assert got["counters"]["engine"] == "spread" and got["counters"]["engineFallbackReason"] == 0, got["counters"]
-    digest = parity.results_digest(got)[0]   # (before same(): under DaemonSets it puts the instance-type lists into a canonical order)
-    same(got, want, prob)
-    auto = solve(prob, AUTO, lib)
-    assert auto["counters"]["engine"] == "spread" and auto["counters"]["engineFallbackReason"] == 0, auto["counters"]
-    assert parity.results_digest(auto)[0] == digest
-    same(auto, want, prob)
-    return got, want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the spread engine still hands back under engines 18 / 19: "spread-operators" refuses and names `reason`,
-    "auto-operators-spread" equals the oracle on the general engine with that reason."""
-    text = refusal(prob, ONLY, lib)
-    assert f"spread engine declined the problem (reason {reason})" in text, text
-    auto = solve(prob, AUTO, lib)
-    assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
-    same(auto, oracle.solve(prob), prob)
-    return auto
+    """One problem five ways (SWITCH.check): the claims' requirements are compared by operator, values and bounds (parity.canon_req)."""
+    return SWITCH.check(oracle, lib, prob, reason=reason, base=base)
 
 
 def zone_of(claim):
@@ -131,7 +98,7 @@ def integer_req(claim):
 
 def two_keys_problem():
     """Pool `both` (weight 10): capacity-type Exists and zone NotIn [test-zone-3], plus `open`; thirty pods with a zone spread
-    (maxSkew 3) and a capacity-type spread (maxSkew 4) — kind 12 of test_spread_engine.mix: loose enough to be satisfiable together —
+    (maxSkew 3) and a capacity-type spread (maxSkew 4) — kind 12 of mix_cases.mix: loose enough to be satisfiable together —
     and six pods without constraints."""
     pools = [fx.node_pool("both", weight=10, requirements=[fx.req(fx.CAPACITY_TYPE, "Exists"), fx.req(fx.ZONE, "NotIn", "test-zone-3")]), fx.node_pool("open")]
     pods = [fx.pod(requests={"cpu": "500m"}, labels=WEB, topology_spread=[fx.spread(fx.ZONE, WEB, max_skew=3), fx.spread(fx.CAPACITY_TYPE, WEB, max_skew=4)]) for _ in range(30)]
@@ -141,7 +108,7 @@ def two_keys_problem():
 # ---- 5: zonal anti-affinity with its inverse group, zonal affinity ----------------------------------------------------------------
 
 def affinity_problem():
-    """Kinds 2 and 10 of test_spread_engine.mix over oc.notin_zone_pool(): two pods with anti-affinity on the zone, labelled with its
+    """Kinds 2 and 10 of mix_cases.mix over oc.notin_zone_pool(): two pods with anti-affinity on the zone, labelled with its
     selector and pinned to test-zone-2 / test-zone-3 (each blocks the zone for the other, through the group and its inverse group),
     a pod the selector matches that owns nothing (the inverse group keeps it out of both: test-zone-1, the open pool), pods with
     zonal self-affinity per label, and pods without constraints."""
@@ -256,7 +223,7 @@ def batch_cells(lib, probs, engine):
 
 
 def lone_cell(lib, prob, engine):
-    r = solve(prob, engine, lib)
+    r = ec.solve(prob, engine, lib)
     return r["counters"]["engine"], r["counters"]["engineFallbackReason"], parity.results_digest(r)[0]
 
 
@@ -267,7 +234,7 @@ FUZZ_KINDS = (0, 0, 1, 1, 2, 3, 4, 5, 6, 7, 9, 10, 12, 12)
 
 def fuzz_problem(seed):
     """One to three weighted NodePools `pool-i` (weight 50 - 10 i, no taints), each with one or two draws of
-    operator_cases._pool_requirement (a repeated key is dropped), then `open`; 30 to 119 pods of test_spread_engine.mix in the kinds
+    operator_cases._pool_requirement (a repeated key is dropped), then `open`; 30 to 119 pods of mix_cases.mix in the kinds
     that rarely leave a pod unschedulable; the 1..12-cpu catalogue."""
     rng = random.Random(88000 + seed)
     pools = []
@@ -279,7 +246,7 @@ def fuzz_problem(seed):
                 seen.add(r["key"]); reqs.append(r)
         pools.append(fx.node_pool(f"pool-{i}", weight=50 - 10 * i, requirements=reqs))
     pools.append(fx.node_pool("open"))
-    pods = tse.mix(rng, rng.randrange(30, 120), kinds=FUZZ_KINDS)
+    pods = mix_cases.mix(rng, rng.randrange(30, 120), kinds=FUZZ_KINDS)
     return fx.problem(fx.fake_instance_types(12), pools, pods)
 
 
@@ -296,17 +263,12 @@ def run_fuzz(oracle, lib, seeds):
     first pass cannot place: the general engine's business) and nothing else. Returns (seeds that ended on the spread engine with
     reason 0, how many of those have a NodePool with a requirement that is not an In set, the seeds of the rest)."""
     on_spread, non_in, rest = 0, 0, []
-    for seed in seeds:
-        prob = fuzz_problem(seed)
-        got = solve(prob, AUTO, lib)
-        same(got, oracle.solve(prob), prob)
-        c = got["counters"]
-        if c["engine"] == "spread":
-            assert c["engineFallbackReason"] == 0, (seed, c)
+    for seed, prob, _, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, fuzz_problem(seed)) for seed in seeds), AUTO, pops=False):
+        if on == "spread":
             on_spread += 1
             non_in += has_non_in_pool(prob)
         else:
-            assert (c["engine"], c["engineFallbackReason"]) == ("general", 27), (seed, c)
+            assert (on, reason) == ("general", 27), (seed, got["counters"])
             rest.append(seed)
     print(f"auto-operators-spread kept {on_spread} of {len(seeds)} seeds on the spread engine, {non_in} of them over a NodePool with a requirement "
           f"that is not an In set; reason 27 for seeds {rest}")

@@ -8,62 +8,29 @@ error can be Topology (3): the pod's domain choice leaves a template's requireme
 second round PLACES pods (scheduler.go:442-446): a pod with required affinity to a pod later in the queue fails at its first pop
 and succeeds at a later one, so `pops` exceeds pods + failed pods, the queue gets shorter between retries, and the pods behind a
 success get further pops."""
-import daemonset_cases as dc
+import engine_checks as ec
+import mix_cases
 import operator_cases as oc
-import parity
 import spread_limit_cases as slc
 import spread_node_cases as sn
 import spread_operator_cases as soc
-import test_spread_engine as tse
 import unschedulable_cases as uc
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler
 
-solve, same = dc.solve, dc.same
-AUTO, ONLY = "auto-unschedulable-spread", "spread-unschedulable"   # 22, 23
-BASE, BASE_ONLY = "auto-unschedulable", "spread-operators"         # 20, 19: every switch but the one under test
+# 22, 23 over 20 / 19 (every switch but the one under test): what every setting up to 21 does is to decline with reason 27. The
+# oracle may leave pod errors or place every pod in its second round; queue pops are compared.
+SWITCH = ec.Switch("spread", only="spread-unschedulable", auto="auto-unschedulable-spread", base="auto-unschedulable", base_only="spread-operators",
+                   reasons=(27,), pops=True)
+AUTO, ONLY, BASE, BASE_ONLY = SWITCH.auto, SWITCH.only, SWITCH.base, SWITCH.base_only
 WEB = {"app": "web"}
 errors_of, n_pods = uc.errors_of, uc.n_pods
-
-
-def where(res):
-    return res["counters"]["engine"], res["counters"]["engineFallbackReason"]
+check_declined = SWITCH.declined
 
 
 def check_engine(oracle, lib, prob, want=None):
-    """One problem five ways. The oracle's answer (`want`: computed before). "auto-unschedulable" (20) ends on the general engine
-    with reason 27 and equals it; "spread-operators" (19) refuses and names 27: what every setting up to 21 does.
-    "spread-unschedulable" and "auto-unschedulable-spread" end on the spread engine — no fallback, reason 0 — and equal the oracle in
-    claims and their order, hostnames, pod errors with their flags, the reference-equivalent evaluation count (dc.same) and queue
-    pops; the two give one digest."""
-    want = want or oracle.solve(prob)
-    plain = solve(prob, BASE, lib)
-    assert where(plain) == ("general", 27), plain["counters"]
-    same(plain, want)
-    text = soc.refusal(prob, BASE_ONLY, lib)
-    assert "spread engine declined the problem (reason 27)" in text, text
-    out = []
-    for engine in (ONLY, AUTO):
-        got = solve(prob, engine, lib)
-        assert where(got) == ("spread", 0), (engine, got["counters"])
-        digest = parity.results_digest(got)[0]   # (before same(): under DaemonSets it puts the instance-type lists into a canonical order)
-        same(got, want)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (engine, got["counters"]["pops"], want["counters"]["pops"])
-        out.append((got, digest))
-    assert out[0][1] == out[1][1]
-    return out[0][0], want
-
-
-def check_declined(oracle, lib, prob, reason):
-    """A problem the spread engine still hands back under 22 / 23: "spread-unschedulable" refuses and names `reason` (0: the batch is
-    not offered to a fast engine at all, "outside its shape"), "auto-unschedulable-spread" equals the oracle on the general engine
-    with it."""
-    text = soc.refusal(prob, ONLY, lib)
-    assert ("outside its shape" if reason == 0 else f"spread engine declined the problem (reason {reason})") in text, text
-    auto = solve(prob, AUTO, lib)
-    assert where(auto) == ("general", reason), auto["counters"]
-    same(auto, oracle.solve(prob))
-    return auto
+    """One problem five ways (SWITCH.check; `want`: the oracle's answer, computed before), in claims and their order, hostnames, pod
+    errors with their flags, the reference-equivalent evaluation count and queue pops."""
+    return SWITCH.check(oracle, lib, prob, want=want)
 
 
 # ---- the building blocks ---------------------------------------------------------------------------------------------------------------
@@ -243,22 +210,6 @@ def declined_problems():
             ("pod-lt", more(lt), 1), ("min-values", minv, 1), ("limit-stages", stages, 29)]
 
 
-# ---- repeated solves ---------------------------------------------------------------------------------------------------------------------
-
-def digests_of_repeated_solves(lib, prob, engine, n):
-    """limit_cases.digests_of_repeated_solves for a spread handle."""
-    s = NewScheduler(dict(prob, options=dict(prob.get("options", {}), engine=engine)), solver_lib=lib)
-    try:
-        out = set()
-        for _ in range(n):
-            r = s.Solve()
-            assert where(r) == ("spread", 0), r["counters"]
-            out.add(parity.results_digest(r)[0])
-        return out, r
-    finally:
-        s.close()
-
-
 # ---- fuzz ----------------------------------------------------------------------------------------------------------------------------------
 
 SHAPE_REASONS = set(range(1, 9)) | {20, 21, 25, 26, 29} | set(range(30, 37)) | set(range(40, 52)) | {60, 61, 62, 100}   # decline.h without 27
@@ -269,24 +220,16 @@ def run_fuzz(oracle, lib, family, seeds):
     engine does so with a shape reason, never 27, and is printed with it. Returns (seeds with pod errors in the oracle, seeds on the
     spread engine, {seed: reason} of the rest)."""
     with_errors, on_spread, rest = 0, 0, {}
-    for seed in seeds:
-        prob = family(seed)
-        want = oracle.solve(prob)
+    for seed, _, want, got, on, reason in ec.fuzz_cases(oracle, lib, ((seed, family(seed)) for seed in seeds), AUTO, pops=True):
         with_errors += bool(want["podErrors"])
-        got = solve(prob, AUTO, lib)
-        sn.same(got, want, prob)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (seed, got["counters"]["pops"], want["counters"]["pops"])
-        engine, reason = where(got)
         assert reason != 27, (seed, got["counters"])
-        if engine == "spread":
-            assert reason == 0, (seed, got["counters"])
+        if on == "spread":
             on_spread += 1
-        else:
-            assert engine in ("general", "cursor") and (engine == "cursor" or reason in SHAPE_REASONS), (seed, got["counters"])
-            if engine == "general":
-                rest[seed] = reason
+        elif on == "general":
+            assert reason in SHAPE_REASONS, (seed, got["counters"])
+            rest[seed] = reason
     print(f"{AUTO}: {on_spread} of {len(seeds)} seeds of {family.__module__}.{family.__name__} on the spread engine ({with_errors} with pod errors in the oracle); reasons of the rest {rest}")
     return with_errors, on_spread, rest
 
 
-FAMILIES = {"operators": (soc.fuzz_problem, list(range(120))), "limits": (tse.fuzz_problem, slc.FUZZ_SEEDS), "nodes": (sn.fuzz_problem, list(range(48)))}
+FAMILIES = {"operators": (soc.fuzz_problem, list(range(120))), "limits": (mix_cases.fuzz_problem, slc.FUZZ_SEEDS), "nodes": (sn.fuzz_problem, list(range(48)))}

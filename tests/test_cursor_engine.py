@@ -4,7 +4,6 @@ options.engine = "cursor" (the cursor engine or an error — never the fallback)
 (L1-strict), and with the general engine. Shapes the cursor engine declines must be declined LOUDLY under engine="cursor"
 and solved — identically to the oracle — by the automatic fallback. The GPU run of the same comparisons is
 tests/test_gpu_parity.py."""
-import copy
 import random
 
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import parity
 from karpenter_amd import fixtures as fx
 from karpenter_amd.scheduling import NewScheduler, Unsupported
+from mix_cases import lite_problem  # noqa: F401  (tests/test_gpu_parity.py reads it here)
 from test_device_algorithm import emu  # noqa: F401  (fixture)
 
 
@@ -77,52 +77,6 @@ def test_the_x16_pin_at_one_million_pods_on_the_emulation(emu):
     assert r["counters"]["engine"] == "cursor" and r["counters"]["cursorMemoryPlan"] == 1
     assert len(r["newNodeClaims"]) == g["claims"] and r["counters"]["referenceBinEvaluations"] == g["binEvaluations"]
     assert parity.results_digest(r)[0] == g["digest"]
-
-
-def lite_problem(rng, n_pods):
-    """Random provisioning batches of the shape the cursor engine solves: In selectors on arch / os / zone / capacity type and
-    a custom NodePool label, taints + tolerations, weighted pools, instance types whose allocatable vectors do not dominate
-    each other (several Pareto-maximal types per requirement set), requests that straddle them."""
-    kwok = rng.random() < 0.4
-    if kwok:
-        its = fx.kwok_catalog(rng.choice([24, 72, 144, 300])); wk = fx.KWOK_WELL_KNOWN; zones = list(fx.KWOK_ZONES)
-    else:
-        its = copy.deepcopy(fx.fake_instance_types(rng.choice([6, 20, 60]))); wk = fx.FAKE_WELL_KNOWN; zones = ["test-zone-1", "test-zone-2", "test-zone-3"]
-        for it in its:   # cpu-heavy and memory-heavy shapes: no single type dominates
-            if rng.random() < 0.5:
-                it["capacity"]["memory"] = f"{rng.choice([1, 2, 4, 8, 64, 256])}Gi"
-            if rng.random() < 0.3:
-                it["capacity"]["pods"] = str(rng.choice([3, 8, 30, 110]))
-    archs = sorted({v for it in its for r in it["requirements"] if r["key"] == fx.ARCH for v in r["values"]})
-    pools, teams = [], []
-    for i in range(rng.choice([0, 0, 1, 2])):
-        kw = {}
-        reqs = []
-        if rng.random() < 0.4: reqs.append(fx.req(fx.ZONE, "In", *rng.sample(zones, rng.choice([1, 2, 3]))))
-        if rng.random() < 0.3: reqs.append(fx.req(fx.CAPACITY_TYPE, "In", rng.choice(["spot", "on-demand"])))
-        if rng.random() < 0.4: kw["taints"] = [{"key": "dedicated", "value": f"t{i}", "effect": "NoSchedule"}]
-        if rng.random() < 0.5: kw["labels"] = {"team": f"t{i}"}; teams.append(f"t{i}")
-        if rng.random() < 0.3: kw["limits"] = {"cpu": "100000"}     # present, never binding
-        pools.append(fx.node_pool(f"pool-{i}", weight=rng.randrange(1, 20), requirements=reqs, **kw))
-    pools.append(fx.node_pool("catch-all", weight=0))   # every pod without a team selector can land here
-    if kwok:
-        for np_ in pools: np_["nodeClassLabelKey"] = "karpenter.kwok.sh/kwoknodeclass"
-    sizes = [(c, m) for c in (100, 250, 700, 1500, 3000) for m in (64, 300, 1024, 5000)]
-    classes = []
-    for _ in range(rng.randrange(1, 40)):
-        sel = {}
-        if rng.random() < 0.3: sel[fx.ARCH] = rng.choice(archs)
-        if rng.random() < 0.3: sel[fx.ZONE] = rng.choice(zones[:2])
-        if rng.random() < 0.2: sel[fx.CAPACITY_TYPE] = rng.choice(["spot", "on-demand"])
-        if rng.random() < 0.15: sel[fx.OS] = "linux"
-        if teams and rng.random() < 0.15: sel["team"] = rng.choice(teams)
-        reqs = None
-        if fx.ZONE not in sel and rng.random() < 0.2: reqs = [fx.req(fx.ZONE, "In", *rng.sample(zones, 2))]
-        tol = [{"key": "dedicated", "operator": "Exists"}] if (rng.random() < 0.4 or "team" in sel) else None
-        c, m = rng.choice(sizes)
-        classes.append(dict(requests={"cpu": f"{c}m", "memory": f"{m}Mi"}, node_selector=sel or None, node_requirements=reqs, tolerations=tol))
-    pods = [fx.pod(**rng.choice(classes)) for _ in range(n_pods)]
-    return fx.problem(its, pools, pods, well_known=wk)
 
 
 @pytest.mark.parametrize("block", range(5))

@@ -4,7 +4,7 @@ flattener, against the oracle in claims, instance-type lists, pod assignment and
 problems are tests/limit_cases.py's; the device run is tests/test_gpu_cursor_limits.py."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import limit_cases as lc
 import parity
 from karpenter_amd import fixtures as fx
@@ -48,9 +48,9 @@ def test_daemonsets(oracle, emu):
     assert lc.stages(got) == (1, 3)       # 48 -> 40 -> 32 -> 24: the 32-cpu type leaves the list with three claims open
     # the ten pods of the existing test: the limit does not bind, engines 11 / 12 behave as 7 / 8
     ten = lc.daemonset_problem(10)
-    loose = dc.solve(ten, "cursor-limits", emu)
+    loose = ec.solve(ten, "cursor-limits", emu)
     assert loose["counters"]["engine"] == "cursor" and lc.stages(loose) == (0, None)
-    dc.same(loose, oracle.solve(ten))
+    ec.same(loose, oracle.solve(ten), ten)
     got, want = lc.check_engine(oracle, emu, lc.daemonset_overhead_problem())
     assert lc.stages(got)[0] == 1 and set(lc.pool_of(want)) == {"first", "second"}
 
@@ -68,7 +68,7 @@ def test_four_rows_of_class_slots(oracle, emu):
     got, want = lc.check_engine(oracle, emu, prob)
     assert lc.rows(got) == 4              # the kernel says which instantiation ran: more than 64 classes were live at once
     assert lc.stages(got)[0] >= 3 and set(lc.pool_of(want)) == {"limited", "catch-all"}
-    assert lc.rows(dc.solve(lc.early_stage_problem(), "cursor-limits", emu)) == 1   # ... and one row where two classes are
+    assert lc.rows(ec.solve(lc.early_stage_problem(), "cursor-limits", emu)) == 1   # ... and one row where two classes are
 
 
 def test_memory_plan_1(oracle, emu):
@@ -105,14 +105,14 @@ def test_stage_exhaustion(oracle, emu):
 
 def test_a_hundred_solves_on_one_handle(oracle, emu):
     prob = lc.cpu_chain_problem(True)
-    digests, last = lc.digests_of_repeated_solves(emu, prob, "auto-limits", 100)
+    digests, last = ec.digests_of_repeated_solves(emu, prob, "auto-limits", 100, "cursor")
     assert len(digests) == 1
-    dc.same(last, oracle.solve(prob))
+    ec.same(last, oracle.solve(prob), prob)
     # ... and with stages to forget
     prob = lc.stage_chain_problem(3)
-    digests, last = lc.digests_of_repeated_solves(emu, prob, "cursor-limits", 20)
+    digests, last = ec.digests_of_repeated_solves(emu, prob, "cursor-limits", 20, "cursor")
     assert len(digests) == 1 and lc.stages(last)[0] == 21
-    dc.same(last, oracle.solve(prob))
+    ec.same(last, oracle.solve(prob), prob)
 
 
 def test_batch(oracle, emu):
@@ -125,8 +125,8 @@ def test_batch(oracle, emu):
             got = SolveBatch(scheds)
             assert [g["counters"]["engine"] for g in got] == ["cursor"] * 3
             for g, (p, e) in zip(got, probs):
-                assert parity.results_digest(g)[0] == parity.results_digest(dc.solve(p, e, emu))[0]
-                dc.same(g, oracle.solve(p))
+                assert parity.results_digest(g)[0] == parity.results_digest(ec.solve(p, e, emu))[0]
+                ec.same(g, oracle.solve(p), p)
             assert lc.stages(got[1]) == (1, 4)
     finally:
         for s in scheds:
@@ -138,14 +138,14 @@ def test_engines_0_to_10_still_decline(oracle, emu):
     a problem without limits counts the same work under the new names."""
     for prob, reason in ((lc.cpu_chain_problem(True), 24), (lc.nodes_zero_problem(), 23)):
         for engine in ("auto", "auto-nodes"):
-            c = dc.solve(prob, engine, emu)["counters"]
+            c = ec.solve(prob, engine, emu)["counters"]
             assert (c["engine"], c["engineFallbackReason"]) == ("general", reason)
         for engine in ("cursor", "cursor-nodes"):
             with pytest.raises(Unsupported, match=rf"cursor engine declined the problem \(reason {reason}\)"):
-                dc.solve(prob, engine, emu)
-    a = dc.solve(fx.config1(), "auto", emu)["counters"]
+                ec.solve(prob, engine, emu)
+    a = ec.solve(fx.config1(), "auto", emu)["counters"]
     for engine in ("auto-limits", "cursor-limits"):
-        r = dc.solve(fx.config1(), engine, emu)
+        r = ec.solve(fx.config1(), engine, emu)
         c = r["counters"]
         assert c["engine"] == "cursor" and lc.stages(r) == (0, None)
         assert (c["binEvaluations"], c["phaseCycles"][21], c["slowSorts"], c["referenceBinEvaluations"], c["pops"]) == \
@@ -158,7 +158,7 @@ def test_refusal_names_the_reason(emu):
     node = fx.state_node("node-0", its[5], "test-zone-1", "on-demand", "default", used={"cpu": "500m", "pods": "1"})
     pods = [fx.pod(requests={"cpu": "900m"}) for _ in range(8)] + [fx.pod(requests={"cpu": "1"}, host_ports=[8080]) for _ in range(2)]
     with pytest.raises(Unsupported, match=r"reason 34"):
-        dc.solve(fx.problem(its, [fx.node_pool(limits={"cpu": "10"})], pods, state_nodes=[node]), "cursor-limits", emu)
+        ec.solve(fx.problem(its, [fx.node_pool(limits={"cpu": "10"})], pods, state_nodes=[node]), "cursor-limits", emu)
 
 
 def test_seeded_fuzz(oracle, emu):

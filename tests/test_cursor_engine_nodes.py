@@ -3,7 +3,7 @@ emulation of the device code (tests/emu, test infrastructure only), the real C A
 by claim, node by node and in the reference-equivalent evaluation count. The device run is tests/test_gpu_cursor_nodes.py."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import existing_node_cases as en
 import parity
 from karpenter_amd import fixtures as fx
@@ -63,20 +63,20 @@ def test_step_limit(oracle, emu):
     """maxSteps (the ctx deadline's stand-in): a step is a queue pop across both stages; the cursor engine equals the general engine
     stopped at the same step."""
     prob = fx.with_existing_nodes(fx.config2(pods=2000, n_types=60, seed=6), 30, seed=1)
-    full = dc.solve(prob, "cursor-nodes", emu)
+    full = ec.solve(prob, "cursor-nodes", emu)
     uid_on_node = {u for e in full["existingNodes"] for u in e["pods"]}
     assert 200 < len(uid_on_node) < 1900
     for steps in (1, 63, 64, 65, 150, 1200, 1999):
-        c = dc.solve(dict(prob, options=dict(prob["options"], maxSteps=steps)), "cursor-nodes", emu)
-        g = dc.solve(dict(prob, options=dict(prob["options"], maxSteps=steps)), "general", emu)
+        c = ec.solve(dict(prob, options=dict(prob["options"], maxSteps=steps)), "cursor-nodes", emu)
+        g = ec.solve(dict(prob, options=dict(prob["options"], maxSteps=steps)), "general", emu)
         assert c["counters"]["engine"] == "cursor" and c["timedOut"] and g["timedOut"], steps
         parity.assert_same_results(c, g)
         assert c["scheduledPods"] == g["scheduledPods"] == steps and c["counters"]["pops"] == g["counters"]["pops"]
         assert c["counters"]["referenceBinEvaluations"] == g["counters"]["referenceBinEvaluations"]
     # a limit the queue never reaches is no limit
-    c = dc.solve(dict(prob, options=dict(prob["options"], maxSteps=2000)), "cursor-nodes", emu)
+    c = ec.solve(dict(prob, options=dict(prob["options"], maxSteps=2000)), "cursor-nodes", emu)
     assert not c["timedOut"]
-    dc.same(c, oracle.solve(prob))
+    ec.same(c, oracle.solve(prob), prob)
 
 
 def test_step_limit_inside_the_node_prefix(oracle, emu):
@@ -88,8 +88,8 @@ def test_step_limit_inside_the_node_prefix(oracle, emu):
     want = oracle.solve(prob)
     assert en.on_nodes(want) == 10 and want["newNodeClaims"]       # queue order: the ten 1-cpu pods first
     for steps in (4, 10, 11):
-        c = dc.solve(dict(prob, options={"maxSteps": steps}), "cursor-nodes", emu)
-        g = dc.solve(dict(prob, options={"maxSteps": steps}), "general", emu)
+        c = ec.solve(dict(prob, options={"maxSteps": steps}), "cursor-nodes", emu)
+        g = ec.solve(dict(prob, options={"maxSteps": steps}), "general", emu)
         assert c["counters"]["engine"] == "cursor" and c["timedOut"] and g["timedOut"]
         parity.assert_same_results(c, g)
         assert c["scheduledPods"] == steps and c["counters"]["referenceBinEvaluations"] == g["counters"]["referenceBinEvaluations"]
@@ -105,7 +105,7 @@ def test_repeated_solves_and_batches(oracle, emu):
         digests.add(parity.results_digest(r)[0])
     s.close()
     assert len(digests) == 1
-    dc.same(r, oracle.solve(prob))
+    ec.same(r, oracle.solve(prob), prob)
     # ksolve_solve_batch: such handles run alone through solve(), plain ones in the batched cursor kernel
     probs = [fx.with_existing_nodes(fx.config2(pods=1200, n_types=60, seed=90 + i), 40 + 30 * i, seed=i) if i % 2 == 0 else fx.config2(pods=1200, n_types=60, seed=90 + i) for i in range(5)]
     scheds = [NewScheduler(dict(p, options=dict(p["options"], engine="auto-nodes")), solver_lib=emu) for p in probs]
@@ -113,8 +113,8 @@ def test_repeated_solves_and_batches(oracle, emu):
         got = SolveBatch(scheds)
         assert [g["counters"]["engine"] for g in got] == ["cursor"] * 5
         for g, p in zip(got, probs):
-            assert parity.results_digest(g)[0] == parity.results_digest(dc.solve(p, "auto-nodes", emu))[0]
-            dc.same(g, oracle.solve(p))
+            assert parity.results_digest(g)[0] == parity.results_digest(ec.solve(p, "auto-nodes", emu))[0]
+            ec.same(g, oracle.solve(p), p)
             assert (en.on_nodes(g) > 0) == bool(p["stateNodes"])
     for s in scheds:
         s.close()
@@ -122,10 +122,10 @@ def test_repeated_solves_and_batches(oracle, emu):
 
 def _declined(oracle, emu, prob, reason, match="cursor engine"):
     with pytest.raises(Unsupported, match=match):
-        dc.solve(prob, "cursor-nodes", emu)
-    auto = dc.solve(prob, "auto-nodes", emu)
+        ec.solve(prob, "cursor-nodes", emu)
+    auto = ec.solve(prob, "auto-nodes", emu)
     assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == reason, auto["counters"]
-    dc.same(auto, oracle.solve(prob))
+    ec.same(auto, oracle.solve(prob), prob)
 
 
 def test_declines(oracle, emu):
@@ -156,12 +156,12 @@ def test_declines(oracle, emu):
 def test_other_engines_still_refuse_nodes(emu):
     """"auto" and "cursor" behave as before; a problem without nodes launches no new kernel and counts the same work under the new names."""
     prob = en.block_edge_problem(5)
-    assert dc.solve(prob, "auto", emu)["counters"]["engine"] == "general"
+    assert ec.solve(prob, "auto", emu)["counters"]["engine"] == "general"
     with pytest.raises(Unsupported, match="cursor engine"):
-        dc.solve(prob, "cursor", emu)
-    a = dc.solve(fx.config1(), "auto", emu)["counters"]
+        ec.solve(prob, "cursor", emu)
+    a = ec.solve(fx.config1(), "auto", emu)["counters"]
     for engine in ("auto-nodes", "cursor-nodes"):
-        c = dc.solve(fx.config1(), engine, emu)["counters"]
+        c = ec.solve(fx.config1(), engine, emu)["counters"]
         assert c["engine"] == "cursor" and c["phaseCycles"][19] == 0
         assert (c["binEvaluations"], c["phaseCycles"][21], c["slowSorts"], c["referenceBinEvaluations"], c["pops"]) == \
                (a["binEvaluations"], a["phaseCycles"][21], a["slowSorts"], a["referenceBinEvaluations"], a["pops"])

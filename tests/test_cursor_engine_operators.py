@@ -3,6 +3,7 @@ ksolve_fast_records; engines "auto-operators" / "cursor-operators"): through the
 infrastructure only), the real C ABI and the real flattener, against the oracle in claims, instance-type lists, claim requirements
 (operator and values), pod assignment and the reference-equivalent evaluation count. The problems are tests/operator_cases.py's; the
 device run is tests/test_gpu_cursor_operators.py."""
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
 from karpenter_amd import fixtures as fx
@@ -82,7 +83,7 @@ def test_existing_nodes_and_a_daemonset(oracle, emu):
     prob = oc.nodes_problem()
     got, want = oc.check_engine(oracle, emu, prob, 34, base="auto-nodes", base_cursor="cursor-nodes")
     assert sum(len(e["pods"]) for e in want.get("existingNodes", [])) > 0 and oc.claims_of(want, "above")
-    plain = oc.solve(prob, "auto", emu)["counters"]
+    plain = ec.solve(prob, "auto", emu)["counters"]
     assert (plain["engine"], plain["engineFallbackReason"]) == ("general", 0)
 
 
@@ -91,16 +92,16 @@ def test_still_declined(oracle, emu):
     oc.check_declined(oracle, emu, oc.min_values_problem(), 1)
     oc.check_declined(oracle, emu, oc.pod_gt_problem(), 1)
     prob = oc.spread_problem()
-    auto = oc.solve(prob, "auto-operators", emu)
+    auto = ec.solve(prob, "auto-operators", emu)
     assert auto["counters"]["engine"] == "general", auto["counters"]
-    oc.same(auto, oracle.solve(prob))
+    ec.same(auto, oracle.solve(prob), prob)
 
 
 def test_in_only_pools_count_the_same_work(emu):
     """A problem without such pools does the same work under the new names as under "auto"."""
-    a = oc.solve(fx.config1(), "auto", emu)["counters"]
+    a = ec.solve(fx.config1(), "auto", emu)["counters"]
     for engine in ("auto-operators", "cursor-operators"):
-        c = oc.solve(fx.config1(), engine, emu)["counters"]
+        c = ec.solve(fx.config1(), engine, emu)["counters"]
         assert c["engine"] == "cursor"
         assert (c["binEvaluations"], c["slowSorts"], c["referenceBinEvaluations"], c["pops"]) == (a["binEvaluations"], a["slowSorts"], a["referenceBinEvaluations"], a["pops"])
 

@@ -3,9 +3,7 @@ ksolve_fast_records; engines "auto-pod-operators" / "cursor-pod-operators"): thr
 test infrastructure only), the real C ABI and the real flattener, against the oracle in claims, instance-type lists, claim
 requirements (operator and values), pod assignment and the reference-equivalent evaluation count. The problems are
 tests/pod_operator_cases.py's; the device run is tests/test_gpu_cursor_pod_operators.py."""
-import os
-import subprocess
-
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
 import pod_operator_cases as pc
@@ -110,70 +108,20 @@ def test_still_declined(oracle, emu):
     pc.check_declined(oracle, emu, pc.notin_bounds_problem(), 11)
     pc.check_declined(oracle, emu, pc.exists_undefined_problem(), 12)
     prob = pc.spread_problem()                                   # the spread engine: 4 under every setting
-    auto = pc.solve(prob, pc.AUTO, emu)
+    auto = ec.solve(prob, pc.AUTO, emu)
     assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", 4), auto["counters"]
-    pc.same(auto, oracle.solve(prob))
-    plain = pc.solve(oc.pod_notin_problem(), pc.BASE, emu)["counters"]
+    ec.same(auto, oracle.solve(prob), prob)
+    plain = ec.solve(oc.pod_notin_problem(), pc.BASE, emu)["counters"]
     assert (plain["engine"], plain["engineFallbackReason"]) == ("general", 4)
 
 
 def test_positive_batches_count_the_same_work(emu):
     """A problem without such pods does the same work under the new names as under "auto"."""
-    a = pc.solve(fx.config1(), "auto", emu)["counters"]
+    a = ec.solve(fx.config1(), "auto", emu)["counters"]
     for engine in (pc.AUTO, pc.ENGINE):
-        c = pc.solve(fx.config1(), engine, emu)["counters"]
+        c = ec.solve(fx.config1(), engine, emu)["counters"]
         assert c["engine"] == "cursor"
         assert (c["binEvaluations"], c["slowSorts"], c["referenceBinEvaluations"], c["pops"]) == (a["binEvaluations"], a["slowSorts"], a["referenceBinEvaluations"], a["pops"])
-
-
-ROWS_0_25 = """\
-0 0 0 1 0 0 0 0 0 0 0 0 0 0 0 auto
-1 1 0 0 0 0 0 0 0 0 0 0 0 0 0 general
-2 2 0 1 0 0 0 0 0 0 0 0 0 0 0 cursor
-3 2 1 0 0 0 0 0 0 0 0 0 0 0 0 cursor-wide
-4 2 2 0 0 0 0 0 0 0 0 0 0 0 0 cursor-hbm
-5 2 0 0 1 0 0 0 0 0 0 0 0 0 0 cursor-pair
-6 3 0 0 0 0 0 0 0 0 0 0 0 0 0 spread
-7 0 0 1 0 1 0 0 0 0 0 0 0 0 0 auto-nodes
-8 2 0 1 0 1 0 0 0 0 0 0 0 0 0 cursor-nodes
-9 0 0 1 0 1 1 0 0 0 0 0 0 0 0 auto-nodes-spread
-10 3 0 0 0 0 1 0 0 0 0 0 0 0 0 spread-nodes
-11 0 0 1 0 1 0 1 0 0 0 0 0 0 0 auto-limits
-12 2 0 1 0 1 0 1 0 0 0 0 0 0 0 cursor-limits
-13 0 0 1 0 1 1 1 1 0 0 0 0 0 0 auto-limits-spread
-14 3 0 0 0 0 1 0 1 0 0 0 0 0 0 spread-limits
-15 0 0 1 0 1 1 1 1 1 0 0 0 0 0 auto-operators
-16 2 0 1 0 1 0 1 0 1 0 0 0 0 0 cursor-operators
-17 2 0 0 0 0 0 0 0 0 0 0 0 0 0 -
-18 0 0 1 0 1 1 1 1 1 1 0 0 0 0 auto-operators-spread
-19 3 0 0 0 0 1 0 1 0 1 0 0 0 0 spread-operators
-20 0 0 1 0 1 1 1 1 1 1 1 0 0 0 auto-unschedulable
-21 2 0 1 0 1 0 1 0 1 0 1 0 0 0 cursor-unschedulable
-22 0 0 1 0 1 1 1 1 1 1 1 1 0 0 auto-unschedulable-spread
-23 3 0 0 0 0 1 0 1 0 1 0 1 0 0 spread-unschedulable
-24 0 0 1 0 1 1 1 1 1 1 1 1 1 0 auto-filters-spread
-25 3 0 0 0 0 1 0 1 0 1 0 1 1 0 spread-filters
-"""   # (value, run, first plan, pick, pair, nodes, s-nodes, limits, s-limits, ops, s-ops, unsched, s-unsched, s-filters, pod-ops, name)
-
-
-def test_rows_of_the_engine_table(tmp_path):
-    """csrc/engine_setting.h holds rows 26 and 27 — 24 and 21 plus the pod_operators switch — and leaves 0-25, 17 and the policy of a
-    value past the table as they were: every row printed by a program that includes the header."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "rows.cpp"
-    src.write_text('#include <cstdio>\n#include "engine_setting.h"\nstatic void row(int v, const ksi::EnginePolicy& p) {\n'
-                   '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s\\n", v, (int)p.run, p.first_plan, p.pick_plan, p.pair, p.nodes, p.spread_nodes, p.limits, p.spread_limits,\n'
-                   '         p.operators, p.spread_operators, p.unschedulable, p.spread_unschedulable, p.spread_filters, p.pod_operators, p.name ? p.name : "-");\n}\n'
-                   'int main() { for (unsigned v = 0; v <= ksi::kEngineSettingCount; ++v) row((int)v, ksi::engine_policy(v));\n'
-                   '  printf("%u %u %u %u\\n", ksi::engine_value("auto-pod-operators"), ksi::engine_value("cursor-pod-operators"), ksi::engine_value("spread-filters"), ksi::engine_value("no-such-name")); }\n')
-    exe = tmp_path / "rows"
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(root, "karpenter_amd", "csrc"), "-o", str(exe), str(src)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    assert lines[:26] == ROWS_0_25.splitlines()
-    assert lines[26] == lines[24].replace("24 ", "26 ", 1).replace(" 0 auto-filters-spread", " 1 auto-pod-operators")
-    assert lines[27] == lines[21].replace("21 ", "27 ", 1).replace(" 0 cursor-unschedulable", " 1 cursor-pod-operators")
-    assert lines[28] == "28 2 0 0 0 0 0 0 0 0 0 0 0 0 0 -"       # past the table: the cursor engine alone, no switch
-    assert lines[29] == "26 27 25 0"
 
 
 def test_seeded_fuzz(oracle, emu):

@@ -5,7 +5,7 @@ hostnames, pod errors with their flags, queue pops and the reference-equivalent 
 tests/unschedulable_cases.py's; the device run is tests/test_gpu_cursor_unschedulable.py."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import limit_cases as lc
 import parity
 import unschedulable_cases as uc
@@ -53,7 +53,7 @@ def test_error_changes_at_the_retry(oracle, emu):
     Limits (7) at its second, once the pool has run into its limit: the reported error is that of the LAST attempt."""
     prob = uc.error_changes_problem()
     big = next(p["uid"] for p in prob["pods"] if p["requests"]["cpu"] == "100")
-    early = dc.solve(dict(prob, options=dict(prob.get("options", {}), maxSteps=1)), "cursor-unschedulable", emu)
+    early = ec.solve(dict(prob, options=dict(prob.get("options", {}), maxSteps=1)), "cursor-unschedulable", emu)
     assert early["timedOut"] and (early["podErrors"][big]["code"], early["podErrors"][big]["diag"]) == (4, 21)
     got, want = uc.check_engine(oracle, emu, prob)
     assert (got["podErrors"][big]["code"], got["podErrors"][big]["diag"]) == (7, 0)
@@ -61,9 +61,9 @@ def test_error_changes_at_the_retry(oracle, emu):
 
 def test_plain_batches_count_the_same_work(emu):
     """A batch without such pods does the same work under the new names as under "auto"."""
-    a = dc.solve(fx.config1(), "auto", emu)["counters"]
+    a = ec.solve(fx.config1(), "auto", emu)["counters"]
     for engine in ("auto-unschedulable", "cursor-unschedulable"):
-        c = dc.solve(fx.config1(), engine, emu)["counters"]
+        c = ec.solve(fx.config1(), engine, emu)["counters"]
         assert c["engine"] == "cursor"
         assert (c["binEvaluations"], c["slowSorts"], c["referenceBinEvaluations"], c["pops"]) == (a["binEvaluations"], a["slowSorts"], a["referenceBinEvaluations"], a["pops"])
 
@@ -71,10 +71,10 @@ def test_plain_batches_count_the_same_work(emu):
 def test_repeated_solves(oracle, emu):
     """Twenty solves of one handle: the set-aside list starts empty every time (setup())."""
     for prob in (uc.tail_run_problem(), fx.with_existing_nodes(uc.tail_run_problem(), 4, seed=1), uc.error_changes_problem()):
-        digests, last = lc.digests_of_repeated_solves(emu, prob, "cursor-unschedulable", 20)
+        digests, last = ec.digests_of_repeated_solves(emu, prob, "cursor-unschedulable", 20, "cursor")
         assert len(digests) == 1
         want = oracle.solve(prob)
-        dc.same(last, want)
+        ec.same(last, want, mode=ec.SETS)
         assert last["counters"]["pops"] == want["counters"]["pops"]
 
 
@@ -88,8 +88,8 @@ def test_step_limit(emu, nodes):
     pods, pops = uc.n_pods(prob), uc.n_pods(prob) + 1
     for steps in range(pods - 2, pops + 2):
         limited = dict(prob, options=dict(prob.get("options", {}), maxSteps=steps))
-        c = dc.solve(limited, "cursor-unschedulable", emu)
-        g = dc.solve(limited, "general", emu)
+        c = ec.solve(limited, "cursor-unschedulable", emu)
+        g = ec.solve(limited, "general", emu)
         assert c["counters"]["engine"] == "cursor" and c["counters"]["engineFallbackReason"] == 0, (steps, c["counters"])
         assert c["timedOut"] == g["timedOut"] == (steps < pops), (steps, c["timedOut"], g["timedOut"])
         parity.assert_same_results(c, g)
@@ -102,9 +102,9 @@ def test_still_declined(oracle, emu):
     makes a relaxation row, and such a batch is not offered to a fast engine at all (reason 0, "outside its shape"). A pod with a
     NotIn, Gt or Lt requirement of its own keeps its reason (4, 1, 1), and so does a NodePool with minValues (1)."""
     prob = uc.spread_problem()
-    auto = dc.solve(prob, "auto-unschedulable", emu)
+    auto = ec.solve(prob, "auto-unschedulable", emu)
     assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", 27), auto["counters"]
-    dc.same(auto, oracle.solve(prob))
+    ec.same(auto, oracle.solve(prob), prob)
     uc.check_declined(oracle, emu, uc.preference_problem(), 0)
     for _, prob, reason in uc.pod_operator_problems():
         uc.check_declined(oracle, emu, prob, reason)

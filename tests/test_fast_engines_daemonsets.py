@@ -5,6 +5,7 @@ by claim and in the reference-equivalent evaluation count. The device run of the
 import pytest
 
 import daemonset_cases as dc
+import engine_checks as ec
 import parity
 from karpenter_amd import fixtures as fx
 from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported
@@ -23,9 +24,9 @@ def test_known_answers_on_the_cursor_engine(oracle, emu):
     assert int(req["cpu"]) == 2 * 10**9 and int(req["pods"]) == 2 * 10**9                 # suite_test.go:2155-2172
     # the full default catalogue has five resource dimensions (two GPU vendors): declined as before, DaemonSets or not
     prob = fx.problem(fx.fake_default_instance_types(), [fx.node_pool()], [fx.pod(requests={"cpu": "1", "memory": "1Gi"})], daemonset_pods=[fx.pod(requests={"cpu": "1", "memory": "1Gi"})])
-    auto = dc.solve(prob, "auto", emu)
+    auto = ec.solve(prob, "auto", emu)
     assert auto["counters"]["engine"] == "general"
-    dc.same(auto, oracle.solve(prob))
+    ec.same(auto, oracle.solve(prob), prob)
 
 
 @pytest.mark.parametrize("kind", ["a", "b", "c"])
@@ -34,9 +35,9 @@ def test_production_like_daemonsets_on_the_cursor_engine(oracle, emu, kind):
         q = fx.with_daemonsets(prob, kind)
         got, _ = dc.check_engine(oracle, emu, q, "cursor", PLANS)
         assert not got["podErrors"]
-    pair = dc.solve(fx.with_daemonsets(fx.config1(), kind), "cursor-pair", emu)   # one row of class slots: the two-wavefront kernel's plan
+    pair = ec.solve(fx.with_daemonsets(fx.config1(), kind), "cursor-pair", emu)   # one row of class slots: the two-wavefront kernel's plan
     assert pair["counters"]["engine"] == "cursor"
-    dc.same(pair, oracle.solve(fx.with_daemonsets(fx.config1(), kind)))
+    ec.same(pair, oracle.solve(fx.with_daemonsets(fx.config1(), kind)), mode=ec.SETS)
 
 
 @pytest.mark.parametrize("kind,pods", [("a", 2000), ("b", 5000), ("c", 20000)])
@@ -90,11 +91,11 @@ def test_types_that_cannot_hold_their_daemons(oracle, emu):
     # a DaemonSet no type can hold: every pod is unschedulable — the general engine owns the error codes
     prob = fx.problem(its, [fx.node_pool()], pods, daemonset_pods=[fx.pod(requests={"cpu": "1000"})])
     with pytest.raises(Unsupported, match="cursor engine"):
-        dc.solve(prob, "cursor", emu)
-    auto = dc.solve(prob, "auto", emu)
+        ec.solve(prob, "cursor", emu)
+    auto = ec.solve(prob, "auto", emu)
     assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == 27
     want = oracle.solve(prob)
-    dc.same(auto, want)
+    ec.same(auto, want, mode=ec.SETS)
     assert len(want["podErrors"]) == 30 and not want["newNodeClaims"]
 
 
@@ -107,10 +108,10 @@ def test_nodepool_limits_with_daemonsets(oracle, emu):
     # limits that bind: declined as without DaemonSets, auto equals the oracle
     prob = fx.problem(its, [fx.node_pool(limits={"cpu": "20"})], pods, daemonset_pods=ds)
     with pytest.raises(Unsupported, match="cursor engine"):
-        dc.solve(prob, "cursor", emu)
-    auto = dc.solve(prob, "auto", emu)
+        ec.solve(prob, "cursor", emu)
+    auto = ec.solve(prob, "auto", emu)
     assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] in (23, 24)
-    dc.same(auto, oracle.solve(prob))
+    ec.same(auto, oracle.solve(prob), prob)
     # Whether the limit binds depends on subtractMax (scheduler.go:1049-1066) taking its maximum over the types that fit size +
     # overhead: a 900Mi pod fits the 32-cpu / 1Gi type alone but not beside a 200Mi DaemonSet, so a claim's options are the 8-cpu
     # type only and each of the two claims takes 8 cpu of the 48 — the 32-cpu type is never excluded (48 -> 40 -> 32). Counting 32
@@ -123,7 +124,7 @@ def test_nodepool_limits_with_daemonsets(oracle, emu):
     got, want = dc.check_engine(oracle, emu, prob, "cursor")
     assert len(want["newNodeClaims"]) == 2 and all(c["instanceTypes"] == ["cpu-8-mem-64"] for c in want["newNodeClaims"])
     # (without the DaemonSet the first claim does keep the 32-cpu type, 32 cpu are taken and the type is excluded before the second claim)
-    without = dc.solve(fx.problem(its, [fx.node_pool(limits={"cpu": "48"})], pods), "auto", emu)
+    without = ec.solve(fx.problem(its, [fx.node_pool(limits={"cpu": "48"})], pods), "auto", emu)
     assert without["counters"]["engine"] == "general" and without["counters"]["engineFallbackReason"] == 24
 
 
@@ -138,14 +139,14 @@ def test_still_declined_with_daemonsets(oracle, emu):
     nodes = fx.problem(its, [fx.node_pool()], [fx.pod(requests={"cpu": "900m"}) for _ in range(8)], daemonset_pods=ds, state_nodes=[node])
     for p, engine in ((prob, "cursor"), (nodes, "cursor"), (spread, "spread")):
         with pytest.raises(Unsupported, match=f"{engine} engine"):
-            dc.solve(p, engine, emu)
-        auto = dc.solve(p, "auto", emu)
+            ec.solve(p, engine, emu)
+        auto = ec.solve(p, "auto", emu)
         assert auto["counters"]["engine"] == "general"
-        dc.same(auto, oracle.solve(p))
+        ec.same(auto, oracle.solve(p), p)
 
 
 CURSOR_SEEDS = list(range(60))
-# spread_fuzz_problem builds on test_spread_engine.fuzz_problem, whose seeds = 2 mod 5 draw a NodePool limit of 20 cpu (it binds) and
+# spread_fuzz_problem builds on mix_cases.fuzz_problem, whose seeds = 2 mod 5 draw a NodePool limit of 20 cpu (it binds) and
 # whose seeds = 3 mod 4 draw the kinds that leave pods unschedulable: both are the general engine's with or without DaemonSets. Of
 # the sixty seeds kept the oracle alone reports pod errors for six.
 SPREAD_SEEDS = [s for s in range(200) if s % 5 != 2 and s % 4 != 3][:60]
@@ -184,8 +185,8 @@ def test_repeated_solves_and_batches_of_daemonset_handles(oracle, emu):
         got = SolveBatch(scheds)
         assert [g["counters"]["engine"] for g in got] == ["cursor"] * 6 + ["spread"] * 2
         for g, w, p in zip(got, want, probs):
-            assert parity.results_digest(g)[0] == parity.results_digest(dc.solve(p, "auto", emu))[0]   # ... and byte for byte what ksolve_solve returns
-            dc.same(g, w)
+            assert parity.results_digest(g)[0] == parity.results_digest(ec.solve(p, "auto", emu))[0]   # ... and byte for byte what ksolve_solve returns
+            ec.same(g, w, mode=ec.SETS)
     for s in scheds:
         s.close()
 

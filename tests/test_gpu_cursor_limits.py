@@ -3,20 +3,13 @@
 the ones tests/test_cursor_engine_limits.py runs on the emulation, at the same small shapes."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import limit_cases as lc
 import parity
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_cpu_chain(oracle):
@@ -84,13 +77,13 @@ def test_stage_exhaustion(oracle):
 
 def test_a_hundred_solves_on_one_handle(oracle):
     prob = lc.cpu_chain_problem(True)
-    digests, last = lc.digests_of_repeated_solves(None, prob, "auto-limits", 100)
+    digests, last = ec.digests_of_repeated_solves(None, prob, "auto-limits", 100, "cursor")
     assert len(digests) == 1
-    dc.same(last, oracle.solve(prob))
+    ec.same(last, oracle.solve(prob), prob)
     prob = lc.stage_chain_problem(3)
-    digests, last = lc.digests_of_repeated_solves(None, prob, "cursor-limits", 20)
+    digests, last = ec.digests_of_repeated_solves(None, prob, "cursor-limits", 20, "cursor")
     assert len(digests) == 1 and lc.stages(last)[0] == 21
-    dc.same(last, oracle.solve(prob))
+    ec.same(last, oracle.solve(prob), prob)
 
 
 def test_seeded_fuzz(oracle):

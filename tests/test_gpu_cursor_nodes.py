@@ -2,7 +2,7 @@
 tests/test_cursor_engine_nodes.py that exercise the kernel's paths, against the oracle."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import existing_node_cases as en
 import parity
 from karpenter_amd import fixtures as fx
@@ -53,4 +53,4 @@ def test_hundred_solves_one_digest(oracle):
         digests.add(parity.results_digest(r)[0])
     s.close()
     assert r["counters"]["engine"] == "cursor" and len(digests) == 1
-    dc.same(r, oracle.solve(prob))
+    ec.same(r, oracle.solve(prob), prob)

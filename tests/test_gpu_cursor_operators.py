@@ -6,17 +6,10 @@ import pytest
 
 import limit_cases as lc
 import operator_cases as oc
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_bounds_on_a_key_no_pod_selects_on(oracle):

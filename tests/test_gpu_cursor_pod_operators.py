@@ -4,20 +4,14 @@ csrc/ksolve_pack_fast_podops.hip): the product library through the C ABI against
 tests/pod_operator_cases.py — the ones tests/test_cursor_engine_pod_operators.py runs on the emulation, at the same small shapes."""
 import pytest
 
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
 import pod_operator_cases as pc
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_zone_notin_over_an_open_pool(oracle):
@@ -90,10 +84,10 @@ def test_still_declined(oracle):
     pc.check_declined(oracle, None, pc.notin_bounds_problem(), 11)
     pc.check_declined(oracle, None, pc.exists_undefined_problem(), 12)
     prob = pc.spread_problem()
-    auto = pc.solve(prob, pc.AUTO, None)
+    auto = ec.solve(prob, pc.AUTO, None)
     assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", 4), auto["counters"]
-    pc.same(auto, oracle.solve(prob))
-    plain = pc.solve(oc.pod_notin_problem(), pc.BASE, None)["counters"]
+    ec.same(auto, oracle.solve(prob), prob)
+    plain = ec.solve(oc.pod_notin_problem(), pc.BASE, None)["counters"]
     assert (plain["engine"], plain["engineFallbackReason"]) == ("general", 4)
 
 

@@ -4,22 +4,15 @@ tests/unschedulable_cases.py — the ones tests/test_cursor_engine_unschedulable
 (the 3,600-claim plan escalation stays on the emulation)."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
 import limit_cases as lc
 import unschedulable_cases as uc
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
 
 HAND = uc.hand_problems(with_escalation=False)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 @pytest.mark.parametrize("name", [name for name, _, _ in HAND])
@@ -33,9 +26,9 @@ def test_hand_problem(oracle, name):
 
 def test_repeated_solves(oracle):
     prob = fx.with_existing_nodes(uc.tail_run_problem(), 4, seed=1)
-    digests, last = lc.digests_of_repeated_solves(None, prob, "cursor-unschedulable", 20)
+    digests, last = ec.digests_of_repeated_solves(None, prob, "cursor-unschedulable", 20, "cursor")
     assert len(digests) == 1
-    dc.same(last, oracle.solve(prob))
+    ec.same(last, oracle.solve(prob), prob)
 
 
 def test_seeded_fuzz(oracle):

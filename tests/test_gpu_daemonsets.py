@@ -4,19 +4,14 @@ fallback reason 0, so none can pass by falling back to the general engine. The e
 import pytest
 
 import daemonset_cases as dc
+import engine_checks as ec
 import parity
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, device_available
+from karpenter_amd.scheduling import NewScheduler
 from test_fast_engines_daemonsets import CURSOR_SEEDS, SPREAD_SEEDS
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_known_answers_on_the_device(oracle):
@@ -56,4 +51,4 @@ def test_one_hundred_solves_of_one_handle(oracle):
         digests.add(parity.results_digest(r)[0])
     s.close()
     assert len(digests) == 1
-    dc.same(r, oracle.solve(prob))
+    ec.same(r, oracle.solve(prob), prob)

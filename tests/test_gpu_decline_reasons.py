@@ -9,20 +9,14 @@ capacities, which carry no `nodes`): it stops a template only when nothing is le
 the reason-23 case gives its first NodePool `nodes: 0`, the only limit below the claims the pods need that can bind."""
 import pytest
 
-import daemonset_cases as dc
+import engine_checks as ec
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported, device_available
+from karpenter_amd.scheduling import NewScheduler, SolveBatch, Unsupported
 
 pytestmark = pytest.mark.gpu
 
 AB = {"a": "b"}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def pods(n, engine, **kw):
@@ -72,11 +66,11 @@ def test_limit_reasons(oracle, limit, engine):
     reason, claims = LIMIT_CASES[limit, engine]
     want = oracle.solve(prob)
     assert len(want["newNodeClaims"]) == claims
-    auto = dc.solve(prob, "auto", None)
-    dc.same(auto, want)
+    auto = ec.solve(prob, "auto", None)
+    ec.same(auto, want, mode=ec.SETS)
     assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
     with pytest.raises(Unsupported, match=rf"{engine} engine declined the problem \(reason {reason}\)"):
-        dc.solve(prob, engine, None)
+        ec.solve(prob, engine, None)
 
 
 @pytest.mark.parametrize("engine", ["cursor", "spread"])
@@ -84,9 +78,9 @@ def test_limits_that_never_bind_stay_on_the_fast_engine(oracle, engine):
     prob = loose_limits_problem(engine)
     want = oracle.solve(prob)
     assert len(want["newNodeClaims"]) == LOOSE_CLAIMS[engine] and len({c["nodePool"] for c in want["newNodeClaims"]}) == 3 and not want["podErrors"]
-    auto = dc.solve(prob, "auto", None)
+    auto = ec.solve(prob, "auto", None)
     assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == (engine, 0), auto["counters"]
-    dc.same(auto, want)
+    ec.same(auto, want, mode=ec.SETS)
 
 
 def test_batch_hands_back_a_handle_out_of_claim_slots(oracle):
@@ -104,7 +98,7 @@ def test_batch_hands_back_a_handle_out_of_claim_slots(oracle):
         s.close()
     assert [(g["counters"]["engine"], g["counters"]["engineFallbackReason"]) for g in got] == [("general", 26), ("cursor", 0)]
     for g, w in zip(got, want):
-        dc.same(g, w)
+        ec.same(g, w, mode=ec.SETS)
 
 
 @pytest.mark.parametrize("engine", ["cursor", "spread"])
@@ -117,8 +111,8 @@ def test_an_unschedulable_pod_twice_on_one_handle(oracle, engine):
         for _ in range(2):
             got = s.Solve()
             assert (got["counters"]["engine"], got["counters"]["engineFallbackReason"]) == ("general", 27), got["counters"]
-            dc.same(got, oracle.solve(prob))   # (same() sorts the option lists in place: a fresh document per comparison)
+            ec.same(got, oracle.solve(prob), prob)   # (same() sorts the option lists in place: a fresh document per comparison)
     finally:
         s.close()
     with pytest.raises(Unsupported, match=rf"{engine} engine declined the problem \(reason 27\)"):
-        dc.solve(prob, engine, None)
+        ec.solve(prob, engine, None)

@@ -6,18 +6,12 @@ import os
 import pytest
 
 import parity
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, device_available
+from karpenter_amd.scheduling import NewScheduler
 
 pytestmark = pytest.mark.gpu
 AMD = {fx.ARCH: "amd64"}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def check(oracle, prob, solver_lib=None):

@@ -5,17 +5,11 @@ with 13 to 64 claims in flight, against the oracle. The CPU run of the same code
 import pytest
 
 import parity
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import NewScheduler, SolveBatch, device_available
+from karpenter_amd.scheduling import NewScheduler, SolveBatch
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def same(got, want):

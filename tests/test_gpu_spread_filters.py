@@ -4,22 +4,16 @@ through the C ABI against the oracle, on the problems of tests/spread_filter_cas
 tests/test_spread_engine_filters.py runs on the emulation, at the same small shapes."""
 import pytest
 
+import engine_checks as ec
 import spread_filter_cases as sf
 import spread_limit_cases as sl
 import spread_node_cases as sn
 import spread_operator_cases as so
 import test_spread_engine_filters as cpu
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_owner_only(oracle):
@@ -106,7 +100,7 @@ def test_old_settings_stay_as_they_are():
         for engine in ("auto", "auto-operators-spread", "auto-unschedulable-spread"):
             complement = engine == "auto" and so.has_non_in_pool(prob)
             assert sf.lone_cell(None, prob, engine)[:2] == ("general", 3 if complement else 43), engine
-        assert "spread engine declined the problem (reason 43)" in sf.refusal(prob, "spread-unschedulable", None)
+        assert "spread engine declined the problem (reason 43)" in ec.refusal(prob, "spread-unschedulable", None)
     prob = so.node_filter_problem()
     positive = dict(prob, nodePools=[p for p in prob["nodePools"] if p["name"] == "open"])
     assert not so.has_non_in_pool(positive) and sf.lone_cell(None, positive, "auto")[:2] == ("general", 43)

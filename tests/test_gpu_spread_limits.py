@@ -3,20 +3,15 @@ engines "auto-limits-spread" / "spread-limits"): the product library through the
 tests/spread_limit_cases.py — the ones tests/test_spread_engine_limits.py runs on the emulation, at the same small shapes."""
 import pytest
 
+import engine_checks as ec
 import limit_cases as lc
 import parity
 import spread_limit_cases as sl
 import spread_node_cases as sn
-from karpenter_amd.scheduling import Unsupported, device_available
+from gpu_support import built  # noqa: F401  (fixture)
+from karpenter_amd.scheduling import Unsupported
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 @pytest.mark.parametrize("cfg,limits,n_limited,n_open", sl.MIX)
@@ -33,9 +28,9 @@ def test_node_limit(oracle):
     want = oracle.solve(loose)
     digests = set()
     for engine in ("auto", "spread-limits"):
-        r = sl.solve(loose, engine, None)
+        r = ec.solve(loose, engine, None)
         assert r["counters"]["engine"] == "spread" and r["counters"]["engineFallbackReason"] == 0, (engine, r["counters"])
-        sl.same(r, want, loose)
+        ec.same(r, want, loose)
         digests.add(parity.results_digest(r)[0])
     assert len(digests) == 1 and sl.stages(r) == (0, None)
 
@@ -69,11 +64,11 @@ def test_repeated_solves_on_one_handle(oracle):
     prob = sl.zonal_chain_problem()
     digests, words, last = sl.repeated_solves(None, prob, "auto-limits-spread", 100)
     assert len(digests) == 1 and words == {(0, 5)}
-    sl.same(last, oracle.solve(prob), prob)
+    ec.same(last, oracle.solve(prob), prob)
     prob = sl.stage_chain_problem(3)
     digests, words, last = sl.repeated_solves(None, prob, "spread-limits", 20)
     assert len(digests) == 1 and {w[0] for w in words} == {21}
-    sl.same(last, oracle.solve(prob), prob)
+    ec.same(last, oracle.solve(prob), prob)
 
 
 def test_seeded_fuzz(oracle):
@@ -84,11 +79,11 @@ def test_seeded_fuzz(oracle):
 def test_engines_0_to_12_are_unchanged(oracle):
     for prob in (sl.mix_problem(*sl.MIX[0][:2]), sl.zonal_chain_problem()):
         for engine in ("auto", "auto-limits"):
-            c = sl.solve(prob, engine, None)["counters"]
+            c = ec.solve(prob, engine, None)["counters"]
             assert (c["engine"], c["engineFallbackReason"]) == ("general", 24), (engine, c)
         with pytest.raises(Unsupported, match=r"spread engine declined the problem \(reason 24\)"):
-            sl.solve(prob, "spread", None)
+            ec.solve(prob, "spread", None)
     prob = lc.cpu_chain_problem(True)
-    got = sl.solve(prob, "auto-limits-spread", None)
+    got = ec.solve(prob, "auto-limits-spread", None)
     assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0 and lc.stages(got) == (0, 5)
-    lc.same(got, oracle.solve(prob))
+    ec.same(got, oracle.solve(prob), prob)

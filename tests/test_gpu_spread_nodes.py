@@ -2,6 +2,7 @@
 of tests/test_spread_engine_nodes.py that cross a 64-node block and a claim window, against the oracle."""
 import pytest
 
+import engine_checks as ec
 import parity
 import spread_node_cases as sn
 from karpenter_amd import fixtures as fx
@@ -46,4 +47,4 @@ def test_hundred_solves_one_digest(oracle):
     assert r["counters"]["engine"] == "spread" and r["counters"]["engineFallbackReason"] == 0 and len(digests) == 1
     assert sn.on_nodes(r) > 0
     assert digests == {parity.results_digest(oracle.solve(prob))[0]}
-    sn.same(r, oracle.solve(prob), prob)
+    ec.same(r, oracle.solve(prob), prob)

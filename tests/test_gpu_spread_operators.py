@@ -4,22 +4,16 @@ the product library through the C ABI against the oracle, on the problems of tes
 tests/test_spread_engine_operators.py runs on the emulation, at the same small shapes."""
 import pytest
 
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
 import spread_limit_cases as sl
 import spread_node_cases as sn
 import spread_operator_cases as so
+from gpu_support import built  # noqa: F401  (fixture)
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import device_available
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 def test_notin_on_the_spread_key(oracle):
@@ -36,8 +30,8 @@ def test_counted_but_not_narrowed(oracle):
     assert len(kept) == 3 and all(len(c["pods"]) == 1 for c in kept)
     assert so.pods_by_zone(got, so.spread_uids(prob)) == {"test-zone-1": 2, "test-zone-2": 2, "test-zone-3": 2}
     concrete = so.counted_problem("In")
-    other = so.solve(concrete, so.ONLY, None)
-    so.same(other, oracle.solve(concrete), concrete)
+    other = ec.solve(concrete, so.ONLY, None)
+    ec.same(other, oracle.solve(concrete), concrete)
     assert so.pods_by_zone(other, so.spread_uids(concrete)) == {"test-zone-1": 3, "test-zone-2": 3}
 
 
@@ -68,7 +62,7 @@ def test_does_not_exist_on_the_spread_key(oracle):
 def test_limit_stages(oracle):
     for prob, bare in ((so.limit_mix_problem(), sl.mix_problem(*sl.MIX[0][:2])), (so.limit_chain_problem(), sl.zonal_chain_problem())):
         got, want = so.check_engine(oracle, None, prob, 0)
-        assert sl.stages(got) == sl.stages(so.solve(bare, "auto-limits-spread", None)) and sl.stages(got)[1] is not None
+        assert sl.stages(got) == sl.stages(ec.solve(bare, "auto-limits-spread", None)) and sl.stages(got)[1] is not None
         assert all((fx.FAKE_INTEGER_LABEL, "Exists", 1, None) in so.complement_kinds(c) for c in got["newNodeClaims"])
     prob = so.limit_notin_problem()
     got, want = so.check_engine(oracle, None, prob, 3)
@@ -81,11 +75,11 @@ def test_existing_nodes(oracle):
     for prob in (so.nodes_mix_problem(), so.nodes_limit_problem()):
         want = oracle.solve(prob)
         assert not want["podErrors"] and sn.on_nodes(want) > 0
-        plain = so.solve(prob, "auto-nodes-spread", None)
+        plain = ec.solve(prob, "auto-nodes-spread", None)
         assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", 34), plain["counters"]
-        got = so.solve(prob, so.AUTO, None)
+        got = ec.solve(prob, so.AUTO, None)
         assert (got["counters"]["engine"], got["counters"]["engineFallbackReason"]) == ("spread", 0), got["counters"]
-        so.same(got, want, prob)
+        ec.same(got, want, prob)
         assert sn.on_nodes(got) == sn.on_nodes(want)
 
 
@@ -125,11 +119,11 @@ def test_old_settings_stay_as_they_are():
     for engine in ("auto", "auto-operators"):
         assert so.lone_cell(None, prob, engine)[:2] == ("general", 3)
     for engine in ("spread", "spread-limits"):
-        assert "spread engine declined the problem (reason 3)" in so.refusal(prob, engine, None)
+        assert "spread engine declined the problem (reason 3)" in ec.refusal(prob, engine, None)
     prob = so.bounds_problem()
     for engine in ("auto", "auto-operators"):
         assert so.lone_cell(None, prob, engine)[:2] == ("general", 0)
-    assert "spread engine requested for a problem outside its shape" in so.refusal(prob, "spread", None)
+    assert "spread engine requested for a problem outside its shape" in ec.refusal(prob, "spread", None)
 
 
 def test_seeded_fuzz(oracle):

@@ -5,11 +5,12 @@ tests/spread_unschedulable_cases.py — the ones tests/test_spread_engine_unsche
 shapes (tens of pods)."""
 import pytest
 
+import engine_checks as ec
 import limit_cases as lc
 import parity
 import spread_operator_cases as soc
 import spread_unschedulable_cases as suc
-from karpenter_amd.scheduling import device_available
+from gpu_support import built  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +18,6 @@ HAND = suc.hand_problems()
 FURTHER = suc.further_problems()
 NAMES = [name for name, _, _ in HAND] + [name for name, _ in FURTHER]
 PROBLEMS = dict([(name, prob) for name, prob, _ in HAND] + FURTHER)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def built():
-    import __graft_entry__
-    __graft_entry__.build()
-    assert device_available(), "GPU tests need a usable gfx950 device and karpenter_amd/libksolve.so (no CPU fallback)"
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -38,10 +32,10 @@ def test_hand_problem(oracle, name):
 
 def test_repeated_solves(oracle):
     for name in ("chain-nodes", "chain+limits"):
-        digests, last = suc.digests_of_repeated_solves(None, PROBLEMS[name], suc.ONLY, 20)
+        digests, last = ec.digests_of_repeated_solves(None, PROBLEMS[name], suc.ONLY, 20, "spread")
         assert len(digests) == 1, name
         want = oracle.solve(PROBLEMS[name])
-        suc.same(last, want)
+        ec.same(last, want, mode=ec.SETS)
         assert last["counters"]["pops"] == want["counters"]["pops"]
 
 
@@ -56,9 +50,9 @@ def test_the_device_counts_what_the_emulation_counts(oracle):
     """chain+tail40 — 138 pops, kept verdicts replayed and invalidated by the successes between them — on the device and on the
     host emulation of the same source: every counter both report agrees (pops, evaluations, windows read, limit stages)."""
     prob = PROBLEMS["chain+tail40"]
-    dev = suc.solve(prob, suc.ONLY, None)
-    emu = suc.solve(prob, suc.ONLY, parity.build_emu())
-    assert suc.where(dev) == suc.where(emu) == ("spread", 0)
+    dev = ec.solve(prob, suc.ONLY, None)
+    emu = ec.solve(prob, suc.ONLY, parity.build_emu())
+    assert ec.where(dev) == ec.where(emu) == ("spread", 0)
     assert parity.results_digest(dev)[0] == parity.results_digest(emu)[0]
     skip = {"cursorClaimStateInHBM", "cursorMemoryPlan", "cursorAttempts"}
     keys = [k for k, v in emu["counters"].items() if isinstance(v, (int, str, bool)) and k not in skip and not k.lower().endswith(("ms", "cycles", "seconds"))]

@@ -6,37 +6,18 @@ import random
 
 import pytest
 
+import engine_checks as ec
 import parity
+from engine_checks import same, solve
 from karpenter_amd import fixtures as fx
 from karpenter_amd.scheduling import NewScheduler, Unsupported, device_available
+from mix_cases import fuzz_problem, mix
 from test_device_algorithm import emu  # noqa: F401  (fixture)
-
-
-def solve(prob, engine, lib):
-    s = NewScheduler(dict(prob, options=dict(prob.get("options", {}), engine=engine)), solver_lib=lib)
-    try:
-        return s.Solve()
-    finally:
-        s.close()
-
-
-def same(got, want):
-    parity.assert_same_results(got, want)
-    assert got["counters"]["referenceBinEvaluations"] == want["counters"]["binEvaluations"]   # V
-    assert abs(got["packingCost"] - want["packingCost"]) < 1e-9 * max(1.0, want["packingCost"])
 
 
 def check_spread(oracle, lib, prob):
     """engine=spread must solve it (no fallback) and equal the oracle; so must auto (which has to pick it) and the general engine."""
-    want = oracle.solve(prob)
-    got = solve(prob, "spread", lib)
-    assert got["counters"]["engine"] == "spread", got["counters"]
-    same(got, want)
-    auto = solve(prob, "auto", lib)
-    assert auto["counters"]["engine"] == "spread", auto["counters"]
-    same(auto, want)
-    same(solve(prob, "general", lib), want)
-    return got, want
+    return ec.three_ways(oracle, lib, prob, "spread", mode=ec.STRICT)
 
 
 @pytest.mark.parametrize("pods,types,seed", [(300, 144, 1), (1500, 144, 5), (4000, 500, 42), (2500, 60, 9)])
@@ -51,73 +32,6 @@ def test_few_anti_affinity_pods_many_claims_without_one(oracle, emu):
     prob = fx.config3(pods=3000, n_types=20, seed=11, anti_affinity_pods=40)
     got, _ = check_spread(oracle, emu, prob)
     assert len(got["newNodeClaims"]) > 40
-
-
-def mix(rng, n, zones=("test-zone-1", "test-zone-2", "test-zone-3"), letters="abc", kinds=range(12), big=False, filters=False):
-    labels = [{"my-label": c} for c in letters]
-    cpus = [100, 250, 500, 1000, 1500] if not big else [1000, 2000, 4000]
-    res = lambda: {"cpu": f"{rng.choice(cpus)}m", "memory": f"{rng.choice([100, 256, 512, 1024])}Mi"}
-    pods = []
-    lonely = 0
-    for _ in range(n):
-        kind = rng.choice(list(kinds))
-        lab, sel = rng.choice(labels), rng.choice(labels)
-        kw = dict(labels=lab, requests=res())
-        if kind == 0:
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel, max_skew=rng.choice([1, 1, 2, 3]))]
-        elif kind == 1:
-            kw["topology_spread"] = [fx.spread(fx.HOSTNAME, sel, max_skew=rng.choice([1, 1, 2]))]
-        elif kind == 2:
-            kw["pod_requirements"] = [fx.affinity_term(fx.ZONE, lab if rng.random() < 0.8 else sel)]
-        elif kind == 3:
-            kw["pod_anti_requirements"] = [fx.affinity_term(fx.HOSTNAME, lab if rng.random() < 0.7 else sel)]
-        elif kind == 4:
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel), fx.spread(fx.HOSTNAME, sel, max_skew=2)]
-        elif kind == 5:
-            kw["node_selector"] = {fx.ZONE: rng.choice(zones)}
-            if filters and rng.random() < 0.5:
-                kw["topology_spread"] = [fx.spread(fx.CAPACITY_TYPE, sel)]
-        elif kind == 6:
-            kw["node_selector"] = {fx.CAPACITY_TYPE: rng.choice(["spot", "on-demand"])}
-            if filters:
-                kw["topology_spread"] = [fx.spread(fx.ZONE, sel, max_skew=rng.choice([1, 2]))]
-        elif kind == 7 and not filters:
-            kw["topology_spread"] = [fx.spread(fx.CAPACITY_TYPE, sel)]
-        elif kind == 8:    # two groups on dictionary keys: each narrows from the claim's own set (topology.go:226-250)
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel, max_skew=rng.choice([1, 2])), fx.spread(fx.CAPACITY_TYPE, sel)]
-        elif kind == 12:   # ... loose enough to be satisfiable together
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel, max_skew=3), fx.spread(fx.CAPACITY_TYPE, sel, max_skew=4)]
-        elif kind == 9:    # minDomains (topologygroup.go:318-320)
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel, min_domains=rng.choice([2, 3, 3, 5] if rng.random() < 0.1 else [2, 3]), max_skew=rng.choice([1, 2]))]
-        elif kind == 10 and lonely < 2:   # anti-affinity on a dictionary key: a pod blocks every zone it could land in — a few of them, pinned to a zone each
-            lonely += 1
-            kw["pod_anti_requirements"] = [fx.affinity_term(fx.ZONE, {"zone-lonely": "x"})]
-            kw["labels"] = dict(lab, **{"zone-lonely": "x"})
-            kw["node_selector"] = {fx.ZONE: zones[lonely]}
-        elif kind == 11:   # spread and affinity on the same key
-            kw["topology_spread"] = [fx.spread(fx.ZONE, sel, max_skew=2)]
-            kw["pod_requirements"] = [fx.affinity_term(fx.ZONE, lab)]
-        pods.append(fx.pod(**kw))
-    return pods
-
-
-def fuzz_problem(seed):
-    rng = random.Random(7000 + seed)
-    kwok = seed % 2 == 0
-    zones = tuple(fx.KWOK_ZONES[:3]) if kwok else ("test-zone-1", "test-zone-2", "test-zone-3")
-    # (three seeds of four draw from the kinds that rarely leave a pod unschedulable — such a batch is the general engine's —, the fourth from all)
-    kinds = range(12) if seed % 4 == 3 else (0, 0, 1, 1, 2, 3, 4, 5, 6, 7, 9, 10, 12, 12)
-    pods = mix(rng, rng.randrange(30, 160), zones=zones, kinds=kinds, big=seed % 4 == 3, filters=seed % 8 == 7)
-    pools = [fx.node_pool()]
-    if seed % 3 == 1:
-        pools = [fx.node_pool("a", requirements=[fx.req(fx.ZONE, "In", *zones[:2])], weight=10), fx.node_pool("b")]
-    if seed % 5 == 2:
-        pools = [fx.node_pool("few", limits={"cpu": "20"}, weight=5), fx.node_pool("rest")]
-    if kwok:
-        for np_ in pools:
-            np_["nodeClassLabelKey"] = "karpenter.kwok.sh/kwoknodeclass"
-        return fx.problem(fx.kwok_catalog(24), pools, pods, well_known=fx.KWOK_WELL_KNOWN)
-    return fx.problem(fx.fake_instance_types(12), pools, pods)
 
 
 @pytest.mark.parametrize("seed", range(96))

@@ -3,6 +3,7 @@ five Record sites; csrc/topo_nodes.h topo_node_filter_cut; engines "auto-filters
 emulation of the device code (tests/emu, test infrastructure only), the real C ABI and the real flattener, against the oracle in
 claims, instance-type lists, claim requirements, pod assignment, pod errors, queue pops and the reference-equivalent evaluation count.
 The problems are tests/spread_filter_cases.py's; the device run is tests/test_gpu_spread_filters.py."""
+import engine_checks as ec
 import spread_filter_cases as sf
 import spread_limit_cases as sl
 import spread_node_cases as sn
@@ -112,7 +113,7 @@ def test_old_settings_stay_as_they_are(emu):
         for engine in ("auto", "auto-operators-spread", "auto-unschedulable-spread"):
             complement = engine == "auto" and so.has_non_in_pool(prob)
             assert sf.lone_cell(emu, prob, engine)[:2] == ("general", 3 if complement else 43), engine
-        assert "spread engine declined the problem (reason 43)" in sf.refusal(prob, "spread-unschedulable", emu)
+        assert "spread engine declined the problem (reason 43)" in ec.refusal(prob, "spread-unschedulable", emu)
     prob = so.node_filter_problem()
     positive = dict(prob, nodePools=[p for p in prob["nodePools"] if p["name"] == "open"])
     assert not so.has_non_in_pool(positive) and sf.lone_cell(emu, positive, "auto")[:2] == ("general", 43)

@@ -5,6 +5,7 @@ assignment and the reference-equivalent evaluation count. The problems are tests
 tests/test_gpu_spread_limits.py."""
 import pytest
 
+import engine_checks as ec
 import limit_cases as lc
 import spread_limit_cases as sl
 import spread_node_cases as sn
@@ -23,15 +24,15 @@ def test_node_limit(oracle, emu):
     got, want = sl.check_engine(oracle, emu, sl.mix_problem((300, 144, 1), {"nodes": "0"}))
     assert sl.pool_of(want) == ["open"] * 60
     assert sl.stages(got) == (0, None)
-    assert sl.solve(sl.mix_problem((300, 144, 1), {"nodes": "0"}), "auto", emu)["counters"]["engineFallbackReason"] == 23
+    assert ec.solve(sl.mix_problem((300, 144, 1), {"nodes": "0"}), "auto", emu)["counters"]["engineFallbackReason"] == 23
     # a limit that never binds: the spread engine under every setting, one digest
     loose = sl.mix_problem((300, 144, 1), {"nodes": "20"})
     want = oracle.solve(loose)
     digests = set()
     for engine in ("auto", "spread", "spread-limits", "auto-limits-spread"):
-        r = sl.solve(loose, engine, emu)
+        r = ec.solve(loose, engine, emu)
         assert r["counters"]["engine"] == "spread" and r["counters"]["engineFallbackReason"] == 0, (engine, r["counters"])
-        sl.same(r, want, loose)
+        ec.same(r, want, loose)
         digests.add(sl.parity.results_digest(r)[0])
     assert len(digests) == 1 and sl.stages(r) == (0, None)
 
@@ -68,12 +69,12 @@ def test_repeated_solves_on_one_handle(oracle, emu):
     prob = sl.zonal_chain_problem()
     digests, words, last = sl.repeated_solves(emu, prob, "auto-limits-spread", 100)
     assert len(digests) == 1 and words == {(0, 5)}
-    sl.same(last, oracle.solve(prob), prob)
+    ec.same(last, oracle.solve(prob), prob)
     # ... and with stages to forget
     prob = sl.stage_chain_problem(3)
     digests, words, last = sl.repeated_solves(emu, prob, "spread-limits", 20)
     assert len(digests) == 1 and {w[0] for w in words} == {21}
-    sl.same(last, oracle.solve(prob), prob)
+    ec.same(last, oracle.solve(prob), prob)
 
 
 def test_seeded_fuzz(oracle, emu):
@@ -85,11 +86,11 @@ def test_engines_0_to_12_are_unchanged(oracle, emu):
     names it; a topology-free problem under 13 runs on the cursor engine with its stages."""
     for prob in (sl.mix_problem(*sl.MIX[0][:2]), sl.zonal_chain_problem()):
         for engine in ("auto", "auto-limits"):
-            c = sl.solve(prob, engine, emu)["counters"]
+            c = ec.solve(prob, engine, emu)["counters"]
             assert (c["engine"], c["engineFallbackReason"]) == ("general", 24), (engine, c)
         with pytest.raises(Unsupported, match=r"spread engine declined the problem \(reason 24\)"):
-            sl.solve(prob, "spread", emu)
+            ec.solve(prob, "spread", emu)
     prob = lc.cpu_chain_problem(True)
-    got = sl.solve(prob, "auto-limits-spread", emu)
+    got = ec.solve(prob, "auto-limits-spread", emu)
     assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0 and lc.stages(got) == (0, 5)
-    lc.same(got, oracle.solve(prob))
+    ec.same(got, oracle.solve(prob), prob)

@@ -4,6 +4,7 @@ oracle claim by claim, node by node and in the reference-equivalent evaluation c
 tests/test_gpu_spread_nodes.py."""
 import pytest
 
+import engine_checks as ec
 import parity
 import spread_node_cases as sn
 from karpenter_amd import fixtures as fx
@@ -114,10 +115,10 @@ def test_two_passes_through_launch(oracle, emu):
 
 def _declined(oracle, emu, prob, reason):
     with pytest.raises(Unsupported, match="spread engine"):
-        sn.solve(prob, "spread-nodes", emu)
-    auto = sn.solve(prob, "auto-nodes-spread", emu)
+        ec.solve(prob, "spread-nodes", emu)
+    auto = ec.solve(prob, "auto-nodes-spread", emu)
     assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == reason, auto["counters"]
-    sn.same(auto, oracle.solve(prob), prob)
+    ec.same(auto, oracle.solve(prob), prob)
 
 
 TAINT = {"key": "dedicated", "value": "batch", "effect": "NoSchedule"}
@@ -153,30 +154,30 @@ def test_the_decline_mix(oracle, emu):
     prob = fx.with_existing_nodes(fx.config3(pods=2500, n_types=60, seed=9), 130, seed=3, fill=(0.5, 1.0))
     want = oracle.solve(prob)
     assert want["podErrors"] and sn.on_nodes(want) > 0
-    auto = sn.solve(prob, "auto-nodes-spread", emu)
+    auto = ec.solve(prob, "auto-nodes-spread", emu)
     assert auto["counters"]["engine"] == "general" and auto["counters"]["engineFallbackReason"] == 27
-    sn.same(auto, want, prob)
+    ec.same(auto, want, prob)
 
 
 def test_other_engines_are_unchanged(oracle, emu):
     prob = sn.block_edge_problem(5)
     with pytest.raises(Unsupported, match="spread engine"):                 # 6 still refuses a problem with nodes
-        sn.solve(prob, "spread", emu)
-    c = sn.solve(prob, "auto-nodes", emu)["counters"]                       # 7 still answers nodes + topology with general / 34
+        ec.solve(prob, "spread", emu)
+    c = ec.solve(prob, "auto-nodes", emu)["counters"]                       # 7 still answers nodes + topology with general / 34
     assert c["engine"] == "general" and c["engineFallbackReason"] == 34
-    assert sn.solve(prob, "auto", emu)["counters"]["engine"] == "general"
+    assert ec.solve(prob, "auto", emu)["counters"]["engine"] == "general"
     # nodes and no topology: the cursor engine with its node stage under 9, as under 7
     plain = fx.with_existing_nodes(fx.config2(pods=600, n_types=60, seed=4), 20, seed=3)
-    got = sn.solve(plain, "auto-nodes-spread", emu)
+    got = ec.solve(plain, "auto-nodes-spread", emu)
     assert got["counters"]["engine"] == "cursor" and got["counters"]["engineFallbackReason"] == 0 and sn.on_nodes(got) > 0
-    sn.same(got, oracle.solve(plain), plain)
+    ec.same(got, oracle.solve(plain), plain)
     with pytest.raises(Unsupported, match="spread engine"):
-        sn.solve(plain, "spread-nodes", emu)
+        ec.solve(plain, "spread-nodes", emu)
     # topology and no nodes: the kernel without the node path, the same counters as under 0 / 6
     topo = fx.config3(pods=600, n_types=60, seed=2)
     keys = ("binEvaluations", "slowSorts", "referenceBinEvaluations", "pops")
     for new, old in (("auto-nodes-spread", "auto"), ("spread-nodes", "spread")):
-        a, b = sn.solve(topo, new, emu), sn.solve(topo, old, emu)
+        a, b = ec.solve(topo, new, emu), ec.solve(topo, old, emu)
         assert a["counters"]["engine"] == b["counters"]["engine"] == "spread"
         assert [a["counters"][k] for k in keys] == [b["counters"][k] for k in keys]
         assert parity.results_digest(a)[0] == parity.results_digest(b)[0]
@@ -185,19 +186,19 @@ def test_other_engines_are_unchanged(oracle, emu):
 def test_step_limit(oracle, emu):
     """maxSteps (the ctx deadline's stand-in): a step is a queue pop, whether the pod lands on a node or on a NodeClaim."""
     prob = sn.mix_problem((1500, 144, 5), 40)
-    full = sn.solve(prob, "spread-nodes", emu)
+    full = ec.solve(prob, "spread-nodes", emu)
     assert 200 < sn.on_nodes(full) < 1400
     for steps in (1, 5, 63, 64, 65, 200, 777, 1499):     # (the queue's first pods land on nodes: the small limits lie inside a run of node placements)
         opts = dict(prob, options=dict(prob["options"], maxSteps=steps))
-        s, g = sn.solve(opts, "spread-nodes", emu), sn.solve(opts, "general", emu)
+        s, g = ec.solve(opts, "spread-nodes", emu), ec.solve(opts, "general", emu)
         assert s["counters"]["engine"] == "spread" and s["timedOut"] and g["timedOut"], steps
         parity.assert_same_results(s, g)
         assert s["scheduledPods"] == g["scheduledPods"] == steps and s["counters"]["pops"] == g["counters"]["pops"]
         assert s["counters"]["referenceBinEvaluations"] == g["counters"]["referenceBinEvaluations"]
-    assert sn.on_nodes(sn.solve(dict(prob, options=dict(prob["options"], maxSteps=5)), "spread-nodes", emu)) == 5
-    s = sn.solve(dict(prob, options=dict(prob["options"], maxSteps=1500)), "spread-nodes", emu)
+    assert sn.on_nodes(ec.solve(dict(prob, options=dict(prob["options"], maxSteps=5)), "spread-nodes", emu)) == 5
+    s = ec.solve(dict(prob, options=dict(prob["options"], maxSteps=1500)), "spread-nodes", emu)
     assert not s["timedOut"]
-    sn.same(s, oracle.solve(prob), prob)
+    ec.same(s, oracle.solve(prob), prob)
 
 
 def test_repeated_solves_and_batches(oracle, emu):
@@ -210,7 +211,7 @@ def test_repeated_solves_and_batches(oracle, emu):
         digests.add(parity.results_digest(r)[0])
     s.close()
     assert len(digests) == 1
-    sn.same(r, oracle.solve(prob), prob)
+    ec.same(r, oracle.solve(prob), prob)
     # ksolve_solve_batch: nodes + topology and nodes only run alone through solve(), plain ones in the batched cursor kernel
     probs = [sn.mix_problem((300, 144, 1), 5), fx.with_existing_nodes(fx.config2(pods=800, n_types=60, seed=91), 30, seed=1),
              fx.config2(pods=800, n_types=60, seed=92), sn.block_edge_problem(65), fx.config2(pods=500, n_types=60, seed=93)]
@@ -220,8 +221,8 @@ def test_repeated_solves_and_batches(oracle, emu):
         got = SolveBatch(scheds)
         assert [g["counters"]["engine"] for g in got] == engines
         for g, p in zip(got, probs):
-            assert parity.results_digest(g)[0] == parity.results_digest(sn.solve(p, "auto-nodes-spread", emu))[0]
-            sn.same(g, oracle.solve(p), p)
+            assert parity.results_digest(g)[0] == parity.results_digest(ec.solve(p, "auto-nodes-spread", emu))[0]
+            ec.same(g, oracle.solve(p), p)
             assert (sn.on_nodes(g) > 0) == bool(p["stateNodes"])
     for s in scheds:
         s.close()

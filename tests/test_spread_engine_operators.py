@@ -3,6 +3,7 @@ csrc/fast_engine.h FastCold::setup, the records of ksolve_fast_records; engines 
 the host emulation of the device code (tests/emu, test infrastructure only), the real C ABI and the real flattener, against the
 oracle in claims, instance-type lists, claim requirements, pod assignment and the reference-equivalent evaluation count. The problems
 are tests/spread_operator_cases.py's; the device run is tests/test_gpu_spread_operators.py."""
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
 import spread_limit_cases as sl
@@ -36,7 +37,7 @@ def test_counted_but_not_narrowed(oracle, emu):
     other = oracle.solve(concrete)
     assert not other["podErrors"]
     assert so.pods_by_zone(other, so.spread_uids(concrete)) == {"test-zone-1": 3, "test-zone-2": 3}   # the comparison pins the guard-bit rule only because the two differ
-    so.same(so.solve(concrete, so.ONLY, emu), other, concrete)
+    ec.same(ec.solve(concrete, so.ONLY, emu), other, concrete)
 
 
 def test_bounds(oracle, emu):
@@ -78,7 +79,7 @@ def test_limit_stages(oracle, emu):
     Gt 0; so.limit_notin_problem() is the case whose stage claims print NotIn itself."""
     for prob, bare in ((so.limit_mix_problem(), sl.mix_problem(*sl.MIX[0][:2])), (so.limit_chain_problem(), sl.zonal_chain_problem())):
         got, want = so.check_engine(oracle, emu, prob, 0)
-        assert sl.stages(got) == sl.stages(so.solve(bare, "auto-limits-spread", emu)) and sl.stages(got)[1] is not None   # (a limit bound)
+        assert sl.stages(got) == sl.stages(ec.solve(bare, "auto-limits-spread", emu)) and sl.stages(got)[1] is not None   # (a limit bound)
         assert all((fx.FAKE_INTEGER_LABEL, "Exists", 1, None) in so.complement_kinds(c) for c in got["newNodeClaims"])
     chain = so.claims_of(got, "second")
     assert chain and all(so.zone_of(c)[0] == "In" for c in chain)
@@ -95,11 +96,11 @@ def test_existing_nodes(oracle, emu):
     for prob in (so.nodes_mix_problem(), so.nodes_limit_problem()):
         want = oracle.solve(prob)
         assert not want["podErrors"] and sn.on_nodes(want) > 0
-        plain = so.solve(prob, "auto-nodes-spread", emu)
+        plain = ec.solve(prob, "auto-nodes-spread", emu)
         assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", 34), plain["counters"]
-        got = so.solve(prob, so.AUTO, emu)
+        got = ec.solve(prob, so.AUTO, emu)
         assert (got["counters"]["engine"], got["counters"]["engineFallbackReason"]) == ("spread", 0), got["counters"]
-        so.same(got, want, prob)
+        ec.same(got, want, prob)
         assert sn.on_nodes(got) == sn.on_nodes(want)
 
 
@@ -139,13 +140,13 @@ def test_old_settings_stay_as_they_are(emu):
     for engine in ("auto", "auto-operators"):
         assert so.lone_cell(emu, prob, engine)[:2] == ("general", 3)
     for engine in ("spread", "spread-limits"):
-        assert "spread engine declined the problem (reason 3)" in so.refusal(prob, engine, emu)
+        assert "spread engine declined the problem (reason 3)" in ec.refusal(prob, engine, emu)
     prob = so.bounds_problem()
     for engine in ("auto", "auto-nodes-spread", "auto-limits-spread", "auto-operators"):
         assert so.lone_cell(emu, prob, engine)[:2] == ("general", 0)
-    assert "spread engine requested for a problem outside its shape" in so.refusal(prob, "spread", emu)
+    assert "spread engine requested for a problem outside its shape" in ec.refusal(prob, "spread", emu)
     # ... and 17 is still the cursor engine alone, without a name: the new names do not decode to it
-    assert "cursor engine requested for a problem outside its shape" in so.refusal(oc.spread_problem(), 17, emu)
+    assert "cursor engine requested for a problem outside its shape" in ec.refusal(oc.spread_problem(), 17, emu)
 
 
 def test_seeded_fuzz(oracle, emu):

@@ -9,6 +9,8 @@ import os
 
 import pytest
 
+import engine_checks as ec
+import mix_cases
 import parity
 import spread_limit_cases as slc
 import spread_unschedulable_cases as suc
@@ -59,10 +61,10 @@ def test_error_changes_at_the_retry(oracle, emu, wanted):
     and with Limits (7) at its second, once the pool has run into its limit: the reported error is that of the LAST attempt."""
     prob = PROBLEMS["limits"]
     big = next(p["uid"] for p in prob["pods"] if p["requests"]["cpu"] == "100")
-    early = suc.solve(dict(prob, options=dict(prob.get("options", {}), maxSteps=1)), suc.ONLY, emu)
-    assert suc.where(early) == ("spread", 0), early["counters"]
+    early = ec.solve(dict(prob, options=dict(prob.get("options", {}), maxSteps=1)), suc.ONLY, emu)
+    assert ec.where(early) == ("spread", 0), early["counters"]
     assert early["timedOut"] and (early["podErrors"][big]["code"], early["podErrors"][big]["diag"]) == (4, 21)
-    got = suc.solve(prob, suc.ONLY, emu)
+    got = ec.solve(prob, suc.ONLY, emu)
     assert (got["podErrors"][big]["code"], got["podErrors"][big]["diag"]) == (7, 0)
     assert (wanted["limits"]["podErrors"][big]["code"], wanted["limits"]["podErrors"][big]["diag"]) == (7, 0)
 
@@ -72,9 +74,9 @@ def test_step_limit_inside_the_second_round(emu):
     engine stopped at the same step in claims, assignments and pod errors."""
     prob = PROBLEMS["chain+web"]
     limited = dict(prob, options=dict(prob.get("options", {}), maxSteps=14))
-    s = suc.solve(limited, suc.ONLY, emu)
-    g = suc.solve(limited, "general", emu)
-    assert suc.where(s) == ("spread", 0), s["counters"]
+    s = ec.solve(limited, suc.ONLY, emu)
+    g = ec.solve(limited, "general", emu)
+    assert ec.where(s) == ("spread", 0), s["counters"]
     assert s["timedOut"] and g["timedOut"]
     parity.assert_same_results(s, g)
     assert s["counters"]["pops"] == g["counters"]["pops"] == 14
@@ -84,9 +86,9 @@ def test_step_limit_inside_the_second_round(emu):
 def test_repeated_solves(emu, wanted):
     """Twenty solves of one handle: the set-aside list and the kept verdicts start empty every time."""
     for name in ("chain-nodes", "chain+limits"):
-        digests, last = suc.digests_of_repeated_solves(emu, PROBLEMS[name], suc.ONLY, 20)
+        digests, last = ec.digests_of_repeated_solves(emu, PROBLEMS[name], suc.ONLY, 20, "spread")
         assert len(digests) == 1, name
-        suc.same(last, wanted[name])
+        ec.same(last, wanted[name], mode=ec.SETS)
         assert last["counters"]["pops"] == wanted[name]["counters"]["pops"]
 
 
@@ -102,13 +104,12 @@ def test_seeded_fuzz(oracle, emu, family):
 
 
 def test_the_unschedulable_fuzz_seed_ends_on_the_spread_engine(oracle, emu):
-    import test_spread_engine as tse
-    prob = tse.fuzz_problem(slc.FUZZ_UNSCHEDULABLE[0])
+    prob = mix_cases.fuzz_problem(slc.FUZZ_UNSCHEDULABLE[0])
     want = oracle.solve(prob)
     assert len(want["podErrors"]) == 1
-    got = suc.solve(prob, suc.AUTO, emu)
-    assert suc.where(got) == ("spread", 0), got["counters"]
-    suc.same(got, want)
+    got = ec.solve(prob, suc.AUTO, emu)
+    assert ec.where(got) == ("spread", 0), got["counters"]
+    ec.same(got, want, mode=ec.SETS)
     assert got["counters"]["pops"] == want["counters"]["pops"]
 
 
@@ -137,7 +138,7 @@ def test_the_cursor_engine_under_22_behaves_as_under_20(oracle, emu):
     cursor engine, with the digest 20 gives."""
     import unschedulable_cases as uc
     for prob in (uc.tail_run_problem(), uc.error_changes_problem()):
-        a, b = suc.solve(prob, suc.BASE, emu), suc.solve(prob, suc.AUTO, emu)
-        assert suc.where(a) == suc.where(b) == ("cursor", 0)
+        a, b = ec.solve(prob, suc.BASE, emu), ec.solve(prob, suc.AUTO, emu)
+        assert ec.where(a) == ec.where(b) == ("cursor", 0)
         assert parity.results_digest(a)[0] == parity.results_digest(b)[0]
         assert a["counters"]["pops"] == b["counters"]["pops"]

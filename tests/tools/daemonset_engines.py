@@ -6,14 +6,10 @@ The problems come from this file's own tree; --tree DIR solves them with the kar
 that predates fixtures.with_daemonsets), so that two commits are timed on identical inputs.
 usage: python tests/tools/daemonset_engines.py [--pods N] [--types N] [--kind a|b|c] [--repeats N] [--tree DIR] [--skip-general]"""
 import argparse
-import importlib.util
 import json
 import os
-import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def main():
@@ -22,34 +18,21 @@ def main():
     ap.add_argument("--types", type=int, default=500)
     ap.add_argument("--kind", default="c")
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--tree", default=et.ROOT)
     ap.add_argument("--skip-general", action="store_true")
     args = ap.parse_args()
-    spec = importlib.util.spec_from_file_location("daemonset_fixtures", os.path.join(ROOT, "karpenter_amd", "fixtures.py"))
-    fx = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fx)
+    fx = et.own_fixtures("daemonset_fixtures")
     tree = os.path.abspath(args.tree)
-    sys.path.insert(0, tree)
-    sys.path.insert(0, os.path.join(tree, "tests"))
+    et.use_tree(tree)
     import parity
-    from karpenter_amd.scheduling import NewScheduler
-    out = {"tool": "daemonset_engines", "tree": os.path.relpath(tree, ROOT), "pods": args.pods, "types": args.types, "kind": args.kind, "legs": {}}
+    out = {"tool": "daemonset_engines", "tree": os.path.relpath(tree, et.ROOT), "pods": args.pods, "types": args.types, "kind": args.kind, "legs": {}}
     shapes = {"config2": fx.config2(pods=args.pods, n_types=args.types, seed=42), "config3": fx.config3(pods=args.pods, n_types=args.types, seed=42)}
     for shape, base in shapes.items():
         legs = [("daemonsets_auto", fx.with_daemonsets(base, args.kind), "auto"), ("plain_auto", base, "auto")]
         if not args.skip_general:
             legs.insert(1, ("daemonsets_general", fx.with_daemonsets(base, args.kind), "general"))
         for leg, prob, engine in legs:
-            s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-            s.Solve(want_results=False)
-            times, kernel = [], []
-            for _ in range(args.repeats):
-                t = time.perf_counter()
-                r = s.Solve(want_results=False)
-                times.append(time.perf_counter() - t)
-                kernel.append(r["timings"][0]["pack_kernel_ms"])
-            r = s.Solve()
-            s.close()
+            r, times, kernel = et.timed_on_one_handle(prob, engine, args.repeats)
             out["legs"][f"{shape}.{leg}"] = {"engine": r["counters"]["engine"], "engineFallbackReason": r["counters"]["engineFallbackReason"], "claims": r["counters"]["claims"],
                                             "pack_kernel_ms": [round(k, 3) for k in kernel], "solve_s": [round(x, 4) for x in times],
                                             "results_digest": parity.results_digest(r)[0]}

@@ -13,13 +13,8 @@ usage: python tests/tools/limits_engines.py [--pods N] [--types N] [--repeats N]
 import argparse
 import copy
 import json
-import os
-import statistics
-import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def main():
@@ -30,23 +25,10 @@ def main():
     ap.add_argument("--engines", default="auto,general,auto-limits")
     ap.add_argument("--oracle", action="store_true")
     args = ap.parse_args()
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
 
     base = fx.config2(pods=args.pods, n_types=args.types, seed=42)
-    free, _ = solve_fresh(base, "auto", True)
+    free, _ = et.solve_fresh(base, "auto", True)
     heavy = max(base["nodePools"], key=lambda p: p["weight"])["name"]
     n_heavy = sum(1 for c in free["newNodeClaims"] if c["nodePool"] == heavy)
     top_cpu = max(fx.quantity_float(it["capacity"]["cpu"]) for it in base["instanceTypes"])
@@ -57,22 +39,11 @@ def main():
             p["limits"] = {"cpu": str(limit)}
     out = {"tool": "limits_engines", "pods": args.pods, "types": args.types, "limitedPool": heavy, "limitCpu": limit,
            "claimsWithoutLimits": {"all": len(free["newNodeClaims"]), heavy: n_heavy}, "engines": {}}
-    want = None
-    if args.oracle:
-        import oracle
-        want = parity.results_digest(oracle.solve(prob))[0]
+    want = et.oracle_digest(prob) if args.oracle else None
     for engine in args.engines.split(","):
-        solve_fresh(prob, engine, False)   # warm-up
-        times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-        r, _ = solve_fresh(prob, engine, True)
+        r, _, leg = et.timed_leg(prob, engine, args.repeats, pods=args.pods)
         c = r["counters"]
-        med = statistics.median(times)
-        pools = {}
-        for cl in r["newNodeClaims"]:
-            pools[cl["nodePool"]] = pools.get(cl["nodePool"], 0) + 1
-        leg = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "claimsByPool": pools, "podErrors": len(r["podErrors"]),
-               "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "pods_per_s": round(args.pods / med),
-               "results_digest": parity.results_digest(r)[0]}
+        leg.update(claimsByPool=et.claims_by_pool(r), podErrors=len(r["podErrors"]))
         if engine in ("auto-limits", "cursor-limits") and c["engine"] == "cursor":
             v = c["phaseCycles"][23] & 0xFFFFFFFFFFFFFFFF   # stages | rows of class slots << 16 | claims at the first exclusion << 32
             leg["limitStages"] = v & 0xFFFF
@@ -81,11 +52,11 @@ def main():
             leg["equals_oracle"] = leg["results_digest"] == want
         out["engines"][engine] = leg
     legs = out["engines"]
-    out["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
+    out["digests_agree"] = et.digests_agree(legs)
     if "auto" in legs and "auto-limits" in legs:
-        out["auto_over_auto_limits"] = round(legs["auto"]["median_s"] / legs["auto-limits"]["median_s"], 2)
+        out["auto_over_auto_limits"] = et.over(legs, "auto", "auto-limits")
     if "general" in legs and "auto-limits" in legs:
-        out["general_over_auto_limits"] = round(legs["general"]["median_s"] / legs["auto-limits"]["median_s"], 2)
+        out["general_over_auto_limits"] = et.over(legs, "general", "auto-limits")
     print(json.dumps(out), flush=True)
 
 

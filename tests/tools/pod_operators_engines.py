@@ -10,13 +10,8 @@ agree (with --oracle: and equal the oracle's).
 usage: python tests/tools/pod_operators_engines.py [--pods 20000,100000] [--types N] [--repeats N] [--engines a,b] [--oracle]"""
 import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def workload(fx, pods, types):
@@ -48,51 +43,28 @@ def main():
     ap.add_argument("--engines", default="auto-filters-spread,auto-pod-operators")
     ap.add_argument("--oracle", action="store_true")
     args = ap.parse_args()
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
 
     out = {"tool": "pod_operators_engines", "types": args.types, "podRequirements": ["zone NotIn [one zone] on every third pod group", "capacity-type NotIn [spot] on every eighteenth"], "sizes": {}}
     for pods in [int(x) for x in args.pods.split(",")]:
         prob, f_zone, f_ct = workload(fx, pods, args.types)
         size = {"podsWithZoneNotIn": round(f_zone, 3), "podsWithCapacityTypeNotIn": round(f_ct, 3), "engines": {}}
-        want = None
-        if args.oracle:
-            import oracle
-            want = parity.results_digest(oracle.solve(prob))[0]
+        want = et.oracle_digest(prob) if args.oracle else None
         for engine in args.engines.split(","):
-            solve_fresh(prob, engine, False)   # warm-up
-            times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-            r, _ = solve_fresh(prob, engine, True)
-            c = r["counters"]
-            med = statistics.median(times)
-            pools, zone_reqs = {}, {}
+            r, times, leg = et.timed_leg(prob, engine, args.repeats, pods=pods)
+            zone_reqs = {}
             for cl in r["newNodeClaims"]:
-                pools[cl["nodePool"]] = pools.get(cl["nodePool"], 0) + 1
                 q = next((q for q in cl["requirements"] if q["key"] == fx.ZONE), None)
                 k = "none" if q is None else f"{q['operator']} x{len(q['values'])}"
                 zone_reqs[k] = zone_reqs.get(k, 0) + 1
-            leg = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "claimsByPool": pools, "zoneRequirements": zone_reqs,
-                   "podErrors": len(r["podErrors"]), "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "min_s": round(min(times), 4), "max_s": round(max(times), 4),
-                   "pods_per_s": round(pods / med), "results_digest": parity.results_digest(r)[0]}
+            leg.update(claimsByPool=et.claims_by_pool(r), zoneRequirements=zone_reqs, podErrors=len(r["podErrors"]), min_s=round(min(times), 4), max_s=round(max(times), 4))
             if want is not None:
                 leg["equals_oracle"] = leg["results_digest"] == want
             size["engines"][engine] = leg
         legs = size["engines"]
-        size["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
+        size["digests_agree"] = et.digests_agree(legs)
         if "auto-filters-spread" in legs and "auto-pod-operators" in legs:
-            size["fallback_over_pod_operators"] = round(legs["auto-filters-spread"]["median_s"] / legs["auto-pod-operators"]["median_s"], 2)
+            size["fallback_over_pod_operators"] = et.over(legs, "auto-filters-spread", "auto-pod-operators")
         out["sizes"][str(pods)] = size
     print(json.dumps(out), flush=True)
 

@@ -12,13 +12,10 @@ usage: python tests/tools/spread_filters_engines.py [--pods 20000,100000] [--typ
 import argparse
 import copy
 import json
-import os
-import statistics
 import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
+
 ENGINES = ("auto-unschedulable-spread", "auto-filters-spread")
 
 
@@ -43,36 +40,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--variants", default="selectors,plain")
     args = ap.parse_args()
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
 
     out = {"tool": "spread_filters_engines", "types": args.types, "repeats": args.repeats, "cases": {}}
     for pods in [int(x) for x in args.pods.split(",")]:
         for name, prob in variants(fx, pods, args.types, args.variants.split(",")):
             case = {"pods": pods, "engines": {}}
             for engine in ENGINES:
-                solve_fresh(prob, engine, False)   # warm-up
-                times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-                r, _ = solve_fresh(prob, engine, True)
-                c = r["counters"]
-                case["engines"][engine] = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "pops": c["pops"],
-                                           "podErrors": len(r["podErrors"]), "solve_s": [round(x, 4) for x in times], "median_s": round(statistics.median(times), 4),
-                                           "results_digest": parity.results_digest(r)[0]}
+                r, _, leg = et.timed_leg(prob, engine, args.repeats)
+                leg.update(pops=r["counters"]["pops"], podErrors=len(r["podErrors"]))
+                case["engines"][engine] = leg
             legs = case["engines"]
-            case["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
-            case["base_over_filters"] = round(legs[ENGINES[0]]["median_s"] / legs[ENGINES[1]]["median_s"], 2)
+            case["digests_agree"] = et.digests_agree(legs)
+            case["base_over_filters"] = et.over(legs, *ENGINES)
             out["cases"][name] = case
             print(json.dumps({name: case}), file=sys.stderr, flush=True)
     print(json.dumps(out), flush=True)

@@ -16,12 +16,9 @@ usage: python tests/tools/spread_limits_engines.py [--sizes 20000,100000] [--typ
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def main():
@@ -30,64 +27,41 @@ def main():
     ap.add_argument("--types", type=int, default=500)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--engines", default="auto,general,spread-limits")
-    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--tree", default=et.ROOT)
     ap.add_argument("--oracle", action="store_true")
     args = ap.parse_args()
     tree = os.path.abspath(args.tree)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    sys.path.insert(0, tree)
-    import parity
-    from karpenter_amd.scheduling import NewScheduler
+    et.use_tree(tree)
     import spread_limit_cases as sl   # (this file's own tree has it, whichever package solves the problems)
     fx = sl.fx
 
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
-
     for pods in (int(x) for x in args.sizes.split(",")):
         cfg = (pods, args.types, 42)
-        free, _ = solve_fresh(sl.mix_problem(cfg, None), "auto", True)
+        free, _ = et.solve_fresh(sl.mix_problem(cfg, None), "auto", True)
         assert free["counters"]["engine"] == "spread", free["counters"]
         n_heavy = sum(1 for c in free["newNodeClaims"] if c["nodePool"] == "limited")
         top_cpu = max(fx.quantity_float(it["capacity"]["cpu"]) for it in fx.config3(pods=5, n_types=args.types, seed=42)["instanceTypes"])
         limit = int((max(1, n_heavy // 3) + 0.5) * top_cpu)   # (the half: one narrower list before the pool is used up)
         prob = sl.mix_problem(cfg, {"cpu": str(limit)})
-        out = {"tool": "spread_limits_engines", "tree": os.path.relpath(tree, ROOT), "pods": pods, "types": args.types, "limitCpu": limit,
+        out = {"tool": "spread_limits_engines", "tree": os.path.relpath(tree, et.ROOT), "pods": pods, "types": args.types, "limitCpu": limit,
                "claimsWithoutLimits": {"all": len(free["newNodeClaims"]), "limited": n_heavy}, "engines": {}}
-        want = None
-        if args.oracle:
-            import oracle
-            want = parity.results_digest(oracle.solve(prob))[0]
+        want = et.oracle_digest(prob) if args.oracle else None
         for engine in args.engines.split(","):
             print(f"{pods} pods, {engine}: solving", file=sys.stderr, flush=True)   # (progress, no figure: the JSON line comes last)
-            r, _ = solve_fresh(prob, engine, True)
-            times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-            c = r["counters"]
-            med = statistics.median(times)
-            pools = {}
-            for cl in r["newNodeClaims"]:
-                pools[cl["nodePool"]] = pools.get(cl["nodePool"], 0) + 1
-            leg = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "claimsByPool": pools, "podErrors": len(r["podErrors"]),
-                   "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "pods_per_s": round(pods / med), "results_digest": parity.results_digest(r)[0]}
-            if c["engine"] == "spread" and engine in ("spread-limits", "auto-limits-spread"):
+            r, _, leg = et.timed_leg(prob, engine, args.repeats, pods=pods)
+            leg.update(claimsByPool=et.claims_by_pool(r), podErrors=len(r["podErrors"]))
+            if leg["engine"] == "spread" and engine in ("spread-limits", "auto-limits-spread"):
                 leg["limitStages"], leg["claimsAtFirstExclusion"] = sl.stages(r)
             if want is not None:
                 leg["equals_oracle"] = leg["results_digest"] == want
             out["engines"][engine] = leg
         legs = out["engines"]
-        digests = {l["results_digest"] for l in legs.values()} | ({want} if want is not None else set())
-        assert len(digests) == 1, {e: l["results_digest"] for e, l in legs.items()}
+        assert et.digests_agree(legs, want), {e: l["results_digest"] for e, l in legs.items()}
         out["digests_agree"] = True
         if "auto" in legs and "spread-limits" in legs:
-            out["auto_over_spread_limits"] = round(legs["auto"]["median_s"] / legs["spread-limits"]["median_s"], 2)
+            out["auto_over_spread_limits"] = et.over(legs, "auto", "spread-limits")
         if "general" in legs and "spread-limits" in legs:
-            out["general_over_spread_limits"] = round(legs["general"]["median_s"] / legs["spread-limits"]["median_s"], 2)
+            out["general_over_spread_limits"] = et.over(legs, "general", "spread-limits")
         print(json.dumps(out), flush=True)
 
 

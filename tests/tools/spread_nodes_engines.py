@@ -9,15 +9,12 @@ The problem comes from this file's own tree; --tree DIR solves it with the karpe
 predates the node path: only --engines general works there), so that two commits are timed on identical inputs.
 usage: python tests/tools/spread_nodes_engines.py [--pods N] [--nodes N] [--types N] [--fill lo,hi] [--repeats N] [--engines a,b] [--tree DIR] [--oracle]"""
 import argparse
-import importlib.util
 import json
 import os
 import statistics
 import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def main():
@@ -28,39 +25,23 @@ def main():
     ap.add_argument("--fill", default="0.2,0.9", help="lo,hi: how full the existing nodes are (fixtures.with_existing_nodes)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--engines", default="general,auto-nodes-spread,spread-nodes")
-    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--tree", default=et.ROOT)
     ap.add_argument("--oracle", action="store_true")
     args = ap.parse_args()
-    spec = importlib.util.spec_from_file_location("spread_nodes_fixtures", os.path.join(ROOT, "karpenter_amd", "fixtures.py"))
-    fx = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fx)
+    fx = et.own_fixtures("spread_nodes_fixtures")
     tree = os.path.abspath(args.tree)
-    sys.path.insert(0, tree)
-    sys.path.insert(0, os.path.join(tree, "tests"))
+    et.use_tree(tree)
     import parity
-    from karpenter_amd.scheduling import NewScheduler, Unsupported
+    from karpenter_amd.scheduling import Unsupported
     prob = fx.with_daemonsets(fx.with_existing_nodes(fx.config3(pods=args.pods, n_types=args.types), args.nodes, seed=3, fill=tuple(float(x) for x in args.fill.split(","))), "c")
-    out = {"tool": "spread_nodes_engines", "tree": os.path.relpath(tree, ROOT), "pods": args.pods, "nodes": args.nodes, "fill": args.fill, "types": args.types, "engines": {}}
-    want = None
-    if args.oracle:
-        import oracle
-        want = parity.results_digest(oracle.solve(prob))[0]
+    out = {"tool": "spread_nodes_engines", "tree": os.path.relpath(tree, et.ROOT), "pods": args.pods, "nodes": args.nodes, "fill": args.fill, "types": args.types, "engines": {}}
+    want = et.oracle_digest(prob) if args.oracle else None
     for engine in args.engines.split(","):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
         try:
-            s.Solve(want_results=False)
+            r, times, kernel = et.timed_on_one_handle(prob, engine, args.repeats)
         except Unsupported as e:   # "spread-nodes" refuses what "auto-nodes-spread" hands to the general engine
-            s.close()
             out["engines"][engine] = {"refused": str(e)}
             continue
-        times, kernel = [], []
-        for _ in range(args.repeats):
-            t = time.perf_counter()
-            r = s.Solve(want_results=False)
-            times.append(time.perf_counter() - t)
-            kernel.append(r["timings"][0]["pack_kernel_ms"])
-        r = s.Solve()
-        s.close()
         print(f"{engine}: {[round(x, 3) for x in times]} s", file=sys.stderr, flush=True)   # (progress: the JSON line comes last)
         c = r["counters"]
         leg_errors = len(r["podErrors"])

@@ -10,13 +10,9 @@ and the digest; then the ratio of the two medians. No ratio is asserted.
 usage: python tests/tools/spread_operators_engines.py [--sizes 20000,100000] [--types N] [--repeats N] [--engines a,b] [--oracle]"""
 import argparse
 import json
-import os
-import statistics
 import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
 
 
 def problem(fx, pods, types):
@@ -35,47 +31,25 @@ def main():
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--solver-lib", default=None, help="a test build of the solver library (the host emulation), to try the tool without a device")
     args = ap.parse_args()
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    sys.path.insert(0, ROOT)
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)), solver_lib=args.solver_lib)
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
 
     for pods in (int(x) for x in args.sizes.split(",")):
         prob = problem(fx, pods, args.types)
         out = {"tool": "spread_operators_engines", "pods": pods, "types": args.types, "engines": {}}
-        want = None
-        if args.oracle:
-            import oracle
-            want = parity.results_digest(oracle.solve(prob))[0]
+        want = et.oracle_digest(prob) if args.oracle else None
         for engine in args.engines.split(","):
             print(f"{pods} pods, {engine}: solving", file=sys.stderr, flush=True)   # (progress, no figure: the JSON line comes last)
-            r, _ = solve_fresh(prob, engine, True)
-            times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-            c = r["counters"]
-            med = statistics.median(times)
+            r, _, leg = et.timed_leg(prob, engine, args.repeats, pods=pods, solver_lib=args.solver_lib)
             kept = sum(1 for cl in r["newNodeClaims"] if any(q["complement"] for q in cl["requirements"]))
-            leg = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "claimsWithAComplementRequirement": kept,
-                   "podErrors": len(r["podErrors"]), "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "pods_per_s": round(pods / med),
-                   "results_digest": parity.results_digest(r)[0]}
+            leg.update(claimsWithAComplementRequirement=kept, podErrors=len(r["podErrors"]))
             if want is not None:
                 leg["equals_oracle"] = leg["results_digest"] == want
             out["engines"][engine] = leg
         legs = out["engines"]
-        digests = {l["results_digest"] for l in legs.values()} | ({want} if want is not None else set())
-        assert len(digests) == 1, {e: l["results_digest"] for e, l in legs.items()}
+        assert et.digests_agree(legs, want), {e: l["results_digest"] for e, l in legs.items()}
         out["digests_agree"] = True
         if "auto-operators" in legs and "auto-operators-spread" in legs:
-            out["auto_operators_over_auto_operators_spread"] = round(legs["auto-operators"]["median_s"] / legs["auto-operators-spread"]["median_s"], 2)
+            out["auto_operators_over_auto_operators_spread"] = et.over(legs, "auto-operators", "auto-operators-spread")
         print(json.dumps(out), flush=True)
 
 

@@ -18,15 +18,14 @@ import argparse
 import json
 import os
 import re
-import statistics
 import subprocess
 import sys
 import tempfile
-import time
 from collections import Counter
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
+
+ROOT = et.ROOT
 ENGINES = ("auto-unschedulable", "auto-unschedulable-spread")
 PARENT_CASES = ["spread+big", "chain", "limits"]
 GOLDEN = os.path.join(ROOT, "tests", "golden", "spread_unschedulable_parent.json")
@@ -123,38 +122,19 @@ def main():
     args = ap.parse_args()
     if args.record_parent:
         return record_parent(args.record_parent)
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
-
     out = {"tool": "spread_unschedulable_engines", "types": args.types, "repeats": args.repeats, "cases": {}}
     for pods in [int(x) for x in args.pods.split(",")]:
         for name, prob in variants(fx, pods, args.types, args.variants.split(",")):
             case = {"pods": pods, "engines": {}}
             for engine in ENGINES:
-                solve_fresh(prob, engine, False)   # warm-up
-                times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-                r, _ = solve_fresh(prob, engine, True)
-                c = r["counters"]
-                med = statistics.median(times)
-                case["engines"][engine] = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "pops": c["pops"],
-                                           "podErrors": {str(k): v for k, v in sorted(Counter(e["code"] for e in r["podErrors"].values()).items())},
-                                           "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "results_digest": parity.results_digest(r)[0]}
+                r, _, leg = et.timed_leg(prob, engine, args.repeats)
+                leg.update(pops=r["counters"]["pops"], podErrors={str(k): v for k, v in sorted(Counter(e["code"] for e in r["podErrors"].values()).items())})
+                case["engines"][engine] = leg
             legs = case["engines"]
-            case["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
+            case["digests_agree"] = et.digests_agree(legs)
             case["pops_agree"] = len({l["pops"] for l in legs.values()}) == 1
-            case["base_over_spread_unschedulable"] = round(legs[ENGINES[0]]["median_s"] / legs[ENGINES[1]]["median_s"], 2)
+            case["base_over_spread_unschedulable"] = et.over(legs, *ENGINES)
             out["cases"][name] = case
             print(json.dumps({name: case}), file=sys.stderr, flush=True)
     print(json.dumps(out), flush=True)

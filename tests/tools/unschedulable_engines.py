@@ -11,14 +11,11 @@ each solve and their median, the Results digest; whether the digests of a case a
 usage: python tests/tools/unschedulable_engines.py [--pods 20000,100000] [--types N] [--repeats N]"""
 import argparse
 import json
-import os
-import statistics
 import sys
-import time
 from collections import Counter
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import engine_timing as et
+
 ENGINES = ("auto-operators-spread", "auto-unschedulable")
 
 
@@ -28,20 +25,7 @@ def main():
     ap.add_argument("--types", type=int, default=500)
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
     from karpenter_amd import fixtures as fx
-    from karpenter_amd.scheduling import NewScheduler
-
-    def solve_fresh(prob, engine, want_results):
-        s = NewScheduler(dict(prob, options=dict(prob["options"], engine=engine)))
-        try:
-            t = time.perf_counter()
-            r = s.Solve(want_results=want_results)
-            return r, time.perf_counter() - t
-        finally:
-            s.close()
 
     cases = []
     for pods in [int(x) for x in args.pods.split(",")]:
@@ -62,18 +46,12 @@ def main():
     for name, pods, prob in cases:
         case = {"pods": pods, "engines": {}}
         for engine in ENGINES:
-            solve_fresh(prob, engine, False)   # warm-up
-            times = [solve_fresh(prob, engine, False)[1] for _ in range(args.repeats)]
-            r, _ = solve_fresh(prob, engine, True)
-            c = r["counters"]
-            med = statistics.median(times)
-            case["engines"][engine] = {"engine": c["engine"], "engineFallbackReason": c["engineFallbackReason"], "claims": c["claims"], "pops": c["pops"],
-                                       "podErrors": {str(k): v for k, v in sorted(Counter(e["code"] for e in r["podErrors"].values()).items())},
-                                       "solve_s": [round(x, 4) for x in times], "median_s": round(med, 4), "pods_per_s": round(pods / med),
-                                       "results_digest": parity.results_digest(r)[0]}
+            r, _, leg = et.timed_leg(prob, engine, args.repeats, pods=pods)
+            leg.update(pops=r["counters"]["pops"], podErrors={str(k): v for k, v in sorted(Counter(e["code"] for e in r["podErrors"].values()).items())})
+            case["engines"][engine] = leg
         legs = case["engines"]
-        case["digests_agree"] = len({l["results_digest"] for l in legs.values()}) == 1
-        case["base_over_unschedulable"] = round(legs[ENGINES[0]]["median_s"] / legs[ENGINES[1]]["median_s"], 2)
+        case["digests_agree"] = et.digests_agree(legs)
+        case["base_over_unschedulable"] = et.over(legs, *ENGINES)
         out["cases"][name] = case
     print(json.dumps(out), flush=True)
     return 0 if all(c["digests_agree"] for c in out["cases"].values()) else 1

@@ -13,18 +13,19 @@ import os
 import sys
 from collections import Counter
 
-import daemonset_cases as dc
+import engine_checks as ec
 import limit_cases as lc
 import operator_cases as oc
-import parity
 from karpenter_amd import fixtures as fx
-from karpenter_amd.scheduling import Unsupported
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import engine_matrix  # noqa: E402
 
-same, solve = dc.same, dc.solve
-BASE = "auto-operators-spread"   # 18: every switch but the one under test
+# 20, 21 over 18 / 16 (every switch but the one under test): what every setting up to 19 does is to decline with reason 27. The
+# oracle leaves pods unschedulable; queue pops are compared.
+SWITCH = ec.Switch("cursor", only="cursor-unschedulable", auto="auto-unschedulable", base="auto-operators-spread", base_only="cursor-operators",
+                   reasons=(27,), errors=True, pops=True)
+BASE = SWITCH.base
 ABSENT = "test-zone-9"
 
 
@@ -38,41 +39,15 @@ def errors_of(res):
 
 
 def check_engine(oracle, lib, prob, base=BASE):
-    """One problem five ways. The oracle leaves pods unschedulable. `base` (18) ends on the general engine with reason 27 and equals
-    the oracle: what every setting up to 19 does; "cursor-operators" refuses and names 27. "cursor-unschedulable" and
-    "auto-unschedulable" end on the cursor engine — no fallback, reason 0 — and equal the oracle in claims and their order, hostnames,
-    pod errors with their flags, the reference-equivalent evaluation count (dc.same) and queue pops; the two give one digest."""
-    want = oracle.solve(prob)
-    assert want["podErrors"], "the oracle schedules every pod of this problem"
-    plain = solve(prob, base, lib)
-    assert (plain["counters"]["engine"], plain["counters"]["engineFallbackReason"]) == ("general", 27), plain["counters"]
-    same(plain, want)
-    oc.refuses(prob, "cursor-operators", lib, 27)
-    out = []
-    for engine in ("cursor-unschedulable", "auto-unschedulable"):
-        got = solve(prob, engine, lib)
-        assert (got["counters"]["engine"], got["counters"]["engineFallbackReason"]) == ("cursor", 0), (engine, got["counters"])
-        same(got, want)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (engine, got["counters"]["pops"], want["counters"]["pops"])
-        out.append(got)
-    assert parity.results_digest(out[0])[0] == parity.results_digest(out[1])[0]
-    return out[0], want
+    """One problem five ways (SWITCH.check), in claims and their order, hostnames, pod errors with their flags, the
+    reference-equivalent evaluation count and queue pops."""
+    return SWITCH.check(oracle, lib, prob, base=base)
 
 
 def check_declined(oracle, lib, prob, reason):
-    """A problem the cursor engine still hands back under 20 / 21: "cursor-unschedulable" refuses and names `reason` (0: the batch is
-    not offered to a fast engine at all, "outside its shape"), "auto-unschedulable" equals the oracle on the general engine with it."""
-    try:
-        solve(prob, "cursor-unschedulable", lib)
-    except Unsupported as e:
-        assert ("outside its shape" if reason == 0 else f"cursor engine declined the problem (reason {reason})") in str(e), str(e)
-    else:
-        raise AssertionError("cursor-unschedulable solved a problem it must refuse")
-    auto = solve(prob, "auto-unschedulable", lib)
-    assert (auto["counters"]["engine"], auto["counters"]["engineFallbackReason"]) == ("general", reason), auto["counters"]
-    want = oracle.solve(prob)
-    assert want["podErrors"]
-    same(auto, want)
+    """SWITCH.declined (reason 0: the batch is not offered to a fast engine at all) for a problem that leaves pods unschedulable."""
+    auto = SWITCH.declined(oracle, lib, prob, reason)
+    assert auto["podErrors"]   # (the oracle's: declined() held the two equal)
     return auto
 
 
@@ -270,21 +245,12 @@ def run_fuzz(oracle, lib, seeds):
     "auto-unschedulable": every seed equals the oracle, pops included; a seed that leaves the cursor engine does so with 29 or a shape
     reason, never 27. Returns (seeds with pod errors in the oracle, seeds that stayed on the cursor engine, {seed: reason} of the rest)."""
     with_errors, on_cursor, rest = 0, 0, {}
-    for seed in seeds:
-        prob = lc.fuzz_problem(seed)
-        want = oracle.solve(prob)
+    for seed, _, want, got, on, r in ec.fuzz_cases(oracle, lib, ((seed, lc.fuzz_problem(seed)) for seed in seeds), SWITCH.auto, pops=True, mode=SWITCH.mode):
         with_errors += bool(want["podErrors"])
-        got = solve(prob, "auto-unschedulable", lib)
-        same(got, want)
-        assert got["counters"]["pops"] == want["counters"]["pops"], (seed, got["counters"]["pops"], want["counters"]["pops"])
-        c = got["counters"]
-        if c["engine"] == "cursor":
-            assert c["engineFallbackReason"] == 0, (seed, c)
+        if on == "cursor":
             on_cursor += 1
         else:
-            assert c["engine"] == "general", (seed, c)
-            r = c["engineFallbackReason"]
-            assert r != 27 and (r == 29 or r in lc.SHAPE_REASONS), (seed, c)
+            assert r != 27 and (r == 29 or r in lc.SHAPE_REASONS), (seed, got["counters"])
             rest[seed] = r
     print(f"auto-unschedulable kept {on_cursor} of {len(seeds)} seeds on the cursor engine ({with_errors} with pod errors in the oracle); reasons of the rest {rest}")
     return with_errors, on_cursor, rest
