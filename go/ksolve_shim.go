@@ -196,3 +196,66 @@ func SolveBatch(ctx context.Context, scheds []*DeviceScheduler, pods [][]*corev1
 	}
 	return results, errs
 }
+
+// ManyStats is what one SolveMany call did with its schedulers (ksolve_many_stats).
+type ManyStats struct {
+	SpreadLaunches, SpreadMembers, CursorMembers, GeneralMembers, HandedBack, AloneMembers, ProbeMembers, Refused uint32
+}
+
+// SolveMany runs Solve() for several independent schedulers in ONE call, each on the engine Solve() would run
+// (ksolve_solve_many): every member gets the result its own Solve() would have given it, and members of the spread engine's
+// shape — topology problems — share launches, one wavefront per problem. SolveBatch keeps its behaviour and does not know
+// the spread engine: callers that hold several provisioning passes, component shards of a topology batch or the simulations
+// of a consolidation pass with topology call this one. results[i] / errs[i] are what scheds[i].Solve(ctx, pods[i]) would have
+// returned.
+func SolveMany(ctx context.Context, scheds []*DeviceScheduler, pods [][]*corev1.Pod) (results []Results, errs []error, stats ManyStats) {
+	results, errs = make([]Results, len(scheds)), make([]error, len(scheds))
+	var onDevice []int
+	var problems []*deviceProblem
+	for i, d := range scheds {
+		p, err := upload(ctx, d.stock, pods[i])
+		switch {
+		case errors.Is(err, ErrKSolveUnsupported):
+			results[i], errs[i] = d.stock.Solve(ctx, pods[i])
+		case err != nil:
+			errs[i] = err
+		default:
+			onDevice, problems = append(onDevice, i), append(problems, p)
+		}
+	}
+	if len(problems) == 0 {
+		return results, errs, stats
+	}
+	// handle pointers, result structs and the counters live in C memory for the duration of the call (cgo pointer-passing rules)
+	n := len(problems)
+	handles := (**C.ksolve_handle)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof((*C.ksolve_handle)(nil)))))
+	outs := (*C.ksolve_results)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.ksolve_results{}))))
+	cst := (*C.ksolve_many_stats)(C.calloc(1, C.size_t(unsafe.Sizeof(C.ksolve_many_stats{}))))
+	defer C.free(unsafe.Pointer(handles))
+	defer C.free(unsafe.Pointer(outs))
+	defer C.free(unsafe.Pointer(cst))
+	hs, rs := unsafe.Slice(handles, n), unsafe.Slice(outs, n)
+	for j, p := range problems {
+		hs[j] = p.handle
+	}
+	stop := watch(ctx, hs...)
+	st := C.ksolve_solve_many(handles, C.uint32_t(n), outs, cst)
+	stop()
+	stats = ManyStats{uint32(cst.spread_launches), uint32(cst.spread_members), uint32(cst.cursor_members), uint32(cst.general_members),
+		uint32(cst.handed_back), uint32(cst.alone_members), uint32(cst.probe_members), uint32(cst.refused)}
+	for j, p := range problems {
+		i := onDevice[j]
+		switch rs[j].status {
+		case C.KSOLVE_OK, C.KSOLVE_ERR_CANCELLED:
+			results[i], errs[i] = p.flat.rehydrate(p.s, &rs[j]), ctx.Err()
+		case C.KSOLVE_ERR_UNSUPPORTED:
+			results[i], errs[i] = p.s.Solve(ctx, pods[i])
+		default:
+			errs[i] = fmt.Errorf("ksolve_solve_many: problem %d: status %d (call status %d): %s", i, int(rs[j].status), int(st),
+				C.GoString(C.ksolve_last_error(p.handle)))
+		}
+		C.ksolve_results_free(&rs[j])
+		p.close()
+	}
+	return results, errs, stats
+}

@@ -448,8 +448,37 @@ ksolve_status ksolve_solve(ksolve_handle* h, ksolve_results* out);
  * form of "partition the batch across the GPUs". Results are identical to n ksolve_solve calls; outs[i].status carries each
  * problem's status.
  * This is the entry point for consolidation sweeps (disruption/helpers.go:53-155 runs one Solve() per candidate set)
- * and for NodePool components of one provisioning pass. */
+ * and for NodePool components of one provisioning pass.
+ * It keeps its behaviour for existing callers, and it does not know the spread engine: ksolve_solve_many (below) does. */
 ksolve_status ksolve_solve_batch(ksolve_handle** handles, uint32_t n, ksolve_results* outs);
+/* What one ksolve_solve_many call did with its handles (every device's share summed). The member counters say which paths a handle
+ * went through, and a handle can go through two: one a fast engine hands back is counted in spread_members or cursor_members AND in
+ * general_members (handed_back says how many); a cursor member that runs out of LDS claim slots in the batched launch (reason 26)
+ * then runs alone on the next memory plan and is counted in cursor_members AND alone_members — its cursor_attempts is the batched
+ * run plus the runs alone, as ksolve_solve counts them; a member re-run on the BIG engine after KSOLVE_ERR_CAPACITY stays where it
+ * was counted. Handles without pods, and handles refused before anything ran, are in none of the member counters; a spread-only
+ * handle the engine declines inside its launch is in spread_members and in refused. */
+typedef struct {
+  uint32_t spread_launches;  /* launches of the spread engine's many-problem kernels (one per kernel flavour present, per device) */
+  uint32_t spread_members;   /* handles that ran in them */
+  uint32_t cursor_members;   /* handles in the cursor engine's batched launch */
+  uint32_t general_members;  /* handles in the general engine's batched launches, the handed-back ones included */
+  uint32_t handed_back;      /* of those: handed back by a fast engine inside this call */
+  uint32_t alone_members;    /* handles solved one after another through ksolve_solve's own path */
+  uint32_t probe_members;
+  uint32_t refused;          /* handles answered with KSOLVE_ERR_UNSUPPORTED */
+} ksolve_many_stats;
+/* Solves n independent problems in one call, each on the engine ksolve_solve would run. The contract:
+ * EVERY MEMBER OF THE CALL GETS THE RESULT ksolve_solve WOULD HAVE GIVEN IT ON A FRESH HANDLE — outcome, error text, engine, fallback
+ * reason, memory plan, attempts and digest. MEMBERS OF THE SPREAD ENGINE'S SHAPE SHARE LAUNCHES.
+ * Spread members (with DaemonSets, existing nodes, complement NodePools or a set-aside list as well) run in one launch per kernel
+ * flavour present — at most six per device — one wavefront each, handed out largest first; a member the engine hands back joins the
+ * general engine's batched launch with its reason, or is refused under a spread-only setting, and never touches another member's
+ * result. Cursor members run in the cursor engine's batched launch where ksolve_solve would run that kernel, alone otherwise; probe
+ * handles go through one sweep per base; everything else runs on the general engine's batched launches. Handles may live on several
+ * devices, as with ksolve_solve_batch. outs[i].status carries each member's status (ksolve_last_error its text); the call returns the
+ * last status that is neither OK nor CANCELLED. stats may be NULL. */
+ksolve_status ksolve_solve_many(ksolve_handle** handles, uint32_t n, ksolve_results* results, ksolve_many_stats* stats /* may be NULL */);
 /* A handle for one probe of `base` (see ksolve_probe). `base` must outlive it and must not be solved concurrently with it;
  * results use the base problem's pod and node numbering (pods outside the probe: assignment -1, error 0; removed nodes take
  * no pods). Works with ksolve_solve, ksolve_solve_batch, ksolve_cancel, ksolve_destroy. A base problem with topology groups

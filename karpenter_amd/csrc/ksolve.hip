@@ -30,6 +30,8 @@ struct HipBackend {
   size_t stage_bytes = 0;
   int device = 0;
   int n_cus = 256;              // compute units of the device (the compact sweep launches what the chip holds at once)
+  void* many_buf = nullptr;     // the table of a many-problem launch this handle led (be_launch_pack_topo_many): kept, grown on demand
+  size_t many_bytes = 0;
 };
 #define HB(h) ((HipBackend*)(h)->backend)
 static bool hip_check(ksolve_handle* h, hipError_t e, const char* what) {
@@ -746,6 +748,62 @@ static void be_launch_pack_topo_nodes(ksolve_handle* h) {
   else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_nodes_u, "ksolve_pack_topo_nodes_u launch");
   else launch_pack_topo(h, ksolve_pack_topo_nodes, "ksolve_pack_topo_nodes launch");
 }
+// ksolve_solve_many: one launch of the spread engine's many-problem kernel of every flavour that has members (topo_many.h), each on
+// the stream of its first member so that the flavours overlap; every member's T_PACK timer gets the time of its own launch. The
+// launch's table — the members' records, the order table, the ticket counter — lives in a buffer the first member's backend keeps
+// and grows (HipBackend::many_buf): no allocation and no device-wide synchronise per call once it is there. A member whose record
+// could not be uploaded stays out of the launch with its own error; the others run.
+typedef void (*ksolve_pack_topo_many_fn)(const ks::TopoArgs* const*, const uint32_t*, uint32_t*, int);
+static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups) {
+  static const ksolve_pack_topo_many_fn kFn[ksi::kTopoManyFlavours] = {ksolve_pack_topo_many, ksolve_pack_topo_many_u, ksolve_pack_topo_many_f,
+                                                                       ksolve_pack_topo_nodes_many, ksolve_pack_topo_nodes_many_u, ksolve_pack_topo_nodes_many_f};
+  std::vector<ksolve_handle*> live[ksi::kTopoManyFlavours];
+  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
+    int lds_bytes = 0;
+    for (ksolve_handle* h : groups[f]) {
+      ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
+      be_h2d(h, h->d_topo_args, &a, sizeof(a));   // (synchronises the member's stream: its prepass is done before the launch reads its tables)
+      if (!be_ok(h)) continue;
+      live[f].push_back(h);
+      lds_bytes = std::max(lds_bytes, h->tw.plan.total_bytes);
+    }
+    std::vector<ksolve_handle*>& g = live[f];
+    if (g.empty()) continue;
+    ksolve_handle* h0 = g[0];
+    HipBackend* b = HB(h0);
+    const size_t n = g.size();
+    std::vector<char> host(n * sizeof(void*) + n * 4 + 4, 0);   // (the ticket counter starts at 0)
+    const ks::TopoArgs** ptrs = (const ks::TopoArgs**)host.data();
+    for (size_t i = 0; i < n; ++i) ptrs[i] = g[i]->d_topo_args;
+    ksi::topo_many_order(g, (uint32_t*)(host.data() + n * sizeof(void*)));
+    if (host.size() > b->many_bytes) {
+      if (b->many_buf) (void)hipFree(b->many_buf);
+      b->many_buf = nullptr; b->many_bytes = 0;
+      const size_t want = host.size() * 2 + 4096;
+      if (!hip_check(h0, hipMalloc(&b->many_buf, want), "hipMalloc(many)")) continue;
+      b->many_bytes = want;
+    }
+    char* d = (char*)b->many_buf;
+    hip_check(h0, hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, b->stream), "hipMemcpy(many)");
+    hip_check(h0, hipStreamSynchronize(b->stream), "hipStreamSynchronize");   // `host` is a local
+    if (b->failed || !hip_check(h0, hipFuncSetAttribute((const void*)kFn[f], hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) continue;
+    hip_check(h0, hipEventRecord(b->ev0[ksi::T_PACK], b->stream), "hipEventRecord");
+    hipLaunchKernelGGL(kFn[f], dim3((unsigned)n), dim3(64), (size_t)lds_bytes, b->stream, (const ks::TopoArgs* const*)d, (const uint32_t*)(d + n * sizeof(void*)),
+                       (uint32_t*)(d + n * sizeof(void*) + n * 4), (int)n);
+    hip_check(h0, hipGetLastError(), "ksolve_pack_topo_many launch");
+    hip_check(h0, hipEventRecord(b->ev1[ksi::T_PACK], b->stream), "hipEventRecord");
+  }
+  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
+    std::vector<ksolve_handle*>& g = live[f];
+    if (g.empty()) continue;
+    ksolve_handle* h0 = g[0];
+    HipBackend* b = HB(h0);
+    if (!b->failed) hip_check(h0, hipEventSynchronize(b->ev1[ksi::T_PACK]), "hipEventSynchronize");
+    float ms = 0;
+    if (!b->failed && hipEventElapsedTime(&ms, b->ev0[ksi::T_PACK], b->ev1[ksi::T_PACK]) == hipSuccess) h0->timers.ms[ksi::T_PACK] = ms;
+    for (size_t i = 1; i < g.size(); ++i) { g[i]->timers.ms[ksi::T_PACK] = h0->timers.ms[ksi::T_PACK]; if (b->failed) { HB(g[i])->failed = true; g[i]->error = h0->error; } }
+  }
+}
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {
   if (n <= 0) return;
   ksolve_handle* h0 = hs[0];
@@ -1013,6 +1071,12 @@ ksolve_status ksolve_solve_batch(ksolve_handle** hs, uint32_t n, ksolve_results*
   if (hipSetDevice(HB(hs[0])->device) != hipSuccess) return KSOLVE_ERR_DEVICE;
   return ksi::solve_batch(hs, n, outs);
 }
+ksolve_status ksolve_solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats* stats) {
+  if (!hs || !outs || n == 0) return KSOLVE_ERR_INVALID;
+  for (uint32_t i = 0; i < n; ++i) if (!hs[i] || !hs[i]->backend) return KSOLVE_ERR_INVALID;
+  if (hipSetDevice(HB(hs[0])->device) != hipSuccess) return KSOLVE_ERR_DEVICE;
+  return ksi::solve_many(hs, n, outs, stats);
+}
 ksolve_status ksolve_packing_vector(const ksolve_handle* h, const ksolve_results* r, double* count, double* cost) {
   if (!h || !r || !count || !cost) return KSOLVE_ERR_INVALID;
   return ksi::packing_vector(h, r->claims, count, cost);
@@ -1039,6 +1103,7 @@ void ksolve_destroy(ksolve_handle* h) {
     for (void* p : h->allocations) (void)hipFree(p);
     if (b->sort_tmp) (void)hipFree(b->sort_tmp);
     if (b->stage) (void)hipHostFree(b->stage);
+    if (b->many_buf) (void)hipFree(b->many_buf);
     if (b->stream) { for (int i = 0; i < 8; ++i) { (void)hipEventDestroy(b->ev0[i]); (void)hipEventDestroy(b->ev1[i]); } (void)hipStreamDestroy(b->stream); }
     delete b;
   }

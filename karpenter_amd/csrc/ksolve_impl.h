@@ -445,6 +445,7 @@ static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: Top
 static void be_launch_fast_unsched(ksolve_handle* h);               // engines 20 / 21, one thread per pod set aside: fast_unsched_body (errors under the pod indices)
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
+static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups);   // ksolve_solve_many: groups[ksi::kTopoManyFlavours], one ksolve_pack_topo*_many launch per group that has members (block = one ticket = one member, largest first); sets every member's T_PACK timer
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
 static void be_launch_sweep_items(ksolve_handle* h, int n, const ks::SweepItemArgs& a);
 
@@ -3241,6 +3242,214 @@ static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksol
   return worst;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// ksolve_solve_many: many problems in one call, each on the engine solve() would run — every member gets the result solve() would have
+// given it on a fresh handle (outcome, error text, engine, fallback reason, memory plan, attempts, digest), and members of the spread
+// engine's shape share launches. solve_batch above keeps its behaviour (its recorded cells are pinned); this is the call ladder of
+// solve() itself, walked for all members at once:
+//   refusals -> the spread engine's many-problem launches (one per kernel flavour present) -> the cursor engine's batched launch
+//   (alone where solve() would run another kernel) -> the general engine's batched launch, with whatever the fast engines handed back.
+enum { kTopoManyFlavours = 6 };
+// the kernel be_launch_pack_topo / be_launch_pack_topo_nodes would pick: plain, _u, _f, then the three with existing nodes
+static int topo_many_flavour(const ksolve_handle* h) { return (h->tw.nd.dom ? 3 : 0) + (h->fw.filt ? 2 : h->fw.unsched ? 1 : 0); }
+// the order table of one launch: its members by pod count, largest first (ties in input order); tickets are handed out along it
+static void topo_many_order(const std::vector<ksolve_handle*>& g, uint32_t* order) {
+  for (size_t i = 0; i < g.size(); ++i) order[i] = (uint32_t)i;
+  std::stable_sort(order, order + g.size(), [&](uint32_t a, uint32_t b) { return g[a]->n_pods > g[b]->n_pods; });
+}
+
+static ksolve_status solve_many_plain(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats& S) {
+  for (uint32_t i = 0; i < n; ++i) memset(&outs[i], 0, sizeof(outs[i]));
+  std::vector<ksolve_status> st(n, KSOLVE_OK);
+  std::vector<char> done(n, 0);   // the member's answer stands: refused, failed, or solved alone (results complete)
+  const uint32_t n_threads = std::min<uint32_t>(n, std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
+  auto parallel = [&](auto&& fn) {   // (the host-thread pattern of solve_batch_plain)
+    if (n_threads <= 1) { for (uint32_t i = 0; i < n; ++i) fn(i); return; }
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < n_threads; ++t) pool.emplace_back([&, t]() { be_thread_init(hs[0]); for (uint32_t i = t; i < n; i += n_threads) fn(i); });
+    for (auto& th : pool) th.join();
+  };
+  auto refuse = [&](uint32_t i, ksolve_status s) { st[i] = s; done[i] = 1; };
+  auto alone = [&](uint32_t i) { be_results_drop(&outs[i]); st[i] = solve(hs[i], &outs[i], false); outs[i].status = st[i]; done[i] = 1; S.alone_members++; };
+  // what solve() refuses before it runs anything, in its words
+  for (uint32_t i = 0; i < n; ++i)
+    if (hs[i]->resident && hs[i]->has_topology) refuse(i, fail(hs[i], KSOLVE_ERR_INVALID, "a resident cluster with topology groups is solved through probes (ksolve_sweep / ksolve_probe_create): its counts include the bound pod rows"));
+  parallel([&](uint32_t i) { if (done[i]) return; st[i] = solve_prepare(hs[i]); if (st[i] == KSOLVE_OK) be_sync(hs[i]); else done[i] = 1; });
+  std::vector<uint32_t> spread, fast, run;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    ksolve_handle* h = hs[i];
+    if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes)) { refuse(i, h->eng.spread_operators && h->fast_reason ? declined(h, "spread") : outside_shape(h, EnginePolicy::Spread)); continue; }
+    if (h->eng.cursor_only() && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes)) { refuse(i, h->eng.operators && h->fast_reason ? declined(h, "cursor") : outside_shape(h, EnginePolicy::Cursor)); continue; }
+    if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
+      h->fast_reason = ks::DECLINE_NODE_CLASSES;
+      if (h->eng.refuses()) { refuse(i, declined(h, "cursor")); continue; }
+      h->fw.enabled = 0;
+    }
+    if (!h->n_pods) continue;   // nothing to launch: solve_finish
+    if (h->tw.enabled && h->n_classes) spread.push_back(i);
+    else if (h->fw.enabled && !h->pv.big && h->n_classes) {
+      // the batched kernel is the LDS plan of ksolve_pack_fast_g0r*: a handle solve() would run on another kernel (a plan in HBM, the
+      // two-wavefront kernel, the set-aside list, the pod operators) or with kernels around the loop (node stage, limit stages) runs alone
+      if (h->fw.plan.global_state == 0 && !h->fw.plan.helper && !h->fw.nodes && !h->fw.lim && !h->fw.unsched && !h->fw.podops) fast.push_back(i);
+      else alone(i);
+    }
+    else run.push_back(i);
+  }
+  // handed back by a fast engine: the general engine's batched launch takes it, the reason stays on the handle
+  auto hand_back = [&](uint32_t i) {
+    st[i] = solve_prepare(hs[i], false);
+    if (st[i] != KSOLVE_OK) { done[i] = 1; return; }
+    be_sync(hs[i]); run.push_back(i); S.handed_back++;
+  };
+  if (!spread.empty()) {
+    std::vector<ksolve_handle*> groups[kTopoManyFlavours];
+    for (uint32_t i : spread) {
+      ksolve_handle* h = hs[i];   // what solve() does in front of its launch
+      alloc_run_order(h);
+      if (h->tw.nd.dom) { node_static_rows(h); h->tw.nd.dead0 = h->nd_dead0; }
+      groups[topo_many_flavour(h)].push_back(h);
+    }
+    be_launch_pack_topo_many(groups);
+    for (auto& g : groups) if (!g.empty()) S.spread_launches++;
+    S.spread_members += (uint32_t)spread.size();
+    for (uint32_t i : spread) {
+      ksolve_handle* h = hs[i];
+      const FastOutcome o = fast_outcome(h);
+      if (o.done) {
+        h->engine_used = 3;
+        h->fast_reason = 0; h->fast_attempts = 1;
+        if (o.n_claims || h->tw.nd.dom) be_launch_fast_records(h, o.n_claims);
+        if (h->fw.unsched) be_launch_fast_unsched(h);
+        continue;
+      }
+      h->fast_reason = o.reason;
+      if (h->eng.spread_only()) { refuse(i, declined(h, "spread")); continue; }
+      if (h->fast_reason != ks::DECLINE_UNSCHEDULABLE_POD && h->fast_reason != ks::DECLINE_CAPACITY) h->tw.enabled = 0;
+      hand_back(i);
+    }
+  }
+  if (!fast.empty()) {
+    std::vector<ksolve_handle*> g;
+    for (uint32_t i : fast) g.push_back(hs[i]);
+    be_launch_pack_fast_batch(g.data(), (int)g.size());
+    S.cursor_members += (uint32_t)fast.size();
+    for (uint32_t i : fast) {
+      ksolve_handle* h = hs[i];
+      const FastOutcome o = fast_outcome(h);
+      h->fast_attempts = 1;   // the runs of the cursor engine this solve took, as solve() counts them: handed back or not
+      if (o.done) { h->engine_used = 2; h->fast_reason = 0; if (o.n_claims) be_launch_fast_records(h, o.n_claims); continue; }
+      h->fast_reason = o.reason;
+      if (be_ok(h) && h->fast_reason == ks::DECLINE_CLAIM_SLOTS && h->fw.plan.global_state < 2 && !h->opts.lds_claim_cap) {
+        // out of claim slots: the plan solve() would move to after this attempt, then alone on that plan's kernel — one run more than
+        // solve() counts from there on
+        const int had = h->fw.plan.cap;
+        int next = h->fw.plan.global_state + 1;
+        if (next == 1) {
+          fast_plan_set(h, 1, h->fw.plan.rows);
+          const double placed = (double)(o.pops > 0 ? o.pops : 1);
+          const bool holds_all = h->fw.plan.cap >= (int)((h->fast_mc + 63) & ~63u);
+          if (!holds_all && (double)had * (double)h->n_pods / placed * 1.25 > (double)h->fw.plan.cap) next = 2;
+        }
+        fast_plan_set(h, next, h->fw.plan.rows);
+        if (h->fw.plan.cap > had) {
+          // (solve() counts its own runs from zero and is not to be touched: the batched run is added to what it reports, on the
+          // handle and in the results it filled. The member is in cursor_members and in alone_members: ksolve.h says so.)
+          alone(i);
+          h->fast_attempts++;
+          if (outs[i].impl) outs[i].cursor_attempts++;
+          continue;
+        }
+      }
+      if (h->eng.refuses()) { refuse(i, declined(h, "cursor")); continue; }
+      h->fw.enabled = 0;
+      hand_back(i);
+    }
+  }
+  if (!run.empty()) {
+    std::vector<ksolve_handle*> g;
+    for (uint32_t i : run) g.push_back(hs[i]);
+    be_launch_pack_batch(g.data(), (int)g.size());
+    S.general_members += (uint32_t)run.size();
+  }
+  parallel([&](uint32_t i) {
+    if (done[i]) { outs[i].status = st[i]; return; }
+    st[i] = solve_finish(hs[i], &outs[i]);
+    if (st[i] == KSOLVE_ERR_CAPACITY && hs[i]->big_capable && !hs[i]->pv.big) { be_results_drop(&outs[i]); st[i] = solve(hs[i], &outs[i], false); }   // re-run alone on the BIG engine
+    outs[i].status = st[i];
+  });
+  ksolve_status worst = KSOLVE_OK;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (st[i] == KSOLVE_ERR_UNSUPPORTED) S.refused++;
+    if (st[i] != KSOLVE_OK && st[i] != KSOLVE_ERR_CANCELLED) worst = st[i];
+  }
+  return worst;
+}
+
+// one device: probes of a resident cluster run as one sweep per base handle (as in solve_batch_one_device), everything else as above
+static ksolve_status solve_many_one_device(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats& S) {
+  std::vector<uint32_t> plain_idx;
+  std::vector<ksolve_handle*> bases;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!hs[i]->base) { plain_idx.push_back(i); continue; }
+    S.probe_members++;
+    if (std::find(bases.begin(), bases.end(), hs[i]->base) == bases.end()) bases.push_back(hs[i]->base);
+  }
+  if (bases.empty()) return solve_many_plain(hs, n, outs, S);
+  ksolve_status worst = KSOLVE_OK;
+  for (ksolve_handle* b : bases) {
+    std::vector<uint32_t> idx;
+    std::vector<ksolve_handle*> g;
+    for (uint32_t i = 0; i < n; ++i) if (hs[i]->base == b) { idx.push_back(i); g.push_back(hs[i]); }
+    std::vector<ksolve_results> ro(g.size());
+    std::vector<ksolve_status> st(g.size(), KSOLVE_OK);
+    solve_probes(g.data(), (uint32_t)g.size(), ro.data(), st.data(), true);
+    for (size_t k = 0; k < g.size(); ++k) { outs[idx[k]] = ro[k]; if (st[k] != KSOLVE_OK && st[k] != KSOLVE_ERR_CANCELLED) worst = st[k]; }
+  }
+  if (!plain_idx.empty()) {
+    std::vector<ksolve_handle*> g;
+    for (uint32_t i : plain_idx) g.push_back(hs[i]);
+    std::vector<ksolve_results> ro(g.size());
+    const ksolve_status rc = solve_many_plain(g.data(), (uint32_t)g.size(), ro.data(), S);
+    for (size_t k = 0; k < g.size(); ++k) outs[plain_idx[k]] = ro[k];
+    if (rc != KSOLVE_OK) worst = rc;
+  }
+  return worst;
+}
+
+// ksolve_solve_many: the handles' devices side by side (one host thread each, as solve_batch splits them), the counters summed
+static ksolve_status solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats* stats) {
+  std::vector<int> devices;
+  for (uint32_t i = 0; i < n; ++i) { const int dv = be_device_of(hs[i]); if (std::find(devices.begin(), devices.end(), dv) == devices.end()) devices.push_back(dv); }
+  std::vector<ksolve_many_stats> part(devices.size(), ksolve_many_stats{});
+  std::vector<ksolve_status> rc(devices.size(), KSOLVE_OK);
+  if (devices.size() <= 1) rc[0] = solve_many_one_device(hs, n, outs, part[0]);
+  else {
+    std::vector<std::thread> pool;
+    for (size_t g = 0; g < devices.size(); ++g) pool.emplace_back([&, g]() {
+      std::vector<uint32_t> idx;
+      std::vector<ksolve_handle*> grp;
+      for (uint32_t i = 0; i < n; ++i) if (be_device_of(hs[i]) == devices[g]) { idx.push_back(i); grp.push_back(hs[i]); }
+      be_thread_init(grp[0]);
+      std::vector<ksolve_results> ro(grp.size());
+      rc[g] = solve_many_one_device(grp.data(), (uint32_t)grp.size(), ro.data(), part[g]);
+      for (size_t k = 0; k < grp.size(); ++k) outs[idx[k]] = ro[k];
+    });
+    for (auto& th : pool) th.join();
+  }
+  ksolve_status worst = KSOLVE_OK;
+  for (auto r : rc) if (r != KSOLVE_OK) worst = r;
+  if (stats) {
+    *stats = ksolve_many_stats{};
+    for (const ksolve_many_stats& p : part) {
+      stats->spread_launches += p.spread_launches; stats->spread_members += p.spread_members; stats->cursor_members += p.cursor_members;
+      stats->general_members += p.general_members; stats->handed_back += p.handed_back; stats->alone_members += p.alone_members;
+      stats->probe_members += p.probe_members; stats->refused += p.refused;
+    }
+  }
+  return worst;
+}
+
 }  // namespace ksi
 
 #ifdef KSOLVE_HOST_EMULATION
@@ -3268,5 +3477,40 @@ static void be_launch_pack_topo_nodes(ksolve_handle* h) {
   const ks::TopoArgs* a_ = h->d_topo_args;
   ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data());
   eng.solve();
+}
+// The emulated ksolve_pack_topo*_many launches (topo_many.h): a loop over the grid in which every block takes a ticket from the
+// launch's counter and solves the member the order table names, one after another; the LDS segment is the launch's (the largest
+// member's plan), each engine reading its own tw.plan offsets. (The emulation's engine has the set-aside list and the filters built in.)
+static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups) {
+  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
+    std::vector<ksolve_handle*>& g = groups[f];
+    if (g.empty()) continue;
+    const uint32_t n = (uint32_t)g.size();
+    std::vector<uint32_t> order(n);
+    int lds_bytes = 0;
+    for (ksolve_handle* h : g) {
+      ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
+      be_h2d(h, h->d_topo_args, &a, sizeof(a));
+      lds_bytes = std::max(lds_bytes, h->tw.plan.total_bytes);
+    }
+    ksi::topo_many_order(g, order.data());
+    uint32_t next = 0;   // the launch's ticket counter
+    be_tic(g[0], ksi::T_PACK);
+    for (uint32_t block = 0; block < n; ++block) {
+      const uint32_t t = next++;
+      if (t >= n || order[t] >= n) continue;
+      const ks::TopoArgs* a_ = g[order[t]]->d_topo_args;
+      std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
+      if (f >= 3) { ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data()); eng.solve(); }
+      else { ks::TopoEngine<ks::Wave> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data()); eng.solve(); }
+    }
+    be_toc(g[0], ksi::T_PACK);
+    for (ksolve_handle* h : g) h->timers.ms[ksi::T_PACK] = g[0]->timers.ms[ksi::T_PACK];
+  }
+}
+// the emulation's export of ksolve_solve_many (its other exports live with its backend)
+extern "C" ksolve_status ksolve_solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats* stats) {
+  if (!hs || !outs || n == 0) return KSOLVE_ERR_INVALID;
+  return ksi::solve_many(hs, n, outs, stats);
 }
 #endif

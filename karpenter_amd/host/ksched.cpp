@@ -2970,6 +2970,38 @@ extern "C" int ksched_solve_batch(void** sessions, int n, int want_results, char
   return 0;
 }
 
+// Solve() for n sessions in one call, each on the engine ksched_solve would run (ksolve_solve_many: members of the spread engine's
+// shape share launches; every member's document is the one ksched_solve would have returned). outs receives n result documents;
+// stats_json, when not null, a document with the call's eight counters (ksolve_many_stats) — each to be released with ksched_free.
+// Returns 0 on success.
+extern "C" int ksched_solve_many(void** sessions, int n, int want_results, char** outs, char** stats_json) {
+  if (stats_json) *stats_json = nullptr;
+  if (!sessions || n <= 0 || !outs) return 1;
+  std::vector<ksolve_handle*> hs;
+  for (int i = 0; i < n; ++i) {
+    Session* S = (Session*)sessions[i];
+    outs[i] = nullptr;
+    if (!S || !S->handle) { for (int j = 0; j < n; ++j) outs[j] = S ? session_error(S) : error_json("invalid", "null session"); return 1; }
+    hs.push_back(S->handle);
+  }
+  Session* S0 = (Session*)sessions[0];
+  auto many = (decltype(&ksolve_solve_many))dlsym(S0->api.lib, "ksolve_solve_many");
+  if (!many) { for (int j = 0; j < n; ++j) outs[j] = error_json("load", "solver library lacks ksolve_solve_many"); return 1; }
+  std::vector<ksolve_results> res((size_t)n);
+  ksolve_many_stats st{};
+  many(hs.data(), (uint32_t)n, res.data(), &st);
+  for (int i = 0; i < n; ++i) outs[i] = results_json((Session*)sessions[i], res[i], res[i].status, want_results);
+  if (stats_json) {
+    Value v = Value::object();
+    v.set("spread_launches", Value::integer(st.spread_launches)); v.set("spread_members", Value::integer(st.spread_members));
+    v.set("cursor_members", Value::integer(st.cursor_members)); v.set("general_members", Value::integer(st.general_members));
+    v.set("handed_back", Value::integer(st.handed_back)); v.set("alone_members", Value::integer(st.alone_members));
+    v.set("probe_members", Value::integer(st.probe_members)); v.set("refused", Value::integer(st.refused));
+    *stats_json = dup_json(v);
+  }
+  return 0;
+}
+
 // Convenience: open + solve (repeat times, last result returned with every run's timings) + close.
 // ---- NodePool components: the host-side split of one provisioning batch for several devices -----------------------
 // Two NodePools are in one component when some pod may land on either (its REQUIRED constraints on karpenter.sh/nodepool: a node

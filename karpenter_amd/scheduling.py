@@ -59,6 +59,8 @@ def _load_ksched():
         lib.ksched_free.argtypes = [ctypes.c_void_p]
         lib.ksched_solve_batch.restype = ctypes.c_int
         lib.ksched_solve_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        lib.ksched_solve_many.restype = ctypes.c_int
+        lib.ksched_solve_many.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
         lib.ksched_probe.restype = ctypes.c_void_p
         lib.ksched_probe.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
         lib.ksched_sweep.restype = ctypes.c_void_p
@@ -325,6 +327,56 @@ def SolveBatch(schedulers, want_results: bool = True):
         if "error" in doc:
             _raise(doc.get("kind"), doc["error"])
     return [Results(doc) for doc in docs]
+
+
+MANY_STATS = ("spread_launches", "spread_members", "cursor_members", "general_members", "handed_back", "alone_members", "probe_members", "refused")
+
+
+def SolveMany(schedulers, want_results=True, stats=None, errors="raise"):
+    """Solve() for many independent Schedulers in ONE call, each on the engine Solve() would run (ksolve_solve_many): every member
+    gets the Results Solve() would have given it on a fresh handle — outcome, error text, engine, fallback reason, memory plan,
+    attempts, digest — and members of the spread engine's shape (topology problems, with DaemonSets, existing nodes, complement
+    NodePools or kept unschedulable pods as well) share launches, one wavefront per problem. SolveBatch keeps its behaviour and
+    does not know the spread engine: call this one for topology problems and for lists under the "auto-*" / "spread-*" settings.
+    stats: a dict that receives the call's counters (MANY_STATS). errors="raise" raises the first member's exception, as SolveBatch
+    does; errors="return" returns, per member, either its Results or its exception."""
+    if errors not in ("raise", "return"):
+        raise ValueError('errors is "raise" or "return"')
+    schedulers = list(schedulers)
+    if not schedulers:
+        if stats is not None:
+            stats.update({k: 0 for k in MANY_STATS})
+        return []
+    lib = schedulers[0]._lib
+    n = len(schedulers)
+    sessions = (ctypes.c_void_p * n)(*[s._session for s in schedulers])
+    outs = (ctypes.c_void_p * n)()
+    stats_ptr = ctypes.c_void_p()
+    lib.ksched_solve_many(sessions, n, _want(want_results), outs, ctypes.byref(stats_ptr))
+    docs = []
+    try:
+        for i in range(n):   # every document is copied out and released before anything is raised
+            try:
+                docs.append(json.loads(ctypes.string_at(outs[i]).decode()))
+            finally:
+                lib.ksched_free(outs[i])
+        if stats is not None:
+            stats.update(json.loads(ctypes.string_at(stats_ptr).decode()) if stats_ptr else {k: 0 for k in MANY_STATS})
+    finally:
+        if stats_ptr:
+            lib.ksched_free(stats_ptr)
+    members = []
+    for doc in docs:
+        if "error" not in doc:
+            members.append(Results(doc))
+            continue
+        try:
+            _raise(doc.get("kind"), doc["error"])
+        except Exception as e:
+            if errors == "raise":
+                raise
+            members.append(e)
+    return members
 
 
 MAX_INSTANCE_TYPES = 600                      # scheduling.MaxInstanceTypes, nodeclaimtemplate.go:50
