@@ -308,6 +308,12 @@ template <bool H, int R> KS_FN ClaimRecs<H, R> fast_uniform(ClaimRecs<H, R> c) {
 #else
 #define KS_COLD inline
 #endif
+// Which pods the tail behind the fast loop finishes itself (fast_hot_run): 1 sort-only pods, 2 new-claim pods, 4 pods of a class
+// without a slot, 8 pods whose claim's move reaches past the window. A measuring switch: -DKSOLVE_LOOP_TAIL=0 is the engine with
+// every such pod going through fast_slow_run (profiles/loop_events); the results are the same.
+#ifndef KSOLVE_LOOP_TAIL
+#define KSOLVE_LOOP_TAIL 15
+#endif
 
 // requirement-set cache helpers (per lane)
 // One 32-bit multiply (a quarter-rate instruction: 16 cycles of a lone wavefront; the 64-bit product of the first version was three of
@@ -1489,6 +1495,16 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, st
     for (int i = 0; i < 4; ++i) c.cycles[16 + i] = hs->hw[i];
     c.cycles[20] = t_small | (n_small << 44);
     c.cycles[18] = (hs->hw[2] << 32) | (unsigned long long)(hs->mail.simd[0] | (hs->mail.simd[1] << 8) | (hs->mail.simd[2] << 16) | (hs->mail.simd[3] << 24));
+    if (tc && !(hs->hw[0] | hs->hw[1] | hs->hw[2] | hs->hw[3])) {
+      // one wavefront (nothing waited for a refresher, so slots 16..18 are free), timers build only — read by tests/tools/loop_phases.py:
+      //   16  fast_slow_run's sections "block fetch and pending move" | "select" << 32      (cycles; 32 bits each: solves under ~1.7 s)
+      //   17  "commit" | "refresh" << 32
+      //   7, 18, 19  the fast loop's exits per reason (fast_hot_run's count_exit), three counts of 21 bits per slot, reasons 0..8 in
+      //       order (a count wraps at 2M exits; the headline has 14k). Slot 7 otherwise repeats counts that slots 12..15 hold; slot 19
+      //       is the existing-node stage's variant when the problem has nodes (set below: the last three reasons are then lost)
+      c.cycles[16] = hs->tsec[0] | (hs->tsec[1] << 32); c.cycles[17] = hs->tsec[2] | (hs->tsec[3] << 32);
+      c.cycles[7] = hs->tsec[4]; c.cycles[18] = hs->tsec[5]; c.cycles[19] = hs->tsec[6];
+    }
 #endif
     if (F.nodes) c.cycles[19] = (unsigned long long)nd.variant;
     // engines 11 / 12: limit stages created | rows of class slots << 16 | claims open at the first exclusion << 32. Reported as
@@ -1629,6 +1645,34 @@ KS_DEV void fast_helper_run(const FastWork* f, char* lds) {
 }
 #endif
 
+// One stable move in the order (what sort.Slice makes of a single defect while pdqsort stays on its single-move path): the claim x
+// at position a, its count now mv, goes right past the claims with a smaller count. Returns its new position b; positions (a, b]
+// moved left by one (the callers step the cursors inside).
+template <class W, class O16>
+KS_FN int fast_stable_move(O16 okey, O16 oord, int n, int a, uint32_t mv, int x) {
+  int from = a;
+  for (;;) {
+    LaneVar<uint32_t> kv, ov;
+    const uint64_t less = W::ballot([&](int l) {
+      const int i = from + 1 + l;
+      if (i >= n) return false;
+      const uint32_t k = okey[i];
+      kv.at(l) = k; ov.at(l) = oord[i];
+      return k < mv;
+    });
+    const int s_ = less == ~0ull ? 64 : ctz64(~less);   // sorted beyond a: the smaller counts are a prefix
+    if (s_ == 0) break;
+    W::each([&](int l) { if (l < s_) { okey[from + l] = (uint16_t)kv.at(l); oord[from + l] = (uint16_t)ov.at(l); } });
+    from += s_;
+    if (s_ < 64) break;
+  }
+  if (from != a) {
+    if (W::leader()) { okey[from] = (uint16_t)mv; oord[from] = (uint16_t)x; }
+    W::sync();
+  }
+  return from;
+}
+
 // The loop that places pods: a function of its own, WITHOUT calls — whatever happens rarely (a requirement set seen for the
 // first time, a class without a slot, a new claim, pdqsort leaving its single-move path) ends the run with an event code; the
 // driver handles it through FastCold and runs the loop again. So the compiler allocates registers for this loop alone.
@@ -1716,28 +1760,8 @@ KS_COLD int fast_slow_run(FastHotCtx<GS, R> cx, int budget) {
       if (!(a + 1 >= n || (uint32_t)okey[a + 1 < n ? a + 1 : a] >= pend_mv) &&   // something to move ...
           !(n <= 12 || (n >= 50 && !fast_sampled(n, a)))) { ev = FEV_SLOWSORT; ev_arg = a; break; }   // ... and not by the single stable move
       pend_a = -1;
-      // one stable move: the claim at a (count pend_mv) goes right past the claims with a smaller count
-      int from = a;
-      const uint32_t mv = pend_mv;
-      for (;;) {
-        LaneVar<uint32_t> kv, ov;
-        const uint64_t less = W::ballot([&](int l) {
-          const int i = from + 1 + l;
-          if (i >= n) return false;
-          const uint32_t k = okey[i];
-          kv.at(l) = k; ov.at(l) = oord[i];
-          return k < mv;
-        });
-        const int s_ = less == ~0ull ? 64 : ctz64(~less);   // sorted beyond a: the smaller counts are a prefix
-        if (s_ == 0) break;
-        W::each([&](int l) { if (l < s_) { okey[from + l] = (uint16_t)kv.at(l); oord[from + l] = (uint16_t)ov.at(l); } });
-        from += s_;
-        if (s_ < 64) break;
-      }
-      if (from != a) {
-        if (W::leader()) { okey[from] = (uint16_t)mv; oord[from] = (uint16_t)pend_x; }
-        W::sync();
-        const int b = from;   // positions (a, b] moved left by one
+      const int b = fast_stable_move<W>(okey, oord, n, a, pend_mv, pend_x);   // positions (a, b] moved left by one
+      if (b != a) {
         W::each([&](int l) {
 #pragma unroll
           for (int j = 0; j < R; ++j) { const uint32_t r = cur[j].at(l); cur[j].at(l) = r - (uint32_t)(((uint32_t)a < r && r <= (uint32_t)b) ? 1 : 0); }
@@ -1942,7 +1966,7 @@ KS_COLD int fast_slow_run(FastHotCtx<GS, R> cx, int budget) {
     hs->n_steps = n_steps; hs->n_ref = n_ref; hs->ev_arg = ev_arg;
     hs->hot_cycles += W::clock() - t_in;
 #ifdef KSOLVE_PHASE_TIMERS
-    hs->tsec[0] += ts0; hs->tsec[1] += ts1; hs->tsec[2] += ts2; hs->tsec[3] += ts3; hs->tsec[4] += ts4; hs->tsec[5] += ts5; hs->tsec[6] += ts6; hs->tsec[7] += ts7;
+    hs->tsec[0] += ts0; hs->tsec[1] += ts1; hs->tsec[2] += ts2; hs->tsec[3] += ts3;   // (tsec[4..6] are fast_hot_run's exit counts)
 #endif
   }
 #undef KS_SEC
@@ -1961,15 +1985,21 @@ KS_COLD int fast_slow_run(FastHotCtx<GS, R> cx, int budget) {
 // claim is refreshed is cached — and nothing else. A step is a TRANSACTION: every test comes before the first write, and the first
 // thing that is not plain (the last entry before a block where the cancel flag is polled, a pending move, a class without a slot,
 // no acceptor in the window, pdqsort's other paths, a requirement set that is not cached) leaves the loop with the state as it
-// was: the driver runs fast_slow_run for that one pod and comes back. Why two functions: with every rare path inside one loop the
+// was. Behind the loop, outside its body, a TAIL finishes the commonest of those pods from the registers the loop leaves (sort-only,
+// new claim, no slot, a long move: see there) and returns the driver's event; for the rest the driver runs fast_slow_run for that
+// one pod and comes back. Why two functions: with every rare path inside one loop the
 // compiler merged ~30 loop-carried values behind each of them — 274 instructions per pod of which 140 scalar moves, selects and
 // branches (SQ counters, profiles/round5); this loop has ONE path and one exit.
 template <class W, int GS, int R, bool HP = false>
-KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
+KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx, int behind_first) {
   typedef typename FastMem<GS, R>::o16 o16;
   KS_LDS FastHot* const hs = fast_uniform(cx.hs);
+  behind_first = fast_uniform(behind_first);   // the run follows an event of the tail's: where fast_slow_run would have left the queue (see `placed`)
   // (nothing to do here: a pending move / a new claim to place, a step limit — tests —, a stopped solve)
   // (... or no claim yet: the select step reads the order's entries unconditionally, clamped to the last one)
+#ifdef KSOLVE_PHASE_TIMERS
+  if (fast_uniform(hs->pend_a) >= 0 && fast_uniform(hs->max_steps) < 0 && fast_uniform(hs->status) == 0 && W::leader()) hs->tsec[6] += 1ull;   // (exit reason 6, see count_exit)
+#endif
   if (fast_uniform(hs->pend_a) >= 0 || fast_uniform(hs->max_steps) >= 0 || fast_uniform(hs->status) != 0 || fast_uniform(hs->n) <= 0) return FEV_SLOW;
   const o16 okey = fast_uniform(cx.okey), oord = fast_uniform(cx.oord);
   const typename FastMem<GS, R>::States cst = fast_uniform(cx.cst);
@@ -2098,6 +2128,98 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
     for (int j = 1; j < R; ++j) { const uint32_t cj = cur[j].bcast(sl); rc0 = row == j ? cj : rc0; }
     order_reads(rc0);
   };
+  // The pieces of a step that the loop and the tail behind it (below) share, written once: the window's positions that exist, the
+  // claim's state after NodeClaim.Add, the refresh in its two halves (cache reads; predicates) and the record write.
+  auto window_mask = [&]() -> uint64_t {
+    const int rem = n - (int)rc0;                       // (a cursor at the end of the order: none)
+    return rem >= 64 ? ~0ull : ((1ull << (rem < 0 ? 0 : rem)) - 1ull);
+  };
+  struct AddRegs { LaneVar<uint64_t> nmv; LaneVar<int32_t> n0v, n1v, n2v, n3v; };
+  // NodeClaim.Add (nodeclaim.go:247-263): the claim's new state (every lane for the claim it read; lane fo's is the one)
+  auto claim_add = [&](const FastSlot& cs, int fo, AddRegs& s, FastClaim& ns) {
+    W::each([&](int l) {
+      s.nmv.at(l) = mvv.at(l) & cs.cvmask;
+      s.n0v.at(l) = q0.at(l) + cs.size[0]; s.n1v.at(l) = q1.at(l) + cs.size[1]; s.n2v.at(l) = q2.at(l) + cs.size[2]; s.n3v.at(l) = q3.at(l) + cs.size[3];
+    });
+    ns.vmask = s.nmv.bcast(fo);
+    ns.req[0] = s.n0v.bcast(fo); ns.req[1] = s.n1v.bcast(fo); ns.req[2] = s.n2v.bcast(fo); ns.req[3] = s.n3v.bcast(fo);
+  };
+  struct RefreshRegs { LaneVar<uint64_t> mlv[R], evm[R]; LaneVar<int32_t> c0[R], c1[R], c2[R], c3[R]; uint64_t rowm[R]; };
+  // refresh, first half: the cache reads. Several rows of class slots: the two predicates that need no cache entry first (the class
+  // tolerates the claim's template; on every key the class selects on the claim keeps a value) — a row in which no class passes them
+  // has no bit to compute: no cache read, no fit tests (new_slot keeps classes that exclude each other in different rows)
+  auto refresh_reads = [&](const FastClaim& ns, uint32_t tbit, RefreshRegs& g) {
+    if constexpr (R > 1) {
+      W::each([&](int l) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) g.mlv[j].at(l) = ns.vmask & cvm[j].at(l);
+      });
+#pragma unroll
+      for (int j = 0; j < R; ++j)
+        g.rowm[j] = W::ballot([&](int l) { return (tok[j].at(l) & tbit) != 0; }) &
+                    W::ballot([&](int l) { return (((g.mlv[j].at(l) & dm[j].at(l)) + dm[j].at(l)) & gd[j].at(l)) == gd[j].at(l); });
+    } else g.rowm[0] = ~0ull;
+    W::each([&](int l) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        if (R > 1 && g.rowm[j] == 0) continue;
+        const uint64_t m = ns.vmask & cvm[j].at(l);
+        const FastEnt e = ent_live(&ent[fast_hash(m)]);
+        g.mlv[j].at(l) = m; g.evm[j].at(l) = e.vmask;
+        g.c0[j].at(l) = e.cap[0]; g.c1[j].at(l) = e.cap[1]; g.c2[j].at(l) = e.cap[2]; g.c3[j].at(l) = e.cap[3];
+      }
+    });
+  };
+  // refresh, second half: CanAdd's predicates, the acceptance words; on_miss: a requirement set that is not cached
+  auto refresh_words = [&](const FastClaim& ns, uint32_t tbit, RefreshRegs& g, uint64_t (&accw)[R], auto&& on_miss) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      if (R > 1 && g.rowm[j] == 0) { accw[j] = 0; continue; }
+      // every predicate is one compare whose result is the 64-lane mask; the masks are combined in scalar registers
+      const uint64_t tokm = R > 1 ? g.rowm[j] : W::ballot([&](int l) { return (tok[j].at(l) & tbit) != 0; });
+      const uint64_t fldm = R > 1 ? ~0ull : W::ballot([&](int l) { return (((g.mlv[j].at(l) & dm[j].at(l)) + dm[j].at(l)) & gd[j].at(l)) == gd[j].at(l); });   // (several rows: inside rowm already)
+      const uint64_t simm = W::ballot([&](int l) { return g.evm[j].at(l) == g.mlv[j].at(l); });
+      const uint64_t f0 = W::ballot([&](int l) { return z0[j].at(l) <= g.c0[j].at(l) - ns.req[0]; });
+      const uint64_t f1 = W::ballot([&](int l) { return z1[j].at(l) <= g.c1[j].at(l) - ns.req[1]; });
+      const uint64_t f2 = W::ballot([&](int l) { return z2[j].at(l) <= g.c2[j].at(l) - ns.req[2]; });
+      const uint64_t f3 = W::ballot([&](int l) { return z3[j].at(l) <= g.c3[j].at(l) - ns.req[3]; });
+      const uint64_t basem = tokm & fldm, fitm = f0 & f1 & f2 & f3;
+      uint64_t accm = basem & simm & fitm;
+      const uint64_t oddm = basem & ~simm;   // set not at its first probe / not cached / an entry with further Pareto vectors (kFastExtBit)
+      if (KS_UNLIKELY(oddm != 0)) {
+        uint64_t ok2 = 0, missm = 0;
+        W::ballot2([&](int l) {
+          if (!((oddm >> l) & 1)) return 0;
+          FastEnt e;
+          if (fast_lookup(ent, g.mlv[j].at(l), e) < 0) return 2;
+          const int32_t sz[4] = {z0[j].at(l), z1[j].at(l), z2[j].at(l), z3[j].at(l)};
+          return fast_fits(pool, e, ns.req, sz) ? 1 : 0;
+        }, ok2, missm);
+        accm |= ok2;
+        if (missm) on_miss();
+      }
+      accw[j] = accm;
+    }
+  };
+  // the claim's record: its state (lane fo computed it for the claim it read) and the acceptance words
+  auto put_record = [&](int fo, LaneVar<uint32_t>& xw, AddRegs& s, const uint64_t (&accw)[R]) {
+    W::each([&](int l) {
+      if (l == fo) {
+        FastRec<R> mine;
+        mine.vmask = s.nmv.at(l); mine.req[0] = s.n0v.at(l); mine.req[1] = s.n1v.at(l); mine.req[2] = s.n2v.at(l); mine.req[3] = s.n3v.at(l);
+#pragma unroll
+        for (int j = 0; j < R; ++j) mine.acc[j] = accw[j];
+        cst.put_rec(xw.at(l), mine);
+      }
+    });
+  };
+  bool stopped = false;   // the loop left at a pod that is not plain, its pipeline registers still that pod's: the tail's
+#ifdef KSOLVE_PHASE_TIMERS
+  // profiling builds: why the loop ended, counted in tsec[4..6], three counts of 21 bits each: 0 sort-only, 1 no acceptor, 2 a move
+  // that reaches past the window, 3 a class without a slot, 4 a cancel-poll boundary, 5 the queue's last entry / its end, 6 a pending
+  // move or new claim at entry, 7 a requirement set that is not cached, 8 a count at its limit
+  auto count_exit = [&](int why) { if (W::leader()) hs->tsec[4 + why / 3] += 1ull << (21 * (why % 3)); };
+#endif
   for (;;) {   // blocks of the queue
     // entries of this block the loop may place: not the queue's last one, nor the last one before a block at which the cancel flag
     // is polled (a Solve() that ends there reports the order of the last sort the reference would have run: their move stays undone)
@@ -2117,8 +2239,7 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
       const int rws = row;
       uint64_t vm = 0;                                      // the positions of the window that exist
       auto select = [&]() {
-        const int rem = n - (int)rc0;                       // (a cursor at the end of the order: none)
-        vm = rem >= 64 ? ~0ull : ((1ull << (rem < 0 ? 0 : rem)) - 1ull);
+        vm = window_mask();
         return W::ballot([&](int l) { return (awv.at(l) & slbit) != 0; }) & vm;
       };
       uint64_t okm = select();
@@ -2200,13 +2321,8 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
       bad |= cnt >= 65534u ? ~0ull : 0ull;
       // ---- NodeClaim.Add (nodeclaim.go:247-263): the claim's new state (every lane for the claim it read; lane first_ok's is the one) ----
       FastClaim ns;
-      LaneVar<uint64_t> nmv; LaneVar<int32_t> n0v, n1v, n2v, n3v;
-      W::each([&](int l) {
-        nmv.at(l) = mvv.at(l) & cs.cvmask;
-        n0v.at(l) = q0.at(l) + cs.size[0]; n1v.at(l) = q1.at(l) + cs.size[1]; n2v.at(l) = q2.at(l) + cs.size[2]; n3v.at(l) = q3.at(l) + cs.size[3];
-      });
-      ns.vmask = nmv.bcast(first_ok);
-      ns.req[0] = n0v.bcast(first_ok); ns.req[1] = n1v.bcast(first_ok); ns.req[2] = n2v.bcast(first_ok); ns.req[3] = n3v.bcast(first_ok);
+      AddRegs nsv;
+      claim_add(cs, first_ok, nsv, ns);
       // ---- the move of the next add's sort.Slice (scheduler.go:598), decided from the counts the order read brought ----
       const uint32_t mvn = cnt + 1;
       const uint64_t lessm = W::ballot([&](int l) { return kv.at(l) < mvn; }) & vm;   // (the lanes up to first_ok are shifted out)
@@ -2240,7 +2356,7 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
         W::each([&](int l) {
           if (l == fo) {
             FastClaim mine;
-            mine.vmask = nmv.at(l); mine.req[0] = n0v.at(l); mine.req[1] = n1v.at(l); mine.req[2] = n2v.at(l); mine.req[3] = n3v.at(l);
+            mine.vmask = nsv.nmv.at(l); mine.req[0] = nsv.n0v.at(l); mine.req[1] = nsv.n1v.at(l); mine.req[2] = nsv.n2v.at(l); mine.req[3] = nsv.n3v.at(l);
             cst.put_state(xv.at(l), mine);
             W::order();
             mail_store(&mail->word[sq & 1u], (sq << 16) | xv.at(l));
@@ -2334,32 +2450,8 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
       // ---- refresh: CanAdd (nodeclaim.go:124-242) of the claim as it stands now, for the classes of all slots (lane = slot):
       // the next pod's order reads go out first, the cache reads behind them (both in flight together), then the predicates ----
       const uint32_t tbit = 1u << (uint32_t)(ns.vmask >> 56);
-      LaneVar<uint64_t> mlv[R], evm[R];
-      LaneVar<int32_t> c0[R], c1[R], c2[R], c3[R];
-      // several rows of class slots: the two predicates that need no cache entry first (the class tolerates the claim's template; on
-      // every key the class selects on the claim keeps a value) — a row in which no class passes them has no bit to compute: no cache
-      // read, no fit tests (new_slot keeps classes that exclude each other in different rows)
-      uint64_t rowm[R];
-      if constexpr (R > 1) {
-        W::each([&](int l) {
-#pragma unroll
-          for (int j = 0; j < R; ++j) mlv[j].at(l) = ns.vmask & cvm[j].at(l);
-        });
-#pragma unroll
-        for (int j = 0; j < R; ++j)
-          rowm[j] = W::ballot([&](int l) { return (tok[j].at(l) & tbit) != 0; }) &
-                    W::ballot([&](int l) { return (((mlv[j].at(l) & dm[j].at(l)) + dm[j].at(l)) & gd[j].at(l)) == gd[j].at(l); });
-      } else rowm[0] = ~0ull;
-      W::each([&](int l) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          if (R > 1 && rowm[j] == 0) continue;
-          const uint64_t m = ns.vmask & cvm[j].at(l);
-          const FastEnt e = ent_live(&ent[fast_hash(m)]);
-          mlv[j].at(l) = m; evm[j].at(l) = e.vmask;
-          c0[j].at(l) = e.cap[0]; c1[j].at(l) = e.cap[1]; c2[j].at(l) = e.cap[2]; c3[j].at(l) = e.cap[3];
-        }
-      });
+      RefreshRegs rg;
+      refresh_reads(ns, tbit, rg);
       const int fo_ = first_ok;
       LaneVar<uint32_t> xw;   // (the claim ids of this step: the record write below still needs lane first_ok's)
       W::each([&](int l) { xw.at(l) = xv.at(l); });
@@ -2368,55 +2460,25 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
       stage_a(bi + 1);      // entry bi+1 of the block (entry 64 of a full block does not exist: its values are never used)
       W::sched_fence();
       uint64_t accw[R];
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        if (R > 1 && rowm[j] == 0) { accw[j] = 0; continue; }
-        // every predicate is one compare whose result is the 64-lane mask; the masks are combined in scalar registers
-        const uint64_t tokm = R > 1 ? rowm[j] : W::ballot([&](int l) { return (tok[j].at(l) & tbit) != 0; });
-        const uint64_t fldm = R > 1 ? ~0ull : W::ballot([&](int l) { return (((mlv[j].at(l) & dm[j].at(l)) + dm[j].at(l)) & gd[j].at(l)) == gd[j].at(l); });   // (several rows: inside rowm already)
-        const uint64_t simm = W::ballot([&](int l) { return evm[j].at(l) == mlv[j].at(l); });
-        const uint64_t f0 = W::ballot([&](int l) { return z0[j].at(l) <= c0[j].at(l) - ns.req[0]; });
-        const uint64_t f1 = W::ballot([&](int l) { return z1[j].at(l) <= c1[j].at(l) - ns.req[1]; });
-        const uint64_t f2 = W::ballot([&](int l) { return z2[j].at(l) <= c2[j].at(l) - ns.req[2]; });
-        const uint64_t f3 = W::ballot([&](int l) { return z3[j].at(l) <= c3[j].at(l) - ns.req[3]; });
-        const uint64_t basem = tokm & fldm, fitm = f0 & f1 & f2 & f3;
-        uint64_t accm = basem & simm & fitm;
-        const uint64_t oddm = basem & ~simm;   // set not at its first probe / not cached / an entry with further Pareto vectors (kFastExtBit)
-        if (KS_UNLIKELY(oddm != 0)) {
-          uint64_t ok2 = 0, missm = 0;
-          W::ballot2([&](int l) {
-            if (!((oddm >> l) & 1)) return 0;
-            FastEnt e;
-            if (fast_lookup(ent, mlv[j].at(l), e) < 0) return 2;
-            const int32_t sz[4] = {z0[j].at(l), z1[j].at(l), z2[j].at(l), z3[j].at(l)};
-            return fast_fits(pool, e, ns.req, sz) ? 1 : 0;
-          }, ok2, missm);
-          accm |= ok2;
-          if (missm) { rf = x; bfx = bi + 1; }
-        }
-        accw[j] = accm;
-      }
-      // the claim's record: its state (lane first_ok computed it for the claim it read) and the acceptance words
-      W::each([&](int l) {
-        if (l == fo_) {
-          FastRec<R> mine;
-          mine.vmask = nmv.at(l); mine.req[0] = n0v.at(l); mine.req[1] = n1v.at(l); mine.req[2] = n2v.at(l); mine.req[3] = n3v.at(l);
-#pragma unroll
-          for (int j = 0; j < R; ++j) mine.acc[j] = accw[j];
-          cst.put_rec(xw.at(l), mine);
-        }
-      });
+      refresh_words(ns, tbit, rg, accw, [&]() { rf = x; bfx = bi + 1; });
+      put_record(fo_, xw, nsv, accw);
       if constexpr (FastMem<GS, R>::kStateHbm) W::hbm_sync(); else W::order();   // (LDS: no wait — it executes a wavefront's accesses in order, the reads below see these writes)
       gather();     // the next pod's claims (behind this pod's record write): in flight while the loop comes around
       bi++; steps++;
     }
-    if (bi < bf || bf < bn || rf >= 0) break;          // a pod the loop does not place / the block's last entry is not the loop's
+#ifdef KSOLVE_PHASE_TIMERS
+    if (rf >= 0) count_exit(7); else if (bi >= bf && bf < bn) count_exit(base + bn >= np ? 5 : 4);
+#endif
+    if (bi < bf || bf < bn || rf >= 0) { stopped = bi < bf && rf < 0; break; }   // a pod the loop does not place / the block's last entry is not the loop's
     // ---- the block is done: its results, the next block ----
     if (bn > 0) {
       const int dn = bn, b0 = base;
       W::each([&](int l) { if (l < dn) { gqclaim[b0 + l] = oclaim.at(l); gqcnt[b0 + l] = ocnt.at(l); } });
     }
     const int nbase = bn > 0 ? base + 64 : base;
+#ifdef KSOLVE_PHASE_TIMERS
+    if (nbase >= np || (polled && (nbase & 1023) == 0)) count_exit(nbase >= np ? 5 : 4);
+#endif
     if (nbase >= np || (polled && (nbase & 1023) == 0)) break;   // the end of the queue, a block at which the cancel flag is polled: fast_slow_run
     base = nbase;
     bn = np - base < 64 ? np - base : 64;
@@ -2424,6 +2486,141 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
     const int nb = base + 64;
     W::each([&](int l) { bcls.at(l) = nxt_cls.at(l); });
     W::each([&](int l) { if (nb + l < np) nxt_cls.at(l) = gqcls[nb + l]; });
+  }
+  // ---- the tail: four kinds of pod that are only half not-plain are finished here, behind the loop and outside its body, while the
+  // whole state is still in registers (through fast_slow_run each cost a store of the state, its reload with the classes' records,
+  // the select once more from the order, and the state stored and loaded again). The pod is the one whose pipeline registers are
+  // live (xv, kv, awv, mvv, q0..q3, rc0, slbitA, row, sl, clsw): the step's findings are computed again from them.
+  //   sort-only   a claim of the window accepts, its move is decided inside the window, and the only finding is that pdqsort leaves
+  //               its single-move path: the plain commit without the move (the claim's count at its old place), the move left
+  //               pending as fast_slow_run leaves it, FEV_SLOWSORT;
+  //   long move   a claim of the window accepts and its move is not decided inside the window: the same commit, then the pending
+  //               move as fast_slow_run's next turn resolves it — FEV_SLOWSORT, or the one stable move here and FEV_CONT;
+  //   new claim   the class has a slot and no claim from its cursor to the end of the order accepts — the window reaches the end, or
+  //               the four-window scan ran to the end (had it found a window, the select there would not be empty): the cursor goes
+  //               to the end, FEV_NEWCLAIM;
+  //   no slot     the pod's class has no slot: FEV_SLOT, nothing else (fast_slow_run did nothing but find that out).
+  // A count at its limit stays fast_slow_run's, and so does whatever the loop does not meet as a pod of its own: the entries in front
+  // of a cancel-poll block and the queue's last one, a move or a new claim pending at entry, the step limit, the two-wavefront form.
+  int ev = FEV_SLOW, ev_arg = 0;
+  int pa = -1, px = 0; uint32_t pmv = 0;     // a move this function leaves pending
+  unsigned long long n_more = 0;             // select steps beyond the first that fast_slow_run counts for the tail's pod (64 positions each, from the class's cursor)
+  // THE INVARIANT of n_steps (the reported fullEvaluations): it is what the engine counted when every pod that is not plain went
+  // through fast_slow_run — one per 64 positions for the pods that function placed (n_more here), four per 256 for the loop's scans,
+  // and the loop's only in a run that came forward. `behind_first` exists for this count alone: it says where fast_slow_run would
+  // have left the queue before this run (profiles/loop_events/README.md, "The count that stays").
+  // The loop itself came forward: only then are its four-window steps counted — as before, and "before" a run behind the tail began
+  // elsewhere: behind its FEV_CONT (1) one pod later (fast_slow_run had placed that pod, which needs no scan: the tail made sure);
+  // behind its commit of a block's last entry (2) at the next block's first entry (fast_slow_run had switched blocks on its way out)
+  const bool placed = behind_first == 2 ? (bi != 0 || base != base_in + 64)
+                                        : (bi != bi_in || base != base_in) && !(behind_first == 1 && bi == bi_in + 1 && base == base_in);
+  if constexpr (!HP) if (stopped) {
+    const int slot = row * 64 + sl;
+    const uint64_t slbit = slbitA;
+    const uint64_t vm = window_mask();
+    const uint64_t okm = W::ballot([&](int l) { return (awv.at(l) & slbit) != 0; }) & vm;
+    uint32_t cur0 = cur[0].bcast(sl);      // the class's cursor as the step found it (rc0 is the window that holds the acceptor)
+#pragma unroll
+    for (int j = 1; j < R; ++j) { const uint32_t cj = cur[j].bcast(sl); cur0 = row == j ? cj : cur0; }
+    const uint32_t lastm = (uint32_t)((int32_t)clsw >> 31);   // all ones on the class's last entry: its slot is free after it
+    const int first_ok = ctz64(okm | (1ull << 63));
+    const int a = (int)rc0 + first_ok;
+    const int x = (int)xv.bcast(first_ok);
+    const uint32_t cnt = kv.bcast(first_ok);
+    const uint32_t mvn = cnt + 1;
+    const uint64_t lessm = W::ballot([&](int l) { return kv.at(l) < mvn; }) & vm;
+    const int sm = ctz64(~((lessm >> 1) >> first_ok));
+    const bool reach = first_ok + 1 + sm >= 64;
+#ifdef KSOLVE_PHASE_TIMERS
+    count_exit(slbit == 0 ? 3 : okm == 0 ? 1 : cnt >= 65534u ? 8 : reach ? 2 : 0);
+#endif
+    if (okm == 0) {
+      if ((KSOLVE_LOOP_TAIL & 2) != 0 && slbit != 0) {
+        // no in-flight claim accepts the pod: addToNewNodeClaim; the driver moves on to the next pod
+        const bool inside = (int)cur0 < n;
+        const uint32_t nr = inside ? (uint32_t)n : cur0;
+        n_more = inside ? (unsigned long long)((n - (int)cur0 + 63) / 64 - 1) : 0ull;
+        W::each([&](int l) {
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            const bool me = j * 64 + l == slot;
+            cur[j].at(l) = me ? nr : cur[j].at(l);
+            scls[j].at(l) |= me ? lastm : 0u;
+          }
+        });
+        steps++;
+        ev = FEV_NEWCLAIM; ev_arg = slot;
+      } else if ((KSOLVE_LOOP_TAIL & 4) != 0 && slbit == 0) {
+        // the class has no slot: the driver gives it one and the loop comes back to this pod (nothing changes here)
+        ev = FEV_SLOT; ev_arg = (int)(clsw & ~kFastLastBit);
+      }
+    } else if ((KSOLVE_LOOP_TAIL & (reach ? 8 : 1)) != 0 && cnt < 65534u) {
+      // A claim accepts and its count has room: the step was not plain because of the move alone — pdqsort's other paths, or a move
+      // that is not decided inside the window. The plain commit without the move, then the pending move as fast_slow_run resolves it.
+      const FastSlot cs = lds_get(&aslot[slot]);
+      FastClaim ns;
+      AddRegs nsv;
+      claim_add(cs, first_ok, nsv, ns);
+      {
+        const int bb = bi;
+        W::each([&](int l) {
+          const bool mine = l == bb;
+          oclaim.at(l) = mine ? (uint32_t)x : oclaim.at(l); ocnt.at(l) = mine ? cnt : ocnt.at(l);
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            const bool me = j * 64 + l == slot;
+            const uint32_t fm = me ? lastm : 0u;
+            cur[j].at(l) = me ? (uint32_t)a : cur[j].at(l);
+            scls[j].at(l) |= fm; tok[j].at(l) &= ~fm;
+          }
+        });
+      }
+      n_ref += (unsigned long long)((uint32_t)a + 1u);
+      n_more = (unsigned long long)(((uint32_t)a - cur0) >> 6);
+      const uint32_t tbit = 1u << (uint32_t)(ns.vmask >> 56);
+      RefreshRegs rg;
+      refresh_reads(ns, tbit, rg);
+      uint64_t accw[R];
+      refresh_words(ns, tbit, rg, accw, [&]() { rf = x; });
+      {
+        const int rb = (int)rc0, fo = first_ok;
+        W::each([&](int l) { if (l == fo) okey[rb + l] = (uint16_t)(kv.at(l) + 1u); });   // the new count; no entry moves
+      }
+      put_record(first_ok, xv, nsv, accw);
+      if constexpr (FastMem<GS, R>::kOrderHbm || FastMem<GS, R>::kStateHbm) W::hbm_sync();
+      bi++; steps++;
+      pa = a; px = x; pmv = mvn;
+      // (a requirement set that is not cached: the driver computes the claim's words first, the move stays pending for fast_slow_run)
+      if (rf < 0) {
+        W::sync();
+        const bool movable = a + 1 < n && (uint32_t)okey[a + 1 < n ? a + 1 : a] < mvn;          // something to move ...
+        if (movable && !(n <= 12 || (n >= 50 && !fast_sampled(n, a)))) { ev = FEV_SLOWSORT; ev_arg = a; }   // ... and not by the single stable move
+        else {
+          // (only a move that reaches past the window comes here: the loop makes every other single move itself)
+          const int b = movable ? fast_stable_move<W>(okey, oord, n, a, mvn, x) : a;   // positions (a, b] moved left by one
+          if (b != a) {
+            W::each([&](int l) {
+#pragma unroll
+              for (int j = 0; j < R; ++j) { const uint32_t r = cur[j].at(l); cur[j].at(l) = r - (uint32_t)(((uint32_t)a < r && r <= (uint32_t)b) ? 1 : 0); }
+            });
+          }
+          pa = -1;
+          // fast_slow_run went on to place the NEXT pod in the same call, and the select steps it counts (one per 64 positions) are
+          // not the loop's (four per 256): the loop takes that pod only where both count nothing — the loop may place it, it is not
+          // its block's last entry (whose move fast_slow_run always leaves pending, going on once more), its class has a slot and a
+          // claim of the window at its cursor accepts it. Otherwise fast_slow_run places it, as before — unless its class has no slot,
+          // which is all fast_slow_run would find out.
+          if (bi < bn) {
+            stage_a(bi);
+            if (slbitA == 0) { if ((KSOLVE_LOOP_TAIL & 4) != 0) { ev = FEV_SLOT; ev_arg = (int)(clsw & ~kFastLastBit); } }
+            else if (bi < bn - ((base + bn >= np || (polled && ((base + 64) & 1023) == 0)) ? 1 : 0) && bi + 1 < bn) {
+              gather();
+              if ((W::ballot([&](int l) { return (awv.at(l) & slbitA) != 0; }) & window_mask()) != 0) ev = FEV_CONT;
+            }
+          }
+        }
+      }
+    }
   }
   // ---- two wavefronts: nothing stays in flight between two runs of this loop; a miss the refresher reported is the driver's ----
   int rf2 = -1;
@@ -2442,16 +2639,23 @@ KS_COLD int fast_hot_run(FastHotCtx<GS, R> cx) {
 #endif
   }
   // ---- state out (only what this function changes) ----
-  if (bi != bi_in || base != base_in) {
-    if (W::leader()) { hs->base = base; hs->bi = bi; hs->bn = bn; hs->steps = steps; hs->n_ref = n_ref; hs->rf_x = rf; hs->rf_x2 = rf2; hs->n_steps += 4 * n_ext; }
+  if (bi != bi_in || base != base_in || ev == FEV_NEWCLAIM) {
+    if (W::leader()) {
+      hs->base = base; hs->bi = bi; hs->bn = bn; hs->steps = steps; hs->n_ref = n_ref; hs->rf_x = rf; hs->rf_x2 = rf2; hs->n_steps += (placed ? 4 * n_ext : 0ull) + n_more;
+      if (pa >= 0) { hs->pend_a = pa; hs->pend_x = px; hs->pend_mv = pmv; }
+      hs->ev_arg = ev_arg;
+    }
     W::each([&](int l) {
 #pragma unroll
       for (int j = 0; j < R; ++j) { hs->cur[j][l] = cur[j].at(l); hs->scls[j][l] = scls[j].at(l); }
       hs->nxt_cls[l] = nxt_cls.at(l); hs->bcls[l] = bcls.at(l); hs->oclaim[l] = oclaim.at(l); hs->ocnt[l] = ocnt.at(l);
     });
     W::sync();
+  } else if (ev != FEV_SLOW) {   // (FEV_SLOT at the pod the run began with: the state stands as it is in LDS)
+    if (W::leader()) hs->ev_arg = ev_arg;
+    W::sync();
   }
-  return FEV_SLOW;
+  return ev;
 }
 
 // The driver: runs the loop, handles its events through FastCold.
@@ -2497,12 +2701,15 @@ struct FastEngine {
     unsigned long long t_fast = 0, n_fast = 0, t_slow = 0, n_slow = 0;   // profiling builds: shader clock inside the two loops, calls of each
     const unsigned long long t_begin = W::clock();
     const bool use_fast = fast_uniform(h->max_steps) < 0;   // (a step limit — tests — is counted by the general loop)
+    int behind_first = 0;
     for (;;) {
       const unsigned long long tf0 = W::clock();
       // (a new claim waits for its place in the order and the next pod is inside the current block — no block switch, no cancel poll
       // stands before the sort: the driver's event at once, without a turn through fast_slow_run)
       const bool place_now = use_fast && fast_uniform(h->pend_new) != 0 && fast_uniform(h->bi) < fast_uniform(h->bn) && fast_uniform(h->status) == 0;
-      int ev = place_now ? (int)FEV_PLACE : use_fast ? fast_uniform(fast_hot_run<W, GS, R, HP>(cx)) : (int)FEV_SLOW;
+      int ev = place_now ? (int)FEV_PLACE : use_fast ? fast_uniform(fast_hot_run<W, GS, R, HP>(cx, behind_first)) : (int)FEV_SLOW;
+      // (from the fast loop's tail — 1: a long move made there, the next pod is the loop's; 2: it committed its block's last entry)
+      behind_first = !(use_fast && !place_now) ? 0 : ev == FEV_CONT ? 1 : (ev == FEV_SLOWSORT && fast_uniform(h->bi) >= fast_uniform(h->bn)) ? 2 : 0;
       t_fast += W::clock() - tf0; n_fast++;
       if (HP && ev == FEV_DEAD) { cold.bail_code = DECLINE_REFRESHER_DEAD; cold.finish(3, 0, 0, 0, 0, 0, nullptr); return; }   // (the refresher wavefront does not answer)
       if (use_fast && fast_uniform(h->rf_x) >= 0) {

@@ -2800,6 +2800,8 @@ static char* results_json(Session* S, ksolve_results& res, ksolve_status st, int
     counters.set("topologyGroups", Value::integer(S->n_topo_groups)); counters.set("topologyAliasClasses", Value::integer(S->n_alias_classes));
     counters.set("reqWords", Value::integer(rw)); counters.set("itWords", Value::integer(it_words)); counters.set("keys", Value::integer(nk)); counters.set("resources", Value::integer(n_res));
     { Value pc = Value::array(); for (int i = 0; i < 24; ++i) pc.push(Value::integer((int64_t)res.phase_cycles[i])); counters.set("phaseCycles", pc); }
+    // the cursor engine's driver reports how often it ran its one-pod loop (fast_slow_run) in slot 11 of phase_cycles, in every build
+    if (res.engine_used == 2) counters.set("onePodLoopCalls", Value::integer((int64_t)res.phase_cycles[11]));
     out.set("counters", counters);
     out.set("timings", timings);
     out.set("timedOut", Value::boolean(st == KSOLVE_ERR_CANCELLED));
