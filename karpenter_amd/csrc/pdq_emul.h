@@ -537,4 +537,41 @@ struct RegOrder {
   KS_FN void sort() { PdqSort<RegOrder>::sort(*this); }
 };
 
+// arr[b+1 .. a] = arr[b .. a-1] for an LDS-resident array of 16-bit entries, 512 entries per step: every lane takes a 16-byte
+// piece (eight entries), shifts it by one entry through its registers (the entry that crosses into the piece comes from the lane
+// below it) and writes it back in place — from the top piece down, so that a step reads nothing an earlier step wrote. The
+// one-entry-per-lane move this replaces cost a new claim's sort.Slice 43 dependent read-write rounds at 2,763 claims.
+template <class W>
+KS_DEV void shift_right16(KS_LDS uint16_t* arr, int b, int a) {
+  KS_LDS u32x4_alias* const v = (KS_LDS u32x4_alias*)arr;
+  const KS_LDS uint32_t* const dw = (const KS_LDS uint32_t*)arr;
+  for (int e0 = a & ~511; e0 >= 0 && e0 + 511 >= b; e0 -= 512) {
+    LaneVar<uint32_t> d0, d1, d2, d3, pv;
+    const uint32_t below = e0 > 0 ? dw[(e0 >> 1) - 1] : 0u;      // the two entries under the step's first piece
+    W::each([&](int l) {
+      const int e = e0 + 8 * l;
+      d0.at(l) = 0; d1.at(l) = 0; d2.at(l) = 0; d3.at(l) = 0;
+      if (e <= a && e + 7 >= b) { const u32x4_alias x = v[(e0 >> 3) + l]; d0.at(l) = x[0]; d1.at(l) = x[1]; d2.at(l) = x[2]; d3.at(l) = x[3]; }
+    });
+    // (the exchange runs on EVERY lane, then lane 0 takes the word below the step: a lane that is switched off during ds_bpermute
+    // reads as zero for its neighbour — the first build had the exchange inside the select and lane 1 got a zero from lane 0)
+    LaneVar<uint32_t> up;
+    W::each([&](int l) { up.at(l) = d3.shuffle(l, (l + 63) & 63); });
+    W::each([&](int l) { pv.at(l) = l ? up.at(l) : below; });
+    W::each([&](int l) {
+      const int e = e0 + 8 * l;
+      if (!(e <= a && e + 7 > b)) return;
+      auto mix = [&](uint32_t cur, uint32_t prev, int elo) {   // entries elo (low half) and elo + 1 (high half) of one word
+        const uint32_t sh = (cur << 16) | (prev >> 16);
+        const uint32_t m = ((elo > b && elo <= a) ? 0xFFFFu : 0u) | ((elo + 1 > b && elo + 1 <= a) ? 0xFFFF0000u : 0u);
+        return (sh & m) | (cur & ~m);
+      };
+      u32x4_alias y;
+      y[0] = mix(d0.at(l), pv.at(l), e); y[1] = mix(d1.at(l), d0.at(l), e + 2); y[2] = mix(d2.at(l), d1.at(l), e + 4); y[3] = mix(d3.at(l), d2.at(l), e + 6);
+      v[(e0 >> 3) + l] = y;
+    });
+    W::sync();
+  }
+}
+
 }  // namespace ks

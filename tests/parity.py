@@ -44,6 +44,33 @@ def build_hooks():
     return HOOKS_LIB
 
 
+def build_wave_order(kind):
+    """tests/emu/wave_order_probe.cpp, the wavefront primitives and the claim orders alone, compiled one of three ways (seconds each):
+    "dev" — hipcc for gfx950, tests/emu/libwave_order_dev.so (kernels of one wavefront); "host" / "host_reversed" — g++ with the
+    loop-over-lanes Wave, in either lane order, tests/emu/libwave_order_host[_reversed].so. Built when missing or stale."""
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    src = os.path.join(here, "emu", "wave_order_probe.cpp")
+    csrc = os.path.join(root, "karpenter_amd", "csrc")
+    deps = [src, os.path.join(root, "include", "ksolve.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    lib = os.path.join(here, "emu", {"dev": "libwave_order_dev.so", "host": "libwave_order_host.so", "host_reversed": "libwave_order_host_reversed.so"}[kind])
+    if kind == "dev":
+        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"]
+    else:
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DKSOLVE_HOST_EMULATION"] + (["-DKS_EMU_REVERSE_LANES"] if kind == "host_reversed" else [])
+    stale = lambda: not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps)
+    if stale():
+        import fcntl
+        with open(lib + ".lock", "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if stale():
+                tmp = lib + f".{os.getpid()}.tmp"
+                subprocess.check_call(cmd + ["-o", tmp, src])
+                os.replace(tmp, lib)
+    return lib
+
+
 def canon_req(r):
     return (r["key"], r["complement"], tuple(sorted(r["values"])), r["gte"], r["lte"], r["minValues"])
 

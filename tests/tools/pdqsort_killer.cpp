@@ -4,6 +4,7 @@
 // ("gas") until a comparison needs it, and is then frozen at the lowest value still free, so that every pivot ends up among the
 // smallest keys of its range. A tool, not a test:
 //     g++ -O2 -std=c++17 -o /tmp/pdqsort_killer tests/tools/pdqsort_killer.cpp && /tmp/pdqsort_killer 1000 2 > tests/golden/pdqsort_killer_1000.json
+// (`pdqsort_killer 64 2` made tests/golden/pdqsort_killer_64.json: heap_sort within the 64 claims RegOrder holds, tests/wave_order_cases.py.)
 // It prints to stderr how many comparisons the replay of the finished keys takes (25,744 at 1,000 keys, against some 7,000 where the
 // allowance is never used up). tests/tools/result_mutations.py shows that the heapsort runs: without it the case `heapsort` fails.
 #define KSOLVE_HOST_EMULATION 1
