@@ -729,6 +729,23 @@ static void be_launch_pack_fast(ksolve_handle* h) {
   hipLaunchKernelGGL(fn, dim3(1), dim3(two ? 256 : 64), (size_t)lds_bytes, HB(h)->stream, (const ks::FastArgs*)h->d_fast_args);
   hip_check(h, hipGetLastError(), "ksolve_pack_fast launch");
 }
+#ifdef KSOLVE_TEST_HOOKS
+// FastCold alone (fast_cold_probe.h): the instantiations ksolve_test_fast_cold.hip compiles, on the LDS segment of the handle's plan
+static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* d_args, int plan, int rows, int flavour) {
+  typedef void (*fn_t)(const ks::FastColdArgs*);
+  fn_t fn = nullptr;
+  if (plan == 0 && rows == 1) fn = flavour == 2 ? ksolve_test_fast_cold_p_g0r1 : flavour == 1 ? ksolve_test_fast_cold_u_g0r1 : ksolve_test_fast_cold_g0r1;
+  else if (plan == 0) fn = flavour == 2 ? ksolve_test_fast_cold_p_g0r4 : flavour == 1 ? ksolve_test_fast_cold_u_g0r4 : ksolve_test_fast_cold_g0r4;
+  else if (plan == 1 && rows == 1 && flavour == 0) fn = ksolve_test_fast_cold_g1r1;
+  else if (plan == 2 && rows == ks::kFastRows && flavour == 1) fn = ksolve_test_fast_cold_u_g2r4;
+  if (!fn) return 0;
+  const int lds_bytes = h->fw.plan.total_bytes;
+  if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return 0;
+  hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, d_args);
+  hip_check(h, hipGetLastError(), "ksolve_test_fast_cold launch");
+  return (uint32_t)(flavour * 100 + plan * 10 + rows);
+}
+#endif
 static void launch_pack_topo(ksolve_handle* h, void (*fn)(const ks::TopoArgs*), const char* what) {
   const int lds_bytes = h->tw.plan.total_bytes;
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
@@ -1033,6 +1050,10 @@ ksolve_status ksolve_test_eff_alloc(ksolve_test_eff_alloc_io* io) {
 // the cursor engine's claim records and the scatter of the queue's results alone (ksolve_impl.h test_fast_records)
 ksolve_status ksolve_test_fast_records(const ksolve_test_fast_records_in* in, ksolve_test_fast_records_out* out) {
   return test_on_bare_handle("ksolve_test_fast_records", [&](ksolve_handle* h) { return ksi::test_fast_records(h, in, out); });
+}
+// the cold half of the cursor engine alone (ksolve_impl.h test_fast_cold, fast_cold_probe.h)
+ksolve_status ksolve_test_fast_cold(const ksolve_test_fast_cold_in* in, ksolve_test_fast_cold_out* out) {
+  return test_on_bare_handle("ksolve_test_fast_cold", [&](ksolve_handle* h) { return ksi::test_fast_cold(h, in, out); });
 }
 #endif
 ksolve_status ksolve_probe_create(ksolve_handle* base, const ksolve_probe* probe, ksolve_handle** out) {

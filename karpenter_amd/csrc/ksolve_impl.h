@@ -19,6 +19,7 @@
 #include "engine.h"
 #include "kernels.h"
 #include "fast_engine.h"
+#include "fast_cold_probe.h"   // (test builds only; empty otherwise)
 #include "node_stage.h"
 #include "topo_types.h"
 
@@ -350,6 +351,63 @@ typedef struct {
   int32_t* assign; uint32_t* slot;                 // [n_pods]
 } ksolve_test_fast_records_out;
 
+// ksolve_test_fast_cold — TEST BUILDS ONLY: the cold half of the cursor engine (fast_engine.h FastCold: setup(), compat_word, offering_cells,
+// create_entry, fast_lookup / fast_fits / fast_fields_ok, new_slot, new_claim, refresh_claim, filter_diag) alone, on raw host tables. The
+// hook builds the least of ProblemView, Workspace and FastWork the cold code reads, sized and cleared as create() and solve_prepare() do,
+// runs the product's own be_launch_it_index and be_launch_eff_alloc on the tables, lays the LDS out by fast_plan_set, and launches ONE
+// wavefront (fast_cold_probe.h): setup(), then the script. Every index the script and the tables make the kernel form is checked here
+// first. The buffers the probe writes start as bytes of 0xA5. tests/fast_cold_cases.py holds the definition.
+typedef struct {
+  uint32_t n_keys; const uint32_t* key_word_off;
+  const int64_t* value_int;
+  const uint64_t *value_is_int, *value_valid;
+  int32_t key_zone, key_ct, key_it, key_hostname;  // -1: no such key (key_it: required, its dictionary is the type list)
+  uint32_t well_known_mask;
+  uint32_t n_its, n_res, n_zones, n_cts;
+  uint32_t plain, plain_nodes, plain_ops;          // ProblemView's flags
+  const ksolve_reqsets* it_reqs;                   // n_its rows
+  const int64_t* it_alloc;                         // [n_res][n_its]
+  const int64_t* it_cap;                           // [n_res][n_its] (NodePool limits count capacity)
+  const uint64_t* it_off_avail;                    // [n_its] bit zone * 4 + capacity type
+  uint32_t n_templates;
+  const ksolve_reqsets* tmpl_reqs;                 // n_templates rows
+  const uint64_t* tmpl_its;                        // [n_templates][it_words]
+  const uint64_t* tmpl_taints;                     // [n_templates]
+  const int64_t* tmpl_limits;                      // [n_templates][n_res + 1]
+  const uint32_t* tmpl_limit_mask;                 // [n_templates]
+  uint32_t tmpl_ov;                                // templates with daemon overhead; the groups below are read when it is not 0
+  const int32_t* dg_first;                         // [n_templates + 1]
+  const int64_t* dg_ov;                            // [n_dg][n_res]
+  const uint64_t* dg_its;                          // [n_dg][it_words]
+  uint32_t n_classes;
+  const ksolve_reqsets* cls_reqs;                  // n_classes rows
+  const int64_t* cls_requests;                     // [n_classes][n_res]
+  const uint64_t* cls_tolerates;                   // [n_classes]
+  uint32_t ops, lim;                               // FastWork::ops; FastWork::lim present
+  uint32_t rows, plan, flavour;                    // 1 | 4; 0..2; 0 plain, 1 the set-aside list (FastWork::unsched), 2 pod operators as well (FastWork::podops)
+  uint32_t max_claims, cap;                        // Workspace::max_claims; FastPlan::cap is cut to `cap` when that is smaller (0: the plan's own)
+  uint32_t n_ops; const ks::FastColdOp* script;
+} ksolve_test_fast_cold_in;
+// every table is the caller's
+typedef struct {
+  uint32_t kernel;                                 // flavour * 100 + plan * 10 + rows of the instantiation that ran; + 1000 on the host emulation
+  uint32_t it_words, misc_words, cap, t_rows;
+  ks::FastColdScal* scal;                          // [2] behind setup(), behind the script
+  uint64_t* misc;                                  // [2][misc_words] FastMisc
+  ks::FastVar* var; ks::FastPodOps* podops; ks::FastLimits* lim;   // [1] each (podops / lim: untouched without the switch)
+  uint64_t* cls;                                   // [n_classes][5] FastWork::cls
+  uint64_t* t_its;                                 // [t_rows][it_words], t_rows = 32 with lim, n_templates otherwise
+  int64_t* t_remaining;                            // [n_templates][n_res + 1]
+  int64_t* it_eff;                                 // [n_templates][n_res][n_its] (tmpl_ov != 0 only)
+  uint64_t* ent; int32_t* pool;                    // [1024][4], [256][4]
+  uint64_t* ent_its;                               // [1024][it_words]
+  uint64_t* rec;                                   // [max_claims][3 + rows]
+  uint32_t* c_hostseq;                             // [max_claims]
+  uint64_t* aslot; uint32_t *scls, *cur;           // [64 rows][5], [4][64], [4][64]
+  uint64_t* us_cls;                                // [n_classes] (flavours 1, 2)
+  ks::FastColdRes* res; uint64_t* compat;          // [n_ops], [n_ops][it_words]
+} ksolve_test_fast_cold_out;
+
 namespace ks {
 struct ReqalgTestArgs {
   Dict dict;
@@ -417,6 +475,8 @@ struct PhaseRange { ksolve_handle* h; bool open; ~PhaseRange() { if (open) be_ra
 static void be_launch_it_index(ksolve_handle* h, int n, const ks::ItIndexArgs& a);
 #ifdef KSOLVE_TEST_HOOKS
 static void be_launch_reqalg_test(ksolve_handle* h, int n, const ks::ReqalgTestArgs& a);   // one thread per pair: reqalg_test_body
+// one wavefront: fast_cold_probe_body of the instantiation (plan, rows, flavour); returns ksolve_test_fast_cold_out::kernel, 0: no such instantiation in this build
+static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* d_args, int plan, int rows, int flavour);
 #endif
 static void be_launch_row_hash(ksolve_handle* h, int n, const ks::RowArgs& a);
 static void be_launch_row_class(ksolve_handle* h, int n, const ks::RowArgs& a);
@@ -1813,6 +1873,158 @@ static ksolve_status test_fast_records(ksolve_handle* h, const ksolve_test_fast_
     }
   }
   return KSOLVE_OK;
+}
+// FastCold alone (see ksolve_test_fast_cold_in): the tables as create() uploads them, the instance-type index and the effective
+// allocatable by the product's own launches, the workspace as create() and fast_shared_alloc() size it, the LDS plan of fast_plan_set.
+static ksolve_status test_fast_cold(ksolve_handle* h, const ksolve_test_fast_cold_in* in, ksolve_test_fast_cold_out* out) {
+  const char* who = "test_fast_cold";
+  if (!in || !out || !in->it_reqs || !in->it_reqs->mask || !in->it_reqs->defined || !in->it_reqs->complement || !in->it_alloc || !in->it_cap || !in->it_off_avail ||
+      !in->tmpl_reqs || !in->tmpl_reqs->mask || !in->tmpl_reqs->defined || !in->tmpl_reqs->complement || !in->tmpl_its || !in->tmpl_taints || !in->tmpl_limits || !in->tmpl_limit_mask ||
+      !in->cls_reqs || !in->cls_reqs->mask || !in->cls_reqs->defined || !in->cls_reqs->complement || !in->cls_requests || !in->cls_tolerates || (in->n_ops && !in->script) ||
+      !out->scal || !out->misc || !out->var || !out->podops || !out->lim || !out->cls || !out->t_its || !out->t_remaining || !out->ent || !out->pool || !out->ent_its || !out->rec ||
+      !out->c_hostseq || !out->aslot || !out->scls || !out->cur || !out->us_cls || !out->res || !out->compat || (in->tmpl_ov && (!in->dg_first || !in->dg_ov || !in->dg_its || !out->it_eff)))
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: missing table");
+  const uint32_t nk = in->n_keys, n_its = in->n_its, nr = in->n_res, nt = in->n_templates, nc = in->n_classes, n_ops = in->n_ops, mc = in->max_claims;
+  if (n_its < 1 || nr < 1 || nr > (uint32_t)kMaxRes || nt < 1 || nt > 64 || nc < 1 || nc > 32768 || in->n_zones < 1 || in->n_zones > 16 || in->n_cts < 1 || in->n_cts > 4 ||
+      (in->rows != 1 && in->rows != (uint32_t)ks::kFastRows) || in->plan > 2 || in->flavour > 2 || mc < 1 || mc > 65472 || n_ops > 65536)
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: sizes out of range");
+  const uint32_t iw = (n_its + 63) / 64;
+  if (iw > (uint32_t)kMaxItWords) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: more than 2048 instance types");
+  for (const ksolve_reqsets* r : {in->it_reqs, in->tmpl_reqs, in->cls_reqs}) {
+    const uint32_t n = r == in->it_reqs ? n_its : r == in->tmpl_reqs ? nt : nc;
+    if ((!r->gte && any_nonzero(r->has_gte, n)) || (!r->lte && any_nonzero(r->has_lte, n))) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: a has_gte / has_lte bit without the bounds column");
+  }
+  ks::Dict dict{};
+  if (ksolve_status st = test_dict(h, who, nk, in->key_word_off, in->value_int, in->value_is_int, in->value_valid, dict)) return st;
+  const uint32_t rw = (uint32_t)dict.req_words;
+  auto one_word = [&](int32_t k) { return k >= 0 && dict.key_word_off[k + 1] - dict.key_word_off[k] == 1; };
+  if (in->key_it < 0 || in->key_it >= (int32_t)nk || dict.key_word_off[in->key_it + 1] - dict.key_word_off[in->key_it] != iw)
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: instance-type key dictionary must be the instance type list");
+  if (in->key_zone >= (int32_t)nk || in->key_ct >= (int32_t)nk || in->key_hostname >= (int32_t)nk || in->key_zone < -1 || in->key_ct < -1 || in->key_hostname < -1 ||
+      (in->key_zone >= 0 && !one_word(in->key_zone)) || (in->key_ct >= 0 && !one_word(in->key_ct)))
+    return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: zone / capacity-type / hostname key outside the keys or wider than one word");
+  dict.key_it = in->key_it; dict.key_zone = in->key_zone; dict.key_ct = in->key_ct; dict.key_hostname = in->key_hostname; dict.well_known_mask = in->well_known_mask;
+  uint32_t n_dg = 0;
+  if (in->tmpl_ov) {
+    if (nt > 32 || (nt < 32 && (in->tmpl_ov >> nt))) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: tmpl_ov names a template that is not there");
+    if (ksolve_status st = test_groups(h, who, nt, in->dg_first, n_dg)) return st;
+    for (uint32_t t = 0; t < nt; ++t) if (((in->tmpl_ov >> t) & 1u) && in->dg_first[t + 1] == in->dg_first[t]) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: a template of tmpl_ov without a group");
+  }
+  // the script: every class, claim and template id it names
+  for (uint32_t i = 0; i < n_ops; ++i) {
+    const ks::FastColdOp& o = in->script[i];
+    const bool by_vm = o.op >= ks::FCOP_ENTRY && o.op <= ks::FCOP_DIAG, by_k = o.op >= ks::FCOP_SLOT && o.op <= ks::FCOP_ADD;
+    if (!by_vm && !by_k) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: unknown operation");
+    // (a limit stage's id is handed out by the kernel: a script may name ids up to 31 only where stages can exist, and the kernel
+    // refuses one it has not handed out, -3)
+    if (by_vm && (o.vm >> 56) >= (in->lim ? 32u : nt)) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: a requirement set's template outside the templates");
+    if (o.op == ks::FCOP_DIAG && in->flavour < 1) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: filter_diag without the set-aside list");
+    if (by_k && (o.k < 0 || o.k >= (int32_t)nc)) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: a class outside the classes");
+    if (o.op == ks::FCOP_ADD && (o.x < 0 || o.x >= (int32_t)mc)) return fail(h, KSOLVE_ERR_INVALID, "test_fast_cold: a claim outside the claims");
+  }
+  h->n_keys = nk; h->req_words = rw; h->n_res = nr; h->n_its = n_its; h->it_words = iw; h->n_pods = nc; h->n_rows = nc; h->n_classes = nc; h->n_templates = nt;
+  ks::ProblemView& P = h->pv;
+  ks::Workspace& W = h->ws;
+  ks::FastWork& fw = h->fw;
+  P.dict = dict; P.n_res = (int)nr; P.n_its = (int)n_its; P.it_words = (int)iw; P.n_zones = (int)in->n_zones; P.n_cts = (int)in->n_cts;
+  P.lay = ks::RecLayout{(int)rw, (int)iw, (int)nr, (int)nk};
+  P.it_reqs = upload_reqs(h, *in->it_reqs, n_its, rw, nk);
+  P.it_alloc = up(h, in->it_alloc, (size_t)nr * n_its);
+  P.it_cap = up(h, in->it_cap, (size_t)nr * n_its);
+  P.it_off_avail = up(h, in->it_off_avail, n_its);
+  {
+    uint32_t it_keys = 0;   // as create() has it
+    for (uint32_t i = 0; i < n_its; ++i) it_keys |= in->it_reqs->defined[i];
+    P.it_keys = it_keys & ~(1u << in->key_it);
+  }
+  uint64_t* kv_has = dz<uint64_t>(h, (size_t)rw * 64 * iw);
+  uint64_t* key_undef = dz<uint64_t>(h, (size_t)nk * iw);
+  uint64_t* key_compl = dz<uint64_t>(h, (size_t)nk * iw);
+  uint64_t* key_neg = dz<uint64_t>(h, (size_t)nk * iw);
+  uint64_t* alloc_ok = dz<uint64_t>(h, iw);
+  const ks::ItIndexArgs IA{dict, (int)n_its, (int)iw, (int)nr, P.it_reqs, P.it_alloc, kv_has, key_undef, key_compl, key_neg, alloc_ok, dz<uint32_t>(h, 1)};
+  P.kv_has = kv_has; P.key_undef = key_undef; P.key_compl = key_compl; P.key_neg = key_neg; P.it_alloc_ok = alloc_ok;
+  P.n_templates = (int)nt;
+  P.tmpl_reqs = upload_reqs(h, *in->tmpl_reqs, nt, rw, nk);
+  P.tmpl_its = up(h, in->tmpl_its, (size_t)nt * iw);
+  P.tmpl_taints = up(h, in->tmpl_taints, nt);
+  P.tmpl_limits = up(h, in->tmpl_limits, (size_t)nt * (nr + 1));
+  P.tmpl_limit_mask = up(h, in->tmpl_limit_mask, nt);
+  P.n_pods = (int)nc; P.n_rows = (int)nc; P.n_classes = (int)nc;
+  P.cls_reqs = upload_reqs(h, *in->cls_reqs, nc, rw, nk);
+  P.cls_requests = up(h, in->cls_requests, (size_t)nc * nr);
+  P.cls_tolerates = up(h, in->cls_tolerates, nc);
+  P.plain = in->plain ? 1 : 0; P.plain_nodes = in->plain_nodes ? 1 : 0; P.plain_ops = in->plain_ops ? 1 : 0;
+  P.tmpl_ov = in->tmpl_ov;
+  int64_t* eff = nullptr;
+  ks::EffAllocArgs EA{};
+  if (in->tmpl_ov) {
+    eff = dz<int64_t>(h, (size_t)nt * nr * n_its);
+    P.it_eff = eff;
+    P.dg_first = up(h, (const int*)in->dg_first, nt + 1); P.dg_ov = up(h, in->dg_ov, (size_t)n_dg * nr); P.dg_its = up(h, in->dg_its, (size_t)n_dg * iw);
+    EA = ks::EffAllocArgs{(int)nt, (int)n_its, (int)iw, (int)nr, P.tmpl_ov, P.it_alloc, P.dg_first, P.dg_ov, P.dg_its, eff};
+  }
+  // the workspace, as create() sizes it
+  const uint32_t t_rows = in->lim ? std::max(32u, nt) : nt;
+  W.max_claims = (int)mc; W.claim_words = (int)((mc + 63) / 64);
+  W.t_its = dz<uint64_t>(h, (size_t)t_rows * iw);
+  W.t_remaining = dz<int64_t>(h, (size_t)nt * (nr + 1));
+  h->fast_mc = mc;
+  fast_plan_set(h, (int)in->plan, (int)in->rows);
+  if (in->cap && (int)in->cap < fw.plan.cap) fw.plan.cap = (int)in->cap;
+  const uint32_t rows = (uint32_t)fw.plan.rows;
+  fast_shared_alloc(h, mc, sizeof(ks::FastRec<ks::kFastRows>) / 8);
+  { const size_t oc = std::min<size_t>(65472, ((size_t)mc + 63) & ~(size_t)63) + 64; fw.o_key = dz<uint16_t>(h, oc); fw.o_ord = dz<uint16_t>(h, oc); fw.o_snap = dz<uint16_t>(h, oc); }
+  fw.cls = dz<ks::FastSlot>(h, nc); fw.cls_first = dz<uint32_t>(h, nc); fw.cls_last = dz<uint32_t>(h, nc);
+  fw.enabled = 1;
+  fw.ops = in->ops ? 1 : 0;
+  if (in->lim) fw.lim = dz<ks::FastLimits>(h, 1);
+  fw.unsched = in->flavour >= 1 ? 1 : 0;
+  if (fw.unsched) {
+    fw.us_n = dz<uint32_t>(h, 1); fw.us_entry = dz<uint32_t>(h, nc); fw.us_last = dz<uint32_t>(h, nc);
+    fw.us_err = dz<uint8_t>(h, nc); fw.us_diag = dz<uint8_t>(h, nc); fw.us_cls = dz<uint64_t>(h, nc);
+  }
+  fw.podops = in->flavour == 2 ? dz<ks::FastPodOps>(h, 1) : nullptr;
+  // what the probe writes: 0xA5 everywhere
+  const size_t misc_words = sizeof(ks::FastMisc) / 8, rec_words = 3 + rows;
+  ks::FastColdArgs A{};
+  A.ops = up(h, in->script, n_ops); A.n_ops = (int)n_ops;
+  A.res = dz<ks::FastColdRes>(h, n_ops); A.compat = dz<uint64_t>(h, (size_t)n_ops * iw);
+  A.scal = dz<ks::FastColdScal>(h, 2); A.misc = dz<uint64_t>(h, 2 * misc_words);
+  A.ent = dz<uint64_t>(h, (size_t)ks::kFastEnt * 4); A.pool = dz<int32_t>(h, (size_t)ks::kFastPool * 4);
+  A.rec = dz<uint64_t>(h, (size_t)mc * rec_words); A.aslot = dz<uint64_t>(h, (size_t)64 * rows * 5);
+  A.scls = dz<uint32_t>(h, (size_t)ks::kFastRows * 64); A.cur = dz<uint32_t>(h, (size_t)ks::kFastRows * 64);
+  ks::FastColdArgs* d_args = dz<ks::FastColdArgs>(h, 1);
+  if (!be_ok(h)) return KSOLVE_ERR_DEVICE;
+  be_fill(h, A.res, 0xA5, (size_t)(n_ops ? n_ops : 1) * sizeof(ks::FastColdRes)); be_fill(h, A.compat, 0xA5, (size_t)(n_ops ? n_ops : 1) * iw * 8);
+  be_fill(h, A.scal, 0xA5, 2 * sizeof(ks::FastColdScal)); be_fill(h, A.misc, 0xA5, 2 * misc_words * 8);
+  be_fill(h, A.ent, 0xA5, (size_t)ks::kFastEnt * 32); be_fill(h, A.pool, 0xA5, (size_t)ks::kFastPool * 16);
+  be_fill(h, A.rec, 0xA5, (size_t)mc * rec_words * 8); be_fill(h, A.aslot, 0xA5, (size_t)64 * rows * 40);
+  be_fill(h, A.scls, 0xA5, (size_t)ks::kFastRows * 256); be_fill(h, A.cur, 0xA5, (size_t)ks::kFastRows * 256);
+  // solve_prepare()'s phase 1, create()'s effective allocatable
+  be_fill(h, IA.error, 0, 4);
+  be_launch_it_index(h, (int)n_its, IA);
+  if (in->tmpl_ov) be_launch_eff_alloc(h, EA);
+  A.fa = ks::FastArgs{P, W, fw};
+  be_h2d(h, d_args, &A, sizeof(A));
+  out->kernel = be_launch_fast_cold(h, d_args, fw.plan.global_state, (int)rows, (int)in->flavour);
+  if (!out->kernel) return fail(h, KSOLVE_ERR_UNSUPPORTED, "test_fast_cold: this build has no kernel of that plan, rows and flavour");
+  out->it_words = iw; out->misc_words = (uint32_t)misc_words; out->cap = (uint32_t)fw.plan.cap; out->t_rows = t_rows;
+  be_d2h(h, out->scal, A.scal, 2 * sizeof(ks::FastColdScal)); be_d2h(h, out->misc, A.misc, 2 * misc_words * 8);
+  be_d2h(h, out->var, fw.var, sizeof(ks::FastVar));
+  if (fw.podops) be_d2h(h, out->podops, fw.podops, sizeof(ks::FastPodOps));
+  if (fw.lim) be_d2h(h, out->lim, fw.lim, sizeof(ks::FastLimits));
+  be_d2h(h, out->cls, fw.cls, (size_t)nc * sizeof(ks::FastSlot));
+  be_d2h(h, out->t_its, W.t_its, (size_t)t_rows * iw * 8); be_d2h(h, out->t_remaining, W.t_remaining, (size_t)nt * (nr + 1) * 8);
+  if (in->tmpl_ov) be_d2h(h, out->it_eff, eff, (size_t)nt * nr * n_its * 8);
+  be_d2h(h, out->ent, A.ent, (size_t)ks::kFastEnt * 32); be_d2h(h, out->pool, A.pool, (size_t)ks::kFastPool * 16);
+  be_d2h(h, out->ent_its, fw.ent_its, (size_t)ks::kFastEnt * iw * 8);
+  be_d2h(h, out->rec, A.rec, (size_t)mc * rec_words * 8); be_d2h(h, out->c_hostseq, fw.c_hostseq, (size_t)mc * 4);
+  be_d2h(h, out->aslot, A.aslot, (size_t)64 * rows * 40); be_d2h(h, out->scls, A.scls, (size_t)ks::kFastRows * 256); be_d2h(h, out->cur, A.cur, (size_t)ks::kFastRows * 256);
+  if (fw.unsched) be_d2h(h, out->us_cls, fw.us_cls, (size_t)nc * 8);
+  if (n_ops) { be_d2h(h, out->res, A.res, (size_t)n_ops * sizeof(ks::FastColdRes)); be_d2h(h, out->compat, A.compat, (size_t)n_ops * iw * 8); }
+  be_sync(h);
+  return be_ok(h) ? KSOLVE_OK : KSOLVE_ERR_DEVICE;
 }
 #endif
 

@@ -58,3 +58,15 @@ __global__ void ksolve_pack_topo_nodes_many_f(const ks::TopoArgs* const* items, 
 // the cursor engine's existing-node stage (node_stage.h), `remaining` in LDS / in the HBM workspace
 __global__ void ksolve_pack_nodes_lds(const ks::FastArgs* a);
 __global__ void ksolve_pack_nodes_hbm(const ks::FastArgs* a);
+#ifdef KSOLVE_TEST_HOOKS
+// test builds only: FastCold alone, per instantiation (ksolve_test_fast_cold.hip, fast_cold_probe.h)
+namespace ks { struct FastColdArgs; }
+__global__ void ksolve_test_fast_cold_g0r1(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_g0r4(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_u_g0r1(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_u_g0r4(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_p_g0r1(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_p_g0r4(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_g1r1(const ks::FastColdArgs* a);
+__global__ void ksolve_test_fast_cold_u_g2r4(const ks::FastColdArgs* a);
+#endif

@@ -128,6 +128,21 @@ static void be_launch_pack_fast(ksolve_handle* h) {
     else { ks::FastEngine<ks::Wave, 0, ks::kFastRows> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
   }
 }
+// FastCold alone (fast_cold_probe.h): the device kernels' body on the loop-over-lanes Wave. The emulation's FastCold has the set-aside
+// list and the pod operators built in (kFastKeepBuiltIn) and FastWork's switches decide, so every (plan, rows, flavour) runs here.
+static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* a, int plan, int rows, int flavour) {
+  std::vector<char> lds((size_t)h->fw.plan.total_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
+  if (rows == 1) {
+    if (plan == 2) ks::fast_cold_probe_body<ks::Wave, 2, 1, true, true>(a, lds.data());
+    else if (plan == 1) ks::fast_cold_probe_body<ks::Wave, 1, 1, true, true>(a, lds.data());
+    else ks::fast_cold_probe_body<ks::Wave, 0, 1, true, true>(a, lds.data());
+  } else {
+    if (plan == 2) ks::fast_cold_probe_body<ks::Wave, 2, ks::kFastRows, true, true>(a, lds.data());
+    else if (plan == 1) ks::fast_cold_probe_body<ks::Wave, 1, ks::kFastRows, true, true>(a, lds.data());
+    else ks::fast_cold_probe_body<ks::Wave, 0, ks::kFastRows, true, true>(a, lds.data());
+  }
+  return (uint32_t)(1000 + flavour * 100 + plan * 10 + rows);
+}
 static void be_launch_pack_topo(ksolve_handle* h) {
   std::vector<char> lds((size_t)h->tw.plan.total_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
@@ -324,6 +339,10 @@ ksolve_status ksolve_test_eff_alloc(ksolve_test_eff_alloc_io* io) {
 // the cursor engine's claim records and the scatter of the queue's results alone (ksolve_impl.h test_fast_records)
 ksolve_status ksolve_test_fast_records(const ksolve_test_fast_records_in* in, ksolve_test_fast_records_out* out) {
   return test_on_bare_handle("ksolve_test_fast_records", [&](ksolve_handle* h) { return ksi::test_fast_records(h, in, out); });
+}
+// the cold half of the cursor engine alone (ksolve_impl.h test_fast_cold, fast_cold_probe.h)
+ksolve_status ksolve_test_fast_cold(const ksolve_test_fast_cold_in* in, ksolve_test_fast_cold_out* out) {
+  return test_on_bare_handle("ksolve_test_fast_cold", [&](ksolve_handle* h) { return ksi::test_fast_cold(h, in, out); });
 }
 // The product's Go-sort (csrc/go_sort.h, used by the finalize kernel for OrderByPrice) on an array of integer keys:
 // out_perm receives the original indices in sorted order, ties as Go's sort.Slice leaves them.
