@@ -14,12 +14,13 @@ enum Decline : int {
                                        // and under engines 18 / 19 for a topology batch outside plain_topo (pod-side bounds, minValues, ...)
   DECLINE_TEMPLATE_NOT_POSITIVE = 3,   // a NodePool requirement that is not an In set (NotIn, Exists, DoesNotExist; Gt, Lt on the spread engine) — not the cursor engine under engines 15 / 16, not the spread engine under 18 / 19
   DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply) — not the cursor engine under engines 26 / 27, which take NotIn, Exists and
-                                       // DoesNotExist on pods (fast_engine.h, "The cursor engine's pod operators"); the existing-node stage and the spread engine raise it under every setting
+                                       // DoesNotExist on pods (fast_engine.h, "The cursor engine's pod operators"), not the spread engine under 29 / 30 (topo_engine.h, "The spread engine's
+                                       // pod operators") — but for a batch with existing nodes; the existing-node stage raises it under every setting
   DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
   DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits
   DECLINE_QUANTITY_RANGE = 7,          // an allocatable, effective allocatable or request outside 31 bits
-  DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive) — as 4: not the cursor engine under engines 26 / 27
-  // engines 26 / 27 only: what the pod operators leave to the general engine (fast_engine.h, "The cursor engine's pod operators")
+  DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive) — as 4: not the cursor engine under engines 26 / 27, not the spread engine under 29 / 30
+  // engines 26 / 27 and 29 / 30 only: what the pod operators leave to the general engine (fast_engine.h, "The cursor engine's pod operators"; under topology a group's key counts as an In user for 9)
   DECLINE_CLASS_KEY_DEFINEDNESS = 9,   // a custom key some NodePool leaves undefined, with a NotIn / DoesNotExist class and an In / Exists class on it: whether the second kind is
                                        // admissible depends on whether a pod of the first kind joined the claim before (requirements.go:185-193)
   DECLINE_CLASS_DNE_MIXED = 10,        // a key with a DoesNotExist class and a NotIn class or a NotIn NodePool: the packed set "no dictionary value left" would stand for both
@@ -50,14 +51,16 @@ enum Decline : int {
   DECLINE_TOPO_RELAXATION_GROUP = 42,  // a group created by a relaxing pod (topology.go:162-194)
   DECLINE_TOPO_NODE_FILTER = 43,       // a group's TopologyNodeFilter can reject a claim or node (topologynodefilter.go:68-96); create() raises it for tainted nodes.
                                        // Engines 24 / 25 evaluate such filters themselves and keep 43 for what their slots do not hold: a term that is not positive In sets on
-                                       // packed variable keys, more than kTopoFiltTerms terms, more than kTopoFiltSlots filters decided per claim, a filter on a group that is no spread group
+                                       // packed variable keys, more than kTopoFiltTerms terms, more than kTopoFiltSlots filters decided per claim, a filter on a group that is no spread group.
+                                       // Engines 29 / 30 over a batch with negative pods or terms pack NotIn / Exists / DoesNotExist terms too and hold kTopoFiltSlotsPodOps filters; 43 there also for
+                                       // an Exists term on a key with a DoesNotExist class or NodePool and a DoesNotExist term on a key with an Exists / Gt / Lt NodePool (the word cannot tell the bins apart)
   DECLINE_TOPO_SKEW_RANGE = 44,        // dictionary-key spread: maxSkew outside 1..30000, or minDomains above 30000
   DECLINE_TOPO_HOST_AFFINITY = 45,     // pod affinity on the hostname
   DECLINE_TOPO_HOST_GROUPS = 46,       // more hostname groups than kTopoMaxHost
   DECLINE_TOPO_HOST_SKEW = 47,         // hostname spread with maxSkew outside 1..6 (the counters saturate at 7)
   DECLINE_TOPO_INVERSE_KIND = 48,      // an inverse group on a dictionary key that is not anti-affinity
   DECLINE_TOPO_KEY_GROUPS = 49,        // more dictionary-key groups than kTopoMaxZg
-  DECLINE_TOPO_DOMAINS = 50,           // a group's key is not a packed variable key, or has more than kTopoMaxDom domains
+  DECLINE_TOPO_DOMAINS = 50,           // a group's key is not a packed variable key, or has more than kTopoMaxDom domains (29 / 30 over a batch with negative pods or terms: the phantom bit is one of them — fifteen dictionary values)
   DECLINE_TOPO_CLASS = 51,             // a pod class with a hostname limit outside 0..6 or three dictionary-key groups
   // the spread engine's loop
   DECLINE_TOPO_CACHE_FULL = 60,        // no room for a requirement set's cache entry (resolve)

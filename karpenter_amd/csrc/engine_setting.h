@@ -1,4 +1,5 @@
-// engine_setting.h — ksolve_options.engine decoded ONCE: one table with a row per public value, and the policy a row stands for.
+// engine_setting.h — ksolve_options.engine decoded ONCE: a table with a row per public value (and a second one for the values from 29
+// on, below), and the policy a row stands for.
 // Host-only plain C++, no device code: ksolve_impl.h looks a handle's value up in create() and reads the policy from then on
 // (ksolve_handle::eng; the options keep what the caller passed); the host library (host/ksched.cpp) looks the option's NAME up in the
 // same table. include/ksolve.h documents the values for callers; a new value is a new row here and a new line there.
@@ -30,6 +31,8 @@ struct EnginePolicy {
   bool spread_filters;  // the spread engine counts pods through topology node filters that can say no (topo_engine.h, "Topology node filters")
   bool pod_operators;   // the cursor engine takes pod classes with NotIn, Exists and DoesNotExist requirements (fast_engine.h, "The cursor engine's pod operators")
   const char* name;     // options.engine of the host library's problem document; nullptr = no name
+  bool spread_pod_operators = false;   // the spread engine takes such pod classes too, and node-filter terms of those operators (topo_engine.h, "The spread engine's pod operators"); behind
+                                       // `name`, so that the rows of the first table stay as they are written
 
   constexpr bool general_only() const { return run == General; }
   constexpr bool cursor_only() const { return run == Cursor; }
@@ -73,11 +76,26 @@ inline constexpr uint32_t kEngineSettingCount = (uint32_t)(sizeof(kEngineSetting
 // A value past the table is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch.
 inline constexpr EnginePolicy kEngineSettingPastTable = {EnginePolicy::Cursor, 0, false, false, false, false, false, false, false, false, false, false, false, false, nullptr};
 
-inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineSettingCount ? kEngineSettings[value] : kEngineSettingPastTable; }
+// The second table: the rows added since the first one was pinned with its length (28 rows; value 28 is "past the table" for every
+// caller that passed it, as 17 was before it, and stays that). Its first row is value kEngineSettingsMoreFirst; a value behind its
+// last row is past the table again.
+inline constexpr uint32_t kEngineSettingsMoreFirst = 29;
+inline constexpr EnginePolicy kEngineSettingsMore[] = {
+  /* 29 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  true,  "auto-pod-operators-spread", true},   // 26 + the spread engine's pod operators
+  /* 30 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  true,  false, "spread-pod-operators", true},        // 25 + the same
+};
+inline constexpr uint32_t kEngineSettingMoreCount = (uint32_t)(sizeof(kEngineSettingsMore) / sizeof(kEngineSettingsMore[0]));
 
-// The value an option name stands for; 0 ("auto") for a name the table does not hold. (A row without a name has none to match.)
+inline const EnginePolicy& engine_policy(uint32_t value) {
+  if (value < kEngineSettingCount) return kEngineSettings[value];
+  if (value >= kEngineSettingsMoreFirst && value - kEngineSettingsMoreFirst < kEngineSettingMoreCount) return kEngineSettingsMore[value - kEngineSettingsMoreFirst];
+  return kEngineSettingPastTable;
+}
+
+// The value an option name stands for; 0 ("auto") for a name neither table holds. (A row without a name has none to match.)
 inline uint32_t engine_value(const char* name) {
   for (uint32_t v = 0; v < kEngineSettingCount; ++v) if (kEngineSettings[v].name && !strcmp(kEngineSettings[v].name, name)) return v;
+  for (uint32_t v = 0; v < kEngineSettingMoreCount; ++v) if (kEngineSettingsMore[v].name && !strcmp(kEngineSettingsMore[v].name, name)) return kEngineSettingsMoreFirst + v;
   return 0;
 }
 

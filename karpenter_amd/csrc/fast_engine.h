@@ -156,7 +156,7 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   uint8_t* us_diag;
   uint64_t* us_cls;       // [n_pods >= n_classes] by class: the verdict of the class's last failed template walk (FastCold::new_claim), reset by setup()
   uint32_t* pod_qpos;     // [n_pods], behind the existing-node stage only: a pod's position in the FULL queue (ksolve_fast_requeue)
-  FastPodOps* podops;     // [1] engines 26 / 27 (a cursor handle only), null otherwise: setup() accepts pod classes with NotIn, Exists and DoesNotExist requirements — "The cursor engine's pod operators" below. The last field: every other kernel reads the layout it always read
+  FastPodOps* podops;     // [1] engines 26 / 27 (a cursor handle) and 29 / 30 (a spread handle: topo_engine.h, "The spread engine's pod operators"), null otherwise: setup() accepts pod classes with NotIn, Exists and DoesNotExist requirements — "The cursor engine's pod operators" below. The last field: every other kernel reads the layout it always read
 };
 static_assert(offsetof(FastWork, us_n) == offsetof(FastWork, unsched) + 8, "FastWork::filt fills the gap behind unsched: the layout every kernel reads stays what it was");
 
@@ -563,8 +563,11 @@ KS_FN uint64_t fast_po_tmpl_field(const Dict& d, const ReqRef& tr, int k, uint32
   guard = v == 0;           // In [] == DoesNotExist
   return v ? v : ph;
 }
-template <class W, int GS, int R, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn>
+// TP: the pod operators on behalf of the spread engine too (engines 29 / 30; topo_engine.h, "The spread engine's pod operators") —
+// a switch of its own, so that the cursor engine's instantiations are compiled from what they were compiled from.
+template <class W, int GS, int R, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn, bool TP = false>
 struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, std::conditional<PO, FastPodOpsState, FastNoPodOpsState>::type {
+  static_assert(!TP || PO, "the spread engine's pod operators are the pod operators");
   KS_DEV bool po() const { if constexpr (PO) return this->po_on != 0; else return false; }
   const ProblemView* Pk;
   const Workspace* Sk;
@@ -772,9 +775,27 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, st
       for (uint32_t ks_ = tr.defined & ~tr.complement; ks_; ks_ &= ks_ - 1) if (!key_nonempty(d, tr.mask, __builtin_ctz(ks_))) neg |= 1;   // In [] == DoesNotExist
       return neg; })) return DECLINE_TEMPLATE_NOT_POSITIVE;
     // classes: only In sets; the keys they define are the variable keys
-    // ... but for engines 26 / 27 (pod operators, above), on the cursor engine alone
+    // ... but for engines 26 / 27 (pod operators, above) on the cursor engine
+    // ... and for engines 29 / 30 on the spread engine (TP), where the phantom layout is turned on only for a batch that needs it — some
+    // class or some term of a topology node filter is negative (a complement set, or In []) — so that a positive batch packs, and is
+    // declined, exactly as under 24 / 25. Existing nodes stay outside (a negative pod may add a key to a node): such a batch keeps
+    // its reason 4 / 8 below.
     bool pod_ops = false;
-    if constexpr (PO) { pod_ops = !topo && F.podops != nullptr; this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0; }
+    if constexpr (PO && !TP) { pod_ops = !topo && F.podops != nullptr; this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0; }
+    if constexpr (TP) {
+      pod_ops = F.podops != nullptr;
+      if (topo && pod_ops) {
+        auto negative = [&](const ReqRef& r) -> uint64_t {
+          uint64_t neg = (uint64_t)r.complement;
+          for (uint32_t ks_ = r.defined & ~r.complement; ks_; ks_ &= ks_ - 1) if (!key_nonempty(d, r.mask, __builtin_ctz(ks_))) neg |= 1;   // In [] == DoesNotExist
+          return neg;
+        };
+        const uint64_t need = W::reduce_or(nc, [&](int c) { return negative(Pv.cls_reqs.at(d, c)); }) |
+                              W::reduce_or((int)Pv.topo.f_first[Pv.topo.n_groups], [&](int i) { return negative(Pv.topo.f_reqs.at(d, i)); });
+        if (!need || P.n_nodes > 0) pod_ops = false;
+      }
+      this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0;
+    }
     if (!pod_ops && W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) return DECLINE_CLASS_NOT_POSITIVE;
     uint32_t vk = (uint32_t)W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.defined[c]; });
     uint32_t k_dne = 0;   // pod operators: keys some class requires DoesNotExist on
@@ -793,6 +814,12 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, st
         for (uint32_t ks_ = tr.defined & tr.complement; ks_; ks_ &= ks_ - 1) { const int k = __builtin_ctz(ks_); if (req_op(d, tr, k) == OP_NOTIN) t_notin |= 1u << k; }
       }
       const uint32_t wkm = d.well_known_mask;
+      if constexpr (TP) {
+        // (a topology group's domain choice adds an In requirement on its key as a pod's selector would: nodeclaim.go CanAdd)
+        uint32_t kin = kop[OP_IN] | kop[OP_EXISTS];
+        if (topo) kin |= (uint32_t)W::reduce_or(P.topo.n_groups, [&](int g) { return Pv.topo.key[g] >= 0 ? (uint64_t)1 << Pv.topo.key[g] : (uint64_t)0; });
+        if ((kop[OP_NOTIN] | kop[OP_DNE]) & kin & t_undef & ~wkm) return DECLINE_CLASS_KEY_DEFINEDNESS;
+      } else
       if ((kop[OP_NOTIN] | kop[OP_DNE]) & (kop[OP_IN] | kop[OP_EXISTS]) & t_undef & ~wkm) return DECLINE_CLASS_KEY_DEFINEDNESS;
       if (kop[OP_DNE] & (kop[OP_NOTIN] | t_notin)) return DECLINE_CLASS_DNE_MIXED;
       if (kop[OP_NOTIN] & t_bounds) return DECLINE_CLASS_NOTIN_BOUNDS;

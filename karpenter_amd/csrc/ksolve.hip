@@ -756,12 +756,14 @@ static void launch_pack_topo(ksolve_handle* h, void (*fn)(const ks::TopoArgs*), 
 }
 // (engines 22 / 23: the kernels with the set-aside list compiled in; 24 / 25: those with the topology node filters as well)
 static void be_launch_pack_topo(ksolve_handle* h) {
-  if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_f, "ksolve_pack_topo_f launch");
+  if (h->fw.podops) launch_pack_topo(h, ksolve_pack_topo_p, "ksolve_pack_topo_p launch");   // 29 / 30: ... and the pod operators as well
+  else if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_f, "ksolve_pack_topo_f launch");
   else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_u, "ksolve_pack_topo_u launch");
   else launch_pack_topo(h, ksolve_pack_topo, "ksolve_pack_topo launch");
 }
 static void be_launch_pack_topo_nodes(ksolve_handle* h) {
-  if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_nodes_f, "ksolve_pack_topo_nodes_f launch");
+  if (h->fw.podops) launch_pack_topo(h, ksolve_pack_topo_nodes_p, "ksolve_pack_topo_nodes_p launch");
+  else if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_nodes_f, "ksolve_pack_topo_nodes_f launch");
   else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_nodes_u, "ksolve_pack_topo_nodes_u launch");
   else launch_pack_topo(h, ksolve_pack_topo_nodes, "ksolve_pack_topo_nodes launch");
 }

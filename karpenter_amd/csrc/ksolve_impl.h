@@ -1243,6 +1243,11 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       }
       fw.filt = h->eng.spread_filters ? 1 : 0;   // engines 24 / 25: topology node filters that can say no (topo_engine.h, "Topology node filters")
       if (fw.filt) tw.filt = dz<ks::TopoFilt>(h, 1);
+      // engines 29 / 30: pod classes and node-filter terms with NotIn, Exists and DoesNotExist (topo_engine.h, "The spread engine's pod
+      // operators"); the kernels are those of the filters with the switch compiled in, and pod operators go with the set-aside list as
+      // on the cursor engine. Pod-side Gt / Lt and minValues stay outside plain_topo (reason 1 above), whatever the setting.
+      fw.podops = h->eng.spread_pod_operators && fw.unsched && fw.filt ? dz<ks::FastPodOps>(h, 1) : nullptr;
+      if (fw.podops) tw.filt = dz<ks::TopoFilt>(h, 2);   // (kTopoFiltSlotsPodOps slots: a term per Deployment makes a group per Deployment)
       if (fw.ops) {
         // ... and whether this problem has one: what FastCold::setup() declines with reason 3 without the switch (the batch path asks)
         bool complement = any_nonzero(d->tmpl_reqs.complement, d->n_templates) || any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);
@@ -3499,7 +3504,10 @@ static ksolve_status solve_many_plain(ksolve_handle** hs, uint32_t n, ksolve_res
       h->fw.enabled = 0;
     }
     if (!h->n_pods) continue;   // nothing to launch: solve_finish
-    if (h->tw.enabled && h->n_classes) spread.push_back(i);
+    if (h->tw.enabled && h->n_classes) {
+      // (engines 29 / 30: the kernels with the pod operators have no many-problem form — a launch of its own, as solve() makes it)
+      if (h->fw.podops) alone(i); else spread.push_back(i);
+    }
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan of ksolve_pack_fast_g0r*: a handle solve() would run on another kernel (a plan in HBM, the
       // two-wavefront kernel, the set-aside list, the pod operators) or with kernels around the loop (node stage, limit stages) runs alone

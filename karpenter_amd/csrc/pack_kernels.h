@@ -1,6 +1,6 @@
 // pack_kernels.h — the pack kernels (one wavefront per scheduling problem) live in translation units of their own, so that build()
 // compiles them side by side (the general engine's instantiations alone are minutes of one hipcc): ksolve_pack_general.hip,
-// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_fast_unsched.hip, ksolve_pack_fast_podops.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip, ksolve_pack_topo_filter.hip, ksolve_pack_topo_many.hip, ksolve_pack_topo_many_unsched.hip, ksolve_pack_topo_many_filter.hip. ksolve.hip (the HIP backend of the C
+// ksolve_pack_batch.hip, ksolve_pack_sweep4.hip, ksolve_pack_fast.hip, ksolve_pack_fast_unsched.hip, ksolve_pack_fast_podops.hip, ksolve_pack_nodes.hip, ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip, ksolve_pack_topo_unsched.hip, ksolve_pack_topo_filter.hip, ksolve_pack_topo_podops.hip, ksolve_pack_topo_many.hip, ksolve_pack_topo_many_unsched.hip, ksolve_pack_topo_many_filter.hip. ksolve.hip (the HIP backend of the C
 // ABI) launches them through these declarations; no device function crosses a translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +47,9 @@ __global__ void ksolve_pack_topo_nodes_u(const ks::TopoArgs* a);
 // ... and those two with the topology node filters of engines 24 / 25 compiled in as well (ksolve_pack_topo_filter.hip)
 __global__ void ksolve_pack_topo_f(const ks::TopoArgs* a);
 __global__ void ksolve_pack_topo_nodes_f(const ks::TopoArgs* a);
+// ... and those two with the pod operators of engines 29 / 30 compiled in as well (ksolve_pack_topo_podops.hip)
+__global__ void ksolve_pack_topo_p(const ks::TopoArgs* a);
+__global__ void ksolve_pack_topo_nodes_p(const ks::TopoArgs* a);
 // ... and the six once more, many problems per launch (ksolve_solve_many; topo_many.h: block = one ticket = one member, largest first;
 // ksolve_pack_topo_many.hip, ksolve_pack_topo_many_unsched.hip, ksolve_pack_topo_many_filter.hip)
 __global__ void ksolve_pack_topo_many(const ks::TopoArgs* const* items, const uint32_t* order, uint32_t* next, int n);

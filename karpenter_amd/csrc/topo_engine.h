@@ -44,7 +44,29 @@
 //   * a limit stage copies the template's packed set, guard bits included (fast_engine.h limit_stage_id), and the requirement-set
 //     cache and the records read the stage's template through FastLimits::real (create_entry, ksolve_fast_records);
 //   * the existing-node path (topo_nodes.h) reads no template.
-// Pods stay positive (reason 4), and so does everything else the shape check asks.
+// Pods stay positive (reason 4; not under engines 29 / 30, below), and so does everything else the shape check asks.
+//
+// The spread engine's pod operators (engines 29 / 30, FastWork::podops on a spread handle; PO below; fast_engine.h "The cursor
+// engine's pod operators" for the packed form). Pod classes may carry NotIn, Exists and DoesNotExist; FastCold::setup(true) turns the
+// phantom layout on — one more bit on top of every field, "some value outside the dictionary" — only for a batch that has a negative
+// class or a negative term of a topology node filter, so a positive batch is packed and declined exactly as under 24 / 25. With it on:
+//   * a group's domains D are dictionary values and every candidate mask of choose_domains is D & …: no path picks the phantom bit
+//     (spread, minDomains, the affinity bootstrap, anti-affinity, the second group of a TWO class), a choice writes a concrete set and
+//     zc.clear drops the guard bit. podf, the class's field, is "the values outside S" for a NotIn S pod: domainMinCount over the
+//     domains the pod supports (topologygroup.go:300-322). The hot loop has no new instruction. A group's key holds at most fifteen
+//     dictionary values (kTopoMaxDom counts the phantom bit: DECLINE_TOPO_DOMAINS);
+//   * Record (record_zonal) skips a claim whose guard bit is set, now also one that a pod's NotIn narrowed to one dictionary value and
+//     the phantom bit; anti-affinity still never meets such a claim (its own test has made the set concrete);
+//   * a spread pod's own term is a term of its group's TopologyNodeFilter: setup_filters packs NotIn / Exists / DoesNotExist terms like
+//     classes (the guard bit's position in fvm marks a NotIn / DoesNotExist term, which passes a bin that does not define the key),
+//     claim_cut reads a guard bit over a field narrower than all ones on a key the template leaves undefined as a DEFINED key (a NotIn
+//     that pods put there), and topo_filter_matches_po is "the fields share a bit". Exists against DoesNotExist is what the word cannot
+//     tell: declined (43) where such a bin can exist. Such a batch has kTopoFiltSlotsPodOps filter slots;
+//   * a pod whose NotIn leaves a template no value, or whose static verdict is off, fails new_claim's walk with Incompatible (2) before
+//     Topology (3); filter_diag reads a narrowed complement set through compat_word;
+//   * existing nodes with negative pods stay outside (4 / 8): a negative pod may add a key to a node.
+// On the device PO is a compile-time switch like US and FS, with kernels of its own (ksolve_pack_topo_podops.hip, US and FS on as
+// well): every line stands behind `if constexpr (PO)`. The host emulation builds it in and FastWork::podops decides at run time.
 #pragma once
 #include "fast_engine.h"
 #include "run_order.h"
@@ -120,10 +142,11 @@ struct TopoKeepState {
   uint32_t us_epoch = 1;           // commits so far + 1 (0: no verdict)
 };
 struct TopoNoKeepState {};
-template <class W, bool NODES = false, bool US = kFastKeepBuiltIn, bool FS = kFastKeepBuiltIn>
+template <class W, bool NODES = false, bool US = kFastKeepBuiltIn, bool FS = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn>
 struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
   static_assert(!FS || US, "the engines that evaluate node filters keep unschedulable pods too (24 = 22 + filters, 25 = 23 + filters)");
-  FastCold<W, 2, 1> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
+  static_assert(!PO || FS, "the engines that take pod operators evaluate node filters too (29 = 24 + pod operators, 30 = 25 + pod operators)");
+  FastCold<W, 2, 1, kFastKeepBuiltIn, PO, PO> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
   RunOrder<W> order;        // Go's sort.Slice permutation as one ring per pod count
   const ProblemView* Pk; const Workspace* Sk; const FastWork* Fk; const TopoWork* Tk;
   KS_LDS TopoState* st;
@@ -184,7 +207,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
         if (n_zg >= kTopoMaxZg) return DECLINE_TOPO_KEY_GROUPS;
         int var = -1;
         for (int j = 0; j < nvv; ++j) if (Mp->vkey[j] == key) var = j;
-        if (var < 0 || Mp->vwidth[var] > kTopoMaxDom) return DECLINE_TOPO_DOMAINS;
+        if (var < 0 || Mp->vwidth[var] > kTopoMaxDom) return DECLINE_TOPO_DOMAINS;   // (29 / 30 over a batch with negative pods: the width includes the phantom bit — fifteen dictionary values)
         const uint32_t w0 = d.key_word_off[key];
         KS_LDS TopoZg& Z = S_.zg[n_zg];
         const int32_t* c0 = T.counts0 + (size_t)g * T.dom_words * 64;
@@ -248,6 +271,8 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
   }
   // ---- topology node filters (FS; "Topology node filters" above) ----
   KS_DEV bool filters() const { if constexpr (FS) return Fk->filt != 0; else return false; }
+  // pod operators (PO; "The spread engine's pod operators" above): the handle has the switch AND this batch has the phantom layout
+  KS_DEV bool pod_ops() const { if constexpr (PO) return cold.po(); else return false; }
   // the shape check of the filters that can say no, their static verdict per class, and the slots of the rest
   KS_COLD int setup_filters() {
     if constexpr (!FS) return DECLINE_NONE;
@@ -274,13 +299,37 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
         if (b - a > (uint32_t)kTopoFiltTerms) return DECLINE_TOPO_NODE_FILTER;
         for (uint32_t i = a; i < b; ++i) {
           const ReqRef r = T.f_reqs.at(d, (int)i);
-          if (r.complement | r.has_gte | r.has_lte) return DECLINE_TOPO_NODE_FILTER;   // positive In sets without bounds only
+          if ((pod_ops() ? 0u : r.complement) | r.has_gte | r.has_lte) return DECLINE_TOPO_NODE_FILTER;   // positive In sets without bounds only (29 / 30: NotIn, Exists, DoesNotExist too)
           uint32_t left = r.defined;
           uint64_t fvm = 0, fdm = 0;
           for (int j = 0; j < nvv; ++j) {
             const int k = Mp->vkey[j];
             if (!((left >> k) & 1u)) continue;
             left &= ~(1u << k);
+            if constexpr (PO) if (pod_ops() && (bit(r.complement, k) || !r.mask[Mp->vword[j]])) {
+              // packed like a class (fast_engine.h, "The cursor engine's pod operators"): NotIn S = the dictionary's values outside S and the
+              // phantom bit, Exists = all ones, DoesNotExist (== In []) = the phantom bit alone. The guard bit's position in fvm marks a
+              // NotIn / DoesNotExist term: it passes a bin that does not define the key (requirements.go:185-193).
+              const uint64_t ph = 1ull << (Mp->voff[j] + Mp->vwidth[j] - 1), neg = ph << 1;
+              const uint64_t s_ = r.mask[Mp->vword[j]];
+              // what the word cannot tell apart on a bin: Exists against DoesNotExist (the fields share the phantom bit, the sets
+              // share nothing and only one side is negative, requirements.go:260-265) — decided where the key can hold neither
+              // such a bin, declined otherwise
+              uint32_t t_ops = 0;   // bit op: some template requires `op` on the key, bit 4: with Gt / Lt
+              for (int t = 0; t < Tn; ++t) {
+                const ReqRef tr = P.tmpl_reqs.at(d, t);
+                if (bit(tr.defined, k)) t_ops |= (1u << req_op(d, tr, k)) | ((bit(tr.has_gte, k) || bit(tr.has_lte, k)) ? 16u : 0u);
+              }
+              if (!bit(r.complement, k)) {   // DoesNotExist
+                if (t_ops & ((1u << OP_EXISTS) | 16u)) return DECLINE_TOPO_NODE_FILTER;
+                fvm |= ph | neg;
+              } else if (!s_) {              // Exists
+                if (((cold.dne_vars >> j) & 1u) || (t_ops & (1u << OP_DNE))) return DECLINE_TOPO_NODE_FILTER;
+                fvm |= Mp->fmask[j];
+              } else fvm |= (((~s_ & d.value_valid[Mp->vword[j]]) << Mp->voff[j]) & Mp->fmask[j]) | ph | neg;
+              fdm |= Mp->fmask[j];
+              continue;
+            }
             const uint64_t f = (r.mask[Mp->vword[j]] << Mp->voff[j]) & Mp->fmask[j];
             if (!f) return DECLINE_TOPO_NODE_FILTER;   // In [] == DoesNotExist
             fvm |= f; fdm |= Mp->fmask[j];
@@ -312,7 +361,9 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
               const bool sel = (k.dmask & fm) != 0;
               const uint64_t cf = k.cvmask & fm, tf = s.fvm[i] & fm;
               if (sel && !(cf & tf)) never = true;
-              if (!(sel && !(cf & ~tf))) always = false;
+              bool defined = sel;   // (a class that selects on the key — with whatever operator, under 29 / 30 — leaves it defined)
+              if constexpr (PO) defined = sel || ((s.fvm[i] >> (Mp->voff[j] + Mp->vwidth[j])) & 1);   // a NotIn / DoesNotExist term does not need it defined
+              if (!(defined && !(cf & ~tf))) always = false;
             }
             if (!never) { all_never = false; if (always) any_always = true; }
           }
@@ -328,8 +379,13 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       };
       const bool dyn = W::reduce_or(nc, [&](int c) { return (uint64_t)(resolve(c) == 2 ? 1 : 0); }) != 0;
       if (dyn) {
+        if constexpr (PO) {   // (29 / 30 over a batch with negative pods or terms: kTopoFiltSlotsPodOps slots, two TopoFilt in a row)
+          if (ns >= (pod_ops() ? kTopoFiltSlotsPodOps : kTopoFiltSlots)) return DECLINE_TOPO_NODE_FILTER;
+          if (W::leader()) (&ft->slot[0])[ns] = s;
+        } else {
         if (ns >= kTopoFiltSlots) return DECLINE_TOPO_NODE_FILTER;
         if (W::leader()) ft->slot[ns] = s;
+        }
       }
       const uint32_t sbit = dyn ? 1u << ns : 0u;
       W::for_n(nc, [&](int c) {
@@ -356,8 +412,14 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       uint64_t undef = 0;
       for (int j = 0; j < nvv; ++j) {
         const uint64_t guard = 1ull << (Mp->voff[j] + Mp->vwidth[j]);
-        if ((m & guard) && !((tdef >> Mp->vkey[j]) & 1u)) undef |= guard;   // (a guard bit over a key the template defines: its own NotIn / Exists / Gt / Lt)
+        if ((m & guard) && !((tdef >> Mp->vkey[j]) & 1u)) {   // (a guard bit over a key the template defines: its own NotIn / Exists / Gt / Lt)
+          // 29 / 30: ... and over a field narrower than all ones on a key the template leaves undefined: a NotIn / DoesNotExist that
+          // pods put there — the key IS defined (the rule ksolve_fast_records prints by)
+          if constexpr (PO) { if (pod_ops() && (m & Mp->fmask[j]) != Mp->fmask[j]) continue; }
+          undef |= guard;
+        }
       }
+      if constexpr (PO) if (pod_ops()) return topo_filter_cut_po(Tk->filt, Mp, nvv, fs, m, undef, [&](const TopoFiltSlot& s) { return ((s.tmask >> real) & 1u) != 0; });
       return topo_filter_cut(Tk->filt, Mp, nvv, fs, m, undef, [&](const TopoFiltSlot& s) { return ((s.tmask >> real) & 1u) != 0; });
     }
   }
@@ -490,7 +552,7 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
       KS_LDS TopoZg* const Z = &st->zg[ctz64(zs)];
       const uint32_t ow = (uint32_t)fast_uniform((int)(*(const KS_LDS uint32_t*)&Z->type));   // type | var << 8 | off << 16 | width << 24
       const int off = (int)((ow >> 16) & 0xFF), width = (int)(ow >> 24);
-      if ((m2 >> (off + width)) & 1) continue;   // the claim does not define the key (Exists, no values) or still holds its NodePool's own NotIn / Exists / Gt / Lt (engines 18 / 19): not one domain, whatever the field holds
+      if ((m2 >> (off + width)) & 1) continue;   // the claim does not define the key (Exists, no values), still holds its NodePool's own NotIn / Exists / Gt / Lt (engines 18 / 19), or holds what its pods' NotIn / DoesNotExist left (29 / 30 — one dictionary value and the phantom bit included): not one domain, whatever the field holds
       const uint32_t f = (uint32_t)(m2 >> off) & ((1u << width) - 1);
       if ((ow & 0xFF) == 2) {
         // anti-affinity (and its inverse groups) blocks every domain the pod could land in (topology.go:203-206, :213-219)

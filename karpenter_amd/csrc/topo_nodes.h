@@ -63,6 +63,35 @@ KS_FN TopoFiltCut topo_filter_cut(const TopoFilt* ft, const KS_LDS FastMisc* Mp,
   }
   return c;
 }
+// ... under the pod operators of engines 29 / 30 (topo_engine.h, "The spread engine's pod operators"): a term may be NotIn / Exists /
+// DoesNotExist, packed like a class over fields whose top bit is the phantom value; the guard bit's position in fvm marks a NotIn /
+// DoesNotExist term on that key, which passes a bin that does not define the key. On a defined key strict Compatible is "the two
+// fields share a bit" (requirements.go:254-274 with the escape of :260-265 — what setup_filters declines is what this cannot read).
+KS_FN bool topo_filter_matches_po(const TopoFiltSlot& s, const KS_LDS FastMisc* Mp, int nv, uint64_t m, uint64_t undef, bool taints_ok) {
+  if (!taints_ok) return false;
+  if (!s.n_terms) return true;
+  for (int i = 0; i < (int)s.n_terms; ++i) {
+    bool ok = true;
+    for (int j = 0; j < nv; ++j) {
+      const uint64_t fm = Mp->fmask[j];
+      if (!(s.fdm[i] & fm)) continue;
+      const int gb = Mp->voff[j] + Mp->vwidth[j];
+      if ((undef >> gb) & 1) { if (!((s.fvm[i] >> gb) & 1)) ok = false; }
+      else if (!(m & s.fvm[i] & fm)) ok = false;
+    }
+    if (ok) return true;
+  }
+  return false;
+}
+template <class TOK>
+KS_FN TopoFiltCut topo_filter_cut_po(const TopoFilt* ft, const KS_LDS FastMisc* Mp, int nv, uint32_t fs, uint64_t m, uint64_t undef, TOK taints_ok) {
+  TopoFiltCut c; c.h = 0; c.z = 0;
+  for (uint32_t b = fs; b; b &= b - 1) {   // (kTopoFiltSlotsPodOps slots: every bit of the class's word)
+    const TopoFiltSlot s = (&ft->slot[0])[ctz64(b)];
+    if (!topo_filter_matches_po(s, Mp, nv, m, undef, taints_ok(s))) { c.h |= s.hbit; c.z |= s.zbit; }
+  }
+  return c;
+}
 struct TopoNoFilt { static constexpr bool on = false; };   // every other setting: the node commit counts what the class says
 struct TopoNodeFilt { static constexpr bool on = true; uint32_t fs; int nv; const TopoFilt* ft; };   // fs: the class's slots (0: none)
 // ... against an existing node: its packed word from its label row (a node defines a key with ONE value, ksolve_impl.h

@@ -13,6 +13,7 @@ constexpr int kTopoMaxDom = 16;       // domains of such a key
 constexpr int kTopoTrack = 4;         // anti-affinity counters with a list of the claims that hold no member
 constexpr int kTopoFreeCap = 1024;    // entries of such a list (more: the list is dropped, its classes scan the order)
 constexpr int kTopoFiltSlots = 16;    // topology node filters of a problem that are decided per claim / node (engines 24 / 25); more: DECLINE_TOPO_NODE_FILTER
+constexpr int kTopoFiltSlotsPodOps = 32;   // ... of a batch with negative pods or terms under engines 29 / 30: every bit of TopoClass::pad (the handle's TopoFilt is two in a row)
 constexpr int kTopoFiltTerms = 4;     // node-affinity terms of such a filter
 constexpr uint64_t kTopoGuard = 0x8888888888888888ull, kTopoOnes = 0x1111111111111111ull;
 
