@@ -310,7 +310,7 @@ typedef struct {
                                     *     25    spread-filters       spread                     refuses       s-nodes, s-limits, s-operators, s-unschedulable, s-filters
                                     *     26    auto-pod-operators   cursor, spread, general    falls back    as 24, + pod-operators = the cursor engine takes pods with NotIn, Exists and DoesNotExist requirements
                                     *     27    cursor-pod-operators cursor                     refuses       nodes, limits, operators, unschedulable, pod-operators
-                                    *     28    (no name)            cursor                     refuses       - (as 17: what a value past the first table stands for)
+                                    *     28    (no name)            cursor                     refuses       - (as 17: what a value past the table stands for)
                                     *     29    auto-pod-operators-spread cursor, spread, general falls back  as 26, + s-pod-operators = the spread engine takes such pods too, and spread constraints whose
                                     *                                                                          owners carry NotIn, Exists or DoesNotExist (terms of the group's topology node filter)
                                     *     30    spread-pod-operators spread                     refuses       as 25, + s-pod-operators

@@ -1,5 +1,4 @@
-// engine_setting.h — ksolve_options.engine decoded ONCE: a table with a row per public value (and a second one for the values from 29
-// on, below), and the policy a row stands for.
+// engine_setting.h — ksolve_options.engine decoded ONCE: a table with a row per public value, and the policy a row stands for.
 // Host-only plain C++, no device code: ksolve_impl.h looks a handle's value up in create() and reads the policy from then on
 // (ksolve_handle::eng; the options keep what the caller passed); the host library (host/ksched.cpp) looks the option's NAME up in the
 // same table. include/ksolve.h documents the values for callers; a new value is a new row here and a new line there.
@@ -30,9 +29,8 @@ struct EnginePolicy {
   bool spread_unschedulable; // the spread engine does, and retries such pods for real (topo_engine.h, "The spread engine's unschedulable pods")
   bool spread_filters;  // the spread engine counts pods through topology node filters that can say no (topo_engine.h, "Topology node filters")
   bool pod_operators;   // the cursor engine takes pod classes with NotIn, Exists and DoesNotExist requirements (fast_engine.h, "The cursor engine's pod operators")
+  bool spread_pod_operators; // the spread engine takes such pod classes too, and node-filter terms of those operators (topo_engine.h, "The spread engine's pod operators")
   const char* name;     // options.engine of the host library's problem document; nullptr = no name
-  bool spread_pod_operators = false;   // the spread engine takes such pod classes too, and node-filter terms of those operators (topo_engine.h, "The spread engine's pod operators"); behind
-                                       // `name`, so that the rows of the first table stay as they are written
 
   constexpr bool general_only() const { return run == General; }
   constexpr bool cursor_only() const { return run == Cursor; }
@@ -41,61 +39,67 @@ struct EnginePolicy {
   constexpr bool may_spread() const { return run == Auto || run == Spread; }   // (a cursor-only handle never tries the spread engine)
 };
 
-//                                              run                    plan pick   pair   nodes  s-nodes limits s-lim  ops    s-ops  unsched s-uns  s-filt p-ops  name
-inline constexpr EnginePolicy kEngineSettings[] = {
-  /*  0 */ {EnginePolicy::Auto,    0, true,  false, false, false, false, false, false, false, false, false, false, false, "auto"},
-  /*  1 */ {EnginePolicy::General, 0, false, false, false, false, false, false, false, false, false, false, false, false, "general"},
-  /*  2 */ {EnginePolicy::Cursor,  0, true,  false, false, false, false, false, false, false, false, false, false, false, "cursor"},
-  /*  3 */ {EnginePolicy::Cursor,  1, false, false, false, false, false, false, false, false, false, false, false, false, "cursor-wide"},
-  /*  4 */ {EnginePolicy::Cursor,  2, false, false, false, false, false, false, false, false, false, false, false, false, "cursor-hbm"},
-  /*  5 */ {EnginePolicy::Cursor,  0, false, true,  false, false, false, false, false, false, false, false, false, false, "cursor-pair"},
-  /*  6 */ {EnginePolicy::Spread,  0, false, false, false, false, false, false, false, false, false, false, false, false, "spread"},
-  /*  7 */ {EnginePolicy::Auto,    0, true,  false, true,  false, false, false, false, false, false, false, false, false, "auto-nodes"},
-  /*  8 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, false, false, false, false, false, false, false, false, "cursor-nodes"},
-  /*  9 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  false, false, false, false, false, false, false, false, "auto-nodes-spread"},
-  /* 10 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, false, false, false, false, false, false, false, "spread-nodes"},
-  /* 11 */ {EnginePolicy::Auto,    0, true,  false, true,  false, true,  false, false, false, false, false, false, false, "auto-limits"},
-  /* 12 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, false, false, false, false, false, false, "cursor-limits"},
-  /* 13 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  false, false, false, false, false, false, "auto-limits-spread"},
-  /* 14 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, false, false, false, false, false, "spread-limits"},
-  /* 15 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  false, false, false, false, false, "auto-operators"},
-  /* 16 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, false, false, false, false, "cursor-operators"},
-  /* 17 */ {EnginePolicy::Cursor,  0, false, false, false, false, false, false, false, false, false, false, false, false, nullptr},   // no name: what a value past the table stands for (below), kept as it was
-  /* 18 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  false, false, false, false, "auto-operators-spread"},
-  /* 19 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, false, false, false, "spread-operators"},
-  /* 20 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  false, false, false, "auto-unschedulable"},
-  /* 21 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, true,  false, false, false, "cursor-unschedulable"},
-  /* 22 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  false, false, "auto-unschedulable-spread"},
-  /* 23 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  false, false, "spread-unschedulable"},
-  /* 24 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  false, "auto-filters-spread"},
-  /* 25 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  true,  false, "spread-filters"},
-  /* 26 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  true,  "auto-pod-operators"},
-  /* 27 */ {EnginePolicy::Cursor,  0, true,  false, true,  false, true,  false, true,  false, true,  false, false, true,  "cursor-pod-operators"},
-};
-inline constexpr uint32_t kEngineSettingCount = (uint32_t)(sizeof(kEngineSettings) / sizeof(kEngineSettings[0]));
-// A value past the table is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch.
-inline constexpr EnginePolicy kEngineSettingPastTable = {EnginePolicy::Cursor, 0, false, false, false, false, false, false, false, false, false, false, false, false, nullptr};
-
-// The second table: the rows added since the first one was pinned with its length (28 rows; value 28 is "past the table" for every
-// caller that passed it, as 17 was before it, and stays that). Its first row is value kEngineSettingsMoreFirst; a value behind its
-// last row is past the table again.
-inline constexpr uint32_t kEngineSettingsMoreFirst = 29;
-inline constexpr EnginePolicy kEngineSettingsMore[] = {
-  /* 29 */ {EnginePolicy::Auto,    0, true,  false, true,  true,  true,  true,  true,  true,  true,  true,  true,  true,  "auto-pod-operators-spread", true},   // 26 + the spread engine's pod operators
-  /* 30 */ {EnginePolicy::Spread,  0, false, false, false, true,  false, true,  false, true,  false, true,  true,  false, "spread-pod-operators", true},        // 25 + the same
-};
-inline constexpr uint32_t kEngineSettingMoreCount = (uint32_t)(sizeof(kEngineSettingsMore) / sizeof(kEngineSettingsMore[0]));
-
-inline const EnginePolicy& engine_policy(uint32_t value) {
-  if (value < kEngineSettingCount) return kEngineSettings[value];
-  if (value >= kEngineSettingsMoreFirst && value - kEngineSettingsMoreFirst < kEngineSettingMoreCount) return kEngineSettingsMore[value - kEngineSettingsMoreFirst];
-  return kEngineSettingPastTable;
+// A row is a run kind on a first plan, or the row it extends plus the switches it adds.
+constexpr EnginePolicy engine_row(EnginePolicy::Run run, uint8_t first_plan, bool pick_plan, const char* name) {
+  EnginePolicy p{};
+  p.run = run; p.first_plan = first_plan; p.pick_plan = pick_plan; p.name = name;
+  return p;
 }
+template <class... Switch>
+constexpr EnginePolicy engine_row(EnginePolicy from, const char* name, Switch... adds) {
+  from.name = name;
+  ((from.*adds = true), ...);
+  return from;
+}
+// A value without a row is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch, no name. 17 and 28 were
+// such values for every caller that passed them when the rows behind them were added, and stay that.
+inline constexpr EnginePolicy kEngineSettingPastTable = engine_row(EnginePolicy::Cursor, 0, false, nullptr);
+inline constexpr uint32_t kEngineSettingCount = 31;
+struct EngineTable { EnginePolicy row[kEngineSettingCount]; };
+constexpr EngineTable engine_table() {
+  using P = EnginePolicy;
+  EngineTable t{};
+  EnginePolicy* r = t.row;
+  r[0] = engine_row(P::Auto, 0, true, "auto");
+  r[1] = engine_row(P::General, 0, false, "general");
+  r[2] = engine_row(P::Cursor, 0, true, "cursor");
+  r[3] = engine_row(P::Cursor, 1, false, "cursor-wide");
+  r[4] = engine_row(P::Cursor, 2, false, "cursor-hbm");
+  r[5] = engine_row(engine_row(P::Cursor, 0, false, nullptr), "cursor-pair", &P::pair);
+  r[6] = engine_row(P::Spread, 0, false, "spread");
+  r[7] = engine_row(r[0], "auto-nodes", &P::nodes);
+  r[8] = engine_row(r[2], "cursor-nodes", &P::nodes);
+  r[9] = engine_row(r[7], "auto-nodes-spread", &P::spread_nodes);
+  r[10] = engine_row(r[6], "spread-nodes", &P::spread_nodes);
+  r[11] = engine_row(r[7], "auto-limits", &P::limits);
+  r[12] = engine_row(r[8], "cursor-limits", &P::limits);
+  r[13] = engine_row(r[9], "auto-limits-spread", &P::limits, &P::spread_limits);
+  r[14] = engine_row(r[10], "spread-limits", &P::spread_limits);
+  r[15] = engine_row(r[13], "auto-operators", &P::operators);
+  r[16] = engine_row(r[12], "cursor-operators", &P::operators);
+  r[17] = kEngineSettingPastTable;
+  r[18] = engine_row(r[15], "auto-operators-spread", &P::spread_operators);
+  r[19] = engine_row(r[14], "spread-operators", &P::spread_operators);
+  r[20] = engine_row(r[18], "auto-unschedulable", &P::unschedulable);
+  r[21] = engine_row(r[16], "cursor-unschedulable", &P::unschedulable);
+  r[22] = engine_row(r[20], "auto-unschedulable-spread", &P::spread_unschedulable);
+  r[23] = engine_row(r[19], "spread-unschedulable", &P::spread_unschedulable);
+  r[24] = engine_row(r[22], "auto-filters-spread", &P::spread_filters);
+  r[25] = engine_row(r[23], "spread-filters", &P::spread_filters);
+  r[26] = engine_row(r[24], "auto-pod-operators", &P::pod_operators);
+  r[27] = engine_row(r[21], "cursor-pod-operators", &P::pod_operators);
+  r[28] = kEngineSettingPastTable;
+  r[29] = engine_row(r[26], "auto-pod-operators-spread", &P::spread_pod_operators);
+  r[30] = engine_row(r[25], "spread-pod-operators", &P::spread_pod_operators);
+  return t;
+}
+inline constexpr EngineTable kEngineSettings = engine_table();
 
-// The value an option name stands for; 0 ("auto") for a name neither table holds. (A row without a name has none to match.)
+inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineSettingCount ? kEngineSettings.row[value] : kEngineSettingPastTable; }
+
+// The value an option name stands for; 0 ("auto") for a name the table does not hold. (A row without a name has none to match.)
 inline uint32_t engine_value(const char* name) {
-  for (uint32_t v = 0; v < kEngineSettingCount; ++v) if (kEngineSettings[v].name && !strcmp(kEngineSettings[v].name, name)) return v;
-  for (uint32_t v = 0; v < kEngineSettingMoreCount; ++v) if (kEngineSettingsMore[v].name && !strcmp(kEngineSettingsMore[v].name, name)) return kEngineSettingsMoreFirst + v;
+  for (uint32_t v = 0; v < kEngineSettingCount; ++v) if (kEngineSettings.row[v].name && !strcmp(kEngineSettings.row[v].name, name)) return v;
   return 0;
 }
 

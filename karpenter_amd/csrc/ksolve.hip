@@ -706,83 +706,71 @@ static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, 
   float ms = 0;
   if (hipEventElapsedTime(&ms, b->ev0[ksi::T_PACK], b->ev1[ksi::T_PACK]) == hipSuccess) h->timers.ms[ksi::T_PACK] = ms;
 }
-typedef void (*ksolve_pack_fast_fn)(const ks::FastArgs*);
-static ksolve_pack_fast_fn pack_fast_kernel(int plan, int rows, bool unsched, bool podops) {
-  if (podops) {   // engines 26 / 27: the kernels with the set-aside list and the pod operators compiled in
-    if (rows == 1) return plan == 2 ? ksolve_pack_fast_p_g2r1 : plan == 1 ? ksolve_pack_fast_p_g1r1 : ksolve_pack_fast_p_g0r1;
-    return plan == 2 ? ksolve_pack_fast_p_g2r4 : plan == 1 ? ksolve_pack_fast_p_g1r4 : ksolve_pack_fast_p_g0r4;
-  }
-  if (unsched) {   // engines 20 / 21: the kernels with the set-aside list compiled in
-    if (rows == 1) return plan == 2 ? ksolve_pack_fast_u_g2r1 : plan == 1 ? ksolve_pack_fast_u_g1r1 : ksolve_pack_fast_u_g0r1;
-    return plan == 2 ? ksolve_pack_fast_u_g2r4 : plan == 1 ? ksolve_pack_fast_u_g1r4 : ksolve_pack_fast_u_g0r4;
-  }
-  if (rows == 1) return plan == 2 ? ksolve_pack_fast_g2r1 : plan == 1 ? ksolve_pack_fast_g1r1 : ksolve_pack_fast_g0r1;
-  return plan == 2 ? ksolve_pack_fast_g2r4 : plan == 1 ? ksolve_pack_fast_g1r4 : ksolve_pack_fast_g0r4;
-}
+// The function pointers of the rows of pack_flavours.h, in list order: the only column of the kernel matrix that is the HIP backend's own.
+#define KS_ROW_FN(NAME, ...) NAME,
+static const ksolve_pack_fast_fn kPackFastFn[] = {KS_PACK_FAST_ROWS(KS_ROW_FN)};
+static const ksolve_pack_topo_fn kPackTopoFn[] = {KS_PACK_TOPO_ROWS(KS_ROW_FN)};
+static const ksolve_pack_topo_many_fn kPackTopoManyFn[] = {KS_PACK_TOPO_MANY_ROWS(KS_ROW_FN)};
+#ifdef KSOLVE_TEST_HOOKS
+static const ksolve_test_fast_cold_fn kFastColdFn[] = {KS_FAST_COLD_ROWS(KS_ROW_FN)};
+#endif
+#undef KS_ROW_FN
+static void check_launch(ksolve_handle* h, const char* kernel) { hip_check(h, hipGetLastError(), (std::string(kernel) + " launch").c_str()); }
 static void be_launch_pack_fast(ksolve_handle* h) {
   const int lds_bytes = h->fw.plan.total_bytes;
   const bool two = h->fw.plan.helper != 0;   // (plan 0, one row of class slots: placer + refresher)
-  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : pack_fast_kernel(h->fw.plan.global_state, h->fw.plan.rows, h->fw.unsched != 0, h->fw.podops != nullptr);
+  const ks::PackFastRow* row = ks::pack_fast_row(ks::fast_flavour(h->fw), h->fw.plan.global_state, h->fw.plan.rows);
+  if (!two && !row) { HB(h)->failed = true; if (h->error.empty()) h->error = "no cursor-engine kernel of the handle's flavour, plan and rows"; return; }   // (fast_plan_set makes no such plan)
+  const ksolve_pack_fast_fn fn = two ? ksolve_pack_fast2 : kPackFastFn[row - ks::kPackFastRows];
+  note_pack_kernel(h, two ? ks::kPackFastPair : row->kernel);
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));
   hipLaunchKernelGGL(fn, dim3(1), dim3(two ? 256 : 64), (size_t)lds_bytes, HB(h)->stream, (const ks::FastArgs*)h->d_fast_args);
-  hip_check(h, hipGetLastError(), "ksolve_pack_fast launch");
+  check_launch(h, h->pack_kernel[0]);
 }
 #ifdef KSOLVE_TEST_HOOKS
 // FastCold alone (fast_cold_probe.h): the instantiations ksolve_test_fast_cold.hip compiles, on the LDS segment of the handle's plan
 static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* d_args, int plan, int rows, int flavour) {
-  typedef void (*fn_t)(const ks::FastColdArgs*);
-  fn_t fn = nullptr;
-  if (plan == 0 && rows == 1) fn = flavour == 2 ? ksolve_test_fast_cold_p_g0r1 : flavour == 1 ? ksolve_test_fast_cold_u_g0r1 : ksolve_test_fast_cold_g0r1;
-  else if (plan == 0) fn = flavour == 2 ? ksolve_test_fast_cold_p_g0r4 : flavour == 1 ? ksolve_test_fast_cold_u_g0r4 : ksolve_test_fast_cold_g0r4;
-  else if (plan == 1 && rows == 1 && flavour == 0) fn = ksolve_test_fast_cold_g1r1;
-  else if (plan == 2 && rows == ks::kFastRows && flavour == 1) fn = ksolve_test_fast_cold_u_g2r4;
-  if (!fn) return 0;
+  const ks::PackFastRow* row = ks::fast_cold_row((ks::FastFlavour)flavour, plan, rows);
+  if (!row) return 0;
+  const ksolve_test_fast_cold_fn fn = kFastColdFn[row - ks::kFastColdRows];
   const int lds_bytes = h->fw.plan.total_bytes;
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return 0;
   hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, d_args);
-  hip_check(h, hipGetLastError(), "ksolve_test_fast_cold launch");
+  check_launch(h, row->kernel);
   return (uint32_t)(flavour * 100 + plan * 10 + rows);
 }
 #endif
-static void launch_pack_topo(ksolve_handle* h, void (*fn)(const ks::TopoArgs*), const char* what) {
+// the spread engine's kernel of the handle's flavour (engines 22 / 23: the set-aside list compiled in; 24 / 25: the topology node
+// filters as well; 29 / 30: and the pod operators), without or with existing nodes
+static void launch_pack_topo(ksolve_handle* h, const ks::PackTopoRow* row) {
+  const ksolve_pack_topo_fn fn = kPackTopoFn[row - ks::kPackTopoRows];
+  note_pack_kernel(h, row->kernel);
   const int lds_bytes = h->tw.plan.total_bytes;
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
   be_h2d(h, h->d_topo_args, &a, sizeof(a));
   hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::TopoArgs*)h->d_topo_args);
-  hip_check(h, hipGetLastError(), what);
+  check_launch(h, row->kernel);
 }
-// (engines 22 / 23: the kernels with the set-aside list compiled in; 24 / 25: those with the topology node filters as well)
-static void be_launch_pack_topo(ksolve_handle* h) {
-  if (h->fw.podops) launch_pack_topo(h, ksolve_pack_topo_p, "ksolve_pack_topo_p launch");   // 29 / 30: ... and the pod operators as well
-  else if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_f, "ksolve_pack_topo_f launch");
-  else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_u, "ksolve_pack_topo_u launch");
-  else launch_pack_topo(h, ksolve_pack_topo, "ksolve_pack_topo launch");
-}
-static void be_launch_pack_topo_nodes(ksolve_handle* h) {
-  if (h->fw.podops) launch_pack_topo(h, ksolve_pack_topo_nodes_p, "ksolve_pack_topo_nodes_p launch");
-  else if (h->fw.filt) launch_pack_topo(h, ksolve_pack_topo_nodes_f, "ksolve_pack_topo_nodes_f launch");
-  else if (h->fw.unsched) launch_pack_topo(h, ksolve_pack_topo_nodes_u, "ksolve_pack_topo_nodes_u launch");
-  else launch_pack_topo(h, ksolve_pack_topo_nodes, "ksolve_pack_topo_nodes launch");
-}
+static void be_launch_pack_topo(ksolve_handle* h) { launch_pack_topo(h, ks::pack_topo_row(ks::topo_flavour(h->fw), false)); }
+static void be_launch_pack_topo_nodes(ksolve_handle* h) { launch_pack_topo(h, ks::pack_topo_row(ks::topo_flavour(h->fw), true)); }
 // ksolve_solve_many: one launch of the spread engine's many-problem kernel of every flavour that has members (topo_many.h), each on
 // the stream of its first member so that the flavours overlap; every member's T_PACK timer gets the time of its own launch. The
 // launch's table — the members' records, the order table, the ticket counter — lives in a buffer the first member's backend keeps
 // and grows (HipBackend::many_buf): no allocation and no device-wide synchronise per call once it is there. A member whose record
 // could not be uploaded stays out of the launch with its own error; the others run.
-typedef void (*ksolve_pack_topo_many_fn)(const ks::TopoArgs* const*, const uint32_t*, uint32_t*, int);
 static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups) {
-  static const ksolve_pack_topo_many_fn kFn[ksi::kTopoManyFlavours] = {ksolve_pack_topo_many, ksolve_pack_topo_many_u, ksolve_pack_topo_many_f,
-                                                                       ksolve_pack_topo_nodes_many, ksolve_pack_topo_nodes_many_u, ksolve_pack_topo_nodes_many_f};
-  std::vector<ksolve_handle*> live[ksi::kTopoManyFlavours];
-  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
+  std::vector<ksolve_handle*> live[ks::kTopoManyFlavours];
+  for (int f = 0; f < ks::kTopoManyFlavours; ++f) {   // f: the row of ks::kPackTopoManyRows
+    const ksolve_pack_topo_many_fn fn = kPackTopoManyFn[f];
     int lds_bytes = 0;
     for (ksolve_handle* h : groups[f]) {
       ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
       be_h2d(h, h->d_topo_args, &a, sizeof(a));   // (synchronises the member's stream: its prepass is done before the launch reads its tables)
       if (!be_ok(h)) continue;
+      note_pack_kernel(h, ks::kPackTopoManyRows[f].kernel);
       live[f].push_back(h);
       lds_bytes = std::max(lds_bytes, h->tw.plan.total_bytes);
     }
@@ -805,14 +793,14 @@ static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups) {
     char* d = (char*)b->many_buf;
     hip_check(h0, hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, b->stream), "hipMemcpy(many)");
     hip_check(h0, hipStreamSynchronize(b->stream), "hipStreamSynchronize");   // `host` is a local
-    if (b->failed || !hip_check(h0, hipFuncSetAttribute((const void*)kFn[f], hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) continue;
+    if (b->failed || !hip_check(h0, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) continue;
     hip_check(h0, hipEventRecord(b->ev0[ksi::T_PACK], b->stream), "hipEventRecord");
-    hipLaunchKernelGGL(kFn[f], dim3((unsigned)n), dim3(64), (size_t)lds_bytes, b->stream, (const ks::TopoArgs* const*)d, (const uint32_t*)(d + n * sizeof(void*)),
+    hipLaunchKernelGGL(fn, dim3((unsigned)n), dim3(64), (size_t)lds_bytes, b->stream, (const ks::TopoArgs* const*)d, (const uint32_t*)(d + n * sizeof(void*)),
                        (uint32_t*)(d + n * sizeof(void*) + n * 4), (int)n);
-    hip_check(h0, hipGetLastError(), "ksolve_pack_topo_many launch");
+    check_launch(h0, ks::kPackTopoManyRows[f].kernel);
     hip_check(h0, hipEventRecord(b->ev1[ksi::T_PACK], b->stream), "hipEventRecord");
   }
-  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
+  for (int f = 0; f < ks::kTopoManyFlavours; ++f) {
     std::vector<ksolve_handle*>& g = live[f];
     if (g.empty()) continue;
     ksolve_handle* h0 = g[0];
@@ -833,6 +821,7 @@ static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {
     ks::FastArgs a{hs[i]->pv, hs[i]->ws, hs[i]->fw};
     be_h2d(hs[i], hs[i]->d_fast_args, &a, sizeof(a));
     ptrs[(size_t)i] = hs[i]->d_fast_args;
+    note_pack_kernel(hs[i], ks::kPackFastBatch);
     lds_bytes = std::max(lds_bytes, hs[i]->fw.plan.total_bytes);
   }
   const ks::FastArgs** d_ptrs = nullptr;
@@ -842,7 +831,7 @@ static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {
   if (hip_check(h0, hipFuncSetAttribute((const void*)ksolve_pack_fast_batch, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) {
     hip_check(h0, hipEventRecord(b->ev0[ksi::T_PACK], b->stream), "hipEventRecord");
     hipLaunchKernelGGL(ksolve_pack_fast_batch, dim3((unsigned)n), dim3(64), (size_t)lds_bytes, b->stream, (const ks::FastArgs* const*)d_ptrs);
-    hip_check(h0, hipGetLastError(), "ksolve_pack_fast_batch launch");
+    check_launch(h0, ks::kPackFastBatch);
     hip_check(h0, hipEventRecord(b->ev1[ksi::T_PACK], b->stream), "hipEventRecord");
     hip_check(h0, hipEventSynchronize(b->ev1[ksi::T_PACK]), "hipEventSynchronize");
     float ms = 0;
@@ -872,11 +861,12 @@ static void be_launch_fast_unsched(ksolve_handle* h) {
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
   const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
   const ksolve_pack_fast_fn fn = hbm ? ksolve_pack_nodes_hbm : ksolve_pack_nodes_lds;
+  note_pack_kernel(h, hbm ? ks::kPackNodesHbm : ks::kPackNodesLds);
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));
   hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::FastArgs*)h->d_fast_args);
-  hip_check(h, hipGetLastError(), "ksolve_pack_nodes launch");
+  check_launch(h, h->pack_kernel[0]);
   const int n = (int)h->n_pods;
   const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
   hipLaunchKernelGGL(ksolve_fast_requeue, grid_for(n), dim3(256), 0, HB(h)->stream, n, q);
@@ -1057,6 +1047,9 @@ ksolve_status ksolve_test_fast_records(const ksolve_test_fast_records_in* in, ks
 ksolve_status ksolve_test_fast_cold(const ksolve_test_fast_cold_in* in, ksolve_test_fast_cold_out* out) {
   return test_on_bare_handle("ksolve_test_fast_cold", [&](ksolve_handle* h) { return ksi::test_fast_cold(h, in, out); });
 }
+// the fast engines' pack kernel launched for the handle last, and the one before it (pack_flavours.h names; NULL: none yet)
+const char* ksolve_test_last_pack_kernel(const ksolve_handle* h) { return h ? h->pack_kernel[0] : nullptr; }
+const char* ksolve_test_previous_pack_kernel(const ksolve_handle* h) { return h ? h->pack_kernel[1] : nullptr; }
 #endif
 ksolve_status ksolve_probe_create(ksolve_handle* base, const ksolve_probe* probe, ksolve_handle** out) {
   if (!out) return KSOLVE_ERR_INVALID;

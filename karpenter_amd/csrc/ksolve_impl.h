@@ -16,6 +16,7 @@
 
 #include "../../include/ksolve.h"
 #include "engine_setting.h"
+#include "pack_flavours.h"
 #include "engine.h"
 #include "kernels.h"
 #include "fast_engine.h"
@@ -112,6 +113,7 @@ struct ksolve_handle {
   bool sweep_arena_refused = false;   // the last sweep_run stopped because the device refused its arena (sweep() then halves the launch)
   size_t sweep_last_total = 0;   // arena bytes the last sweep_run laid out (held against sweep_probe_bytes by the test builds)
   char* sweep_fin = nullptr; size_t sweep_fin_bytes = 0;     // finalize outputs + gathered claim records of a sweep
+  const char* pack_kernel[2] = {nullptr, nullptr};   // the pack kernels the backend launched for this handle last ([0]) and before that: a row's name of pack_flavours.h (note_pack_kernel; read by the test builds)
 #ifdef KSOLVE_TEST_HOOKS
   uint32_t test_row_kernel = 0;   // which classing kernel be_launch_row_hash launched last (KSOLVE_TEST_ROW_KERNEL_*) | rows per block << 8
 #endif
@@ -472,6 +474,8 @@ static void be_range_drop(ksolve_handle* h);   // closes the trace range of a be
 // a phase that has several error exits: the range be_tic opened is closed on whichever way out (the marker trace nested wrongly
 // for the rest of the process after a failed sweep)
 struct PhaseRange { ksolve_handle* h; bool open; ~PhaseRange() { if (open) be_range_drop(h); } };
+// every pack launch of the fast engines leaves the name of its kernel on the handle (a row of pack_flavours.h, both backends alike)
+static inline void note_pack_kernel(ksolve_handle* h, const char* kernel) { h->pack_kernel[1] = h->pack_kernel[0]; h->pack_kernel[0] = kernel; }
 static void be_launch_it_index(ksolve_handle* h, int n, const ks::ItIndexArgs& a);
 #ifdef KSOLVE_TEST_HOOKS
 static void be_launch_reqalg_test(ksolve_handle* h, int n, const ks::ReqalgTestArgs& a);   // one thread per pair: reqalg_test_body
@@ -487,12 +491,7 @@ static void be_launch_pack_fast(ksolve_handle* h);                 // one wavefr
 static void be_launch_pack_topo(ksolve_handle* h);                 // one wavefront: TopoEngine::solve
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n);   // block b = the cursor engine on problem b; sets every handle's T_PACK timer
 static void be_launch_fast_records(ksolve_handle* h, int n_claims); // one wavefront per claim: fast_record_body; then fast_scatter_body per queue entry
-#ifdef KSOLVE_HOST_EMULATION
-// (the emulation's launch is the loop over the grid)
-static void be_launch_eff_alloc(ksolve_handle*, const ks::EffAllocArgs& a) { for (int t = 0; t < a.n_templates; ++t) for (int it = 0; it < a.n_its; ++it) ks::eff_alloc_body(t, it, a); }
-#else
 static void be_launch_eff_alloc(ksolve_handle* h, const ks::EffAllocArgs& a);   // ksolve_fast_eff_alloc: one thread per (template, instance type)
-#endif
 static void be_launch_fast_queue(ksolve_handle* h, bool count_live);   // one thread per queue entry: fast_queue_body (+ ksolve_fast_overlap when asked)
 static void be_launch_pack_batch(ksolve_handle** hs, int n);
 static void be_thread_init(ksolve_handle* h);   // makes the handle's device current on a worker thread   // one block per handle; sets every handle's T_PACK timer
@@ -505,7 +504,7 @@ static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: Top
 static void be_launch_fast_unsched(ksolve_handle* h);               // engines 20 / 21, one thread per pod set aside: fast_unsched_body (errors under the pod indices)
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
-static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups);   // ksolve_solve_many: groups[ksi::kTopoManyFlavours], one ksolve_pack_topo*_many launch per group that has members (block = one ticket = one member, largest first); sets every member's T_PACK timer
+static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups);   // ksolve_solve_many: groups[ks::kTopoManyFlavours] by row of ks::kPackTopoManyRows, one ksolve_pack_topo*_many launch per group that has members (block = one ticket = one member, largest first); sets every member's T_PACK timer
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
 static void be_launch_sweep_items(ksolve_handle* h, int n, const ks::SweepItemArgs& a);
 
@@ -1984,12 +1983,13 @@ static ksolve_status test_fast_cold(ksolve_handle* h, const ksolve_test_fast_col
   fw.enabled = 1;
   fw.ops = in->ops ? 1 : 0;
   if (in->lim) fw.lim = dz<ks::FastLimits>(h, 1);
-  fw.unsched = in->flavour >= 1 ? 1 : 0;
+  const ks::FastFlavour flavour = (ks::FastFlavour)in->flavour;
+  fw.unsched = ks::flavour_us(flavour) ? 1 : 0;
   if (fw.unsched) {
     fw.us_n = dz<uint32_t>(h, 1); fw.us_entry = dz<uint32_t>(h, nc); fw.us_last = dz<uint32_t>(h, nc);
     fw.us_err = dz<uint8_t>(h, nc); fw.us_diag = dz<uint8_t>(h, nc); fw.us_cls = dz<uint64_t>(h, nc);
   }
-  fw.podops = in->flavour == 2 ? dz<ks::FastPodOps>(h, 1) : nullptr;
+  fw.podops = ks::flavour_po(flavour) ? dz<ks::FastPodOps>(h, 1) : nullptr;
   // what the probe writes: 0xA5 everywhere
   const size_t misc_words = sizeof(ks::FastMisc) / 8, rec_words = 3 + rows;
   ks::FastColdArgs A{};
@@ -3466,9 +3466,8 @@ static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksol
 // solve() itself, walked for all members at once:
 //   refusals -> the spread engine's many-problem launches (one per kernel flavour present) -> the cursor engine's batched launch
 //   (alone where solve() would run another kernel) -> the general engine's batched launch, with whatever the fast engines handed back.
-enum { kTopoManyFlavours = 6 };
-// the kernel be_launch_pack_topo / be_launch_pack_topo_nodes would pick: plain, _u, _f, then the three with existing nodes
-static int topo_many_flavour(const ksolve_handle* h) { return (h->tw.nd.dom ? 3 : 0) + (h->fw.filt ? 2 : h->fw.unsched ? 1 : 0); }
+// the many-problem form of the kernel be_launch_pack_topo would pick (pack_flavours.h); nullptr: there is none, the member runs alone
+static const ks::PackTopoRow* topo_many_row(const ksolve_handle* h) { return ks::pack_topo_many_row(ks::topo_flavour(h->fw), h->tw.nd.dom != nullptr); }
 // the order table of one launch: its members by pod count, largest first (ties in input order); tickets are handed out along it
 static void topo_many_order(const std::vector<ksolve_handle*>& g, uint32_t* order) {
   for (size_t i = 0; i < g.size(); ++i) order[i] = (uint32_t)i;
@@ -3506,7 +3505,7 @@ static ksolve_status solve_many_plain(ksolve_handle** hs, uint32_t n, ksolve_res
     if (!h->n_pods) continue;   // nothing to launch: solve_finish
     if (h->tw.enabled && h->n_classes) {
       // (engines 29 / 30: the kernels with the pod operators have no many-problem form — a launch of its own, as solve() makes it)
-      if (h->fw.podops) alone(i); else spread.push_back(i);
+      if (topo_many_row(h)) spread.push_back(i); else alone(i);
     }
     else if (h->fw.enabled && !h->pv.big && h->n_classes) {
       // the batched kernel is the LDS plan of ksolve_pack_fast_g0r*: a handle solve() would run on another kernel (a plan in HBM, the
@@ -3523,12 +3522,12 @@ static ksolve_status solve_many_plain(ksolve_handle** hs, uint32_t n, ksolve_res
     be_sync(hs[i]); run.push_back(i); S.handed_back++;
   };
   if (!spread.empty()) {
-    std::vector<ksolve_handle*> groups[kTopoManyFlavours];
+    std::vector<ksolve_handle*> groups[ks::kTopoManyFlavours];
     for (uint32_t i : spread) {
       ksolve_handle* h = hs[i];   // what solve() does in front of its launch
       alloc_run_order(h);
       if (h->tw.nd.dom) { node_static_rows(h); h->tw.nd.dead0 = h->nd_dead0; }
-      groups[topo_many_flavour(h)].push_back(h);
+      groups[topo_many_row(h) - ks::kPackTopoManyRows].push_back(h);
     }
     be_launch_pack_topo_many(groups);
     for (auto& g : groups) if (!g.empty()) S.spread_launches++;
@@ -3673,64 +3672,5 @@ static ksolve_status solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* 
 }  // namespace ksi
 
 #ifdef KSOLVE_HOST_EMULATION
-#include "topo_engine.h"
-// The host emulation's launches of the node kernels (the other launches of the emulation live with its backend): a kernel launch is a loop over its grid.
-static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
-  const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
-  std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
-  ks::FastArgs a{h->pv, h->ws, h->fw};
-  be_h2d(h, h->d_fast_args, &a, sizeof(a));
-  if (hbm) ks::pack_nodes_body<ks::Wave, true>(h->d_fast_args, lds.data());
-  else ks::pack_nodes_body<ks::Wave, false>(h->d_fast_args, lds.data());
-  const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);
-  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_requeue_body(i, q);
-  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_remark_body(i, q);
-}
-static void be_launch_fast_unsched(ksolve_handle* h) {
-  const ks::FastUnschedArgs a = ksi::fast_unsched_args(h);
-  for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_unsched_body(i, a);
-}
-static void be_launch_pack_topo_nodes(ksolve_handle* h) {
-  std::vector<char> lds((size_t)h->tw.plan.total_bytes + 64, (char)0xA5);
-  ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
-  be_h2d(h, h->d_topo_args, &a, sizeof(a));
-  const ks::TopoArgs* a_ = h->d_topo_args;
-  ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data());
-  eng.solve();
-}
-// The emulated ksolve_pack_topo*_many launches (topo_many.h): a loop over the grid in which every block takes a ticket from the
-// launch's counter and solves the member the order table names, one after another; the LDS segment is the launch's (the largest
-// member's plan), each engine reading its own tw.plan offsets. (The emulation's engine has the set-aside list and the filters built in.)
-static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups) {
-  for (int f = 0; f < ksi::kTopoManyFlavours; ++f) {
-    std::vector<ksolve_handle*>& g = groups[f];
-    if (g.empty()) continue;
-    const uint32_t n = (uint32_t)g.size();
-    std::vector<uint32_t> order(n);
-    int lds_bytes = 0;
-    for (ksolve_handle* h : g) {
-      ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
-      be_h2d(h, h->d_topo_args, &a, sizeof(a));
-      lds_bytes = std::max(lds_bytes, h->tw.plan.total_bytes);
-    }
-    ksi::topo_many_order(g, order.data());
-    uint32_t next = 0;   // the launch's ticket counter
-    be_tic(g[0], ksi::T_PACK);
-    for (uint32_t block = 0; block < n; ++block) {
-      const uint32_t t = next++;
-      if (t >= n || order[t] >= n) continue;
-      const ks::TopoArgs* a_ = g[order[t]]->d_topo_args;
-      std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
-      if (f >= 3) { ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data()); eng.solve(); }
-      else { ks::TopoEngine<ks::Wave> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data()); eng.solve(); }
-    }
-    be_toc(g[0], ksi::T_PACK);
-    for (ksolve_handle* h : g) h->timers.ms[ksi::T_PACK] = g[0]->timers.ms[ksi::T_PACK];
-  }
-}
-// the emulation's export of ksolve_solve_many (its other exports live with its backend)
-extern "C" ksolve_status ksolve_solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats* stats) {
-  if (!hs || !outs || n == 0) return KSOLVE_ERR_INVALID;
-  return ksi::solve_many(hs, n, outs, stats);
-}
+#include "emu_launches.h"   // (the host emulation's share of the backend that is written against this header's internals; TEST ONLY)
 #endif

@@ -1,24 +1,25 @@
-// ksolve_pack_fast.hip — the cursor engine (fast_engine.h).
+// ksolve_pack_fast.hip — the cursor engine (fast_engine.h), compiled once per flavour (pack_flavours.h) with -DKS_PACK_FLAVOUR=<n>: every
+// build defines the rows of its flavour in KS_PACK_FAST_ROWS, in list order. An object per flavour, so that the kernels every other
+// setting runs are compiled without a later switch's code and keep their object.
 #include "pack_kernels.h"
 
-// The cursor engine (fast_engine.h) for purely positive provisioning batches: one wavefront, O(1) steps. Compiled per memory plan
+#ifndef KS_PACK_FLAVOUR
+#error "ksolve_pack_fast.hip is compiled per flavour: -DKS_PACK_FLAVOUR=<FastFlavour>"
+#endif
+// For purely positive provisioning batches: one wavefront, O(1) steps. Compiled per memory plan
 // (GS = 0: claim records and order in LDS; 1: records in HBM — problems that need more in-flight claims than a CU's LDS holds
 // beside the caches, the host retries here when the LDS plan ran out of claims; 2: the order arrays in HBM too, up to 65,472
 // in-flight claims — the exact configs[3] batch of 10M pods, 27,345) and per number of class-slot rows (FastPlan::rows).
-#define KS_PACK_FAST(NAME, GS, R)                                                   \
-  __global__ void __launch_bounds__(64) NAME(const ks::FastArgs* a) {               \
-    extern __shared__ __attribute__((aligned(16))) char lds[];                      \
-    ks::FastEngine<ks::Wave, GS, R> eng(&a->pv, &a->ws, &a->fw, lds);               \
-    eng.solve();                                                                    \
+#define KS_PACK_FAST(NAME, FL, GS, R)                                                                                                      \
+  __global__ void __launch_bounds__(64) NAME(const ks::FastArgs* a) {                                                                      \
+    extern __shared__ __attribute__((aligned(16))) char lds[];                                                                             \
+    ks::FastEngine<ks::Wave, GS, R, false, ks::flavour_us(ks::FastFlavour::FL), ks::flavour_po(ks::FastFlavour::FL)> eng(&a->pv, &a->ws, &a->fw, lds); \
+    eng.solve();                                                                                                                           \
   }
-KS_PACK_FAST(ksolve_pack_fast_g0r1, 0, 1)
-KS_PACK_FAST(ksolve_pack_fast_g1r1, 1, 1)
-KS_PACK_FAST(ksolve_pack_fast_g2r1, 2, 1)
-KS_PACK_FAST(ksolve_pack_fast_g0r4, 0, ks::kFastRows)
-KS_PACK_FAST(ksolve_pack_fast_g1r4, 1, ks::kFastRows)
-KS_PACK_FAST(ksolve_pack_fast_g2r4, 2, ks::kFastRows)
+KS_CAT(KS_PACK_FAST_ROWS_, KS_PACK_FLAVOUR)(KS_PACK_FAST)
 #undef KS_PACK_FAST
 static_assert(ks::kFastRows == 4, "the kernels' names say four rows");
+#if KS_PACK_FLAVOUR == 0
 // The LDS plan with one row of class slots on TWO wavefronts (FastPlan::helper; fast_engine.h FastMail): wavefront 0 places the
 // pods, another one recomputes the acceptance words of the claim a pod was added to while wavefront 0 is at the next pod. The two must
 // sit on DIFFERENT SIMDs to issue side by side, and where the dispatcher puts a workgroup's wavefronts is its business: the
@@ -49,3 +50,4 @@ __global__ void __launch_bounds__(64) ksolve_pack_fast_batch(const ks::FastArgs*
   if (a->fw.plan.rows == 1) { ks::FastEngine<ks::Wave, 0, 1> eng(&a->pv, &a->ws, &a->fw, lds); eng.solve(); }
   else { ks::FastEngine<ks::Wave, 0, ks::kFastRows> eng(&a->pv, &a->ws, &a->fw, lds); eng.solve(); }
 }
+#endif

@@ -1,5 +1,5 @@
 // topo_types.h — what the host side (ksolve_impl.h: buffers, LDS plan, kernel arguments) shares with the spread engine
-// (topo_engine.h, compiled into ksolve_pack_topo.hip, ksolve_pack_topo_nodes.hip and the test emulation only).
+// (topo_engine.h, compiled into ksolve_pack_topo.hip, ksolve_pack_topo_many.hip and the test emulation only).
 #pragma once
 #include "fast_engine.h"
 #include "run_order.h"

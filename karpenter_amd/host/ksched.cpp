@@ -2264,6 +2264,9 @@ extern "C" int ksched_cancel(void* session) {
   if (!S || !S->handle || !S->api.cancel) return -1;
   return (int)S->api.cancel(S->handle);
 }
+// The session's handle of the solver library (ksolve_handle*), for a caller that asks that library about it through the C ABI itself
+// (ksolve_last_kernel_ms, ksolve_last_error, an entry point of a test build). The session owns it: valid until ksched_close.
+extern "C" void* ksched_solver_handle(void* session) { return session ? (void*)((Session*)session)->handle : nullptr; }
 // One probe of a resident cluster (ksolve_probe_create): `probe_json` = {"removeNodes": [node names], "pods": [uids]}.
 // The new session shares the base session's tables on the host and on the device; close it before the base session.
 // the session's node -> bound pods table (CSR) and the pods every simulation schedules (pending pods, pods of deleting nodes): built

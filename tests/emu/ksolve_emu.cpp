@@ -105,12 +105,24 @@ static void be_launch_pack(ksolve_handle* h) {
   for (auto& g : gaps) __asan_unpoison_memory_region(lds.data() + g.first, (size_t)g.second);
 #endif
 }
-static void be_launch_pack_fast(ksolve_handle* h) {
+// The plan / rows dispatch of the cursor engine's instantiations, once: run(plan, rows) with both as compile-time constants. (The
+// emulation's engines have every switch built in — kFastKeepBuiltIn — and FastWork's switches decide at run time.)
+template <class F> static void with_plan_rows(int plan, int rows, F run) {
+  auto with_rows = [&](auto gs) {
+    if (rows == 1) run(gs, std::integral_constant<int, 1>());
+    else run(gs, std::integral_constant<int, ks::kFastRows>());
+  };
+  if (plan == 2) with_rows(std::integral_constant<int, 2>());
+  else if (plan == 1) with_rows(std::integral_constant<int, 1>());
+  else with_rows(std::integral_constant<int, 0>());
+}
+// the cursor engine on the handle's plan, noted as `kernel`: the name of the device kernel this run stands for
+static void run_pack_fast(ksolve_handle* h, const char* kernel) {
   std::vector<char> lds((size_t)h->fw.plan.total_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));
   const ks::FastArgs* a_ = h->d_fast_args;
-  const int gs = h->fw.plan.global_state;
+  note_pack_kernel(h, kernel);
   if (h->fw.plan.helper) {
     // ksolve_pack_fast2: the placer's code; the refresher wavefront is a function the placer calls when it waits for it
     ks::FastHot* hs = (ks::FastHot*)(lds.data() + h->fw.plan.off_hot);
@@ -118,29 +130,19 @@ static void be_launch_pack_fast(ksolve_handle* h) {
     ks::fast_emu_helper_k<1>() = ks::FastHelperK<1>();
     { const char* v = getenv("KSOLVE_EMU_REFRESHER_EAGER"); ks::fast_emu_helper_eager() = v && v[0] == '1'; }
     ks::FastEngine<ks::Wave, 0, 1, true> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve();
-  } else if (h->fw.plan.rows == 1) {
-    if (gs == 2) { ks::FastEngine<ks::Wave, 2, 1> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
-    else if (gs) { ks::FastEngine<ks::Wave, 1, 1> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
-    else { ks::FastEngine<ks::Wave, 0, 1> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
-  } else {
-    if (gs == 2) { ks::FastEngine<ks::Wave, 2, ks::kFastRows> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
-    else if (gs) { ks::FastEngine<ks::Wave, 1, ks::kFastRows> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
-    else { ks::FastEngine<ks::Wave, 0, ks::kFastRows> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); }
+    return;
   }
+  with_plan_rows(h->fw.plan.global_state, h->fw.plan.rows, [&](auto gs, auto r) { ks::FastEngine<ks::Wave, gs(), r()> eng(&a_->pv, &a_->ws, &a_->fw, lds.data()); eng.solve(); });
+}
+// the kernel the device backend would launch, from the same lookup
+static void be_launch_pack_fast(ksolve_handle* h) {
+  run_pack_fast(h, h->fw.plan.helper ? ks::kPackFastPair : ks::pack_fast_row(ks::fast_flavour(h->fw), h->fw.plan.global_state, h->fw.plan.rows)->kernel);
 }
 // FastCold alone (fast_cold_probe.h): the device kernels' body on the loop-over-lanes Wave. The emulation's FastCold has the set-aside
 // list and the pod operators built in (kFastKeepBuiltIn) and FastWork's switches decide, so every (plan, rows, flavour) runs here.
 static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* a, int plan, int rows, int flavour) {
   std::vector<char> lds((size_t)h->fw.plan.total_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
-  if (rows == 1) {
-    if (plan == 2) ks::fast_cold_probe_body<ks::Wave, 2, 1, true, true>(a, lds.data());
-    else if (plan == 1) ks::fast_cold_probe_body<ks::Wave, 1, 1, true, true>(a, lds.data());
-    else ks::fast_cold_probe_body<ks::Wave, 0, 1, true, true>(a, lds.data());
-  } else {
-    if (plan == 2) ks::fast_cold_probe_body<ks::Wave, 2, ks::kFastRows, true, true>(a, lds.data());
-    else if (plan == 1) ks::fast_cold_probe_body<ks::Wave, 1, ks::kFastRows, true, true>(a, lds.data());
-    else ks::fast_cold_probe_body<ks::Wave, 0, ks::kFastRows, true, true>(a, lds.data());
-  }
+  with_plan_rows(plan, rows, [&](auto gs, auto r) { ks::fast_cold_probe_body<ks::Wave, gs(), r(), true, true>(a, lds.data()); });
   return (uint32_t)(1000 + flavour * 100 + plan * 10 + rows);
 }
 static void be_launch_pack_topo(ksolve_handle* h) {
@@ -148,6 +150,7 @@ static void be_launch_pack_topo(ksolve_handle* h) {
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
   be_h2d(h, h->d_topo_args, &a, sizeof(a));
   const ks::TopoArgs* a_ = h->d_topo_args;
+  note_pack_kernel(h, ks::pack_topo_row(ks::topo_flavour(h->fw), false)->kernel);
   ks::TopoEngine<ks::Wave> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data());
   eng.solve();
 }
@@ -168,7 +171,7 @@ static void be_launch_fast_queue(ksolve_handle* h, bool count_live) {
   for (int i = 0; i < (int)h->n_pods; ++i) ks::fast_mark_body(i, q);
 }
 static void be_launch_pack_fast_batch(ksolve_handle** hs, int n) {
-  for (int i = 0; i < n; ++i) { be_tic(hs[i], ksi::T_PACK); be_launch_pack_fast(hs[i]); be_toc(hs[i], ksi::T_PACK); }
+  for (int i = 0; i < n; ++i) { be_tic(hs[i], ksi::T_PACK); run_pack_fast(hs[i], ks::kPackFastBatch); be_toc(hs[i], ksi::T_PACK); }   // (one launch on the device: block b = problem b)
 }
 static void be_launch_pack_batch(ksolve_handle** hs, int n) {
   for (int i = 0; i < n; ++i) { be_tic(hs[i], ksi::T_PACK); be_launch_pack(hs[i]); be_toc(hs[i], ksi::T_PACK); }
@@ -344,6 +347,9 @@ ksolve_status ksolve_test_fast_records(const ksolve_test_fast_records_in* in, ks
 ksolve_status ksolve_test_fast_cold(const ksolve_test_fast_cold_in* in, ksolve_test_fast_cold_out* out) {
   return test_on_bare_handle("ksolve_test_fast_cold", [&](ksolve_handle* h) { return ksi::test_fast_cold(h, in, out); });
 }
+// the fast engines' pack kernel the device backend would have launched for the handle last, and the one before it (pack_flavours.h)
+const char* ksolve_test_last_pack_kernel(const ksolve_handle* h) { return h ? h->pack_kernel[0] : nullptr; }
+const char* ksolve_test_previous_pack_kernel(const ksolve_handle* h) { return h ? h->pack_kernel[1] : nullptr; }
 // The product's Go-sort (csrc/go_sort.h, used by the finalize kernel for OrderByPrice) on an array of integer keys:
 // out_perm receives the original indices in sorted order, ties as Go's sort.Slice leaves them.
 void ksolve_emu_go_sort(const long long* keys, int n, int* out_perm) {

@@ -45,52 +45,57 @@ def test_the_record_exercises_what_it_is_for():
     assert not missing, missing
 
 
-# every row of csrc/engine_setting.h's kEngineSettings, the row a value past the table decodes to, and four engine_value lookups
-# (value, run, first plan, pick, pair, nodes, s-nodes, limits, s-limits, ops, s-ops, unsched, s-unsched, s-filters, pod-ops, name)
+# every row of csrc/engine_setting.h's table, the row a value past the table decodes to, and six engine_value lookups
+# (value, run, first plan, pick, pair, nodes, s-nodes, limits, s-limits, ops, s-ops, unsched, s-unsched, s-filters, pod-ops, s-pod-ops, name)
 ENGINE_TABLE = """\
-0 0 0 1 0 0 0 0 0 0 0 0 0 0 0 auto
-1 1 0 0 0 0 0 0 0 0 0 0 0 0 0 general
-2 2 0 1 0 0 0 0 0 0 0 0 0 0 0 cursor
-3 2 1 0 0 0 0 0 0 0 0 0 0 0 0 cursor-wide
-4 2 2 0 0 0 0 0 0 0 0 0 0 0 0 cursor-hbm
-5 2 0 0 1 0 0 0 0 0 0 0 0 0 0 cursor-pair
-6 3 0 0 0 0 0 0 0 0 0 0 0 0 0 spread
-7 0 0 1 0 1 0 0 0 0 0 0 0 0 0 auto-nodes
-8 2 0 1 0 1 0 0 0 0 0 0 0 0 0 cursor-nodes
-9 0 0 1 0 1 1 0 0 0 0 0 0 0 0 auto-nodes-spread
-10 3 0 0 0 0 1 0 0 0 0 0 0 0 0 spread-nodes
-11 0 0 1 0 1 0 1 0 0 0 0 0 0 0 auto-limits
-12 2 0 1 0 1 0 1 0 0 0 0 0 0 0 cursor-limits
-13 0 0 1 0 1 1 1 1 0 0 0 0 0 0 auto-limits-spread
-14 3 0 0 0 0 1 0 1 0 0 0 0 0 0 spread-limits
-15 0 0 1 0 1 1 1 1 1 0 0 0 0 0 auto-operators
-16 2 0 1 0 1 0 1 0 1 0 0 0 0 0 cursor-operators
-17 2 0 0 0 0 0 0 0 0 0 0 0 0 0 -
-18 0 0 1 0 1 1 1 1 1 1 0 0 0 0 auto-operators-spread
-19 3 0 0 0 0 1 0 1 0 1 0 0 0 0 spread-operators
-20 0 0 1 0 1 1 1 1 1 1 1 0 0 0 auto-unschedulable
-21 2 0 1 0 1 0 1 0 1 0 1 0 0 0 cursor-unschedulable
-22 0 0 1 0 1 1 1 1 1 1 1 1 0 0 auto-unschedulable-spread
-23 3 0 0 0 0 1 0 1 0 1 0 1 0 0 spread-unschedulable
-24 0 0 1 0 1 1 1 1 1 1 1 1 1 0 auto-filters-spread
-25 3 0 0 0 0 1 0 1 0 1 0 1 1 0 spread-filters
-26 0 0 1 0 1 1 1 1 1 1 1 1 1 1 auto-pod-operators
-27 2 0 1 0 1 0 1 0 1 0 1 0 0 1 cursor-pod-operators
-28 2 0 0 0 0 0 0 0 0 0 0 0 0 0 -
-26 27 25 0
-"""   # (28: past the table — the cursor engine alone, no switch; the last line: auto-pod-operators, cursor-pod-operators, spread-filters, no-such-name)
+0 0 0 1 0 0 0 0 0 0 0 0 0 0 0 0 auto
+1 1 0 0 0 0 0 0 0 0 0 0 0 0 0 0 general
+2 2 0 1 0 0 0 0 0 0 0 0 0 0 0 0 cursor
+3 2 1 0 0 0 0 0 0 0 0 0 0 0 0 0 cursor-wide
+4 2 2 0 0 0 0 0 0 0 0 0 0 0 0 0 cursor-hbm
+5 2 0 0 1 0 0 0 0 0 0 0 0 0 0 0 cursor-pair
+6 3 0 0 0 0 0 0 0 0 0 0 0 0 0 0 spread
+7 0 0 1 0 1 0 0 0 0 0 0 0 0 0 0 auto-nodes
+8 2 0 1 0 1 0 0 0 0 0 0 0 0 0 0 cursor-nodes
+9 0 0 1 0 1 1 0 0 0 0 0 0 0 0 0 auto-nodes-spread
+10 3 0 0 0 0 1 0 0 0 0 0 0 0 0 0 spread-nodes
+11 0 0 1 0 1 0 1 0 0 0 0 0 0 0 0 auto-limits
+12 2 0 1 0 1 0 1 0 0 0 0 0 0 0 0 cursor-limits
+13 0 0 1 0 1 1 1 1 0 0 0 0 0 0 0 auto-limits-spread
+14 3 0 0 0 0 1 0 1 0 0 0 0 0 0 0 spread-limits
+15 0 0 1 0 1 1 1 1 1 0 0 0 0 0 0 auto-operators
+16 2 0 1 0 1 0 1 0 1 0 0 0 0 0 0 cursor-operators
+17 2 0 0 0 0 0 0 0 0 0 0 0 0 0 0 -
+18 0 0 1 0 1 1 1 1 1 1 0 0 0 0 0 auto-operators-spread
+19 3 0 0 0 0 1 0 1 0 1 0 0 0 0 0 spread-operators
+20 0 0 1 0 1 1 1 1 1 1 1 0 0 0 0 auto-unschedulable
+21 2 0 1 0 1 0 1 0 1 0 1 0 0 0 0 cursor-unschedulable
+22 0 0 1 0 1 1 1 1 1 1 1 1 0 0 0 auto-unschedulable-spread
+23 3 0 0 0 0 1 0 1 0 1 0 1 0 0 0 spread-unschedulable
+24 0 0 1 0 1 1 1 1 1 1 1 1 1 0 0 auto-filters-spread
+25 3 0 0 0 0 1 0 1 0 1 0 1 1 0 0 spread-filters
+26 0 0 1 0 1 1 1 1 1 1 1 1 1 1 0 auto-pod-operators
+27 2 0 1 0 1 0 1 0 1 0 1 0 0 1 0 cursor-pod-operators
+28 2 0 0 0 0 0 0 0 0 0 0 0 0 0 0 -
+29 0 0 1 0 1 1 1 1 1 1 1 1 1 1 1 auto-pod-operators-spread
+30 3 0 0 0 0 1 0 1 0 1 0 1 1 0 1 spread-pod-operators
+31 2 0 0 0 0 0 0 0 0 0 0 0 0 0 0 -
+26 27 25 29 30 0
+"""   # (17, 28: no row of their own, 31: past the table — the cursor engine alone, no switch; the last line: auto-pod-operators,
+#        cursor-pod-operators, spread-filters, auto-pod-operators-spread, spread-pod-operators, no-such-name)
 
 
 def test_rows_of_the_engine_table(tmp_path):
-    """Every row of csrc/engine_setting.h, 17 and the policy of a value past the table included, printed by a program that includes the
-    header."""
+    """Every row of csrc/engine_setting.h, 17, 28 and the policy of a value past the table included, printed by a program that includes
+    the header."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = tmp_path / "rows.cpp"
     src.write_text('#include <cstdio>\n#include "engine_setting.h"\nstatic void row(int v, const ksi::EnginePolicy& p) {\n'
-                   '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s\\n", v, (int)p.run, p.first_plan, p.pick_plan, p.pair, p.nodes, p.spread_nodes, p.limits, p.spread_limits,\n'
-                   '         p.operators, p.spread_operators, p.unschedulable, p.spread_unschedulable, p.spread_filters, p.pod_operators, p.name ? p.name : "-");\n}\n'
-                   'int main() { for (unsigned v = 0; v <= ksi::kEngineSettingCount; ++v) row((int)v, ksi::engine_policy(v));\n'
-                   '  printf("%u %u %u %u\\n", ksi::engine_value("auto-pod-operators"), ksi::engine_value("cursor-pod-operators"), ksi::engine_value("spread-filters"), ksi::engine_value("no-such-name")); }\n')
+                   '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s\\n", v, (int)p.run, p.first_plan, p.pick_plan, p.pair, p.nodes, p.spread_nodes, p.limits, p.spread_limits,\n'
+                   '         p.operators, p.spread_operators, p.unschedulable, p.spread_unschedulable, p.spread_filters, p.pod_operators, p.spread_pod_operators, p.name ? p.name : "-");\n}\n'
+                   'int main() { for (unsigned v = 0; v <= 31; ++v) row((int)v, ksi::engine_policy(v));\n'
+                   '  printf("%u %u %u %u %u %u\\n", ksi::engine_value("auto-pod-operators"), ksi::engine_value("cursor-pod-operators"), ksi::engine_value("spread-filters"),\n'
+                   '         ksi::engine_value("auto-pod-operators-spread"), ksi::engine_value("spread-pod-operators"), ksi::engine_value("no-such-name")); }\n')
     exe = tmp_path / "rows"
     subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(root, "karpenter_amd", "csrc"), "-o", str(exe), str(src)])
     assert subprocess.check_output([str(exe)], text=True).splitlines() == ENGINE_TABLE.splitlines()

@@ -1,6 +1,6 @@
 """GPU tests (run with -m gpu on an MI355X) of the cursor engine's pod operators (csrc/fast_engine.h "The cursor engine's pod
 operators", ksolve_fast_records; engines "auto-pod-operators" / "cursor-pod-operators"; the kernels of
-csrc/ksolve_pack_fast_podops.hip): the product library through the C ABI against the oracle, on the problems of
+csrc/ksolve_pack_fast.hip compiled for the PodOps flavour of csrc/pack_flavours.h): the product library through the C ABI against the oracle, on the problems of
 tests/pod_operator_cases.py — the ones tests/test_cursor_engine_pod_operators.py runs on the emulation, at the same small shapes."""
 import pytest
 

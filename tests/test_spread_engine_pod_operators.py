@@ -147,8 +147,8 @@ def test_positive_batches_are_unchanged(emu):
         assert sp.lone_cell(emu, prob, sp.ONLY) == sp.lone_cell(emu, prob, "spread-filters"), i
 
 
-# the rows of the second table in test_engine_matrix.ENGINE_TABLE's columns with one more in front of the name (s-pod-ops), the row a
-# value past it decodes to, and three engine_value lookups
+# rows 29 and 30 in test_engine_matrix.ENGINE_TABLE's columns (s-pod-ops in front of the name), the row a value past the table decodes
+# to, and three engine_value lookups
 ROWS_29_31 = """\
 29 0 0 1 0 1 1 1 1 1 1 1 1 1 1 1 auto-pod-operators-spread
 30 3 0 0 0 0 1 0 1 0 1 0 1 1 0 1 spread-pod-operators
@@ -159,15 +159,15 @@ ROWS_29_31 = """\
 
 def test_rows_of_the_second_engine_table(tmp_path):
     """csrc/engine_setting.h from a small program, as test_engine_matrix reads it: values 0-28 print what ENGINE_TABLE pins — 28 stays
-    the value past the first table — and none of them carries the new switch; 29 / 30 are the rows of the second table (26 and 25 with
-    the switch), their names map back, 31 is past it."""
+    the value without a row it was — and none of them carries the new switch; 29 / 30 are the rows behind it (26 and 25 with the
+    switch), their names map back, 31 is past the table."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = tmp_path / "rows.cpp"
     src.write_text('#include <cstdio>\n#include "engine_setting.h"\nstatic void row(int v, const ksi::EnginePolicy& p, bool more) {\n'
                    '  printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d ", v, (int)p.run, p.first_plan, p.pick_plan, p.pair, p.nodes, p.spread_nodes, p.limits, p.spread_limits,\n'
                    '         p.operators, p.spread_operators, p.unschedulable, p.spread_unschedulable, p.spread_filters, p.pod_operators);\n'
                    '  if (more) printf("%d ", p.spread_pod_operators);\n  printf("%s\\n", p.name ? p.name : "-");\n}\n'
-                   'int main() { for (unsigned v = 0; v <= 28; ++v) { if (ksi::engine_policy(v).spread_pod_operators) return 1; row((int)v, ksi::engine_policy(v), false); }\n'
+                   'int main() { for (unsigned v = 0; v <= 28; ++v) { if (ksi::engine_policy(v).spread_pod_operators) return 1; row((int)v, ksi::engine_policy(v), true); }\n'
                    '  for (unsigned v = 29; v <= 31; ++v) row((int)v, ksi::engine_policy(v), true);\n'
                    '  printf("%u %u %u\\n", ksi::engine_value("auto-pod-operators-spread"), ksi::engine_value("spread-pod-operators"), ksi::engine_value("no-such-name")); }\n')
     exe = tmp_path / "rows"
