@@ -314,7 +314,11 @@ typedef struct {
                                     *     29    auto-pod-operators-spread cursor, spread, general falls back  as 26, + s-pod-operators = the spread engine takes such pods too, and spread constraints whose
                                     *                                                                          owners carry NotIn, Exists or DoesNotExist (terms of the group's topology node filter)
                                     *     30    spread-pod-operators spread                     refuses       as 25, + s-pod-operators
-                                    *   above 30: no name; as 17.
+                                    *     31    (no name)            cursor                     refuses       - (as 17: what a value past the table stood for when 32 / 33 were added)
+                                    *     32    auto-pod-operators-nodes cursor, spread, general falls back   as 29, + node-pod-operators = the cursor engine's existing-node stage takes pods with NotIn,
+                                    *                                                                          Exists and DoesNotExist requirements too
+                                    *     33    cursor-pod-operators-nodes cursor                   refuses       as 27, + node-pod-operators
+                                    *   above 33: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
@@ -367,6 +371,12 @@ typedef struct {
                                     * (csrc/topo_engine.h, "The spread engine's unschedulable pods"). A batch with a preference pod is not
                                     * offered to a fast engine at all (reason 0); a nodeSelector next to a spread (43), pod-side NotIn (4),
                                     * Gt / Lt and minValues (1) still go to the general engine.
+                                    * node-pod-operators: a batch with existing nodes AND pods with NotIn, Exists or DoesNotExist stays on the
+                                    * cursor engine: against a node's single-valued label sets such a pod's verdict is as static as a positive
+                                    * pod's (csrc/node_stage.h, "Pod operators beside existing nodes") — instead of reason 4 / 8 from the stage,
+                                    * which every setting below 32 still gives. Reason 37 for the one shape that is not static: a key some node
+                                    * lacks with a NotIn pod and an In / Exists pod on it. The loop's by-design declines 9-12 apply as under
+                                    * 26 / 27; topology batches with nodes and such pods (4) still go to the general engine.
                                     * All give identical Results. */
 } ksolve_options;
 

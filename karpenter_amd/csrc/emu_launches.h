@@ -12,12 +12,16 @@
 // (the emulation's launch is the loop over the grid)
 static void be_launch_eff_alloc(ksolve_handle*, const ks::EffAllocArgs& a) { for (int t = 0; t < a.n_templates; ++t) for (int it = 0; it < a.n_its; ++it) ks::eff_alloc_body(t, it, a); }
 // The node kernels: a kernel launch is a loop over its grid.
-static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm, bool pod_ops) {
   const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
   std::vector<char> lds((size_t)lds_bytes + 64, (char)0xA5);   // garbage, like the device's LDS at kernel start
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));
-  note_pack_kernel(h, hbm ? ks::kPackNodesHbm : ks::kPackNodesLds);
+  note_pack_kernel(h, ks::pack_nodes_kernel(hbm, pod_ops));   // the kernel the device backend launches, from the same lookup
+  if (pod_ops) {
+    if (hbm) ks::pack_nodes_body<ks::Wave, true, true>(h->d_fast_args, lds.data());
+    else ks::pack_nodes_body<ks::Wave, false, true>(h->d_fast_args, lds.data());
+  } else
   if (hbm) ks::pack_nodes_body<ks::Wave, true>(h->d_fast_args, lds.data());
   else ks::pack_nodes_body<ks::Wave, false>(h->d_fast_args, lds.data());
   const ks::FastRequeueArgs q = ksi::fast_requeue_args(h);

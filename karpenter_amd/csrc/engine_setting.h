@@ -30,6 +30,7 @@ struct EnginePolicy {
   bool spread_filters;  // the spread engine counts pods through topology node filters that can say no (topo_engine.h, "Topology node filters")
   bool pod_operators;   // the cursor engine takes pod classes with NotIn, Exists and DoesNotExist requirements (fast_engine.h, "The cursor engine's pod operators")
   bool spread_pod_operators; // the spread engine takes such pod classes too, and node-filter terms of those operators (topo_engine.h, "The spread engine's pod operators")
+  bool node_pod_operators;   // the cursor engine's existing-node stage takes such pod classes too (node_stage.h, "Pod operators beside existing nodes")
   const char* name;     // options.engine of the host library's problem document; nullptr = no name
 
   constexpr bool general_only() const { return run == General; }
@@ -51,10 +52,10 @@ constexpr EnginePolicy engine_row(EnginePolicy from, const char* name, Switch...
   ((from.*adds = true), ...);
   return from;
 }
-// A value without a row is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch, no name. 17 and 28 were
+// A value without a row is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch, no name. 17, 28 and 31 were
 // such values for every caller that passed them when the rows behind them were added, and stay that.
 inline constexpr EnginePolicy kEngineSettingPastTable = engine_row(EnginePolicy::Cursor, 0, false, nullptr);
-inline constexpr uint32_t kEngineSettingCount = 31;
+inline constexpr uint32_t kEngineSettingCount = 34;
 struct EngineTable { EnginePolicy row[kEngineSettingCount]; };
 constexpr EngineTable engine_table() {
   using P = EnginePolicy;
@@ -91,6 +92,9 @@ constexpr EngineTable engine_table() {
   r[28] = kEngineSettingPastTable;
   r[29] = engine_row(r[26], "auto-pod-operators-spread", &P::spread_pod_operators);
   r[30] = engine_row(r[25], "spread-pod-operators", &P::spread_pod_operators);
+  r[31] = kEngineSettingPastTable;
+  r[32] = engine_row(r[29], "auto-pod-operators-nodes", &P::node_pod_operators);
+  r[33] = engine_row(r[27], "cursor-pod-operators-nodes", &P::node_pod_operators);
   return t;
 }
 inline constexpr EngineTable kEngineSettings = engine_table();

@@ -97,7 +97,7 @@ struct FastNodes {
   uint32_t n_placed;      // pods placed on existing nodes (queue pops of the stage that the loop does not see)
   uint32_t limit_hit;     // the step limit ended the solve inside or right behind the stage's entries: the solve's status is "stopped" whatever the loop says
   uint32_t variant;       // 1: `remaining` and the nodes' pod counts in LDS, 2: in the HBM workspace (reported as phase_cycles[19])
-  uint32_t bail;          // a reason of fast_engine.h setup() the stage found first (a class that is not positive: DECLINE_CLASS_NOT_POSITIVE, DECLINE_CLASS_EMPTY_IN): the loop stops with it
+  uint32_t bail;          // a reason of fast_engine.h setup() the stage found first (a class that is not positive: DECLINE_CLASS_NOT_POSITIVE, DECLINE_CLASS_EMPTY_IN) or, under engines 32 / 33, DECLINE_NODE_KEY_DEFINEDNESS: the loop stops with it
   unsigned long long n_ref;     // candidate nodes the reference would have evaluated (scheduler.go:614-656)
   unsigned long long n_tests;   // (class, node) resource tests of the stage
 };

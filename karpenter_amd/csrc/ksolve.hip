@@ -858,10 +858,10 @@ static void be_launch_fast_unsched(ksolve_handle* h) {
   hipLaunchKernelGGL(ksolve_fast_unsched, grid_for(n), dim3(256), 0, HB(h)->stream, n, ksi::fast_unsched_args(h));
   hip_check(h, hipGetLastError(), "ksolve_fast_unsched launch");
 }
-static void be_launch_pack_nodes(ksolve_handle* h, bool hbm) {
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm, bool pod_ops) {
   const int lds_bytes = ks::node_stage_plan((int)h->n_classes, (int)h->n_nodes, (int)h->n_res, hbm).total_bytes;
-  const ksolve_pack_fast_fn fn = hbm ? ksolve_pack_nodes_hbm : ksolve_pack_nodes_lds;
-  note_pack_kernel(h, hbm ? ks::kPackNodesHbm : ks::kPackNodesLds);
+  const ksolve_pack_fast_fn fn = pod_ops ? (hbm ? ksolve_pack_nodes_hbm_p : ksolve_pack_nodes_lds_p) : (hbm ? ksolve_pack_nodes_hbm : ksolve_pack_nodes_lds);
+  note_pack_kernel(h, ks::pack_nodes_kernel(hbm, pod_ops));
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::FastArgs a{h->pv, h->ws, h->fw};
   be_h2d(h, h->d_fast_args, &a, sizeof(a));

@@ -502,7 +502,7 @@ static void be_free(ksolve_handle* h, void* p);   // releases one be_alloc'ed bl
 static void be_launch_node_dead0(ksolve_handle* h, int n_blocks, const ks::NodeDeadArgs& a);   // one wavefront per 64 nodes
 static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: TopoEngine<W, true>::solve (existing nodes: topo_nodes.h)
 static void be_launch_fast_unsched(ksolve_handle* h);               // engines 20 / 21, one thread per pod set aside: fast_unsched_body (errors under the pod indices)
-static void be_launch_pack_nodes(ksolve_handle* h, bool hbm);   // ksolve_pack_nodes (node_stage.h): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
+static void be_launch_pack_nodes(ksolve_handle* h, bool hbm, bool pod_ops);   // ksolve_pack_nodes (node_stage.h; pod_ops: its _p kernels, engines 32 / 33): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
 static void be_launch_pack_topo_many(std::vector<ksolve_handle*>* groups);   // ksolve_solve_many: groups[ks::kTopoManyFlavours] by row of ks::kPackTopoManyRows, one ksolve_pack_topo*_many launch per group that has members (block = one ticket = one member, largest first); sets every member's T_PACK timer
 static void be_launch_claim_gather(ksolve_handle* h, int n, const ks::ClaimGatherArgs& a);
@@ -3195,7 +3195,9 @@ static void fast_nodes_stage(ksolve_handle* h) {
   node_static_rows(h);
   h->fw.nd_dead0 = h->nd_dead0;
   be_fill(h, h->fw.cls_first, 0xFF, (size_t)nc * 4); be_fill(h, h->fw.cls_last, 0, (size_t)nc * 4);   // (the compacted queue's, rebuilt behind the stage)
-  be_launch_pack_nodes(h, ks::node_stage_hbm((int)nc, (int)h->n_nodes, (int)h->n_res));
+  // engines 32 / 33: the stage with pod operators (node_stage.h, "Pod operators beside existing nodes") in front of the PodOps loop. The
+  // setting picks the kernel, not the batch; under every other setting the stage hands a batch with negative pods back (4 / 8)
+  be_launch_pack_nodes(h, ks::node_stage_hbm((int)nc, (int)h->n_nodes, (int)h->n_res), h->eng.node_pod_operators && h->fw.podops);
   // From here to the end of the solve the queue IS the compacted one: entry j is pod nd_pod[j]. The loop's record and the scatter of
   // its results (be_launch_fast_records) read the queue's pods through the view; solve_prepare sorts the queue anew for every solve.
   P.sorted_pods = h->fw.nd_pod;

@@ -54,7 +54,20 @@ template <bool HBM> struct NodeStageMem {
 #endif
 };
 
-template <class W, bool HBM>
+// Pod operators beside existing nodes (engines 32 / 33; PO). A pod class with NotIn, Exists or DoesNotExist (In [] is DoesNotExist)
+// meets a node whose label sets are single-valued In sets (reason 32 guarantees it):
+//   * a key the node defines as In {a}: whatever is compatible intersects to In {a} again (requirements.go:133-140), so the node is
+//     unchanged — In S passes iff a is in S, NotIn S iff a is not in S, Exists passes, DoesNotExist fails (requirements.go:254-274);
+//   * a key the node lacks: In / Exists fail (requirements.go:189; existing nodes pass no AllowUndefined, existingnode.go:100),
+//     NotIn / DoesNotExist pass, and ExistingNode.Add (existingnode.go:172-176) then writes the pod's requirement onto the node. Behind
+//     a DoesNotExist pod a later In / Exists pod still fails (empty intersection, positive incoming operator) and a later NotIn /
+//     DoesNotExist pod still passes (both sides negative, requirements.go:260-264): the verdicts are what they were. Behind a NotIn
+//     [b] pod a later NotIn / DoesNotExist pod still passes — but an In [c] pod, c != b, or an Exists pod now PASSES where it failed.
+// So the (class, node) verdict up to resources stays static — the rows of ksolve_node_dead0 (nodecheck.h, kneg) carry exactly these
+// verdicts — but for one shape: a key some node lacks that carries both a NotIn class and an In (non-empty) or Exists class. The
+// stage looks for it before any pod is placed, per key over all nodes and all classes (conservative, never optimistic), and hands the
+// batch back with DECLINE_NODE_KEY_DEFINEDNESS. Otherwise the loop below is the one of the positive stage: `remaining` only shrinks.
+template <class W, bool HBM, bool PO = false>
 KS_DEV void pack_nodes_body(const FastArgs* a, char* lds) {
   const ProblemView& P = a->pv; const Workspace& S = a->ws; const FastWork& F = a->fw;
   const Dict& d = P.dict;
@@ -69,8 +82,29 @@ KS_DEV void pack_nodes_body(const FastArgs* a, char* lds) {
   const uint64_t* const dead0 = fast_uniform(F.nd_dead0);
   FastNodes out{};
   out.variant = HBM ? 2u : 1u;
-  // ---- the shape: the stage rests on positive pod sets (a NotIn / DoesNotExist pod may ADD a key to a node: not static). The
-  // reasons are those of fast_engine.h setup(), which would find the same classes behind the stage ----
+  if constexpr (PO) {
+    // ---- the shape with pod operators (above): three reductions, one verdict per key ----
+    const ProblemView& Pv = P;
+    const uint32_t* const ndef = S.n_defined0;
+    const uint32_t all_keys = d.n_keys >= 32 ? 0xFFFFFFFFu : (1u << d.n_keys) - 1;
+    auto keys_with = [&](bool notin) {
+      return (uint32_t)W::reduce_or(nc, [&](int c) {
+        const ReqRef cr = Pv.cls_reqs.at(d, c);
+        uint64_t m = 0;
+        for (uint32_t ks_ = cr.defined; ks_; ks_ &= ks_ - 1) {
+          const int k = __builtin_ctz(ks_);
+          const int op = req_op(d, cr, k);
+          if (notin ? op == OP_NOTIN : (op == OP_IN || op == OP_EXISTS)) m |= 1ull << k;
+        }
+        return m; });
+    };
+    const uint32_t k_notin = keys_with(true);       // keys some class uses with NotIn
+    const uint32_t k_positive = keys_with(false);   // ... with In (non-empty) or Exists
+    const uint32_t k_undef = (uint32_t)W::reduce_or(nn, [&](int e) { return (uint64_t)(~ndef[e] & all_keys); });   // keys some node leaves undefined
+    if (k_notin & k_positive & k_undef) out.bail = DECLINE_NODE_KEY_DEFINEDNESS;
+  } else
+  // ---- the shape: the stage rests on positive pod sets (a NotIn / DoesNotExist pod may ADD a key to a node: not static; engines
+  // 32 / 33 take such pods, above). The reasons are those of fast_engine.h setup(), which would find the same classes behind the stage ----
   {
     const ProblemView& Pv = P;
     if (W::reduce_or(nc, [&](int c) { return (uint64_t)Pv.cls_reqs.complement[c]; })) out.bail = DECLINE_CLASS_NOT_POSITIVE;

@@ -76,9 +76,12 @@ inline constexpr PackFastRow kFastColdRows[] = {KS_FAST_COLD_ROWS(KS_ROW_FAST)};
 // the many-problem kernels there are: solve_many groups its spread members by the index of their row
 constexpr int kTopoManyFlavours = (int)(sizeof(kPackTopoManyRows) / sizeof(kPackTopoManyRows[0]));
 // the cursor engine's kernels outside the matrix: the two-wavefront kernel of the LDS plan, the batched form (both of the plain
-// flavour only) and the existing-node stage in front of the loop (node_stage.h; `remaining` in LDS / in the HBM workspace)
+// flavour only) and the existing-node stage in front of the loop (node_stage.h; `remaining` in LDS / in the HBM workspace; _p: with
+// the stage's pod operators, engines 32 / 33 — a bool of the stage's own, not a FastFlavour: the loop behind it is the PodOps flavour's)
 inline constexpr char kPackFastPair[] = "ksolve_pack_fast2", kPackFastBatch[] = "ksolve_pack_fast_batch";
 inline constexpr char kPackNodesLds[] = "ksolve_pack_nodes_lds", kPackNodesHbm[] = "ksolve_pack_nodes_hbm";
+inline constexpr char kPackNodesLdsPodOps[] = "ksolve_pack_nodes_lds_p", kPackNodesHbmPodOps[] = "ksolve_pack_nodes_hbm_p";
+inline const char* pack_nodes_kernel(bool hbm, bool pod_ops) { return pod_ops ? (hbm ? kPackNodesHbmPodOps : kPackNodesLdsPodOps) : (hbm ? kPackNodesHbm : kPackNodesLds); }
 
 // The row of the kernel both backends launch; nullptr where no kernel exists.
 template <class Row, int N, class F> inline const Row* pack_row_where(const Row (&rows)[N], F match) {

@@ -39,6 +39,8 @@ KS_PACK_TOPO_MANY_ROWS(KS_DECLARE)
 // the cursor engine's existing-node stage (node_stage.h), `remaining` in LDS / in the HBM workspace
 __global__ void ksolve_pack_nodes_lds(const ks::FastArgs* a);
 __global__ void ksolve_pack_nodes_hbm(const ks::FastArgs* a);
+__global__ void ksolve_pack_nodes_lds_p(const ks::FastArgs* a);
+__global__ void ksolve_pack_nodes_hbm_p(const ks::FastArgs* a);
 #ifdef KSOLVE_TEST_HOOKS
 // test builds only: FastCold alone, per instantiation (ksolve_test_fast_cold.hip, fast_cold_probe.h)
 namespace ks { struct FastColdArgs; }
