@@ -3203,473 +3203,7 @@ static void fast_nodes_stage(ksolve_handle* h) {
   P.sorted_pods = h->fw.nd_pod;
 }
 
-// What a fast engine's kernel left behind: done = it solved the problem (or was stopped by a step limit / cancel flag) and its results
-// stand; otherwise `reason` says why not (decline.h) — the kernel's own for status 3, DECLINE_CAPACITY for status 1, the handle's as
-// it was after a device error — and `pops` how far a status-3 run got. The counters are downloaded for status 3 only.
-struct FastOutcome { bool done; int status, n_claims; uint32_t reason; unsigned long long pops; };
-static FastOutcome fast_outcome(ksolve_handle* h) {
-  FastOutcome o{false, 0, 0, h->fast_reason, 0};
-  be_d2h(h, &o.status, h->ws.status_out, 4);
-  be_d2h(h, &o.n_claims, h->ws.n_claims_out, 4);
-  be_sync(h);
-  o.done = be_ok(h) && o.status != 3 && o.status != 1;
-  if (be_ok(h) && o.status == 3) {
-    ks::Counters ctr{};
-    be_d2h(h, &ctr, h->ws.counters, sizeof(ctr));
-    be_sync(h);
-    o.reason = (uint32_t)ctr.decline;
-    o.pops = ctr.queue_pops;
-  } else if (be_ok(h) && o.status == 1) o.reason = ks::DECLINE_CAPACITY;
-  return o;
-}
-
-static void be_results_drop(ksolve_results* r) { if (r && r->impl) { delete (ResultsImpl*)r->impl; r->impl = nullptr; } }
-static ksolve_status solve(ksolve_handle* h, ksolve_results* out, bool fresh_context = true) {
-  memset(out, 0, sizeof(*out));
-  if (h->resident && h->has_topology) return fail(h, KSOLVE_ERR_INVALID, "a resident cluster with topology groups is solved through probes (ksolve_sweep / ksolve_probe_create): its counts include the bound pod rows");
-  if (h->base) { ksolve_status st = KSOLVE_OK; solve_probes(&h, 1, out, &st, fresh_context); return st; }
-  ksolve_status st = solve_prepare(h, fresh_context);
-  if (st != KSOLVE_OK) return st;
-  if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes))
-    return h->eng.spread_operators && h->fast_reason ? declined(h, "spread") : outside_shape(h, EnginePolicy::Spread);
-  if (h->eng.cursor_only() && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes))
-    return h->eng.operators && h->fast_reason ? declined(h, "cursor") : outside_shape(h, EnginePolicy::Cursor);
-  if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
-    // more pod classes than the node stage keeps cursors for: the general engine (nothing has run yet)
-    h->fast_reason = ks::DECLINE_NODE_CLASSES;
-    if (h->eng.refuses()) return declined(h, "cursor");
-    h->fw.enabled = 0;
-  }
-  if (h->tw.enabled && h->n_pods && h->n_classes) {
-    // the spread engine first; status 3 = "not my shape / stopped before any result": the general engine takes over
-    alloc_run_order(h);
-    be_tic(h, T_PACK);
-    if (h->tw.nd.dom) {
-      // existing nodes (engine 9 / 10): the static (class, node) rows for this solve's classes, then the kernel with the node path.
-      // It resets the nodes' remaining resources, pod counts and counters from the pristine tables itself.
-      node_static_rows(h);
-      h->tw.nd.dead0 = h->nd_dead0;
-      be_launch_pack_topo_nodes(h);
-    } else be_launch_pack_topo(h);
-    be_toc(h, T_PACK);
-    const FastOutcome o = fast_outcome(h);
-    if (o.done) {
-      h->engine_used = 3;
-      h->fast_reason = 0; h->fast_attempts = 1;
-      if (o.n_claims || h->tw.nd.dom) be_launch_fast_records(h, o.n_claims);   // (pods on existing nodes are scattered with the queue's results even when no claim was opened)
-      if (h->fw.unsched) be_launch_fast_unsched(h);   // engines 22 / 23: the errors of the pods that ended on the set-aside list (none: nothing is written)
-      return solve_finish(h, out);
-    }
-    h->fast_reason = o.reason;
-    if (h->eng.spread_only()) return declined(h, "spread");
-    if (h->fast_reason != ks::DECLINE_UNSCHEDULABLE_POD && h->fast_reason != ks::DECLINE_CAPACITY) h->tw.enabled = 0;   // not its shape: later solves of this handle go straight to the general engine
-    st = solve_prepare(h, false);
-    if (st != KSOLVE_OK) return st;
-  }
-  if (h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes) {
-    // the cursor engine first; status 3 = "not my shape / stopped before any result": the general engine takes over — unless all
-    // that stopped it was the number of claims its LDS plan holds (DECLINE_CLAIM_SLOTS, reason 26): then once more with the claims' state in HBM
-    h->fast_attempts = 0;
-    for (;;) {
-      h->fast_attempts++;
-      be_tic(h, T_PACK);
-      if (h->fw.nodes) fast_nodes_stage(h);   // existing nodes first (scheduler.go:594); the loop solves the pods they left
-      be_launch_pack_fast(h);
-      be_toc(h, T_PACK);
-      const FastOutcome o = fast_outcome(h);
-      if (o.done) {
-        h->engine_used = 2;
-        h->fast_reason = 0;   // (a first attempt that ran out of LDS claim slots is not a fallback to the general engine)
-        if (o.n_claims) be_launch_fast_records(h, o.n_claims);
-        if (h->fw.unsched) be_launch_fast_unsched(h);   // the errors of the pods it set aside (none: nothing is written)
-        return solve_finish(h, out);
-      }
-      h->fast_reason = o.reason;   // (DECLINE_CAPACITY, 100 = more claims than max_claims: the general engine reports it, or moves to BIG)
-      if (be_ok(h) && h->fast_reason == ks::DECLINE_CLAIM_SLOTS && h->fw.plan.global_state < 2 && !h->opts.lds_claim_cap) {
-        // out of claim slots: the next plan (later solves of this handle start there). The attempt says how many pods its
-        // claims took: when the whole queue, at that rate and a quarter more, would not fit plan 1 either, go to plan 2 at once.
-        const int had = h->fw.plan.cap;
-        int next = h->fw.plan.global_state + 1;
-        if (next == 1) {
-          fast_plan_set(h, 1, h->fw.plan.rows);
-          // (under engines 20 / 21 the pops include the pods set aside, which took no claim: the rate is then an underestimate and the
-          // choice leans to plan 1; harmless — a plan 1 that runs out as well ends with 26 again and moves to plan 2)
-          const double placed = (double)(o.pops > 0 ? o.pops : 1);
-          const bool holds_all = h->fw.plan.cap >= (int)((h->fast_mc + 63) & ~63u);   // plan 1 has a slot for every claim the problem may open
-          if (!holds_all && (double)had * (double)h->n_pods / placed * 1.25 > (double)h->fw.plan.cap) next = 2;
-        }
-        fast_plan_set(h, next, h->fw.plan.rows);
-        if (h->fw.plan.cap > had) {
-          st = solve_prepare(h, false);
-          if (st != KSOLVE_OK) return st;
-          continue;
-        }
-      }
-      break;
-    }
-    if (h->eng.refuses()) return declined(h, "cursor");
-    h->fw.enabled = 0;   // later solves of this handle go straight to the general engine
-    st = solve_prepare(h, false);
-    if (st != KSOLVE_OK) return st;
-  }
-  be_tic(h, T_PACK);
-  if (h->n_pods) be_launch_pack(h);
-  be_toc(h, T_PACK);
-  if (!h->pv.big && h->big_capable) {
-    int status = 0;
-    be_d2h(h, &status, h->ws.status_out, 4);
-    be_sync(h);
-    if (status == 1) {
-      // more in-flight claims than the LDS-resident order holds: this problem runs on the BIG engine from now on
-      h->pv.big = 1; h->pv.lite = 0; h->pv.lds = h->lds_big;
-      alloc_run_order(h);
-      st = solve_prepare(h, false);
-      if (st != KSOLVE_OK) return st;
-      be_tic(h, T_PACK);
-      be_launch_pack(h);
-      be_toc(h, T_PACK);
-    }
-  }
-  return solve_finish(h, out);
-}
-
-// Many independent problems, one launch: block b of the pack kernel is the wavefront of problem b. This is how
-// consolidation sweeps (helpers.go:53-155: one Solve() per candidate set) and NodePool components fill the chip.
-static ksolve_status solve_batch_plain(ksolve_handle** hs, uint32_t n, ksolve_results* outs) {
-  for (uint32_t i = 0; i < n; ++i) memset(&outs[i], 0, sizeof(outs[i]));
-  std::vector<ksolve_status> st(n, KSOLVE_OK);
-  // The prepass (classes, queue order) and the result download of different problems are independent: a few host
-  // threads drive them on the problems' own streams so that the launches and copies of different problems overlap.
-  const uint32_t n_threads = std::min<uint32_t>(n, std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
-  auto parallel = [&](auto&& fn) {
-    if (n_threads <= 1) { for (uint32_t i = 0; i < n; ++i) fn(i); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < n_threads; ++t) pool.emplace_back([&, t]() { be_thread_init(hs[0]); for (uint32_t i = t; i < n; i += n_threads) fn(i); });
-    for (auto& th : pool) th.join();
-  };
-  parallel([&](uint32_t i) { st[i] = solve_prepare(hs[i]); outs[i].status = st[i]; if (st[i] == KSOLVE_OK) be_sync(hs[i]); });
-  // problems of the cursor engine's shape go to it (one block each); the ones it hands back (status 3), and all others, run
-  // on the general engine's batched launch
-  std::vector<ksolve_handle*> fast, run;
-  std::vector<char> alone(n, 0);   // solved on their own (results complete)
-  for (uint32_t i = 0; i < n; ++i) {
-    if (st[i] != KSOLVE_OK || !hs[i]->n_pods) continue;
-    ksolve_handle* h = hs[i];
-    if (h->tw.enabled && (h->daemon_groups || h->tw.nd.dom || h->spread_complement || h->fw.unsched) && h->n_classes) {
-      // a DaemonSet problem of the spread engine's shape, one with existing nodes (engine 9 / 10), one over complement templates (18 / 19) or any spread handle that keeps unschedulable pods (22 / 23): alone through solve(), so that the batch runs the engine ksolve_solve would
-      be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1;
-    }
-    else if (h->fw.enabled && !h->pv.big && h->n_classes) {
-      // the batched kernel is the LDS plan; a handle whose claims live in HBM (an earlier Solve() moved it there, or engine =
-      // cursor-wide / cursor-hbm) runs alone on the kernel of its plan
-      if (h->fw.plan.global_state == 0 && !h->fw.nodes && !h->fw.lim && !h->fw.unsched) fast.push_back(h);   // (a handle with the existing-node stage runs alone too: its kernels precede the loop; so does one of engines 11 / 12, and one of 20 / 21: a kernel follows its loop)
-      else { be_results_drop(&outs[i]); st[i] = solve(h, &outs[i], false); outs[i].status = st[i]; alone[i] = 1; }
-    }
-    else if (h->eng.refuses()) st[i] = fail(h, KSOLVE_ERR_UNSUPPORTED, "cursor engine requested for a problem outside its shape");   // (the batch path's short form; a spread-only handle gets the cursor wording too: a known wart)
-    else run.push_back(h);
-  }
-  if (!fast.empty()) {
-    be_launch_pack_fast_batch(fast.data(), (int)fast.size());
-    std::vector<int> handed_back(fast.size(), 0);
-    for (size_t k = 0; k < fast.size(); ++k) {
-      ksolve_handle* h = fast[k];
-      const FastOutcome o = fast_outcome(h);
-      if (o.done) { h->engine_used = 2; if (o.n_claims) be_launch_fast_records(h, o.n_claims); continue; }
-      h->fast_reason = o.reason;
-      handed_back[k] = 1;
-    }
-    for (size_t k = 0; k < fast.size(); ++k) {
-      if (!handed_back[k]) continue;
-      ksolve_handle* h = fast[k];
-      uint32_t idx = 0;
-      while (hs[idx] != h) ++idx;
-      if (h->fast_reason == ks::DECLINE_CLAIM_SLOTS && !h->opts.lds_claim_cap) {
-        // more in-flight claims than the LDS plan holds: alone, on the plans that keep them in HBM (solve() escalates further)
-        fast_plan_set(h, 1, h->fw.plan.rows);
-        be_results_drop(&outs[idx]); st[idx] = solve(h, &outs[idx], false); outs[idx].status = st[idx]; alone[idx] = 1;
-        continue;
-      }
-      if (h->eng.refuses()) { st[idx] = declined(h, "cursor"); continue; }
-      h->fw.enabled = 0;
-      st[idx] = solve_prepare(h, false);
-      if (st[idx] == KSOLVE_OK) { be_sync(h); run.push_back(h); }
-    }
-  }
-  if (!run.empty()) be_launch_pack_batch(run.data(), (int)run.size());
-  parallel([&](uint32_t i) {
-    if (alone[i]) return;
-    if (st[i] != KSOLVE_OK) { outs[i].status = st[i]; return; }
-    st[i] = solve_finish(hs[i], &outs[i]);
-    if (st[i] == KSOLVE_ERR_CAPACITY && hs[i]->big_capable && !hs[i]->pv.big) { be_results_drop(&outs[i]); st[i] = solve(hs[i], &outs[i], false); }   // re-run alone on the BIG engine
-    outs[i].status = st[i];   // solve_finish zeroes `out` before it can fail: the per-problem status must survive that
-  });
-  ksolve_status worst = KSOLVE_OK;
-  for (uint32_t i = 0; i < n; ++i) if (st[i] != KSOLVE_OK && st[i] != KSOLVE_ERR_CANCELLED) worst = st[i];
-  return worst;
-}
-
-static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksolve_results* outs);
-// ksolve_solve_batch: the handles' devices side by side (one host thread each), one batch per device
-static ksolve_status solve_batch(ksolve_handle** hs, uint32_t n, ksolve_results* outs) {
-  std::vector<int> devices;
-  for (uint32_t i = 0; i < n; ++i) { const int dv = be_device_of(hs[i]); if (std::find(devices.begin(), devices.end(), dv) == devices.end()) devices.push_back(dv); }
-  if (devices.size() <= 1) return solve_batch_one_device(hs, n, outs);
-  std::vector<ksolve_status> rc(devices.size(), KSOLVE_OK);
-  std::vector<std::thread> pool;
-  for (size_t g = 0; g < devices.size(); ++g) pool.emplace_back([&, g]() {
-    std::vector<uint32_t> idx;
-    std::vector<ksolve_handle*> grp;
-    for (uint32_t i = 0; i < n; ++i) if (be_device_of(hs[i]) == devices[g]) { idx.push_back(i); grp.push_back(hs[i]); }
-    be_thread_init(grp[0]);
-    std::vector<ksolve_results> ro(grp.size());
-    rc[g] = solve_batch_one_device(grp.data(), (uint32_t)grp.size(), ro.data());
-    for (size_t k = 0; k < grp.size(); ++k) outs[idx[k]] = ro[k];
-  });
-  for (auto& th : pool) th.join();
-  ksolve_status worst = KSOLVE_OK;
-  for (auto r : rc) if (r != KSOLVE_OK) worst = r;
-  return worst;
-}
-
-// one device: probes of a resident cluster run as one sweep per base handle, everything else as above
-static ksolve_status solve_batch_one_device(ksolve_handle** hs, uint32_t n, ksolve_results* outs) {
-  std::vector<uint32_t> plain_idx;
-  std::vector<ksolve_handle*> bases;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!hs[i]->base) { plain_idx.push_back(i); continue; }
-    if (std::find(bases.begin(), bases.end(), hs[i]->base) == bases.end()) bases.push_back(hs[i]->base);
-  }
-  if (bases.empty()) return solve_batch_plain(hs, n, outs);
-  ksolve_status worst = KSOLVE_OK;
-  for (ksolve_handle* b : bases) {
-    std::vector<uint32_t> idx;
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i = 0; i < n; ++i) if (hs[i]->base == b) { idx.push_back(i); g.push_back(hs[i]); }
-    std::vector<ksolve_results> ro(g.size());
-    std::vector<ksolve_status> st(g.size(), KSOLVE_OK);
-    solve_probes(g.data(), (uint32_t)g.size(), ro.data(), st.data(), true);
-    for (size_t k = 0; k < g.size(); ++k) { outs[idx[k]] = ro[k]; if (st[k] != KSOLVE_OK && st[k] != KSOLVE_ERR_CANCELLED) worst = st[k]; }
-  }
-  if (!plain_idx.empty()) {
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i : plain_idx) g.push_back(hs[i]);
-    std::vector<ksolve_results> ro(g.size());
-    const ksolve_status rc = solve_batch_plain(g.data(), (uint32_t)g.size(), ro.data());
-    for (size_t k = 0; k < g.size(); ++k) outs[plain_idx[k]] = ro[k];
-    if (rc != KSOLVE_OK) worst = rc;
-  }
-  return worst;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// ksolve_solve_many: many problems in one call, each on the engine solve() would run — every member gets the result solve() would have
-// given it on a fresh handle (outcome, error text, engine, fallback reason, memory plan, attempts, digest), and members of the spread
-// engine's shape share launches. solve_batch above keeps its behaviour (its recorded cells are pinned); this is the call ladder of
-// solve() itself, walked for all members at once:
-//   refusals -> the spread engine's many-problem launches (one per kernel flavour present) -> the cursor engine's batched launch
-//   (alone where solve() would run another kernel) -> the general engine's batched launch, with whatever the fast engines handed back.
-// the many-problem form of the kernel be_launch_pack_topo would pick (pack_flavours.h); nullptr: there is none, the member runs alone
-static const ks::PackTopoRow* topo_many_row(const ksolve_handle* h) { return ks::pack_topo_many_row(ks::topo_flavour(h->fw), h->tw.nd.dom != nullptr); }
-// the order table of one launch: its members by pod count, largest first (ties in input order); tickets are handed out along it
-static void topo_many_order(const std::vector<ksolve_handle*>& g, uint32_t* order) {
-  for (size_t i = 0; i < g.size(); ++i) order[i] = (uint32_t)i;
-  std::stable_sort(order, order + g.size(), [&](uint32_t a, uint32_t b) { return g[a]->n_pods > g[b]->n_pods; });
-}
-
-static ksolve_status solve_many_plain(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats& S) {
-  for (uint32_t i = 0; i < n; ++i) memset(&outs[i], 0, sizeof(outs[i]));
-  std::vector<ksolve_status> st(n, KSOLVE_OK);
-  std::vector<char> done(n, 0);   // the member's answer stands: refused, failed, or solved alone (results complete)
-  const uint32_t n_threads = std::min<uint32_t>(n, std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
-  auto parallel = [&](auto&& fn) {   // (the host-thread pattern of solve_batch_plain)
-    if (n_threads <= 1) { for (uint32_t i = 0; i < n; ++i) fn(i); return; }
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < n_threads; ++t) pool.emplace_back([&, t]() { be_thread_init(hs[0]); for (uint32_t i = t; i < n; i += n_threads) fn(i); });
-    for (auto& th : pool) th.join();
-  };
-  auto refuse = [&](uint32_t i, ksolve_status s) { st[i] = s; done[i] = 1; };
-  auto alone = [&](uint32_t i) { be_results_drop(&outs[i]); st[i] = solve(hs[i], &outs[i], false); outs[i].status = st[i]; done[i] = 1; S.alone_members++; };
-  // what solve() refuses before it runs anything, in its words
-  for (uint32_t i = 0; i < n; ++i)
-    if (hs[i]->resident && hs[i]->has_topology) refuse(i, fail(hs[i], KSOLVE_ERR_INVALID, "a resident cluster with topology groups is solved through probes (ksolve_sweep / ksolve_probe_create): its counts include the bound pod rows"));
-  parallel([&](uint32_t i) { if (done[i]) return; st[i] = solve_prepare(hs[i]); if (st[i] == KSOLVE_OK) be_sync(hs[i]); else done[i] = 1; });
-  std::vector<uint32_t> spread, fast, run;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    ksolve_handle* h = hs[i];
-    if (h->eng.spread_only() && !(h->tw.enabled && h->n_pods && h->n_classes)) { refuse(i, h->eng.spread_operators && h->fast_reason ? declined(h, "spread") : outside_shape(h, EnginePolicy::Spread)); continue; }
-    if (h->eng.cursor_only() && !(h->fw.enabled && !h->pv.big && h->n_pods && h->n_classes)) { refuse(i, h->eng.operators && h->fast_reason ? declined(h, "cursor") : outside_shape(h, EnginePolicy::Cursor)); continue; }
-    if (h->fw.enabled && h->fw.nodes && h->n_classes > (uint32_t)ks::kNodeStageMaxClasses) {
-      h->fast_reason = ks::DECLINE_NODE_CLASSES;
-      if (h->eng.refuses()) { refuse(i, declined(h, "cursor")); continue; }
-      h->fw.enabled = 0;
-    }
-    if (!h->n_pods) continue;   // nothing to launch: solve_finish
-    if (h->tw.enabled && h->n_classes) {
-      // (engines 29 / 30: the kernels with the pod operators have no many-problem form — a launch of its own, as solve() makes it)
-      if (topo_many_row(h)) spread.push_back(i); else alone(i);
-    }
-    else if (h->fw.enabled && !h->pv.big && h->n_classes) {
-      // the batched kernel is the LDS plan of ksolve_pack_fast_g0r*: a handle solve() would run on another kernel (a plan in HBM, the
-      // two-wavefront kernel, the set-aside list, the pod operators) or with kernels around the loop (node stage, limit stages) runs alone
-      if (h->fw.plan.global_state == 0 && !h->fw.plan.helper && !h->fw.nodes && !h->fw.lim && !h->fw.unsched && !h->fw.podops) fast.push_back(i);
-      else alone(i);
-    }
-    else run.push_back(i);
-  }
-  // handed back by a fast engine: the general engine's batched launch takes it, the reason stays on the handle
-  auto hand_back = [&](uint32_t i) {
-    st[i] = solve_prepare(hs[i], false);
-    if (st[i] != KSOLVE_OK) { done[i] = 1; return; }
-    be_sync(hs[i]); run.push_back(i); S.handed_back++;
-  };
-  if (!spread.empty()) {
-    std::vector<ksolve_handle*> groups[ks::kTopoManyFlavours];
-    for (uint32_t i : spread) {
-      ksolve_handle* h = hs[i];   // what solve() does in front of its launch
-      alloc_run_order(h);
-      if (h->tw.nd.dom) { node_static_rows(h); h->tw.nd.dead0 = h->nd_dead0; }
-      groups[topo_many_row(h) - ks::kPackTopoManyRows].push_back(h);
-    }
-    be_launch_pack_topo_many(groups);
-    for (auto& g : groups) if (!g.empty()) S.spread_launches++;
-    S.spread_members += (uint32_t)spread.size();
-    for (uint32_t i : spread) {
-      ksolve_handle* h = hs[i];
-      const FastOutcome o = fast_outcome(h);
-      if (o.done) {
-        h->engine_used = 3;
-        h->fast_reason = 0; h->fast_attempts = 1;
-        if (o.n_claims || h->tw.nd.dom) be_launch_fast_records(h, o.n_claims);
-        if (h->fw.unsched) be_launch_fast_unsched(h);
-        continue;
-      }
-      h->fast_reason = o.reason;
-      if (h->eng.spread_only()) { refuse(i, declined(h, "spread")); continue; }
-      if (h->fast_reason != ks::DECLINE_UNSCHEDULABLE_POD && h->fast_reason != ks::DECLINE_CAPACITY) h->tw.enabled = 0;
-      hand_back(i);
-    }
-  }
-  if (!fast.empty()) {
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i : fast) g.push_back(hs[i]);
-    be_launch_pack_fast_batch(g.data(), (int)g.size());
-    S.cursor_members += (uint32_t)fast.size();
-    for (uint32_t i : fast) {
-      ksolve_handle* h = hs[i];
-      const FastOutcome o = fast_outcome(h);
-      h->fast_attempts = 1;   // the runs of the cursor engine this solve took, as solve() counts them: handed back or not
-      if (o.done) { h->engine_used = 2; h->fast_reason = 0; if (o.n_claims) be_launch_fast_records(h, o.n_claims); continue; }
-      h->fast_reason = o.reason;
-      if (be_ok(h) && h->fast_reason == ks::DECLINE_CLAIM_SLOTS && h->fw.plan.global_state < 2 && !h->opts.lds_claim_cap) {
-        // out of claim slots: the plan solve() would move to after this attempt, then alone on that plan's kernel — one run more than
-        // solve() counts from there on
-        const int had = h->fw.plan.cap;
-        int next = h->fw.plan.global_state + 1;
-        if (next == 1) {
-          fast_plan_set(h, 1, h->fw.plan.rows);
-          const double placed = (double)(o.pops > 0 ? o.pops : 1);
-          const bool holds_all = h->fw.plan.cap >= (int)((h->fast_mc + 63) & ~63u);
-          if (!holds_all && (double)had * (double)h->n_pods / placed * 1.25 > (double)h->fw.plan.cap) next = 2;
-        }
-        fast_plan_set(h, next, h->fw.plan.rows);
-        if (h->fw.plan.cap > had) {
-          // (solve() counts its own runs from zero and is not to be touched: the batched run is added to what it reports, on the
-          // handle and in the results it filled. The member is in cursor_members and in alone_members: ksolve.h says so.)
-          alone(i);
-          h->fast_attempts++;
-          if (outs[i].impl) outs[i].cursor_attempts++;
-          continue;
-        }
-      }
-      if (h->eng.refuses()) { refuse(i, declined(h, "cursor")); continue; }
-      h->fw.enabled = 0;
-      hand_back(i);
-    }
-  }
-  if (!run.empty()) {
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i : run) g.push_back(hs[i]);
-    be_launch_pack_batch(g.data(), (int)g.size());
-    S.general_members += (uint32_t)run.size();
-  }
-  parallel([&](uint32_t i) {
-    if (done[i]) { outs[i].status = st[i]; return; }
-    st[i] = solve_finish(hs[i], &outs[i]);
-    if (st[i] == KSOLVE_ERR_CAPACITY && hs[i]->big_capable && !hs[i]->pv.big) { be_results_drop(&outs[i]); st[i] = solve(hs[i], &outs[i], false); }   // re-run alone on the BIG engine
-    outs[i].status = st[i];
-  });
-  ksolve_status worst = KSOLVE_OK;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (st[i] == KSOLVE_ERR_UNSUPPORTED) S.refused++;
-    if (st[i] != KSOLVE_OK && st[i] != KSOLVE_ERR_CANCELLED) worst = st[i];
-  }
-  return worst;
-}
-
-// one device: probes of a resident cluster run as one sweep per base handle (as in solve_batch_one_device), everything else as above
-static ksolve_status solve_many_one_device(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats& S) {
-  std::vector<uint32_t> plain_idx;
-  std::vector<ksolve_handle*> bases;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!hs[i]->base) { plain_idx.push_back(i); continue; }
-    S.probe_members++;
-    if (std::find(bases.begin(), bases.end(), hs[i]->base) == bases.end()) bases.push_back(hs[i]->base);
-  }
-  if (bases.empty()) return solve_many_plain(hs, n, outs, S);
-  ksolve_status worst = KSOLVE_OK;
-  for (ksolve_handle* b : bases) {
-    std::vector<uint32_t> idx;
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i = 0; i < n; ++i) if (hs[i]->base == b) { idx.push_back(i); g.push_back(hs[i]); }
-    std::vector<ksolve_results> ro(g.size());
-    std::vector<ksolve_status> st(g.size(), KSOLVE_OK);
-    solve_probes(g.data(), (uint32_t)g.size(), ro.data(), st.data(), true);
-    for (size_t k = 0; k < g.size(); ++k) { outs[idx[k]] = ro[k]; if (st[k] != KSOLVE_OK && st[k] != KSOLVE_ERR_CANCELLED) worst = st[k]; }
-  }
-  if (!plain_idx.empty()) {
-    std::vector<ksolve_handle*> g;
-    for (uint32_t i : plain_idx) g.push_back(hs[i]);
-    std::vector<ksolve_results> ro(g.size());
-    const ksolve_status rc = solve_many_plain(g.data(), (uint32_t)g.size(), ro.data(), S);
-    for (size_t k = 0; k < g.size(); ++k) outs[plain_idx[k]] = ro[k];
-    if (rc != KSOLVE_OK) worst = rc;
-  }
-  return worst;
-}
-
-// ksolve_solve_many: the handles' devices side by side (one host thread each, as solve_batch splits them), the counters summed
-static ksolve_status solve_many(ksolve_handle** hs, uint32_t n, ksolve_results* outs, ksolve_many_stats* stats) {
-  std::vector<int> devices;
-  for (uint32_t i = 0; i < n; ++i) { const int dv = be_device_of(hs[i]); if (std::find(devices.begin(), devices.end(), dv) == devices.end()) devices.push_back(dv); }
-  std::vector<ksolve_many_stats> part(devices.size(), ksolve_many_stats{});
-  std::vector<ksolve_status> rc(devices.size(), KSOLVE_OK);
-  if (devices.size() <= 1) rc[0] = solve_many_one_device(hs, n, outs, part[0]);
-  else {
-    std::vector<std::thread> pool;
-    for (size_t g = 0; g < devices.size(); ++g) pool.emplace_back([&, g]() {
-      std::vector<uint32_t> idx;
-      std::vector<ksolve_handle*> grp;
-      for (uint32_t i = 0; i < n; ++i) if (be_device_of(hs[i]) == devices[g]) { idx.push_back(i); grp.push_back(hs[i]); }
-      be_thread_init(grp[0]);
-      std::vector<ksolve_results> ro(grp.size());
-      rc[g] = solve_many_one_device(grp.data(), (uint32_t)grp.size(), ro.data(), part[g]);
-      for (size_t k = 0; k < grp.size(); ++k) outs[idx[k]] = ro[k];
-    });
-    for (auto& th : pool) th.join();
-  }
-  ksolve_status worst = KSOLVE_OK;
-  for (auto r : rc) if (r != KSOLVE_OK) worst = r;
-  if (stats) {
-    *stats = ksolve_many_stats{};
-    for (const ksolve_many_stats& p : part) {
-      stats->spread_launches += p.spread_launches; stats->spread_members += p.spread_members; stats->cursor_members += p.cursor_members;
-      stats->general_members += p.general_members; stats->handed_back += p.handed_back; stats->alone_members += p.alone_members;
-      stats->probe_members += p.probe_members; stats->refused += p.refused;
-    }
-  }
-  return worst;
-}
+#include "solve_calls.h"   // ksolve_solve, ksolve_solve_batch, ksolve_solve_many: the engine ladder's steps and the three drivers that walk them
 
 }  // namespace ksi
 

@@ -1,4 +1,4 @@
-"""scheduling.SolveMany (ksolve_solve_many; csrc/ksolve_impl.h solve_many, csrc/topo_many.h) — the member lists and the checks that
+"""scheduling.SolveMany (ksolve_solve_many; csrc/solve_calls.h solve_many_plain, csrc/topo_many.h) — the member lists and the checks that
 tests/test_solve_many.py runs through the host emulation and tests/test_gpu_solve_many.py on the device, at the same shapes.
 
 The contract under test: every member of the call gets the result Solve() gives the same problem on a fresh handle of its own —
@@ -80,22 +80,22 @@ def same_as_oracle(oracle, members, results):
 
 # ---- 1: the engine matrix ---------------------------------------------------------------------------------------------------------------
 
-def matrix_cells(lib):
-    """{cell name: cell} for every problem of the engine matrix under every setting, the problems of one setting opened on fresh
-    handles and solved in ONE SolveMany; named as the record names the lone solves ("…|alone")."""
-    probs = em.problems()
+def matrix_cells(lib, settings=None, probs=None, way="alone"):
+    """{cell name: cell} for every problem of the engine matrix (or `probs`) under every setting (or `settings`), the problems of one
+    setting opened on fresh handles and solved in ONE SolveMany; named as the record names the lone solves ("…|alone"), or by `way`."""
+    probs = em.problems() if probs is None else probs
     out = {}
-    for setting in em.SETTINGS:
+    for setting in (em.SETTINGS if settings is None else settings):
         opened = []
         for name, prob in probs:
             try:
                 opened.append((name, NewScheduler(with_engine(prob, setting), solver_lib=lib)))
             except Exception as e:   # (a problem the host library refuses to open under the setting is its own cell, as in the record)
-                out[f"{name}|{setting}|alone"] = em._cell(exc=e)
+                out[f"{name}|{setting}|{way}"] = em._cell(exc=e)
         try:
             results, _ = many([s for _, s in opened])
             for (name, _), r in zip(opened, results):
-                out[f"{name}|{setting}|alone"] = cell_of(r)
+                out[f"{name}|{setting}|{way}"] = cell_of(r)
         finally:
             close_all([s for _, s in opened])
     return out

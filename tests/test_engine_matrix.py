@@ -1,7 +1,9 @@
 """The engine option, pinned (CPU; tests/test_gpu_engine_matrix.py on the device): every problem of tests/tools/engine_matrix.py under
 every value of ksolve_options.engine, alone and in a batch, through the host emulation and the real host library, against the record
 in tests/golden/engine_matrix.json — taken from the commit before the option was decoded through csrc/engine_setting.h's table. Cell
-by cell and field by field: outcome, full error text, engine, fallback reason, memory plan, attempts, Results digest. No cell is skipped."""
+by cell and field by field: outcome, full error text, engine, fallback reason, memory plan, attempts, Results digest. No cell is skipped.
+The later settings (18-27, 29, 30, 32, 33) have a record of their own, tests/golden/engine_matrix_late.json, with SolveMany as a third
+way beside alone and batch: taken from the commit before Solve, SolveBatch and SolveMany were put on the steps of csrc/solve_calls.h."""
 import os
 import subprocess
 import sys
@@ -42,6 +44,33 @@ def test_the_record_exercises_what_it_is_for():
     """Every run kind, each of the five switches changing an outcome, each refusal message family, the first-plan choice, and the
     batch path's "alone" and "handed back" branches have at least one recorded cell."""
     missing = [claim for claim, cells in em.coverage(em.load("emulation")).items() if not cells]
+    assert not missing, missing
+
+
+@pytest.fixture(scope="module")
+def late_matrix(emu):
+    return em.build_late(emu)
+
+
+def test_every_late_cell_equals_the_record(late_matrix):
+    """Settings 18-27, 29, 30, 32 and 33 over em.late_problems(), alone, in a batch and in one SolveMany, against
+    tests/golden/engine_matrix_late.json — taken from the commit before the three call ladders were put on the steps of
+    csrc/solve_calls.h. No cell is skipped."""
+    want = em.load("emulation", em.LATE_FIXTURE)
+    assert len(want) == len(em.late_problems()) * len(em.LATE_SETTINGS) * 3 == 462
+    diff = em.differences(late_matrix, want)
+    assert not diff, f"{len(diff)} fields differ (cell, field, got, recorded): {diff[:12]}"
+
+
+def test_late_many_equals_alone_cell_for_cell(late_matrix):
+    many = {k[:-len("many")] + "alone": v for k, v in late_matrix.items() if k.endswith("|many")}
+    assert len(many) == 154
+    diff = em.differences(many, {k: v for k, v in late_matrix.items() if k.endswith("|alone")})
+    assert not diff, f"{len(diff)} fields differ (cell, field, as a member, alone): {diff[:12]}"
+
+
+def test_the_late_record_exercises_what_it_is_for():
+    missing = [claim for claim, cells in em.late_coverage(em.load("emulation", em.LATE_FIXTURE)).items() if not cells]
     assert not missing, missing
 
 

@@ -12,7 +12,17 @@ code under test (where that commit's host library takes names only, with the one
 library, which decodes the value, is that commit's):
   python tests/tools/engine_matrix.py --record emulation        (host emulation, no GPU)
   python tests/tools/engine_matrix.py --record device           (on the MI355X)
-  python tests/tools/engine_matrix.py --coverage                (what the recorded cells exercise)"""
+  python tests/tools/engine_matrix.py --coverage                (what the recorded cells exercise)
+
+A second, separate record pins the settings that came after that one, rows 18-27, 29, 30, 32 and 33 of csrc/engine_setting.h
+(LATE_SETTINGS), over eleven small problems of the later engines' shapes (late_problems()) and in THREE ways: alone, batch, and "many" —
+one SolveMany of the setting's eleven problems on fresh handles (solve_many_cases.matrix_cells). It is
+tests/golden/engine_matrix_late.json, in the same layout with the same seven fields, taken from the commit BEFORE the three call
+ladders of Solve, SolveBatch and SolveMany were put on one set of steps (csrc/solve_calls.h), with nothing but this tool's lines for
+it added to that commit: the batch's cells that differ from the lone ones are its behaviour as it was, and stay.
+  python tests/tools/engine_matrix.py --record emulation --late
+  python tests/tools/engine_matrix.py --record device --late
+  python tests/tools/engine_matrix.py --coverage --late"""
 import argparse
 import ctypes
 import json
@@ -30,6 +40,13 @@ os.environ.setdefault("KSOLVE_TEST_SOLVER_LIB", "1")
 # value -> the name the host library accepts (include/ksolve.h, ksolve_options.engine)
 SETTINGS = ["auto", "general", "cursor", "cursor-wide", "cursor-hbm", "cursor-pair", "spread", "auto-nodes", "cursor-nodes", "auto-nodes-spread", "spread-nodes",
             "auto-limits", "cursor-limits", "auto-limits-spread", "spread-limits", "auto-operators", "cursor-operators", 17]
+# rows 18-27, 29, 30, 32 and 33 of csrc/engine_setting.h (28 and 31 have no row of their own)
+LATE_SETTINGS = ["auto-operators-spread", "spread-operators", "auto-unschedulable", "cursor-unschedulable", "auto-unschedulable-spread", "spread-unschedulable",
+                 "auto-filters-spread", "spread-filters", "auto-pod-operators", "cursor-pod-operators", "auto-pod-operators-spread", "spread-pod-operators",
+                 "auto-pod-operators-nodes", "cursor-pod-operators-nodes"]
+LATE_FIXTURE = os.path.join(ROOT, "tests", "golden", "engine_matrix_late.json")
+WAYS = ("alone", "batch")
+LATE_WAYS = ("alone", "batch", "many")
 FIELDS = ("outcome", "error", "engine", "engineFallbackReason", "cursorMemoryPlan", "cursorAttempts", "digest")
 
 
@@ -42,6 +59,43 @@ def problems():
         return _problems(fx)
     finally:
         fx._uid_counter[0] = max(before, fx._uid_counter[0])   # (no uid handed out twice to whoever builds problems next)
+
+
+def late_problems():
+    """[(name, problem)] of the late record, built from uid 1 as problems() builds its list. Eleven: "spread-mix-daemonsets" is there
+    for the batch's DaemonSet condition, which no other of them meets on its own; "escalation-open", which the record of settings 0-17
+    has, made room for it (with both, the record would be larger than that one)."""
+    from karpenter_amd import fixtures as fx
+    before, fx._uid_counter[0] = fx._uid_counter[0], 0
+    try:
+        return _late_problems(fx)
+    finally:
+        fx._uid_counter[0] = max(before, fx._uid_counter[0])
+
+
+def _late_problems(fx):
+    import pod_operator_cases as po
+    import pod_operator_node_cases as pn
+    import spread_filter_cases as sf
+    import spread_limit_cases as sl
+    import spread_node_cases as sn
+    import spread_operator_cases as so
+    import spread_pod_operator_cases as sp
+    import spread_unschedulable_cases as su
+    import unschedulable_cases as uc
+    plain = fx.config1()
+    plain = dict(plain, pods=plain["pods"][:40])
+    return [("plain", plain),
+            ("spread-mix", sl.mix_problem((300, 144, 1), None)),
+            ("spread-mix-nodes", sn.mix_problem((300, 144, 1), 5)),
+            ("spread-mix-daemonsets", sn.mix_problem((300, 144, 1), 0, daemonsets=True)),   # (no node: DaemonSets are all that sets it apart from spread-mix)
+            ("spread-complement", so.counted_problem()),
+            ("pinned", uc.pinned_problem()),
+            ("chain-web", su.chain_web_problem()),
+            ("filter-never", sf.never_problem()),
+            ("zone-notin", po.zone_notin_problem()),
+            ("spread-pod-notin", sp.counted_problem()),
+            ("dedicated-nodes", pn.dedicated_problem())]
 
 
 def _problems(fx):
@@ -104,12 +158,15 @@ def _solve_batch(schedulers):
     return cells
 
 
-def build_matrix(solver_lib=None, progress=False, settings=None):
-    """{cell: {field: value}} for every problem, setting (all, or `settings`) and way of solving. solver_lib: the emulation; None = the
-    device library."""
+def build_matrix(solver_lib=None, progress=False, settings=None, probs=None, ways=WAYS):
+    """{cell: {field: value}} for every problem (problems(), or `probs`), setting (SETTINGS, or `settings`) and way of solving ("many":
+    solve_many_cases.matrix_cells). solver_lib: the emulation; None = the device library."""
     from karpenter_amd.scheduling import NewScheduler
-    probs = problems()
+    probs = problems() if probs is None else probs
     out = {}
+    if "many" in ways:
+        import solve_many_cases
+        out.update(solve_many_cases.matrix_cells(solver_lib, SETTINGS if settings is None else settings, probs, way="many"))
 
     def open_all(setting):
         opened = []
@@ -159,9 +216,14 @@ def differences(got, want):
     return out
 
 
-def load(key):
+def build_late(solver_lib=None, progress=False, settings=None):
+    """The late matrix: late_problems() under LATE_SETTINGS (or `settings` of them), alone, batch and many."""
+    return build_matrix(solver_lib, progress, LATE_SETTINGS if settings is None else settings, late_problems(), LATE_WAYS)
+
+
+def load(key, fixture=FIXTURE):
     """The recorded matrix for "emulation" or "device" (the emulation's cells overlaid with the device's differing ones)."""
-    with open(FIXTURE) as f:
+    with open(fixture) as f:
         doc = json.load(f)
     cells = {k: dict(v) for k, v in doc["emulation"].items()}
     if key == "device":
@@ -216,20 +278,57 @@ def coverage(cells):
     return cov
 
 
+def late_coverage(cells):
+    """What the late matrix exercises, as {claim: [cells]}: every claim needs at least one cell. A cell does not say which branch of a
+    driver its handle took; each claim below names the problem and the settings whose handle create() shapes so that only that branch
+    can give the recorded engine."""
+    cov = {}
+    def where(pred):
+        return [k for k, v in sorted(cells.items()) if pred(*k.split("|"), v)]
+    spread_only = lambda s: s.startswith("spread-")
+    solved = lambda v, engine: v["outcome"] == "ok" and v["engine"] == engine and v["engineFallbackReason"] == 0
+    no_many_kernel = ("auto-pod-operators-spread", "spread-pod-operators", "auto-pod-operators-nodes")   # (the settings with spread_pod_operators)
+    # SolveMany, the spread engine
+    cov["many: a spread member in a shared launch"] = where(lambda n, s, w, v: w == "many" and n == "spread-mix" and solved(v, "spread"))
+    cov["many: a spread member without a many-problem kernel, alone"] = where(lambda n, s, w, v: w == "many" and n == "spread-pod-notin" and s in no_many_kernel and solved(v, "spread"))
+    cov["many: a spread hand-back that keeps tw.enabled (27)"] = where(lambda n, s, w, v: w == "many" and v["engine"] == "general" and v["engineFallbackReason"] == 27 and v["cursorAttempts"] == 0)
+    cov["many: a spread hand-back that clears tw.enabled"] = where(lambda n, s, w, v: w == "many" and n in ("filter-never", "spread-pod-notin") and v["engine"] == "general" and v["engineFallbackReason"] in (4, 43))
+    cov["many: spread-only, refused by the engine"] = where(lambda n, s, w, v: w == "many" and spread_only(s) and MESSAGES["spread declined"] in v["error"])
+    cov["many: spread-only, refused by the host"] = where(lambda n, s, w, v: w == "many" and spread_only(s) and MESSAGES["spread outside shape"] in v["error"])
+    # SolveMany, the cursor engine. Every cursor handle of a late setting that SolveMany does not refuse has the limit stages (create():
+    # fw.lim under eng.limits) and so runs alone; the batched kernel under SolveMany is in the record of settings 0-17
+    # (tests/test_solve_many.py). Here it runs for the batch, which leaves the attempts at 0: that is how a cell shows it.
+    cov["a cursor member on the batched kernel"] = where(lambda n, s, w, v: w == "batch" and solved(v, "cursor") and v["cursorAttempts"] == 0)
+    cov["many: a cursor member alone, the set-aside list"] = where(lambda n, s, w, v: w == "many" and n == "pinned" and solved(v, "cursor"))
+    cov["many: a cursor member alone, pod operators"] = where(lambda n, s, w, v: w == "many" and n == "zone-notin" and solved(v, "cursor"))
+    cov["many: a cursor member alone, the node stage"] = where(lambda n, s, w, v: w == "many" and n == "dedicated-nodes" and solved(v, "cursor"))
+    # SolveBatch: a spread handle alone by each of its four conditions — under "auto-operators-spread" (no set-aside list) "spread-mix"
+    # meets none and runs the general engine with reason 0; the three problems beside it meet one each
+    plain_mix = where(lambda n, s, w, v: w == "batch" and n == "spread-mix" and s == "auto-operators-spread" and v["engine"] == "general" and v["engineFallbackReason"] == 0)
+    cov["batch: a spread-shaped handle on the general engine, reason 0"] = plain_mix
+    for what, name in (("daemon_groups", "spread-mix-daemonsets"), ("nd.dom", "spread-mix-nodes"), ("spread_complement", "spread-complement")):
+        cov[f"batch: a spread handle alone, {what}"] = plain_mix and where(lambda n, s, w, v: w == "batch" and n == name and s == "auto-operators-spread" and solved(v, "spread"))
+    cov["batch: a spread handle alone, unsched"] = plain_mix and where(lambda n, s, w, v: w == "batch" and n == "spread-mix" and s == "auto-unschedulable-spread" and solved(v, "spread"))
+    cov["batch: the short outside-shape text, spread-only handle"] = where(lambda n, s, w, v: w == "batch" and spread_only(s) and v["error"].endswith(MESSAGES["batch outside shape"]))
+    return cov
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--record", choices=["emulation", "device"])
     ap.add_argument("--coverage", action="store_true")
-    ap.add_argument("--out", default=FIXTURE)
+    ap.add_argument("--late", action="store_true", help="the record of LATE_SETTINGS (tests/golden/engine_matrix_late.json)")
+    ap.add_argument("--out")
     args = ap.parse_args()
+    args.out = args.out or (LATE_FIXTURE if args.late else FIXTURE)
     if args.coverage:
-        for claim, found in coverage(load("emulation")).items():
+        for claim, found in (late_coverage(load("emulation", LATE_FIXTURE)) if args.late else coverage(load("emulation"))).items():
             print(f"{len(found):4d}  {claim}" + (f"   e.g. {found[0]}" if found else "   MISSING"))
         return
     if not args.record:
         ap.error("--record or --coverage")
     import parity
-    cells = build_matrix(parity.build_emu() if args.record == "emulation" else None, progress=True)
+    cells = (build_late if args.late else build_matrix)(parity.build_emu() if args.record == "emulation" else None, progress=True)
     doc = {}
     if os.path.exists(args.out):
         with open(args.out) as f:

@@ -38,14 +38,14 @@ MUTATIONS = [
      "const bool no_topo_bounds = h->eng.spread_operators ? !pod_bounds : no_bounds;", "const bool no_topo_bounds = h->eng.spread_operators ? true : no_bounds;",
      "test_still_outside_the_shape"),
     ("the records kernel prints the field of a guarded claim", "fast_engine.h",
-     "if ((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) { if (!(tr.defined & kb)) vdef &= ~kb; }",
-     "if (((st.vmask >> (fv.voff[j] + fv.vwidth[j])) & 1) && !(tr.defined & kb)) vdef &= ~kb;",
+     "if (own) { if (!(tr.defined & kb)) vdef &= ~kb; }",
+     "if (own && !(tr.defined & kb)) vdef &= ~kb;",
      "test_counted_but_not_narrowed"),   # (the claims that must still print NotIn [test-zone-1, test-zone-2]; in operator_cases.spread_problem() a spread pod narrows every claim of the pool)
     ("a spread handle of every setting accepts complement templates", "ksolve_impl.h",
      "fw.ops = h->eng.spread_operators ? 1 : 0;", "fw.ops = 1;",
      "test_old_settings_stay_as_they_are"),
-    ("the batch path forgets the complement templates", "ksolve_impl.h",
-     "(h->daemon_groups || h->tw.nd.dom || h->spread_complement)", "(h->daemon_groups || h->tw.nd.dom)",
+    ("the batch path forgets the complement templates", "solve_calls.h",
+     "(h->daemon_groups || h->tw.nd.dom || h->spread_complement || h->fw.unsched)", "(h->daemon_groups || h->tw.nd.dom || h->fw.unsched)",
      "test_in_a_batch"),
     ("with existing nodes the templates' bounds still decline", "ksolve_impl.h",
      "uint32_t why = nodes_decline(common && no_topo_bounds);", "uint32_t why = nodes_decline(common && no_bounds);",

@@ -45,8 +45,8 @@ MUTATIONS = [
     ("a spread handle of every setting gets the pod operators", "ksolve_impl.h",
      "fw.podops = h->eng.spread_pod_operators && fw.unsched && fw.filt ? dz<ks::FastPodOps>(h, 1) : nullptr;", "fw.podops = fw.unsched && fw.filt ? dz<ks::FastPodOps>(h, 1) : nullptr;",
      "test_old_settings_stay_as_they_are"),
-    ("a member with the switch shares the many-problem launch", "ksolve_impl.h",
-     "if (h->fw.podops) alone(i); else spread.push_back(i);", "spread.push_back(i);",
+    ("a member with the switch shares the many-problem launch (of the kernels with the filters)", "solve_calls.h",
+     "ks::pack_topo_many_row(ks::topo_flavour(h->fw),", "ks::pack_topo_many_row(h->fw.podops ? ks::TopoFlavour::Filter : ks::topo_flavour(h->fw),",
      "test_members_of_one_solve_many"),
     ("a class that selects nothing is ALWAYS inside a NotIn term", "topo_engine.h",
      "if (!(defined && !(cf & ~tf))) always = false;", "if (!(defined && (!(cf & ~tf) || !sel))) always = false;",
