@@ -318,7 +318,12 @@ typedef struct {
                                     *     32    auto-pod-operators-nodes cursor, spread, general falls back   as 29, + node-pod-operators = the cursor engine's existing-node stage takes pods with NotIn,
                                     *                                                                          Exists and DoesNotExist requirements too
                                     *     33    cursor-pod-operators-nodes cursor                   refuses       as 27, + node-pod-operators
-                                    *   above 33: no name; as 17.
+                                    *     34    (no name)            cursor                     refuses       - (as 17: what a value past the table stood for when 35 / 36 were added; the table's
+                                    *                                                                          kEngineSettingCount keeps its value 34 = "rows 0-33", the table itself has 37 rows)
+                                    *     35    auto-pod-operators-spread-nodes cursor, spread, general falls back as 32, + s-node-pod-operators = the spread engine takes pods with NotIn, Exists and
+                                    *                                                                          DoesNotExist beside existing nodes too
+                                    *     36    spread-pod-operators-nodes spread                 refuses       as 30, + s-node-pod-operators
+                                    *   above 36: no name; as 17.
                                     *
                                     * The cursor engine (csrc/fast_engine.h) takes problems whose requirement algebra is purely positive (In
                                     * sets only, no topology / existing nodes / minValues / reservations / host ports; DaemonSet overhead is
@@ -376,7 +381,14 @@ typedef struct {
                                     * pod's (csrc/node_stage.h, "Pod operators beside existing nodes") — instead of reason 4 / 8 from the stage,
                                     * which every setting below 32 still gives. Reason 37 for the one shape that is not static: a key some node
                                     * lacks with a NotIn pod and an In / Exists pod on it. The loop's by-design declines 9-12 apply as under
-                                    * 26 / 27; topology batches with nodes and such pods (4) still go to the general engine.
+                                    * 26 / 27; topology batches with nodes and such pods (4) still go to the general engine below 35.
+                                    * s-node-pod-operators: a TOPOLOGY batch with existing nodes AND pods (or spread owners) with NotIn, Exists or
+                                    * DoesNotExist stays on the spread engine (csrc/topo_nodes.h, "Pod operators beside existing nodes on the spread
+                                    * engine"; kernel ksolve_pack_topo_nodes_pn) instead of reason 4 / 8, which every setting below 35 still
+                                    * gives. Reason 37 here too, widened: a key some node lacks with a NotIn pod and an In / Exists pod OR an In /
+                                    * Exists term of a spread constraint's node filter on it; 36 for a node whose value of a spread key would take
+                                    * the index of the phantom bit. The by-design declines 9-12, 43 and 50 of 29 / 30 apply unchanged. A batch
+                                    * without such pods, or without nodes, runs the kernel and gets the outcome of 32 / 30.
                                     * All give identical Results. */
 } ksolve_options;
 

@@ -16,12 +16,13 @@ enum Decline : int {
   DECLINE_CLASS_NOT_POSITIVE = 4,      // a pod requirement that is not an In set (requirements.go:260-265 would apply) — not the cursor engine under engines 26 / 27, which take NotIn, Exists and
                                        // DoesNotExist on pods (fast_engine.h, "The cursor engine's pod operators"), not the spread engine under 29 / 30 (topo_engine.h, "The spread engine's
                                        // pod operators") — but for a batch with existing nodes: the cursor engine's existing-node stage raises it under every setting but engines 32 / 33
-                                       // (node_stage.h, "Pod operators beside existing nodes"); the spread engine with nodes under every setting
+                                       // (node_stage.h, "Pod operators beside existing nodes"); the spread engine with nodes under every setting but engines 35 / 36
+                                       // (topo_nodes.h, "Pod operators beside existing nodes on the spread engine")
   DECLINE_SELECTS_HOST_OR_TYPE = 5,    // pods (or a dictionary-key group) select on kubernetes.io/hostname or the instance type
   DECLINE_KEYS_DO_NOT_PACK = 6,        // the keys pods select on: more than kFastMaxVar, wider than one word, or beyond kFastVarBits bits
   DECLINE_QUANTITY_RANGE = 7,          // an allocatable, effective allocatable or request outside 31 bits
   DECLINE_CLASS_EMPTY_IN = 8,          // a pod requirement In [] (== DoesNotExist: not positive) — as 4: not the cursor engine under engines 26 / 27, not the spread engine under 29 / 30; with existing nodes
-                                       // the cursor engine's stage raises it under every setting but 32 / 33, the spread engine under every setting
+                                       // the cursor engine's stage raises it under every setting but 32 / 33, the spread engine under every setting but 35 / 36
   // engines 26 / 27 and 29 / 30 only: what the pod operators leave to the general engine (fast_engine.h, "The cursor engine's pod operators"; under topology a group's key counts as an In user for 9)
   DECLINE_CLASS_KEY_DEFINEDNESS = 9,   // a custom key some NodePool leaves undefined, with a NotIn / DoesNotExist class and an In / Exists class on it: whether the second kind is
                                        // admissible depends on whether a pod of the first kind joined the claim before (requirements.go:185-193)
@@ -46,9 +47,11 @@ enum Decline : int {
   DECLINE_NODE_CLASSES = 33,           // more pod classes than the node stage keeps cursors for (kNodeStageMaxClasses); decided by solve()
   DECLINE_NODES_NOT_PLAIN = 34,        // existing nodes, and otherwise outside the engine's shape (host ports, volumes, minValues, reservations, resident pods ...)
   DECLINE_NODE_LACKS_KEY = 35,         // spread: a node without a label for a dictionary key some topology group uses
-  DECLINE_NODE_DOMAIN_RANGE = 36,      // spread: a node whose value of such a key lies beyond the kTopoMaxDom domains a group's counters hold
+  DECLINE_NODE_DOMAIN_RANGE = 36,      // spread: a node whose value of such a key lies beyond the kTopoMaxDom domains a group's counters hold (engines 35 / 36, a batch under the phantom layout: beyond the fifteen it leaves)
   DECLINE_NODE_KEY_DEFINEDNESS = 37,   // engines 32 / 33, the cursor engine's existing-node stage: a key some node lacks, with a NotIn class and an In / Exists class on it — a NotIn pod
-                                       // that lands on such a node defines the key there, and the second kind passes from then on (requirements.go:189): the (class, node) rows are not static
+                                       // that lands on such a node defines the key there, and the second kind passes from then on (requirements.go:189): the (class, node) rows are not static.
+                                       // Engines 35 / 36, the spread engine's node path (topo_nodes.h topo_nodes_definedness): the same, and an In / Exists TERM of a topology node filter on the
+                                       // key counts like an In / Exists class (the filter reads the node's pristine label row)
   // TopoEngine::setup_topo()
   DECLINE_TOPO_GROUPS = 40,            // no topology group, more than kTopoMaxGroups, or aliased groups
   DECLINE_TOPO_PREFERENCES = 41,       // a pod with preferences: podDomains = StrictRequirements differs from its requirements (topology.go:230)

@@ -37,7 +37,7 @@ static void be_launch_pack_topo_nodes(ksolve_handle* h) {
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
   be_h2d(h, h->d_topo_args, &a, sizeof(a));
   const ks::TopoArgs* a_ = h->d_topo_args;
-  note_pack_kernel(h, ks::pack_topo_row(ks::topo_flavour(h->fw), true)->kernel);   // the kernel the device backend launches, from the same lookup
+  note_pack_kernel(h, ks::pack_topo_nodes_kernel(ks::topo_flavour(h->fw), spread_nodes_pn(h)));   // the kernel the device backend launches, from the same lookup (the one engine here has NP built in; FastWork::node_podops decides)
   ks::TopoEngine<ks::Wave, true> eng(&a_->pv, &a_->ws, &a_->fw, &a_->tw, lds.data());
   eng.solve();
 }

@@ -2,6 +2,9 @@
 // Host-only plain C++, no device code: ksolve_impl.h looks a handle's value up in create() and reads the policy from then on
 // (ksolve_handle::eng; the options keep what the caller passed); the host library (host/ksched.cpp) looks the option's NAME up in the
 // same table. include/ksolve.h documents the values for callers; a new value is a new row here and a new line there.
+// The table has kEngineTableRows rows. kEngineSettingCount keeps its value and its meaning, "rows 0-33": what the table held before
+// 35 / 36 were added (callers and tests compiled against that number stay right); 34 is a hole like 17, 28 and 31, and the lookups
+// below walk the longer table.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -31,6 +34,7 @@ struct EnginePolicy {
   bool pod_operators;   // the cursor engine takes pod classes with NotIn, Exists and DoesNotExist requirements (fast_engine.h, "The cursor engine's pod operators")
   bool spread_pod_operators; // the spread engine takes such pod classes too, and node-filter terms of those operators (topo_engine.h, "The spread engine's pod operators")
   bool node_pod_operators;   // the cursor engine's existing-node stage takes such pod classes too (node_stage.h, "Pod operators beside existing nodes")
+  bool spread_node_pod_operators; // the spread engine's existing-node path takes such pod classes too (topo_nodes.h, "Pod operators beside existing nodes on the spread engine")
   const char* name;     // options.engine of the host library's problem document; nullptr = no name
 
   constexpr bool general_only() const { return run == General; }
@@ -52,11 +56,12 @@ constexpr EnginePolicy engine_row(EnginePolicy from, const char* name, Switch...
   ((from.*adds = true), ...);
   return from;
 }
-// A value without a row is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch, no name. 17, 28 and 31 were
-// such values for every caller that passed them when the rows behind them were added, and stay that.
+// A value without a row is not an error (yet): the cursor engine only, on the LDS plan as it stands, no switch, no name. 17, 28, 31 and 34
+// were such values for every caller that passed them when the rows behind them were added, and stay that.
 inline constexpr EnginePolicy kEngineSettingPastTable = engine_row(EnginePolicy::Cursor, 0, false, nullptr);
-inline constexpr uint32_t kEngineSettingCount = 34;
-struct EngineTable { EnginePolicy row[kEngineSettingCount]; };
+inline constexpr uint32_t kEngineSettingCount = 34;   // rows 0-33 (kept: see the head of this file)
+inline constexpr uint32_t kEngineTableRows = 37;      // rows 0-36: what the table holds
+struct EngineTable { EnginePolicy row[kEngineTableRows]; };
 constexpr EngineTable engine_table() {
   using P = EnginePolicy;
   EngineTable t{};
@@ -95,15 +100,18 @@ constexpr EngineTable engine_table() {
   r[31] = kEngineSettingPastTable;
   r[32] = engine_row(r[29], "auto-pod-operators-nodes", &P::node_pod_operators);
   r[33] = engine_row(r[27], "cursor-pod-operators-nodes", &P::node_pod_operators);
+  r[34] = kEngineSettingPastTable;
+  r[35] = engine_row(r[32], "auto-pod-operators-spread-nodes", &P::spread_node_pod_operators);
+  r[36] = engine_row(r[30], "spread-pod-operators-nodes", &P::spread_node_pod_operators);
   return t;
 }
 inline constexpr EngineTable kEngineSettings = engine_table();
 
-inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineSettingCount ? kEngineSettings.row[value] : kEngineSettingPastTable; }
+inline const EnginePolicy& engine_policy(uint32_t value) { return value < kEngineTableRows ? kEngineSettings.row[value] : kEngineSettingPastTable; }
 
 // The value an option name stands for; 0 ("auto") for a name the table does not hold. (A row without a name has none to match.)
 inline uint32_t engine_value(const char* name) {
-  for (uint32_t v = 0; v < kEngineSettingCount; ++v) if (kEngineSettings.row[v].name && !strcmp(kEngineSettings.row[v].name, name)) return v;
+  for (uint32_t v = 0; v < kEngineTableRows; ++v) if (kEngineSettings.row[v].name && !strcmp(kEngineSettings.row[v].name, name)) return v;
   return 0;
 }
 

@@ -156,7 +156,8 @@ struct FastWork {   // HBM workspace of the cursor engine (host-allocated when t
   uint8_t* us_diag;
   uint64_t* us_cls;       // [n_pods >= n_classes] by class: the verdict of the class's last failed template walk (FastCold::new_claim), reset by setup()
   uint32_t* pod_qpos;     // [n_pods], behind the existing-node stage only: a pod's position in the FULL queue (ksolve_fast_requeue)
-  FastPodOps* podops;     // [1] engines 26 / 27 (a cursor handle) and 29 / 30 (a spread handle: topo_engine.h, "The spread engine's pod operators"), null otherwise: setup() accepts pod classes with NotIn, Exists and DoesNotExist requirements — "The cursor engine's pod operators" below. The last field: every other kernel reads the layout it always read
+  FastPodOps* podops;     // [1] engines 26 / 27 (a cursor handle) and 29 / 30 (a spread handle: topo_engine.h, "The spread engine's pod operators"), null otherwise: setup() accepts pod classes with NotIn, Exists and DoesNotExist requirements — "The cursor engine's pod operators" below. Behind every field the kernels of the settings below 29 read
+  int node_podops;        // engines 35 / 36 (a spread handle only): setup(true) keeps the pod operators on for a batch with existing nodes (topo_nodes.h, "Pod operators beside existing nodes on the spread engine"). The last field: every other kernel reads the layout it always read
 };
 static_assert(offsetof(FastWork, us_n) == offsetof(FastWork, unsched) + 8, "FastWork::filt fills the gap behind unsched: the layout every kernel reads stays what it was");
 
@@ -565,9 +566,12 @@ KS_FN uint64_t fast_po_tmpl_field(const Dict& d, const ReqRef& tr, int k, uint32
 }
 // TP: the pod operators on behalf of the spread engine too (engines 29 / 30; topo_engine.h, "The spread engine's pod operators") —
 // a switch of its own, so that the cursor engine's instantiations are compiled from what they were compiled from.
-template <class W, int GS, int R, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn, bool TP = false>
+// NP: ... and beside existing nodes (engines 35 / 36; topo_nodes.h, "Pod operators beside existing nodes on the spread engine"): again
+// a switch of its own, handed down the way TP is, so that every other instantiation is compiled from what it was compiled from.
+template <class W, int GS, int R, bool US = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn, bool TP = false, bool NP = false>
 struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, std::conditional<PO, FastPodOpsState, FastNoPodOpsState>::type {
   static_assert(!TP || PO, "the spread engine's pod operators are the pod operators");
+  static_assert(!NP || TP, "pod operators beside existing nodes are the spread engine's pod operators");
   KS_DEV bool po() const { if constexpr (PO) return this->po_on != 0; else return false; }
   const ProblemView* Pk;
   const Workspace* Sk;
@@ -779,7 +783,7 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, st
     // ... and for engines 29 / 30 on the spread engine (TP), where the phantom layout is turned on only for a batch that needs it — some
     // class or some term of a topology node filter is negative (a complement set, or In []) — so that a positive batch packs, and is
     // declined, exactly as under 24 / 25. Existing nodes stay outside (a negative pod may add a key to a node): such a batch keeps
-    // its reason 4 / 8 below.
+    // its reason 4 / 8 below — but in the instantiation of engines 35 / 36 (NP) on a handle that carries the switch (FastWork::node_podops).
     bool pod_ops = false;
     if constexpr (PO && !TP) { pod_ops = !topo && F.podops != nullptr; this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0; }
     if constexpr (TP) {
@@ -792,6 +796,7 @@ struct FastCold : std::conditional<US, FastKeepState, FastNoKeepState>::type, st
         };
         const uint64_t need = W::reduce_or(nc, [&](int c) { return negative(Pv.cls_reqs.at(d, c)); }) |
                               W::reduce_or((int)Pv.topo.f_first[Pv.topo.n_groups], [&](int i) { return negative(Pv.topo.f_reqs.at(d, i)); });
+        if constexpr (NP) { if (!need || (P.n_nodes > 0 && !F.node_podops)) pod_ops = false; } else
         if (!need || P.n_nodes > 0) pod_ops = false;
       }
       this->po_on = pod_ops ? 1 : 0; this->dne_vars = 0;

@@ -744,18 +744,20 @@ static uint32_t be_launch_fast_cold(ksolve_handle* h, const ks::FastColdArgs* d_
 #endif
 // the spread engine's kernel of the handle's flavour (engines 22 / 23: the set-aside list compiled in; 24 / 25: the topology node
 // filters as well; 29 / 30: and the pod operators), without or with existing nodes
-static void launch_pack_topo(ksolve_handle* h, const ks::PackTopoRow* row) {
-  const ksolve_pack_topo_fn fn = kPackTopoFn[row - ks::kPackTopoRows];
-  note_pack_kernel(h, row->kernel);
+static void launch_pack_topo(ksolve_handle* h, const ks::PackTopoRow* row, bool pn = false) {
+  const ksolve_pack_topo_fn fn = pn ? ksolve_pack_topo_nodes_pn : kPackTopoFn[row - ks::kPackTopoRows];
+  const char* const name = pn ? ks::pack_topo_nodes_kernel(row->flavour, true) : row->kernel;
+  note_pack_kernel(h, name);
   const int lds_bytes = h->tw.plan.total_bytes;
   if (!hip_check(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes), "hipFuncSetAttribute(LDS)")) return;
   ks::TopoArgs a{h->pv, h->ws, h->fw, h->tw};
   be_h2d(h, h->d_topo_args, &a, sizeof(a));
   hipLaunchKernelGGL(fn, dim3(1), dim3(64), (size_t)lds_bytes, HB(h)->stream, (const ks::TopoArgs*)h->d_topo_args);
-  check_launch(h, row->kernel);
+  check_launch(h, name);
 }
 static void be_launch_pack_topo(ksolve_handle* h) { launch_pack_topo(h, ks::pack_topo_row(ks::topo_flavour(h->fw), false)); }
-static void be_launch_pack_topo_nodes(ksolve_handle* h) { launch_pack_topo(h, ks::pack_topo_row(ks::topo_flavour(h->fw), true)); }
+// (engines 35 / 36: ksolve_pack_topo_nodes_pn, outside the matrix, where spread_nodes_pn says so — the PodOps flavour's row otherwise)
+static void be_launch_pack_topo_nodes(ksolve_handle* h) { launch_pack_topo(h, ks::pack_topo_row(ks::topo_flavour(h->fw), true), spread_nodes_pn(h)); }
 // ksolve_solve_many: one launch of the spread engine's many-problem kernel of every flavour that has members (topo_many.h), each on
 // the stream of its first member so that the flavours overlap; every member's T_PACK timer gets the time of its own launch. The
 // launch's table — the members' records, the order table, the ticket counter — lives in a buffer the first member's backend keeps

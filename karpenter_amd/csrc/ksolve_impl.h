@@ -500,7 +500,9 @@ static int be_device_available();
 static int be_device_of(const ksolve_handle* h);     // the device ordinal the handle lives on
 static void be_free(ksolve_handle* h, void* p);   // releases one be_alloc'ed block before the handle goes
 static void be_launch_node_dead0(ksolve_handle* h, int n_blocks, const ks::NodeDeadArgs& a);   // one wavefront per 64 nodes
-static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: TopoEngine<W, true>::solve (existing nodes: topo_nodes.h)
+static void be_launch_pack_topo_nodes(ksolve_handle* h);   // one wavefront: TopoEngine<W, true>::solve (existing nodes: topo_nodes.h); ksolve_pack_topo_nodes_pn where spread_nodes_pn(h) says so
+// the one place that chooses between the matrix row and ksolve_pack_topo_nodes_pn (engines 35 / 36), from the setting and the handle
+static bool spread_nodes_pn(const ksolve_handle* h) { return h->eng.spread_node_pod_operators && h->fw.podops && h->n_nodes > 0 && h->fw.node_podops; }
 static void be_launch_fast_unsched(ksolve_handle* h);               // engines 20 / 21, one thread per pod set aside: fast_unsched_body (errors under the pod indices)
 static void be_launch_pack_nodes(ksolve_handle* h, bool hbm, bool pod_ops);   // ksolve_pack_nodes (node_stage.h; pod_ops: its _p kernels, engines 32 / 33): one wavefront; then ksolve_fast_requeue / ksolve_fast_remark per queue entry
 static void be_launch_pack_sweep(ksolve_handle* h, const ks::ProblemView* d_pv, ks::Workspace* d_items, int n, const ks::LdsPlan& plan, const uint32_t* d_order, uint32_t* d_next);   // block b = the general engine on probe b; sets T_PACK
@@ -553,6 +555,20 @@ static ksolve_status fail(ksolve_handle* h, ksolve_status s, const std::string& 
   return s;
 }
 
+// Does some requirement set of the table use NotIn, Exists or DoesNotExist (In [] is DoesNotExist)? What FastCold::setup(true) asks of
+// the pod classes and the node-filter terms before it turns the phantom layout on, asked of the rows they are made from.
+static bool reqs_negative(const ksolve_reqsets& r, uint32_t n, const ks::Dict& dict, uint32_t req_words, uint32_t n_keys) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (r.complement[i]) return true;
+    for (uint32_t k = 0; k < n_keys; ++k) {
+      if (!((r.defined[i] >> k) & 1u)) continue;
+      bool empty = true;
+      for (uint32_t x = dict.key_word_off[k]; x < dict.key_word_off[k + 1]; ++x) empty = empty && !r.mask[(size_t)i * req_words + x];
+      if (empty) return true;
+    }
+  }
+  return false;
+}
 static bool any_nonzero(const uint32_t* p, uint32_t n) {
   if (!p) return false;
   for (uint32_t i = 0; i < n; ++i) if (p[i]) return true;
@@ -1247,6 +1263,11 @@ static ksolve_status create(const ksolve_problem_desc* d, const ksolve_options* 
       // on the cursor engine. Pod-side Gt / Lt and minValues stay outside plain_topo (reason 1 above), whatever the setting.
       fw.podops = h->eng.spread_pod_operators && fw.unsched && fw.filt ? dz<ks::FastPodOps>(h, 1) : nullptr;
       if (fw.podops) tw.filt = dz<ks::TopoFilt>(h, 2);   // (kTopoFiltSlotsPodOps slots: a term per Deployment makes a group per Deployment)
+      // engines 35 / 36: ... and beside existing nodes (topo_nodes.h, "Pod operators beside existing nodes on the spread engine"). The
+      // switch is set for a problem that has nodes and a negative pod row or node-filter term only: every other handle of these
+      // settings runs the kernel, and gets the outcome, of 32 / 30 (spread_nodes_pn below picks the kernel from it)
+      fw.node_podops = h->eng.spread_node_pod_operators && fw.podops && tw.nd.dom &&
+                       (reqs_negative(d->pod_reqs, d->n_pod_rows, P.dict, req_words, d->n_keys) || reqs_negative(d->topo.filter_reqs, d->topo.filter_first[d->topo.n], P.dict, req_words, d->n_keys)) ? 1 : 0;
       if (fw.ops) {
         // ... and whether this problem has one: what FastCold::setup() declines with reason 3 without the switch (the batch path asks)
         bool complement = any_nonzero(d->tmpl_reqs.complement, d->n_templates) || any_nonzero(d->tmpl_reqs.has_gte, d->n_templates) || any_nonzero(d->tmpl_reqs.has_lte, d->n_templates);

@@ -82,6 +82,11 @@ inline constexpr char kPackFastPair[] = "ksolve_pack_fast2", kPackFastBatch[] = 
 inline constexpr char kPackNodesLds[] = "ksolve_pack_nodes_lds", kPackNodesHbm[] = "ksolve_pack_nodes_hbm";
 inline constexpr char kPackNodesLdsPodOps[] = "ksolve_pack_nodes_lds_p", kPackNodesHbmPodOps[] = "ksolve_pack_nodes_hbm_p";
 inline const char* pack_nodes_kernel(bool hbm, bool pod_ops) { return pod_ops ? (hbm ? kPackNodesHbmPodOps : kPackNodesLdsPodOps) : (hbm ? kPackNodesHbm : kPackNodesLds); }
+// the spread engine's kernel outside the matrix: the PodOps flavour with existing nodes and the pod operators kept on beside them
+// (engines 35 / 36, TopoEngine's NP; ksolve_pack_topo_nodes_pn.hip) — a bool of the node path's own, not a TopoFlavour. pn: the setting
+// has the switch, the handle carries the pod operators, and its problem has nodes and a negative class or node-filter term
+// (ksolve_impl.h spread_nodes_pn); every other handle with nodes runs the row of its flavour.
+inline constexpr char kPackTopoNodesPodOpsNodes[] = "ksolve_pack_topo_nodes_pn";   // (looked up by pack_topo_nodes_kernel, below)
 
 // The row of the kernel both backends launch; nullptr where no kernel exists.
 template <class Row, int N, class F> inline const Row* pack_row_where(const Row (&rows)[N], F match) {
@@ -91,6 +96,7 @@ template <class Row, int N, class F> inline const Row* pack_row_where(const Row 
 inline const PackFastRow* pack_fast_row(FastFlavour f, int plan, int rows) { return pack_row_where(kPackFastRows, [&](const PackFastRow& r) { return r.flavour == f && r.plan == plan && r.rows == rows; }); }
 inline const PackFastRow* fast_cold_row(FastFlavour f, int plan, int rows) { return pack_row_where(kFastColdRows, [&](const PackFastRow& r) { return r.flavour == f && r.plan == plan && r.rows == rows; }); }
 inline const PackTopoRow* pack_topo_row(TopoFlavour f, bool nodes) { return pack_row_where(kPackTopoRows, [&](const PackTopoRow& r) { return r.flavour == f && r.nodes == nodes; }); }
+inline const char* pack_topo_nodes_kernel(TopoFlavour f, bool pn) { return pn && f == TopoFlavour::PodOps ? kPackTopoNodesPodOpsNodes : pack_topo_row(f, true)->kernel; }
 inline const PackTopoRow* pack_topo_many_row(TopoFlavour f, bool nodes) { return pack_row_where(kPackTopoManyRows, [&](const PackTopoRow& r) { return r.flavour == f && r.nodes == nodes; }); }
 
 }  // namespace ks

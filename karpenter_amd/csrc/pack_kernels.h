@@ -1,6 +1,6 @@
 // pack_kernels.h — the pack kernels (one wavefront per scheduling problem) live in translation units of their own, so that build()
 // compiles them side by side (the general engine's instantiations alone are minutes of one hipcc): the general engine's
-// ksolve_pack_general.hip, ksolve_pack_batch.hip and ksolve_pack_sweep4.hip, the node stage's ksolve_pack_nodes.hip, and the three
+// ksolve_pack_general.hip, ksolve_pack_batch.hip and ksolve_pack_sweep4.hip, the node stage's ksolve_pack_nodes.hip, ksolve_pack_topo_nodes_pn.hip, and the three
 // units of the fast engines — ksolve_pack_fast.hip, ksolve_pack_topo.hip, ksolve_pack_topo_many.hip — each compiled once per flavour.
 // The fast engines' kernels are declared from the lists of pack_flavours.h, which the units define them from. ksolve.hip (the HIP
 // backend of the C ABI) launches them through these declarations; no device function crosses a translation unit.
@@ -31,6 +31,7 @@ typedef void (*ksolve_pack_topo_fn)(const ks::TopoArgs*);
 #define KS_DECLARE(NAME, FL, ND) __global__ void NAME(const ks::TopoArgs* a);
 KS_PACK_TOPO_ROWS(KS_DECLARE)
 #undef KS_DECLARE
+__global__ void ksolve_pack_topo_nodes_pn(const ks::TopoArgs* a);   // engines 35 / 36, outside the matrix (ksolve_pack_topo_nodes_pn.hip)
 // ... many problems per launch (ksolve_solve_many; topo_many.h: block = one ticket = one member, largest first)
 typedef void (*ksolve_pack_topo_many_fn)(const ks::TopoArgs* const*, const uint32_t*, uint32_t*, int);
 #define KS_DECLARE(NAME, FL, ND) __global__ void NAME(const ks::TopoArgs* const* items, const uint32_t* order, uint32_t* next, int n);

@@ -64,7 +64,9 @@
 //     tell: declined (43) where such a bin can exist. Such a batch has kTopoFiltSlotsPodOps filter slots;
 //   * a pod whose NotIn leaves a template no value, or whose static verdict is off, fails new_claim's walk with Incompatible (2) before
 //     Topology (3); filter_diag reads a narrowed complement set through compat_word;
-//   * existing nodes with negative pods stay outside (4 / 8): a negative pod may add a key to a node.
+//   * existing nodes with negative pods stay outside (4 / 8): a negative pod may add a key to a node — but under engines 35 / 36 (NP
+//     below; topo_nodes.h, "Pod operators beside existing nodes on the spread engine"), which keep the phantom layout on beside nodes,
+//     decline the one shape that is not static (37) and read the node filter's 32 slots on a node.
 // On the device PO is a compile-time switch like US and FS, with kernels of its own (ksolve_pack_topo_podops.hip, US and FS on as
 // well): every line stands behind `if constexpr (PO)`. The host emulation builds it in and FastWork::podops decides at run time.
 #pragma once
@@ -142,11 +144,14 @@ struct TopoKeepState {
   uint32_t us_epoch = 1;           // commits so far + 1 (0: no verdict)
 };
 struct TopoNoKeepState {};
-template <class W, bool NODES = false, bool US = kFastKeepBuiltIn, bool FS = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn>
+// NP: pod operators beside existing nodes (engines 35 / 36, FastWork::node_podops; topo_nodes.h). One kernel of its own
+// (ksolve_pack_topo_nodes_pn); every line stands behind `if constexpr (NP)`, and the host emulation builds it into its engine with nodes.
+template <class W, bool NODES = false, bool US = kFastKeepBuiltIn, bool FS = kFastKeepBuiltIn, bool PO = kFastKeepBuiltIn, bool NP = kFastKeepBuiltIn && NODES>
 struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
+  static_assert(!NP || (NODES && PO), "pod operators beside existing nodes: the node path and the pod operators (35 = 32 + the switch, 36 = 30 + the switch)");
   static_assert(!FS || US, "the engines that evaluate node filters keep unschedulable pods too (24 = 22 + filters, 25 = 23 + filters)");
   static_assert(!PO || FS, "the engines that take pod operators evaluate node filters too (29 = 24 + pod operators, 30 = 25 + pod operators)");
-  FastCold<W, 2, 1, kFastKeepBuiltIn, PO, PO> cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
+  typename std::conditional<NP, FastCold<W, 2, 1, kFastKeepBuiltIn, PO, PO, true>, FastCold<W, 2, 1, kFastKeepBuiltIn, PO, PO>>::type cold;   // the cursor engine's set-up, requirement-set cache and Pareto vectors
   RunOrder<W> order;        // Go's sort.Slice permutation as one ring per pod count
   const ProblemView* Pk; const Workspace* Sk; const FastWork* Fk; const TopoWork* Tk;
   KS_LDS TopoState* st;
@@ -1064,6 +1069,10 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
     const ZChoice zc = choose_domains(zg0, (zselfw & 1u) != 0, cvmask, zkv, p0);
     const ZChoice zd = choose_domains(zg1, (zselfw & 2u) != 0, cvmask, zkv, p1);
     if (!p0 || !p1) { TopoNodePick none; none.node = -1; none.slot = 0; return none; }   // (no domain anywhere: the claim path stops with DECLINE_UNSCHEDULABLE_POD)
+    if constexpr (NP) {   // (the filters' slots under the phantom layout: every bit of the class's word, read by topo_filter_matches_po)
+      TopoNodeFiltPo nf; nf.fs = filters() ? (uint32_t)W::uniform((uint64_t)Tk->cls[k].pad) : 0u; nf.nv = cold.nv; nf.ft = Tk->filt; nf.po = pod_ops();
+      return topo_nodes_place<W, TopoNodeFiltPo>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm, nf);
+    } else
     if constexpr (FS) {
       TopoNodeFilt nf; nf.fs = filters() ? (uint32_t)W::uniform((uint64_t)Tk->cls[k].pad) : 0u; nf.nv = cold.nv; nf.ft = Tk->filt;
       return topo_nodes_place<W, TopoNodeFilt>(Pk, Sk, Tk, st, Mp, k, hlim, hinc, zsel, zg0, zc.vm, zg1, zd.vm, nf);
@@ -1132,6 +1141,10 @@ struct TopoEngine : std::conditional<US, TopoKeepState, TopoNoKeepState>::type {
     {
       const int why = (int)W::uniform((uint64_t)(uint32_t)cold.setup(true));
       if (why) { bail = why; finish(3, 0); return; }
+      if constexpr (NP) if (pod_ops() && Pk->n_nodes > 0) {   // engines 35 / 36: what is not static on a node, before any pod is placed
+        const int whyn = (int)W::uniform((uint64_t)(uint32_t)topo_nodes_definedness<W>(Pk, Sk, Tk));
+        if (whyn) { bail = whyn; finish(3, 0); return; }
+      }
       const int why2 = (int)W::uniform((uint64_t)(uint32_t)setup_topo());
       if (why2) { bail = why2; finish(3, 0); return; }
     }

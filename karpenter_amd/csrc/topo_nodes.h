@@ -111,6 +111,75 @@ KS_COLD TopoFiltCut topo_node_filter_cut(const ProblemView* Pk, const Workspace*
   return topo_filter_cut(ctx.ft, Mp, ctx.nv, ctx.fs, m, undef, [&](const TopoFiltSlot& s) { return !(s.taint && (taints & ~tol[s.group])); });
 }
 
+
+// ---- Pod operators beside existing nodes on the spread engine (engines 35 / 36; TopoEngine's NP) ----
+// A node's label sets are single-valued In sets (reason 32) and existing nodes pass no AllowUndefined (existingnode.go:100), so what
+// node_stage.h says of the cursor engine's stage holds here word for word: the (class, node) verdict up to resources is the row
+// ksolve_node_dead0 computes (nodecheck.h kneg) — TopoNodes::dead0 IS that row, so the half of topo_nodes_place that only moves towards
+// rejection needs nothing new — and the candidate-domain half needs nothing new either: every group key is defined on every node
+// (reason 35), choose_domains evaluates a NotIn S class's field as "the values outside S", and a node's one domain is a dictionary
+// value, never the phantom bit (a value that would be index kTopoMaxDom - 1 under the phantom layout: reason 36, below).
+// Two things are new.
+//  1. The node filter. Under the phantom layout a group's TopologyNodeFilter may hold NotIn / Exists / DoesNotExist terms in up to
+//     kTopoFiltSlotsPodOps slots, read by topo_filter_matches_po. The node's packed word is already in that layout: a key the node
+//     defines is its ONE value bit (no phantom bit, guard clear: a concrete set), a key it lacks is all ones with the guard bit, and
+//     `undef` says so — a NotIn / DoesNotExist term passes it, an In / Exists term fails it (requirements.go:185-193).
+//  2. Definedness. A NotIn S pod that lands on a node lacking key K writes NotIn S onto the node (existingnode.go:172-176); from
+//     then on an In / Exists POD passes where it failed (node_stage.h, reason 37) and so does an In / Exists TERM of a node filter,
+//     which here reads the node's pristine label row. topo_nodes_definedness declines both before any pod is placed. A DoesNotExist
+//     pod needs no decline — behind it, on that node:
+//         later pod / term    In S   Exists   NotIn S   DoesNotExist
+//         before (K lacking)  fails  fails    passes    passes
+//         after (K: In [])    fails  fails    passes    passes        (empty intersection, positive incoming operator; both negative: requirements.go:260-264)
+struct TopoNodeFiltPo { static constexpr bool on = true; uint32_t fs; int nv; const TopoFilt* ft; bool po; };   // po: this batch has the phantom layout
+template <class W>
+KS_COLD TopoFiltCut topo_node_filter_cut(const ProblemView* Pk, const Workspace* Sk, const KS_LDS FastMisc* Mp, TopoNodeFiltPo ctx, int node) {
+  if (!ctx.po) { TopoNodeFilt c; c.fs = ctx.fs; c.nv = ctx.nv; c.ft = ctx.ft; return topo_node_filter_cut<W>(Pk, Sk, Mp, c, node); }
+  const int nn = Pk->n_nodes;
+  const uint32_t ndef = Sk->n_defined0[node];
+  uint64_t m = 0, undef = 0;
+  for (int j = 0; j < ctx.nv; ++j) {
+    const uint64_t guard = 1ull << (Mp->voff[j] + Mp->vwidth[j]);
+    if ((ndef >> Mp->vkey[j]) & 1u) m |= (Sk->n_mask0[(size_t)Mp->vword[j] * nn + node] << Mp->voff[j]) & Mp->fmask[j];   // one dictionary value: the phantom bit stays clear
+    else { m |= Mp->fmask[j] | guard; undef |= guard; }
+  }
+  const uint64_t taints = Pk->node_taints[node];
+  const uint64_t* tol = Pk->topo.f_tolerates;
+  return topo_filter_cut_po(ctx.ft, Mp, ctx.nv, ctx.fs, m, undef, [&](const TopoFiltSlot& s) { return !(s.taint && (taints & ~tol[s.group])); });
+}
+// The shape check of a batch with nodes under the phantom layout, before any pod is placed: DECLINE_NODE_KEY_DEFINEDNESS for a key K
+// that some node lacks, some class uses with NotIn, and some class OR some node-filter term uses with In (non-empty) or Exists — per
+// key over all nodes, classes and terms: conservative, never optimistic —, DECLINE_NODE_DOMAIN_RANGE for a node whose value of a
+// group's key is the index the phantom bit takes. 0: neither.
+template <class W>
+KS_COLD int topo_nodes_definedness(const ProblemView* Pk, const Workspace* Sk, const TopoWork* Tk) {
+  const ProblemView& Pv = *Pk; const Dict& d = Pv.dict;
+  const int nn = Pv.n_nodes, nc = Pv.n_classes;
+  const uint32_t* const ndef = Sk->n_defined0;
+  const uint32_t all_keys = d.n_keys >= 32 ? 0xFFFFFFFFu : (1u << d.n_keys) - 1;
+  auto keys_of = [&](const ReqRef& r, bool notin) {
+    uint64_t m = 0;
+    for (uint32_t ks_ = r.defined; ks_; ks_ &= ks_ - 1) {
+      const int k = __builtin_ctz(ks_);
+      const int op = req_op(d, r, k);
+      if (notin ? op == OP_NOTIN : (op == OP_IN || op == OP_EXISTS)) m |= 1ull << k;
+    }
+    return m;
+  };
+  const uint32_t k_notin = (uint32_t)W::reduce_or(nc, [&](int c) { return keys_of(Pv.cls_reqs.at(d, c), true); });      // keys some class uses with NotIn
+  uint32_t k_positive = (uint32_t)W::reduce_or(nc, [&](int c) { return keys_of(Pv.cls_reqs.at(d, c), false); });        // ... with In (non-empty) or Exists
+  k_positive |= (uint32_t)W::reduce_or((int)Pv.topo.f_first[Pv.topo.n_groups], [&](int i) { return keys_of(Pv.topo.f_reqs.at(d, i), false); });   // ... or some term of a node filter does
+  const uint32_t k_undef = (uint32_t)W::reduce_or(nn, [&](int e) { return (uint64_t)(~ndef[e] & all_keys); });          // keys some node leaves undefined
+  if (k_notin & k_positive & k_undef) return DECLINE_NODE_KEY_DEFINEDNESS;
+  const uint8_t* const dom = Tk->nd.dom;
+  const uint32_t gkeys = (uint32_t)W::reduce_or(Pv.topo.n_groups, [&](int g) { return Pv.topo.key[g] >= 0 ? (uint64_t)1 << Pv.topo.key[g] : (uint64_t)0; });
+  for (uint32_t ks_ = gkeys & all_keys; ks_; ks_ &= ks_ - 1) {
+    const uint8_t* const row = dom + (size_t)__builtin_ctz(ks_) * nn;
+    if (W::reduce_or(nn, [&](int e) { return (uint64_t)(row[e] >= (uint8_t)(kTopoMaxDom - 1) ? 1 : 0); })) return DECLINE_NODE_DOMAIN_RANGE;
+  }
+  return DECLINE_NONE;
+}
+
 // the per-solve state, from the pristine tables (the kernel's own set-up has accepted the problem: at most sixteen hostname groups)
 template <class W>
 KS_COLD void topo_nodes_init(const ProblemView* Pk, const Workspace* Sk, const TopoWork* Tk) {
